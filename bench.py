@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MVSDet plane-sweep hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -14,6 +14,8 @@ resident in HBM before the timed region.  Scenes are independent, so N ranks eac
 metric  = cost volumes / s  (one cost volume = one reference view's (C,D,H,W) variance volume), whole job.
 roofline = algorithmic HBM bytes of the plane-sweep kernel / its mean duration from HIP events recorded inside
            the timed region, against the 8 TB/s HBM3E peak.
+--dump-outputs DIR writes what the last timed step computed (cost volume, depth distribution, voxel volume and counts) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 cpu_baseline = the CPU restatement of the same stage (oracle/) timed on this box's host cores on a bounded
            sample (rank 0, N=1 only).  It is a checker-side measurement: nothing shipped runs on it.
 """
@@ -98,6 +100,8 @@ def run_gpu(args, w, rank, world, device):
     metas = unseen_metas(w, rank, args.warmup + args.steps + 1)
     torch.cuda.synchronize(device)
     ev = []
+    dump_dir = getattr(args, "dump_outputs", None) if rank == 0 else None
+    last_chunk = []   # (first view, cost volume) of the last timed step's last chunk, kept only for --dump-outputs
 
     def step_chunked(i, timed):
         """Cost volume produced in chunks of reference views (fp16 storage); every launch is one chunk."""
@@ -109,10 +113,12 @@ def run_gpu(args, w, rank, world, device):
         for first, var in hp.cost_volume_chunks(packed, geo, w["C"], w["H"], w["W"], w["chunk"], half_out=w.get("half", False),
                                                 events=ev if timed else None):
             keep = var[0, 0, 0].float().abs().sum().reshape(1, 1, 1)  # the consumer stand-in touches the chunk, then drops it
+            if dump_dir and i == args.warmup + args.steps - 1:
+                last_chunk[:] = [first, var]
             del var
-        prob, off, est_depth, est_dens, est_idx, avg = hp.depth_distribution(s.cost_logits)
-        vol, valid = hp.lift_packed(packed, geo, est_depth, est_dens, w["C"], w["H"], w["W"])
-        return keep, vol, valid
+        depth = hp.depth_distribution(s.cost_logits)
+        vol, valid = hp.lift_packed(packed, geo, depth[2], depth[3], w["C"], w["H"], w["W"])
+        return keep, vol, valid, depth
 
     def step(i, timed):
         if w.get("chunk"):
@@ -133,9 +139,9 @@ def run_gpu(args, w, rank, world, device):
         if timed:
             e1.record()
             ev.append((tab[2], tab[3], em, e1))
-        prob, off, est_depth, est_dens, est_idx, avg = hp.depth_distribution(s.cost_logits)
-        vol, valid = hp.lift(feat, packed, geo, est_depth, est_dens)
-        return var, vol, valid
+        depth = hp.depth_distribution(s.cost_logits)
+        vol, valid = hp.lift(feat, packed, geo, depth[2], depth[3])
+        return var, vol, valid, depth
 
     barrier = parallel.barrier if world > 1 else (lambda: None)
 
@@ -158,6 +164,18 @@ def run_gpu(args, w, rank, world, device):
     elapsed = time.perf_counter() - t0
     hp.geometry_stats = {k: hp._geometry.stats[k] - stats0[k] for k in stats0}   # of the timed region
     checksum = float(out[1].abs().sum().item()) + float(out[0][0, 0, 0].abs().sum().item())
+    if dump_dir:
+        var, vol, valid, depth = out
+        arrays = {"volume": vol, "valid": valid}
+        arrays.update(zip(("prob_volume", "depth_offset", "est_depth", "est_densities", "est_depth_index", "avg_depth"), depth))
+        if last_chunk:
+            arrays["variance_last_chunk"] = last_chunk[1]
+            hp.dumped_chunk_first_view = last_chunk[0]
+        else:
+            arrays["variance"] = var
+        hp.dumped = dump_outputs(dump_dir, arrays)
+        del var, vol, valid, depth, arrays
+        last_chunk.clear()
     del out
     # (table ms, slab-kernel ms) per launch; the chunked workload's shard entry point enqueues both behind one pair
     hp.sweep_ms_each = [m.elapsed_time(e) for _, _, m, e in ev] if ev and len(ev[0]) == 4 else [a.elapsed_time(b) for a, b in ev]
@@ -170,6 +188,31 @@ def run_gpu(args, w, rank, world, device):
     if world > 1:
         elapsed = parallel.max_over_ranks(elapsed, device)
     return elapsed, sweep_ms, checksum, hp, scenes
+
+
+DUMP_SAMPLE = 1 << 20   # elements kept of a larger output: 4 MB each, at most 9 arrays -> under 64 MB in all
+
+
+def dump_outputs(dirname, arrays, seed=0):
+    """--dump-outputs: each array as DIR/<name>.npy (float32; float64 stays float64).  An array of more than DUMP_SAMPLE
+    elements is stored as DUMP_SAMPLE of its flattened elements at indices drawn from a generator seeded per array with
+    `seed` (sorted, repeats possible): the same arguments give the same indices, so two builds compare element for element."""
+    os.makedirs(dirname, exist_ok=True)
+    info, total = {}, 0
+    for name, t in arrays.items():
+        t = t.detach()
+        n = t.numel()
+        entry = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", ""), "sampled": None}
+        if n > DUMP_SAMPLE:
+            idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).sort().values
+            t = (t if t.is_contiguous() else t.contiguous()).view(-1)[idx.to(t.device)]
+            entry["sampled"] = {"elements": DUMP_SAMPLE, "seed": seed}
+        a = t.cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        total += a.nbytes
+        info[name] = entry
+    assert total <= 64 << 20, total
+    return info
 
 
 def stage_breakdown(w, hp, scene, device, reps=3):
@@ -1004,8 +1047,13 @@ def main():
                     help="train = configs[2]: fwd + bwd + optimiser step with a stand-in cost network under DDP; "
                          "view-sharded = ONE scene over all ranks (one all-gather of the feature shards + one all-reduce "
                          "of the voxel buffer per scene: parallel.forward_scene_view_sharded)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (cost volume, depth distribution, voxel "
+                         "volume and counts) as DIR/<name>.npy, float32, a seeded sample of the larger arrays (inference mode)")
     ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != "infer":
+        raise SystemExit("bench.py: --dump-outputs is implemented for --mode infer only")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # decided before anything touches the GPU: the parent only launches and relays
@@ -1132,6 +1180,10 @@ def main():
                      "algorithmic_bytes_per_launch": bytes_launch},
         "ranks_seen": ranks_seen, "launch_env": launch_env(), "device_binding": binding, "checksum": checksum,
     }
+    if args.dump_outputs and rank == 0:
+        line["dump_outputs"] = {"dir": args.dump_outputs, "step": args.warmup + args.steps - 1, "arrays": hp.dumped}
+        if w.get("chunk"):
+            line["dump_outputs"]["variance_last_chunk_first_view"] = hp.dumped_chunk_first_view
     if w.get("chunk"):
         line["config"]["views_per_launch"] = w["chunk"]
     extras = rank == 0 and world == 1 and not args.no_extras

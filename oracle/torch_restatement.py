@@ -18,7 +18,13 @@ def homo_warp(src_fea, proj, depth_values):
         rot, trans = proj[:, :3, :3], proj[:, :3, 3:4]
         ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
         pix = torch.stack((xs.reshape(-1), ys.reshape(-1), torch.ones(H * W)))[None].repeat(B, 1, 1)
-        ray = torch.matmul(rot, pix)                                            # module.py:126
+        # module.py:126  ray = rot @ pix.  torch.matmul rounds as the BLAS kernel chosen for the host CPU does (MKL's
+        # AVX-512 and AVX2 paths differ in the last bit, which the variance's cancellation lifts past 1e-5), so the GEMM
+        # inner loop of the golden-generating host is spelled out as oracle/planesweep_oracle.c does:
+        # fmaf(r1, y, r0 * x) + r2, the fused step in float64 (the product is exact there) rounded once to float32
+        x, y = pix[:, 0:1], pix[:, 1:2]
+        ray = (rot[:, :, 0:1] * x).double() + rot[:, :, 1:2].double() * y.double()
+        ray = ray.float() + rot[:, :, 2:3]
         pts = ray.unsqueeze(2) * depth_values.view(B, 1, D, 1) + trans.view(B, 3, 1, 1)   # :128,135
         xy = pts[:, :2] / pts[:, 2:3]                                           # :136
         gx = xy[:, 0] / ((W - 1) / 2) - 1                                       # :137

@@ -38,6 +38,32 @@ def test_single_gpu_line(gpu):
 
 
 @pytest.mark.timeout(600)
+def test_dump_outputs(gpu, tmp_path):
+    """--dump-outputs: the last timed step's outputs as float32 .npy files, under 64 MB, the same from run to run."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny_3v_8d_48x64", "--steps", "2",
+                              "--warmup", "1", "--no-extras", "--cpu-seconds", "0", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=500, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = _last_json(out.stdout)
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["dump_outputs"]["step"] == 2
+        names = set(line["dump_outputs"]["arrays"])
+        assert {"variance", "prob_volume", "est_depth", "est_densities", "volume", "valid"} <= names
+        assert {p.name for p in d.iterdir()} == {n + ".npy" for n in names}
+        arrays = {n: np.load(d / (n + ".npy")) for n in names}
+        assert all(a.dtype == np.float32 for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert line["dump_outputs"]["arrays"]["variance"]["shape"] == [3, 32, 8, 48, 64]
+        assert arrays["variance"].shape == (1 << 20,) and arrays["volume"].shape == (32, 40, 40, 16)
+        assert arrays["valid"].max() > 0
+        runs.append(arrays)
+    for n, a in runs[0].items():
+        np.testing.assert_allclose(runs[1][n], a, rtol=0, atol=1e-6, err_msg=n)
+
+
+@pytest.mark.timeout(600)
 def test_two_rank_launch_dry_run(gpu):
     # `bench.py --gpus 2` alone: the parent starts the two ranks itself (no torchrun on the command line)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
