@@ -473,14 +473,22 @@ int mvsdet_conv3d_k3_bf16x3_io(const void* xs, const float* x, const int64_t* x_
  * (csrc/costreg_mx.h; v_mfma_f32_16x16x32_f16 + v_mfma_scale_f32_16x16x128_f8f6f4): the layer that reads the fp32 variance volume in
  * place, mvs_models/mvsnet.py:76 (conv0).  x, x_strides, scale / shift / relu and the three outputs as for
  * mvsdet_conv3d_k3_bf16x3_io (no residual, no split over the input channels); weight_split_mx from mvsdet_split_conv_weight_mx
- * (mvsdet_split_conv_weight_mx_bytes).  Values within ~2^-15 relative of the exact convolution (bf16x3: 2^-16; whole-network logits
- * 1-2e-5 from float64, the bar is 1e-4).  Inputs beyond fp16's range are cut on a
- * block-uniform power of two (no cliff at 65504). */
+ * (mvsdet_split_conv_weight_mx_bytes).  Error per output: at most 2^-14 * sum over its products of (bmax |w| + wmax |x|) -- bmax the
+ * largest finite |x| of the product's activation block (a tile's halo x 8 channels), wmax that of its weight block -- plus fp32
+ * accumulation; about 2^-15 of the output's scale on data of uniform magnitude (bf16x3: 2^-16; whole-network logits 1-2e-5 from
+ * float64, the bar is 1e-4), more on a small value beside a large one in its block.  A NaN or Inf input stays in its 3x3x3 receptive
+ * field.  Inputs beyond fp16's range are cut on a block-uniform power of two (no cliff at 65504). */
 size_t mvsdet_split_conv_weight_mx_bytes(int Cout, int Cin);   /* 0 unless Cout is a positive multiple of 64 */
 int mvsdet_split_conv_weight_mx(const float* weight, void* weight_split_mx, int Cout, int Cin, mvsdet_stream_t stream);
 int mvsdet_conv3d_k3_fp16mx_f32in(const float* x, const int64_t* x_strides /*HOST[4], NULL = contiguous*/, const void* weight_split_mx,
                                   const float* scale, const float* shift, float* out_f32, void* out_scl, void* out_pscl, int N, int Cin,
                                   int Cout, int D, int H, int W, int relu, mvsdet_stream_t stream);
+/* 1 if the call above can address this view of x, else 0 (the call then fails with MVSDET_ERR_INVALID_ARG: use
+ * mvsdet_conv3d_k3_bf16x3_io): the kernel reads a batch element's Cin channel volumes through one buffer descriptor with 32-bit
+ * byte offsets, so Cin * sC * 4 plus the largest byte offset inside a channel volume must stay below 2^32 and the view's span
+ * below the halo sentinel 0xfffffff0 -- e.g. Cin = 256 at 64 x 240 x 320 does not fit; with Cin % 8 != 0 (a pad channel is read)
+ * the channel stride must also cover a channel volume's extent, which rules out channels interleaved with planes. */
+int mvsdet_conv3d_k3_fp16mx_ok(int N, int Cin, int D, int H, int W, const int64_t* x_strides /*HOST[4], NULL = contiguous*/);
 /* stride 1 in front of a training-mode BatchNorm (module.py:26-37 ConvBnReLU3D under model.train()): the raw fp32 output plus, from
  * the kernel's epilogue, per-channel partial sums of the outputs and of their squares -- stats[c * parts + i] = double2 of channel c
  * in block i of the grid, parts = mvsdet_conv3d_k3_bf16x3_stats_parts(N, D, H, W, x != NULL); stats_bytes >= Cout * parts * 16.

@@ -2170,6 +2170,38 @@ extern "C" int mvsdet_split_conv_weight_mx(const float* weight, void* weight_spl
     return MVSDET_OK;
 }
 
+// Whether mvsdet_conv3d_k3_fp16mx_f32in can address this view of x.  The kernel reads one batch element's Cin channel volumes through
+// ONE buffer descriptor with 32-bit byte offsets (costreg_mx.h): num_records = the span of the view, a voxel's offset inside a channel
+// volume in voffset, channel c's c * sC * 4 in soffset (the channels of the last group beyond Cin clamped to channel Cin), a halo
+// voxel's voffset the sentinel 0xfffffff0.  Every one of them must be formed without wrapping, and every load meant to return 0 must
+// land beyond the span:
+//   * the largest soffset, Cin * sC * 4 (the clamped pad channel), plus the largest in-volume voffset: below 2^32 -- then no sum of a
+//     real voffset and soffset wraps, and sC * 4 and the span (< that sum) fit as well;
+//   * the span <= 0xfffffff0: the sentinel is out of range against num_records, on its own and plus any soffset;
+//   * Cin % 8 != 0 (a pad channel is read): sC * 4 at least one channel volume's extent, so that channel Cin starts beyond the
+//     view.  A view whose channels interleave with its planes (e.g. an (N,D,C,H,W) tensor permuted) would otherwise read real
+//     data there: a wrong block scale, and a NaN or Inf times the pad channel's zero weight outside its receptive field.
+// That out-of-range loads return 0 when voffset + soffset >= num_records (the sum not wrapped) is the hardware's behaviour these
+// limits rely on; tests/test_gpu_conv_edges.py pins it: its inputs sit in NaN canvases with NaN right after channel Cin - 1 and right
+// before every channel (where a wrapped halo offset would land), Cin in {1, 5, 20, 65}, bit for bit against contiguous copies.
+// Larger or interleaved views: the bf16x3 kernels (64-bit channel offsets, no pad-channel loads) are the entry point to use.
+extern "C" int mvsdet_conv3d_k3_fp16mx_ok(int N, int Cin, int D, int H, int W, const int64_t* x_strides) {
+    if (N <= 0 || Cin <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
+    const long long sC = x_strides ? x_strides[1] : (long long)D * H * W;
+    const long long sD = x_strides ? x_strides[2] : (long long)H * W, sH = x_strides ? x_strides[3] : (long long)W;
+    if ((x_strides && x_strides[0] < 0) || sC < 0 || sD < 0 || sH < W) return 0;
+    // strides and extents below 2^31: each product below 2^62, their sum (in elements) below 2^63 + 2^31 -- inside 64 bits; it is
+    // bounded to 2^30 elements before it is scaled to bytes
+    if (sC >= (1LL << 31) || sD >= (1LL << 31) || sH >= (1LL << 31)) return 0;
+    const unsigned long long emax = (unsigned long long)(D - 1) * sD + (unsigned long long)(H - 1) * sH + (W - 1);
+    if (emax >= (1ull << 30)) return 0;
+    const unsigned long long vmax = emax * 4ull;
+    const unsigned long long smax = (unsigned long long)Cin * (unsigned long long)sC * 4ull;
+    const unsigned long long span = (unsigned long long)(Cin - 1) * sC * 4ull + vmax + 4ull;
+    if (Cin % 8 != 0 && (unsigned long long)sC * 4ull < vmax + 4ull) return 0;
+    return smax + vmax < (1ull << 32) && span <= 0xfffffff0ull;
+}
+
 extern "C" int mvsdet_conv3d_k3_fp16mx_f32in(const float* x, const int64_t* x_strides, const void* weight_split_mx, const float* scale,
                                              const float* shift, float* out_f32, void* out_scl, void* out_pscl, int N, int Cin, int Cout,
                                              int D, int H, int W, int relu, mvsdet_stream_t stream) {
@@ -2191,7 +2223,8 @@ extern "C" int mvsdet_conv3d_k3_fp16mx_f32in(const float* x, const int64_t* x_st
     const long long sN = x_strides ? x_strides[0] : (long long)Cin * vol, sC = x_strides ? x_strides[1] : (long long)vol;
     const long long sD = x_strides ? x_strides[2] : (long long)H * W, sH = x_strides ? x_strides[3] : (long long)W;
     MVS_REQUIRE(sN >= 0 && sC >= 0 && sD >= 0 && sH >= W, "%s: bad strides", name);
-    MVS_REQUIRE((long long)(D - 1) * sD + (long long)(H - 1) * sH + W < (1LL << 31), "%s: one channel volume spans more than 2^31 elements", name);
+    MVS_REQUIRE(mvsdet_conv3d_k3_fp16mx_ok(N, Cin, D, H, W, x_strides), "%s: the view (Cin=%d, strides %lld %lld %lld %lld) spans 4 GiB or "
+                "more, or interleaves its channels: beyond the kernel's 32-bit buffer offsets (mvsdet_conv3d_k3_fp16mx_ok; use the bf16x3 kernel)", name, Cin, sN, sC, sD, sH);
     const BfOut dst = make_out(out_f32, out_scl, out_pscl, N, Cout, D, H, W);
     dim3 grid((unsigned)(p.tiles_w * p.tiles_h), (unsigned)p.tiles_d, (unsigned)(N * (Cout / 64)));
     const int xcd_map = options().conv_xcd != 0 && ((long long)grid.x * grid.y * grid.z) % 8 == 0 && (long long)grid.x * grid.y * grid.z >= 64;

@@ -49,6 +49,13 @@ constexpr int kMxSlots = 32;   // 16-byte slots per lane and weight sub-stage
         __builtin_amdgcn_sched_barrier(0);          \
     } while (0)
 
+// |v| for a finite v, NaN for +-Inf and NaN -- which fmaxf drops: the block maximum a stage is scaled by is that of its finite values.
+// An infinite input then stays in its own receptive field (its fp16 product carries it) instead of cutting every other value of its
+// halo tile and 8 channels to zero (tests/test_gpu_mx.py test_non_finite_inputs_stay_in_their_receptive_field).
+__device__ __forceinline__ float mx_finite_abs(float v) {
+    return __builtin_fmaf(fabsf(v), 0.0f, fabsf(v));   // |v| * 0 is 0, or NaN for |v| = Inf
+}
+
 // e2m3 code (sign bit 5, exponent bits 4:3 with bias 1, mantissa bits 2:0; subnormals m / 8 below 1.0; largest 7.5) of v * 2^-e, round
 // to nearest even, saturating.  The same arithmetic as oracle / tools/study/mixed_format_gate.py (q_e2m3).
 __host__ __device__ __forceinline__ unsigned mx_e2m3_code(float v, int e) {
@@ -191,7 +198,7 @@ __global__ __launch_bounds__(TD * TH * 16) void conv3d_k3_fp16mx_kernel(
 #pragma unroll
         for (int k = 0; k < NV; ++k)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) a = fmaxf(a, fabsf(f_reg[k][j]));     // (NaN inputs: fmaxf drops them; the products carry them)
+            for (int j = 0; j < 8; ++j) a = fmaxf(a, mx_finite_abs(f_reg[k][j]));
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) a = fmaxf(a, __shfl_xor(a, off, 64));
         float* spare = reinterpret_cast<float*>(s_in + (size_t)buf * STAGE + NVOX);
@@ -547,7 +554,7 @@ __global__ __launch_bounds__(TD * TH * 16 + 256) void conv3d_k3_fp16mx_ws_kernel
 #pragma unroll
             for (int k = 0; k < NV; ++k)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) a = fmaxf(a, fabsf(f_reg[P][k][j]));
+                for (int j = 0; j < 8; ++j) a = fmaxf(a, mx_finite_abs(f_reg[P][k][j]));
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) a = fmaxf(a, __shfl_xor(a, off, 64));
             float* spare = reinterpret_cast<float*>(s_in + (size_t)buf * STAGE + NVOX);

@@ -1129,16 +1129,35 @@ def split_conv_weight_mx(weight: Tensor) -> Tensor:
     return out
 
 
+def conv3d_k3_fp16mx_ok(x: Tensor) -> bool:
+    """Whether `conv3d_k3_fp16mx` runs this view of x on the fp16 + MX kernel: its 32-bit buffer offsets must cover the view
+    (include/mvsdet_hip.h mvsdet_conv3d_k3_fp16mx_ok: a batch element's Cin channels below 4 GiB of span, and with Cin % 8 != 0 no
+    channels interleaved with the planes)."""
+    import ctypes
+    copied = x.stride(4) != 1 or min(x.stride()) < 0          # `conv3d_k3_fp16mx` reads a contiguous copy of such a view
+    xstr = None if copied else (ctypes.c_int64 * 4)(*[int(v) for v in x.stride()[:4]])
+    return bool(_lib.load().mvsdet_conv3d_k3_fp16mx_ok(*[int(v) for v in x.shape], xstr))
+
+
 def conv3d_k3_fp16mx(x: Tensor, weight_split_mx: Tensor, scale: Optional[Tensor], shift: Optional[Tensor], relu: bool,
-                     outputs=("f32",), scl_out: Optional[SclTensor] = None, pscl_out: Optional[PsclTensor] = None):
+                     outputs=("f32",), scl_out: Optional[SclTensor] = None, pscl_out: Optional[PsclTensor] = None,
+                     weight: Optional[Tensor] = None):
     """Conv3d(Cin -> Cout = 64 m, kernel 3, stride 1, padding 1, no bias) [+ affine] [+ ReLU] of the fp32 (N,Cin,D,H,W) tensor read in
     place (any view with w stride 1), on ONE fp16 and TWO block-scaled FP6 products per fp32-equivalent product (csrc/costreg_mx.h:
     v_mfma_f32_16x16x32_f16 + v_mfma_scale_f32_16x16x128_f8f6f4) instead of bf16x3's three: mvsnet.py:76, the layer that reads the
-    variance volume.  weight_split_mx: `split_conv_weight_mx`.  outputs as for `conv3d_k3_bf16x3`."""
+    variance volume.  weight_split_mx: `split_conv_weight_mx`.  outputs as for `conv3d_k3_bf16x3`.  Error bound: include/mvsdet_hip.h
+    (2^-14 of the products' block maxima; ~2^-15 of the output's scale on data of uniform magnitude).
+    A view the kernel cannot address (`conv3d_k3_fp16mx_ok` False: 4 GiB or more of span per batch element, or interleaved channels) runs on
+    `conv3d_k3_bf16x3` instead, cut from `weight` -- the fp32 (Cout, Cin, 3, 3, 3) weight the split was made from, required then."""
     import ctypes
     _req(x, "x", dim=5)
     if x.stride(4) != 1 or min(x.stride()) < 0:
         x = x.contiguous()
+    if not conv3d_k3_fp16mx_ok(x):
+        if weight is None:
+            raise ValueError(f"conv3d_k3_fp16mx: the view {tuple(x.shape)} / {tuple(x.stride())} is beyond the fp16 + MX kernel's "
+                             "addressing (conv3d_k3_fp16mx_ok): pass weight= for the bf16x3 kernel")
+        return conv3d_k3_bf16x3(x, split_conv_weight(weight), scale, shift, relu, outputs=outputs, scl_out=scl_out, pscl_out=pscl_out)
     N, Cin, D, H, W = x.shape
     dev = x.device
     if (weight_split_mx.dtype != torch.int32 or weight_split_mx.dim() != 6 or not weight_split_mx.is_contiguous()

@@ -82,6 +82,57 @@ def test_argument_checks_do_not_launch(lib):
         lib.mvsdet_packed_bytes(40, 256, 120, 160) + lib.mvsdet_plane_sweep_scratch_bytes(40, 2, 64, 120, 160)
 
 
+def test_fp16mx_view_limits_at_the_32_bit_boundaries(lib):
+    """mvsdet_conv3d_k3_fp16mx_ok: the fp16 + MX conv0 kernel addresses a batch element's channels through one buffer descriptor with
+    32-bit byte offsets -- channel Cin (the clamped pad channel of the last group) at Cin * sC * 4 plus the largest in-volume offset
+    must stay below 2^32, the span below the halo sentinel 0xfffffff0.  Each limit one element either side; the launcher refuses
+    what the predicate refuses before anything is launched (the pointers here are never dereferenced)."""
+    def ok(N, Cin, D, H, W, strides=None):
+        st = None if strides is None else (ctypes.c_int64 * 4)(*strides)
+        return lib.mvsdet_conv3d_k3_fp16mx_ok(N, Cin, D, H, W, st)
+
+    # one channel, one row of W voxels, channel stride sC: the pad channel's last byte is at 4 (sC + W) - 1
+    for W in (1, 1000):
+        assert ok(1, 1, 1, 1, W, (0, (1 << 30) - W, W, W)) == 1
+        assert ok(1, 1, 1, 1, W, (0, (1 << 30) - W + 1, W, W)) == 0
+    # Cin = 2 with D, H, sD, sH all in play: 2 * sC + (D-1) sD + (H-1) sH + W <= 2^30
+    D, H, W, sH = 3, 5, 8, 9
+    sD = H * sH + 2
+    inner = (D - 1) * sD + (H - 1) * sH + W
+    assert (1 << 30) - inner > 0 and ((1 << 30) - inner) % 2 == 0
+    sC = ((1 << 30) - inner) // 2
+    assert ok(1, 2, D, H, W, (2 * sC, sC, sD, sH)) == 1
+    assert ok(1, 2, D, H, W, (2 * sC + 1, sC + 1, sD, sH)) == 0
+    # the span against the sentinel 0xfffffff0 = 4 (2^30 - 4): channel stride 0 (every channel the same volume; no pad channel)
+    assert ok(1, 8, 1, 1, (1 << 30) - 4, (0, 0, 0, (1 << 30) - 4)) == 1
+    assert ok(1, 8, 1, 1, (1 << 30) - 3, (0, 0, 0, (1 << 30) - 3)) == 0
+    # contiguous views (NULL strides): G13's conv0 fits, the reference's full-resolution conv0 (Cin 256 at 64 x 240 x 320) does not
+    assert ok(40, 256, 12, 60, 80) == 1
+    assert ok(1, 256, 64, 240, 320) == 0
+    assert ok(1, 2, 1, 1, 1 << 29) == 0 and ok(1, 1, 1, 1, 1 << 29) == 1
+    # channels interleaved with the planes ((N,D,C,H,W) storage seen as NCDHW): with a pad channel (Cin % 8 != 0) channel Cin would
+    # be real data inside the view -- refused; without one the view is fine
+    D, H, W = 6, 5, 7
+    for Cin, want in ((5, 0), (8, 1), (20, 0)):
+        assert ok(2, Cin, D, H, W, (D * Cin * H * W, H * W, Cin * H * W, W)) == want, Cin
+    ext = (D - 1) * 5 * H * W + (H - 1) * W + W                  # one channel's extent at sD = 5 H W
+    assert ok(1, 5, D, H, W, (0, ext, 5 * H * W, W)) == 1 and ok(1, 5, D, H, W, (0, ext - 1, 5 * H * W, W)) == 0
+    # element offsets inside a channel volume alone past 2^30
+    assert ok(1, 8, 3, 1, 1, (0, 0, 1 << 29, 1)) == 0 and ok(1, 8, 2, 1, 1, (0, 0, (1 << 30) - 5, 1)) == 1
+    # bad shapes / strides
+    assert ok(0, 8, 4, 4, 4) == 0 and ok(1, 0, 4, 4, 4) == 0 and ok(1, 8, 4, 4, 4, (0, 64, 16, 3)) == 0
+    assert ok(1, 8, 4, 4, 4, (-1, 64, 16, 4)) == 0 and ok(1, 8, 4, 4, 4, (512, -64, 16, 4)) == 0
+
+    # the launcher: a refused view is an error before any launch (fake 16-byte-aligned pointers, never dereferenced)
+    fake = ctypes.c_void_p(4096)
+    bad = (ctypes.c_int64 * 4)(0, (1 << 30) - 999, 1000, 1000)
+    assert ok(1, 1, 1, 1, 1000, tuple(bad)) == 0
+    rc = lib.mvsdet_conv3d_k3_fp16mx_f32in(fake, bad, fake, None, None, fake, None, None, 1, 1, 64, 1, 1, 1000, 0, None)
+    assert rc == 1 and b"4 GiB" in lib.mvsdet_last_error()
+    assert lib.mvsdet_conv3d_k3_fp16mx_f32in(fake, None, fake, None, None, fake, None, None, 1, 256, 64, 64, 240, 320, 1, None) == 1
+    assert b"4 GiB" in lib.mvsdet_last_error()
+
+
 def test_ops_have_no_cpu_path():
     import torch
     from mvsdet_amd import ops

@@ -134,3 +134,159 @@ def test_g8_with_conv0_on_the_mixed_format_route(gpu):
     e, e3 = float(np.abs(y.cpu().numpy() - g["logits"]).max()), float(np.abs(y3.cpu().numpy() - g["logits"]).max())
     print(f"G8 logits: fp16mx conv0 {e:.2e}, bf16x3 {e3:.2e}")
     assert e <= 1e-4 and not torch.equal(y, y3)
+
+
+def _hdr_case(N, Cin, Cout, D, H, W, seed, spikes=6):
+    """Variance-like input whose per-channel scales span 10^-3 .. 10^3, with isolated spikes 10^4 above their channel."""
+    g = torch.Generator().manual_seed(seed)
+    f = torch.randn((3, N, Cin, D, H, W), generator=g)
+    x = (f * f).mean(0) - f.mean(0) ** 2
+    x = x * (10.0 ** (torch.rand((1, Cin, 1, 1, 1), generator=g) * 6 - 3))
+    for _ in range(spikes):
+        n, c = int(torch.randint(0, N, (1,), generator=g)), int(torch.randint(0, Cin, (1,), generator=g))
+        d, h, w_ = (int(torch.randint(0, s, (1,), generator=g)) for s in (D, H, W))
+        x[n, c, d, h, w_] *= 1e4
+    w = torch.randn((Cout, Cin, 3, 3, 3), generator=g) / (27 * Cin) ** 0.5
+    return x, w
+
+
+@pytest.mark.parametrize("N,Cin,Cout,D,H,W", [(1, 64, 64, 4, 16, 32), (2, 20, 128, 5, 13, 17), (1, 256, 64, 4, 8, 16)])
+def test_high_dynamic_range_within_the_block_bound(gpu, N, Cin, Cout, D, H, W, record_property):
+    """Per-channel scales over six decades and spikes 10^4 above their block: the error of every output stays within what the
+    scheme guarantees in terms of each block's largest |x| and the weights' sums (tests/conv_bounds.py mx_bound).  Such data can
+    break a bound stated on the output's own summed |products| (tests/fuzz_round6.py's 2^-13): a small value next to a large one
+    in its block loses its FP6 correction terms -- how far past that bound it goes is recorded, not asserted."""
+    from mvsdet_amd import ops
+    from conv_bounds import mx_bound
+    x, w = _hdr_case(N, Cin, Cout, D, H, W, seed=Cin + D)
+    got = ops.conv3d_k3_fp16mx(x.to(gpu), ops.split_conv_weight_mx(w.to(gpu)), None, None, False).double().cpu()
+    ref = F.conv3d(x.double(), w.double(), padding=1)
+    mags = F.conv3d(x.double().abs(), w.double().abs(), padding=1)
+    bound = mx_bound(x, w, None, N, Cin, Cout, D, H, W, (4, 8, 16)) + 2.0 ** -23 * ref.abs()
+    err = (got - ref).abs()
+    assert bool(torch.isfinite(got).all())
+    ratio = float((err / bound).max())
+    fuzz = float((err / (2.0 ** -13 * mags)).max())
+    record_property("block_bound_used", ratio)
+    record_property("summed_products_bound_2m13_used", fuzz)
+    record_property("summed_products_bound_failures", int((err > 2.0 ** -13 * mags).sum()))
+    print(f"HDR {N}x{Cin}->{Cout} {D}x{H}x{W}: block bound used {ratio:.3f}, 2^-13 summed |products| bound used {fuzz:.3f}")
+    assert ratio <= 1.0, ratio
+
+
+def test_non_finite_inputs_stay_in_their_receptive_field(gpu):
+    """A NaN or +-Inf input is non-finite in float64 only inside its 3 x 3 x 3 receptive field.  The stage's block scale
+    (costreg_mx.h publish_amax: fmaxf drops NaN, takes Inf) must not carry it further: every output outside the fields is finite
+    and within the block bound of the finite data."""
+    from mvsdet_amd import ops
+    from conv_bounds import mx_bound
+    N, Cin, Cout, D, H, W = 1, 20, 64, 8, 16, 32
+    g = torch.Generator().manual_seed(77)
+    f = torch.randn((3, N, Cin, D, H, W), generator=g)
+    x = (f * f).mean(0) - f.mean(0) ** 2
+    w = torch.randn((Cout, Cin, 3, 3, 3), generator=g) / (27 * Cin) ** 0.5
+    bad = [(0, 3, 1, 4, 5, float("nan")), (0, 12, 6, 11, 20, float("inf")), (0, 17, 2, 9, 28, float("-inf"))]
+    xb = x.clone()
+    field = torch.zeros((D, H, W), dtype=torch.bool)
+    for n, c, d, h, w_, v in bad:
+        xb[n, c, d, h, w_] = v
+        field[max(d - 1, 0):d + 2, max(h - 1, 0):h + 2, max(w_ - 1, 0):w_ + 2] = True
+    got = ops.conv3d_k3_fp16mx(xb.to(gpu), ops.split_conv_weight_mx(w.to(gpu)), None, None, False).double().cpu()
+    ref = F.conv3d(x.double(), w.double(), padding=1)
+    bound = mx_bound(x, w, None, N, Cin, Cout, D, H, W, (4, 8, 16)) + 2.0 ** -23 * ref.abs()
+    outside = ~field.view(1, 1, D, H, W).expand_as(got)
+    assert bool(torch.isfinite(got[outside]).all()), int((~torch.isfinite(got[outside])).sum())
+    assert bool(((got - ref).abs()[outside] <= bound[outside]).all())
+    assert not bool(torch.isfinite(got[~outside]).all())          # and the fields themselves are not finite
+
+
+def test_views_beyond_32_bit_offsets_run_on_bf16x3(gpu):
+    """A view whose channels span more than 4 GiB (8 channels 0.57 GB apart, NaN between them): mvsdet_conv3d_k3_fp16mx_f32in refuses
+    it (its buffer offsets are 32 bits), ops.conv3d_k3_fp16mx and the network's conv0 run it on the bf16x3 kernel -- the float64
+    convolution within the bf16x3 bound, and the network the same bits as with conv0 on bf16x3 from a contiguous copy."""
+    import ctypes
+    from mvsdet_amd import _lib, ops
+    from mvsdet_amd.costreg import CostRegNet3DGS
+    N, Cin, Cout, D, H, W = 1, 8, 64, 16, 24, 40
+    vol = D * H * W
+    sC = (1 << 32) // (4 * (Cin - 1)) + 64                      # (Cin - 1) * sC * 4 > 2^32: about 4.3 GB in all
+    g = torch.Generator().manual_seed(3)
+    x = torch.rand((N, Cin, D, H, W), generator=g)
+    w = torch.randn((Cout, Cin, 3, 3, 3), generator=g) / (27 * Cin) ** 0.5
+    sc, sh = torch.rand(Cout, generator=g) + 0.5, torch.randn(Cout, generator=g) * 0.1
+    canvas = torch.full(((Cin - 1) * sC + vol,), float("nan"), device=gpu)
+    xv = canvas.as_strided((N, Cin, D, H, W), (Cin * sC, sC, H * W, W, 1))
+    xv.copy_(x.to(gpu))
+    assert not ops.conv3d_k3_fp16mx_ok(xv) and ops.conv3d_k3_fp16mx_ok(xv[:, :1]) and ops.conv3d_k3_fp16mx_ok(x.to(gpu))
+    wd, scd, shd = w.to(gpu), sc.to(gpu), sh.to(gpu)
+    wq = ops.split_conv_weight_mx(wd)
+    out = torch.empty((N, Cout, D, H, W), device=gpu)
+    xs = (ctypes.c_int64 * 4)(*[int(s) for s in xv.stride()[:4]])
+    lib = _lib.load()
+    assert lib.mvsdet_conv3d_k3_fp16mx_f32in(_lib.ptr(xv), xs, _lib.ptr(wq), None, None, _lib.ptr(out), None, None, N, Cin, Cout, D, H, W,
+                                             0, _lib.current_stream(gpu)) == 1
+    assert b"4 GiB" in lib.mvsdet_last_error()
+    with pytest.raises(ValueError, match="addressing"):
+        ops.conv3d_k3_fp16mx(xv, wq, scd, shd, True)
+    got = ops.conv3d_k3_fp16mx(xv, wq, scd, shd, True, weight=wd)
+    assert torch.equal(got, ops.conv3d_k3_bf16x3(x.to(gpu), ops.split_conv_weight(wd), scd, shd, True))
+    ref = torch.relu(F.conv3d(x.double(), w.double(), padding=1) * sc.double().view(1, -1, 1, 1, 1) + sh.double().view(1, -1, 1, 1, 1))
+    mag = F.conv3d(x.double(), w.double().abs(), padding=1) * sc.double().view(1, -1, 1, 1, 1)
+    assert float((got.double().cpu() - ref).abs().max()) <= 3 * 2.0 ** -16 * float(mag.max())
+    net = CostRegNet3DGS(Cin, 64).eval()
+    with torch.no_grad():
+        lcg_fill_state(net, 11)
+        net = net.to(gpu)
+        assert net.conv0_precision == "fp16mx"
+        y = net(xv)
+        net.conv0_precision = "bf16x3"
+        y3 = net(x.to(gpu))
+    assert torch.isfinite(y).all() and torch.equal(y, y3)
+    del canvas, xv
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("seed,hdr", [(0, False), (1, False), (2, True), (3, True)])
+def test_network_logits_against_float64_on_swept_scenes(gpu, seed, hdr, record_property):
+    """The eval default's gate: CostRegNet3DGS (G8 weights) on the variance volume the HIP sweep makes of a synthetic G13-like scene
+    (6 views, C = 256, 12 planes, 60 x 80), against the same module in float64 on the CPU.  hdr: feature channels scaled over three
+    decades (the variance over six).  Errors are max |logit - float64| over max(1, max |float64 logit|); fp16mx must keep a 2x margin
+    under the project's 1e-4 bar, bf16x3 is recorded beside it."""
+    import copy
+    from mvsdet_amd import synthetic
+    from mvsdet_amd.costreg import CostRegNet3DGS
+    from mvsdet_amd.hotpath import MVSDetHotPath
+    N, C, D, hw = 6, 256, 12, (60, 80)
+    meta = synthetic.make_img_meta(N, hw, seed=seed)
+    feat = synthetic.make_features(N, C, hw, seed=seed)
+    if hdr:
+        g = torch.Generator().manual_seed(500 + seed)
+        feat = feat * 10.0 ** (torch.rand((1, C, 1, 1), generator=g) * 3 - 1.5)
+    hp = MVSDetHotPath([40, 40, 16], [0.16, 0.16, 0.2], [0.2, 5.0], D, topk=3)
+    with torch.no_grad():
+        out = hp.forward_scene(feat.to(gpu), meta, cost_logits=synthetic.make_cost_logits(N, D, hw, seed=seed).to(gpu))
+    var = out["variance"]
+    assert tuple(var.shape) == (N, C, D) + hw
+    net = CostRegNet3DGS(C, 64).eval()
+    lcg_fill_state(net, int(load_golden("g8_cost_regularisation")["weight_seed"]))
+    net64 = copy.deepcopy(net).double()
+    net = net.to(gpu)
+    threads = torch.get_num_threads()
+    torch.set_num_threads(min(16, threads))
+    try:
+        with torch.no_grad():
+            assert net.conv0_precision == "fp16mx"
+            y = net(var).double().cpu()
+            net.conv0_precision = "bf16x3"
+            y3 = net(var).double().cpu()
+            y64 = net64(var.double().cpu())
+    finally:
+        torch.set_num_threads(threads)
+    scale = max(1.0, float(y64.abs().max()))
+    e, e3 = float((y - y64).abs().max()) / scale, float((y3 - y64).abs().max()) / scale
+    record_property("fp16mx_logit_err", e)
+    record_property("bf16x3_logit_err", e3)
+    record_property("logit_scale", scale)
+    print(f"scene {seed} hdr={hdr}: variance max {float(var.abs().max()):.3g}, logits scale {scale:.3g}: fp16mx {e:.2e}, bf16x3 {e3:.2e}")
+    assert bool(torch.isfinite(y).all()) and e3 <= 5e-5
+    assert e <= 5e-5, e
