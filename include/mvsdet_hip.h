@@ -311,6 +311,21 @@ int mvsdet_bn3d_relu_bwd_f32(const float* x, const float* grad_out, const float*
                              const float* save_mean, const float* save_invstd, float* grad_x, float* grad_gamma,
                              float* grad_beta, void* workspace, size_t workspace_bytes, int N, int C, long long vol, int relu,
                              mvsdet_stream_t stream);
+/* Training-mode BatchNorm3d with the residual added INSIDE the activation, the tail of the 3-D neck's ResModule
+ * (mmdet3d/models/necks/imvoxel_neck.py:219-230: relu(bn(conv1(h)) + identity)):
+ *   out = [relu](gamma * (x - mean) * invstd + beta + residual), residual (N, C, vol) required;
+ * statistics from a pass over x (partial NULL) or from a producer's partial sums (partial / parts / pivot as in
+ * mvsdet_bn3d_relu_train_fwd_parts_f32); running statistics, save_mean / save_invstd and workspace as above.
+ * Backward: g' = grad_out * [out > 0] (relu; `out` = the forward's output) or grad_out; grad_residual = g' (may be NULL);
+ * grad_x, grad_gamma, grad_beta (the last two may be NULL) as mvsdet_bn3d_relu_bwd_f32 with g' as the masked gradient. */
+int mvsdet_bn3d_res_relu_train_fwd_f32(const float* x, const void* partial, size_t parts, const float* pivot, const float* gamma,
+                                       const float* beta, const float* residual, float* running_mean, float* running_var, float* out,
+                                       float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes, int N, int C,
+                                       long long vol, float momentum, float eps, int relu, mvsdet_stream_t stream);
+int mvsdet_bn3d_res_relu_bwd_f32(const float* x, const float* out, const float* grad_out, const float* gamma, const float* beta,
+                                 const float* save_mean, const float* save_invstd, float* grad_x, float* grad_gamma, float* grad_beta,
+                                 float* grad_residual, void* workspace, size_t workspace_bytes, int N, int C, long long vol, int relu,
+                                 mvsdet_stream_t stream);
 int mvsdet_conv3d_k3_cout2_f32(const float* x, const float* weight, const float* bias, float* out, int N, int Cin,
                                int D, int H, int W, mvsdet_stream_t stream);
 /* The same layer on the SUM of two tensors, x + x2 (x2 NULL: x alone), formed while the halo tiles are staged: mvsnet.py:111-112
@@ -548,6 +563,23 @@ int mvsdet_conv3d_k1_s2_bf16x3(const float* x, const void* wsplit, const float* 
                                int H, int W, int relu, mvsdet_stream_t stream);
 int mvsdet_convT3d_k2_s2_bf16x3(const float* x, const void* wsplit, const float* bias, float* out, int N, int Cin, int Cout, int D,
                                 int H, int W, int relu, mvsdet_stream_t stream);
+/* Their gradients under autograd (bf16x3, no atomics; split-K partial sums added in a fixed order: deterministic).
+ *   mvsdet_conv3d_k1_s2_dx_bf16x3:  grad_x (N,Cin,D,H,W)[.., 2d, 2h, 2w] += sum_o W[o][c] grad_out (N,Cout,D/2,H/2,W/2)[.., d, h, w];
+ *                                   only the even positions are written (accumulated into what grad_x holds); D, H, W even;
+ *                                   wsplit = mvsdet_gemm_split_weight of the (Cin, Cout) matrix W^T (Cin % 128, Cout % 32)
+ *   mvsdet_convT3d_k2_s2_dx_bf16x3: grad_x (N,Cin,D,H,W)[.., v] = sum_{o,p,q,r} W[c][o][p][q][r] grad_out (N,Cout,2D,2H,2W)[.., 2v + (p,q,r)];
+ *                                   wsplit = mvsdet_gemm_split_weight of W.reshape(Cin, 8 Cout) (Cin % 128, 8 Cout % 32)
+ *   mvsdet_neck_gemm_dw_bf16x3:     transposed = 0: dw (Cout, Cin) = sum_{n,v} grad_out (N,Cout,D,H,W)[o, v] x (N,Cin,2D,2H,2W)[c, 2v];
+ *                                   transposed = 1: dw (Cin, Cout, 2,2,2) = sum_{n,v} x (N,Cin,D,H,W)[c, v] grad_out (N,Cout,2D,2H,2W)[o, 2v + pqr];
+ *                                   (D, H, W) = the coarse grid; nsplit > 1 voxel chunks summed in `partial`
+ *                                   (mvsdet_neck_gemm_dw_partial_bytes; 0 when nsplit <= 1: no buffer needed). */
+int mvsdet_conv3d_k1_s2_dx_bf16x3(const float* grad_out, const void* wsplit, float* grad_x, int N, int Cin, int Cout, int D, int H,
+                                  int W, mvsdet_stream_t stream);
+int mvsdet_convT3d_k2_s2_dx_bf16x3(const float* grad_out, const void* wsplit, float* grad_x, int N, int Cin, int Cout, int D, int H,
+                                   int W, mvsdet_stream_t stream);
+size_t mvsdet_neck_gemm_dw_partial_bytes(int Cin, int Cout, int transposed, int nsplit);
+int mvsdet_neck_gemm_dw_bf16x3(const float* x, const float* grad_out, float* dw, float* partial, size_t partial_bytes, int nsplit,
+                               int transposed, int N, int Cin, int Cout, int D, int H, int W, mvsdet_stream_t stream);
 
 #ifdef __cplusplus
 }

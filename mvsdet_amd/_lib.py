@@ -58,6 +58,8 @@ SIGNATURES = {
     "mvsdet_bn3d_relu_train_fwd_res_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, ctypes.c_longlong, _f, _f, _i, _vp],
     "mvsdet_bn3d_relu_train_fwd_parts_f32": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, ctypes.c_longlong, _f, _f, _i, _vp],
     "mvsdet_bn3d_relu_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, ctypes.c_longlong, _i, _vp],
+    "mvsdet_bn3d_res_relu_train_fwd_f32": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, ctypes.c_longlong, _f, _f, _i, _vp],
+    "mvsdet_bn3d_res_relu_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, ctypes.c_longlong, _i, _vp],
     "mvsdet_conv3d_k3_mfma_ws_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_conv3d_k3_dw_partial_bytes": [_i, _i, _i],
     "mvsdet_conv3d_k3_dw_mfma_f32": [_vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp],
@@ -72,6 +74,10 @@ SIGNATURES = {
     "mvsdet_gemm_split_weight": [_vp, _vp, _i, _i, _vp],
     "mvsdet_conv3d_k1_s2_bf16x3": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_convT3d_k2_s2_bf16x3": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_conv3d_k1_s2_dx_bf16x3": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_convT3d_k2_s2_dx_bf16x3": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_neck_gemm_dw_partial_bytes": [_i, _i, _i, _i],
+    "mvsdet_neck_gemm_dw_bf16x3": [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_conv3d_k3_cout2_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "mvsdet_conv3d_k3_cout2_sum_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "mvsdet_backproject_weigh_f32": [_vp, _i64p, _vp, _vp, _vp, _vp, _i64p, _vp, _vp, _vp, _vp,
@@ -117,7 +123,7 @@ SIGNATURES = {
     "mvsdet_conv3d_k3_fp16mx_f32in": [_vp, _i64p, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_conv3d_k3_fp16mx_ok": [_i, _i, _i, _i, _i, _i64p],
 }
-_RESTYPE = {"mvsdet_last_error": ctypes.c_char_p, "mvsdet_conv3d_k3_bf16x3_stats_parts": ctypes.c_size_t, "mvsdet_convT3d_k3_s2_bf16x3_stats_parts": ctypes.c_size_t, "mvsdet_gemm_split_weight_bytes": ctypes.c_size_t, "mvsdet_scl_bytes": ctypes.c_size_t, "mvsdet_pscl_bytes": ctypes.c_size_t,
+_RESTYPE = {"mvsdet_last_error": ctypes.c_char_p, "mvsdet_conv3d_k3_bf16x3_stats_parts": ctypes.c_size_t, "mvsdet_convT3d_k3_s2_bf16x3_stats_parts": ctypes.c_size_t, "mvsdet_gemm_split_weight_bytes": ctypes.c_size_t, "mvsdet_neck_gemm_dw_partial_bytes": ctypes.c_size_t, "mvsdet_scl_bytes": ctypes.c_size_t, "mvsdet_pscl_bytes": ctypes.c_size_t,
             "mvsdet_split_conv_weight_bytes": ctypes.c_size_t, "mvsdet_packed_bytes": ctypes.c_size_t,
             "mvsdet_split_conv_weight_mx_bytes": ctypes.c_size_t,
             "mvsdet_plane_sweep_scratch_bytes": ctypes.c_size_t, "mvsdet_plane_sweep_workspace_bytes": ctypes.c_size_t,

@@ -24,7 +24,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-from .neck import DerivedTensorsMixin, _bn_affine, fp32_under_autocast
+from .neck import DerivedTensorsMixin, _bn_affine, fp32_under_autocast, update_running_stats
 from .scratch import EventPool
 
 
@@ -181,14 +181,7 @@ def _bn_relu_train(bn: nn.BatchNorm3d, x: torch.Tensor, residual: Optional[torch
         out, mean, invstd = ops.bn3d_relu_train(x, bn.weight, bn.bias, bn.eps, False, None, parts, pivot)
         out = out * hook[1][bn].to(out.dtype)
         out = out if residual is None else out + residual
-    if bn.track_running_stats and bn.running_mean is not None:
-        with torch.no_grad():
-            m = x.numel() // x.shape[1]
-            bn.num_batches_tracked += 1
-            mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
-            var = (1.0 / (invstd * invstd) - bn.eps).clamp_min_(0.0) * (m / max(m - 1, 1))
-            bn.running_mean.mul_(1.0 - mom).add_(mean, alpha=mom)
-            bn.running_var.mul_(1.0 - mom).add_(var, alpha=mom)
+    update_running_stats(bn, x, mean, invstd)
     return out
 
 

@@ -157,26 +157,57 @@ __global__ __launch_bounds__(kThreads) void bn_apply_kernel(const float* __restr
     }
 }
 
-// backward reductions: partial[c][split] = (sum g', sum g' * xhat)
+// y = [relu](x * scale_c + shift_c + residual): the residual INSIDE the activation (ResModule, imvoxel_neck.py:219-230:
+// relu(bn(conv1(h)) + identity))
 template <bool VEC>
+__global__ __launch_bounds__(kThreads) void bn_apply_res_in_kernel(const float* __restrict__ x, const float* __restrict__ scale,
+                                                                  const float* __restrict__ shift, const float* __restrict__ residual,
+                                                                  float* __restrict__ y, int C, size_t vol, int relu) {
+    const int c = blockIdx.y, n = blockIdx.z;
+    const float sc = scale[c], sh = shift[c];
+    const size_t base = ((size_t)n * C + c) * vol;
+    const size_t unit = VEC ? 4 : 1, cnt = vol / unit;
+    auto one = [&](float xv, float r) {
+        const float v = fmaf(xv, sc, sh) + r;
+        return relu ? fmaxf(v, 0.f) : v;
+    };
+    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < cnt; i += (size_t)gridDim.x * kThreads) {
+        if (VEC) {
+            const float4 v = *reinterpret_cast<const float4*>(x + base + 4 * i), r = *reinterpret_cast<const float4*>(residual + base + 4 * i);
+            *reinterpret_cast<float4*>(y + base + 4 * i) = make_float4(one(v.x, r.x), one(v.y, r.y), one(v.z, r.z), one(v.w, r.w));
+        } else {
+            y[base + i] = one(x[base + i], residual[base + i]);
+        }
+    }
+}
+
+// backward reductions: partial[c][split] = (sum g', sum g' * xhat)
+// OUTMASK: the ReLU mask is `yout > 0` of the saved forward output (the residual-inside-ReLU form, whose mask x alone does not give)
+template <bool VEC, bool OUTMASK = false>
 __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(const float* __restrict__ x, const float* __restrict__ gy,
                                                                 const float* __restrict__ mean, const float* __restrict__ invstd,
                                                                 const float* __restrict__ scale, const float* __restrict__ shift,
-                                                                double2* __restrict__ partial, int N, int C, size_t vol, int relu) {
+                                                                double2* __restrict__ partial, int N, int C, size_t vol, int relu,
+                                                                const float* __restrict__ yout = nullptr) {
     const int c = blockIdx.x, split = blockIdx.y;
     const float mu = mean[c], is = invstd[c], sc = scale[c], sh = shift[c];
     float s = 0.0f, q = 0.0f;
-    auto one = [&](float xv, float g) {
-        if (relu && !(fmaf(xv, sc, sh) > 0.0f)) g = 0.0f;   // the forward's own arithmetic: the same sign
+    auto one = [&](float xv, float g, float yv) {
+        if (OUTMASK) {
+            if (relu && !(yv > 0.0f)) g = 0.0f;
+        } else if (relu && !(fmaf(xv, sc, sh) > 0.0f)) {
+            g = 0.0f;   // the forward's own arithmetic: the same sign
+        }
         s += g;
         q += g * ((xv - mu) * is);
     };
     for_channel_strip<VEC>(N, C, vol, c, split, gridDim.y, [&](size_t off) {
         if (VEC) {
             const float4 xv = *reinterpret_cast<const float4*>(x + off), g = *reinterpret_cast<const float4*>(gy + off);
-            one(xv.x, g.x); one(xv.y, g.y); one(xv.z, g.z); one(xv.w, g.w);
+            const float4 yv = OUTMASK ? *reinterpret_cast<const float4*>(yout + off) : make_float4(0.f, 0.f, 0.f, 0.f);
+            one(xv.x, g.x, yv.x); one(xv.y, g.y, yv.y); one(xv.z, g.z, yv.z); one(xv.w, g.w, yv.w);
         } else {
-            one(x[off], gy[off]);
+            one(x[off], gy[off], OUTMASK ? yout[off] : 0.0f);
         }
     });
     const double2 r = block_sum2((double)s, (double)q);
@@ -205,27 +236,38 @@ __global__ void bn_bwd_finalize_kernel(const double2* __restrict__ partial, int 
 }
 
 // dx = gamma * invstd * (g' - dbeta/M - xhat * dgamma/M)
-template <bool VEC>
+// OUTMASK: mask from the saved output (see bn_bwd_reduce_kernel), and the masked gradient g' also written to gres (the gradient of the
+// residual added inside the ReLU; NULL = not wanted)
+template <bool VEC, bool OUTMASK = false>
 __global__ __launch_bounds__(kThreads) void bn_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ gy,
                                                                const float* __restrict__ mean, const float* __restrict__ invstd,
                                                                const float* __restrict__ scale, const float* __restrict__ shift,
                                                                const float* __restrict__ sums, float* __restrict__ gx, int C,
-                                                               size_t vol, float inv_m, int relu) {
+                                                               size_t vol, float inv_m, int relu, const float* __restrict__ yout = nullptr,
+                                                               float* __restrict__ gres = nullptr) {
     const int c = blockIdx.y, n = blockIdx.z;
     const float mu = mean[c], is = invstd[c], sc = scale[c], sh = shift[c];
     const float db = sums[2 * c] * inv_m, dg = sums[2 * c + 1] * inv_m;
     const size_t base = ((size_t)n * C + c) * vol;
     const size_t unit = VEC ? 4 : 1, cnt = vol / unit;
+    auto mask = [&](float xv, float g, float yv) {
+        if (OUTMASK) return relu && !(yv > 0.0f) ? 0.0f : g;
+        return relu && !(fmaf(xv, sc, sh) > 0.0f) ? 0.0f : g;
+    };
     auto one = [&](float xv, float g) {
-        if (relu && !(fmaf(xv, sc, sh) > 0.0f)) g = 0.0f;
-        return sc * (g - db - ((xv - mu) * is) * dg);    // sc = gamma * invstd
+        return sc * (g - db - ((xv - mu) * is) * dg);    // sc = gamma * invstd; g already masked
     };
     for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < cnt; i += (size_t)gridDim.x * kThreads) {
         if (VEC) {
             const float4 xv = *reinterpret_cast<const float4*>(x + base + 4 * i), g = *reinterpret_cast<const float4*>(gy + base + 4 * i);
-            *reinterpret_cast<float4*>(gx + base + 4 * i) = make_float4(one(xv.x, g.x), one(xv.y, g.y), one(xv.z, g.z), one(xv.w, g.w));
+            const float4 yv = OUTMASK ? *reinterpret_cast<const float4*>(yout + base + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 gm = make_float4(mask(xv.x, g.x, yv.x), mask(xv.y, g.y, yv.y), mask(xv.z, g.z, yv.z), mask(xv.w, g.w, yv.w));
+            *reinterpret_cast<float4*>(gx + base + 4 * i) = make_float4(one(xv.x, gm.x), one(xv.y, gm.y), one(xv.z, gm.z), one(xv.w, gm.w));
+            if (OUTMASK && gres) *reinterpret_cast<float4*>(gres + base + 4 * i) = gm;
         } else {
-            gx[base + i] = one(x[base + i], gy[base + i]);
+            const float gm = mask(x[base + i], gy[base + i], OUTMASK ? yout[base + i] : 0.0f);
+            gx[base + i] = one(x[base + i], gm);
+            if (OUTMASK && gres) gres[base + i] = gm;
         }
     }
 }
@@ -349,5 +391,76 @@ extern "C" int mvsdet_bn3d_relu_bwd_f32(const float* x, const float* grad_out, c
         hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, agrid, dim3(kThreads), 0, stream, x, grad_out, save_mean, save_invstd, w.scale,
                            w.shift, w.sums, grad_x, C, (size_t)vol, inv_m, relu);
     MVS_LAUNCH_CHECK("bn3d_relu_bwd");
+    return MVSDET_OK;
+}
+
+// Training-mode BatchNorm3d with the residual added INSIDE the activation: out = [relu](gamma (x - mean) invstd + beta + residual)
+// (ResModule: relu(bn(conv1(h)) + identity)).  Statistics from a pass over x (partial NULL) or from a producer's partial sums as in
+// mvsdet_bn3d_relu_train_fwd_parts_f32.
+extern "C" int mvsdet_bn3d_res_relu_train_fwd_f32(const float* x, const void* partial, size_t parts, const float* pivot, const float* gamma,
+                                                  const float* beta, const float* residual, float* running_mean, float* running_var,
+                                                  float* out, float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes,
+                                                  int N, int C, long long vol, float momentum, float eps, int relu, mvsdet_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    MVS_REQUIRE(x && residual && out && save_mean && save_invstd, "bn3d_res_relu_train_fwd: NULL pointer");
+    MVS_REQUIRE(!partial || parts > 0, "bn3d_res_relu_train_fwd: partial sums given with parts=0");
+    MVS_REQUIRE(((uintptr_t)partial & 15u) == 0, "bn3d_res_relu_train_fwd: partial sums must be 16-byte aligned");
+    MVS_REQUIRE((((uintptr_t)x | (uintptr_t)residual | (uintptr_t)out) & 3u) == 0, "bn3d_res_relu_train_fwd: tensors must be 4-byte aligned");
+    if (int rc = bn_check("bn3d_res_relu_train_fwd", N, C, vol, workspace, workspace_bytes)) return rc;
+    const BnWs w = bn_ws(workspace, C);
+    const bool vec = (vol % 4 == 0) && (((uintptr_t)x | (uintptr_t)out | (uintptr_t)residual) & 15u) == 0;
+    if (partial) {
+        hipLaunchKernelGGL(bn_finalize_parts_kernel, dim3((unsigned)C), dim3(kThreads), 0, stream, static_cast<const double2*>(partial), parts, pivot,
+                           gamma, beta, running_mean, running_var, save_mean, save_invstd, w.scale, w.shift, (double)N * (double)vol, momentum, eps);
+    } else {
+        dim3 rgrid((unsigned)C, kBnSplit);
+        if (vec) hipLaunchKernelGGL(bn_stats_kernel<true>, rgrid, dim3(kThreads), 0, stream, x, w.partial, N, C, (size_t)vol);
+        else hipLaunchKernelGGL(bn_stats_kernel<false>, rgrid, dim3(kThreads), 0, stream, x, w.partial, N, C, (size_t)vol);
+        hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 63) / 64), dim3(64), 0, stream, x, (size_t)vol, w.partial, kBnSplit, gamma, beta, running_mean,
+                           running_var, save_mean, save_invstd, w.scale, w.shift, C, (double)N * (double)vol, momentum, eps);
+    }
+    const size_t cnt = (size_t)vol / (vec ? 4 : 1);
+    dim3 agrid((unsigned)std::min<size_t>((cnt + kThreads - 1) / kThreads, 64), (unsigned)C, (unsigned)N);
+    if (vec) hipLaunchKernelGGL(bn_apply_res_in_kernel<true>, agrid, dim3(kThreads), 0, stream, x, w.scale, w.shift, residual, out, C, (size_t)vol, relu);
+    else hipLaunchKernelGGL(bn_apply_res_in_kernel<false>, agrid, dim3(kThreads), 0, stream, x, w.scale, w.shift, residual, out, C, (size_t)vol, relu);
+    MVS_LAUNCH_CHECK("bn3d_res_relu_train_fwd");
+    return MVSDET_OK;
+}
+
+// Its backward: g' = grad_out [out > 0] (relu) or grad_out; grad_residual = g' (NULL = not wanted); grad_x / grad_gamma / grad_beta as
+// mvsdet_bn3d_relu_bwd_f32 with g' in place of the masked gradient.  `out` (the forward's output) is needed when relu != 0.
+extern "C" int mvsdet_bn3d_res_relu_bwd_f32(const float* x, const float* out, const float* grad_out, const float* gamma, const float* beta,
+                                            const float* save_mean, const float* save_invstd, float* grad_x, float* grad_gamma,
+                                            float* grad_beta, float* grad_residual, void* workspace, size_t workspace_bytes, int N, int C,
+                                            long long vol, int relu, mvsdet_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    MVS_REQUIRE(x && grad_out && save_mean && save_invstd && grad_x, "bn3d_res_relu_bwd: NULL pointer");
+    MVS_REQUIRE(out || !relu, "bn3d_res_relu_bwd: NULL pointer (the ReLU mask needs the forward's output)");
+    MVS_REQUIRE((((uintptr_t)x | (uintptr_t)out | (uintptr_t)grad_out | (uintptr_t)grad_x | (uintptr_t)grad_residual) & 3u) == 0,
+                "bn3d_res_relu_bwd: tensors must be 4-byte aligned");
+    if (int rc = bn_check("bn3d_res_relu_bwd", N, C, vol, workspace, workspace_bytes)) return rc;
+    const BnWs w = bn_ws(workspace, C);
+    const float* yout = relu ? out : x;   // relu == 0: no mask (the pointer is read but not used)
+    const bool vec = (vol % 4 == 0) &&
+                     (((uintptr_t)x | (uintptr_t)yout | (uintptr_t)grad_out | (uintptr_t)grad_x | (uintptr_t)grad_residual) & 15u) == 0;
+    hipLaunchKernelGGL(bn_affine_kernel, dim3((C + 63) / 64), dim3(64), 0, stream, gamma, beta, save_mean, save_invstd, w.scale, w.shift, C);
+    dim3 rgrid((unsigned)C, kBnSplit);
+    if (vec)
+        hipLaunchKernelGGL((bn_bwd_reduce_kernel<true, true>), rgrid, dim3(kThreads), 0, stream, x, grad_out, save_mean, save_invstd, w.scale,
+                           w.shift, w.partial, N, C, (size_t)vol, relu, yout);
+    else
+        hipLaunchKernelGGL((bn_bwd_reduce_kernel<false, true>), rgrid, dim3(kThreads), 0, stream, x, grad_out, save_mean, save_invstd, w.scale,
+                           w.shift, w.partial, N, C, (size_t)vol, relu, yout);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 63) / 64), dim3(64), 0, stream, w.partial, kBnSplit, grad_gamma, grad_beta, w.sums, C);
+    const size_t cnt = (size_t)vol / (vec ? 4 : 1);
+    dim3 agrid((unsigned)std::min<size_t>((cnt + kThreads - 1) / kThreads, 64), (unsigned)C, (unsigned)N);
+    const float inv_m = (float)(1.0 / ((double)N * (double)vol));
+    if (vec)
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<true, true>), agrid, dim3(kThreads), 0, stream, x, grad_out, save_mean, save_invstd, w.scale,
+                           w.shift, w.sums, grad_x, C, (size_t)vol, inv_m, relu, yout, grad_residual);
+    else
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<false, true>), agrid, dim3(kThreads), 0, stream, x, grad_out, save_mean, save_invstd, w.scale,
+                           w.shift, w.sums, grad_x, C, (size_t)vol, inv_m, relu, yout, grad_residual);
+    MVS_LAUNCH_CHECK("bn3d_res_relu_bwd");
     return MVSDET_OK;
 }

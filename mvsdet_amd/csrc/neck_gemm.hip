@@ -17,10 +17,16 @@
 // them and writes two 16-byte units; fragments are conflict-free ds_read_b128.  Double-buffered LDS (16 KiB), the next step's
 // channel values fetched into registers before this step's MFMAs.
 //
+// Training (autograd) adds the two layers' input gradients as MODEs 2 and 3 of the same kernel (A = the transposed / reshaped
+// weight matrix, split per call) and their weight gradients as one NT GEMM that reduces over the voxels (neck_gemm_dw_bf16x3_kernel:
+// both operands activations, cut into bf16 pieces on the way into the LDS; split-K partial sums added in a fixed order).
+//
 // Row order for the transposed layer: m = 8 o + 4 p + 2 q + r, so that the 32x32 accumulator's rows (reg & 3) + 4 (lane >> 5)
 // + 8 (reg >> 2) give a lane four output channels (reg >> 2) at depth parity p = lane >> 5 with (q, r) = reg & 3: a float2
 // store {r = 0, 1} per (channel, q), contiguous along w across the lanes of a row.
 #include "common.h"
+
+#include <algorithm>
 
 namespace mvsdet {
 
@@ -63,7 +69,11 @@ __global__ __launch_bounds__(kThreads) void gemm_split_weight_kernel(const float
 }
 
 // MODE 0: pointwise stride-2 convolution (x (N,K,D,H,W), out (N,M,D/2,H/2,W/2), voxel = coarse voxel, gather at 2x);
-// MODE 1: transposed k2 s2 (x (N,K,D,H,W), rows m = 8 o + 4 p + 2 q + r, out (N,M/8,2D,2H,2W))
+// MODE 1: transposed k2 s2 (x (N,K,D,H,W), rows m = 8 o + 4 p + 2 q + r, out (N,M/8,2D,2H,2W));
+// MODE 2: input gradient of MODE 0 (x = grad_out (N,K,D/2,H/2,W/2), rows m = input channels, out (N,M,D,H,W) ACCUMULATED at the even
+//         positions only -- the other positions are not touched; bias unused);
+// MODE 3: input gradient of MODE 1 (x = grad_out (N,K/8,2D,2H,2W), k = 8 o + 4 p + 2 q + r gathered from each voxel's 2x2x2 cube,
+//         rows m = input channels, out (N,M,D,H,W); bias unused)
 template <int MODE>
 __global__ __launch_bounds__(kThreads) void neck_gemm_bf16x3_kernel(const float* __restrict__ x, const uint4* __restrict__ ws,
                                                                     const float* __restrict__ bias, float* __restrict__ out, int M,
@@ -71,10 +81,12 @@ __global__ __launch_bounds__(kThreads) void neck_gemm_bf16x3_kernel(const float*
     __shared__ uint4 s_b[2][2][4][kNgBN];   // [stage][piece][k-group of 8][voxel]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = blockIdx.z, m0 = blockIdx.y * kNgBM, v0 = blockIdx.x * kNgBN;
-    // the voxel grid the columns run over: MODE 0 the coarse output grid, MODE 1 the input grid
-    const int Dv = MODE == 0 ? D / 2 : D, Hv = MODE == 0 ? H / 2 : H, Wv = MODE == 0 ? W / 2 : W;
+    // the voxel grid the columns run over: MODEs 0 and 2 the coarse grid of D x H x W, MODEs 1 and 3 the grid D x H x W itself
+    const bool coarse = MODE == 0 || MODE == 2;
+    const int Dv = coarse ? D / 2 : D, Hv = coarse ? H / 2 : H, Wv = coarse ? W / 2 : W;
     const int V = Dv * Hv * Wv;
-    const size_t plane = (size_t)D * H * W;
+    // channel pitch of the B operand: MODE 0 / 1 x on D x H x W, MODE 2 grad_out on the coarse grid, MODE 3 grad_out on 2D x 2H x 2W
+    const size_t plane = MODE == 2 ? (size_t)V : MODE == 3 ? (size_t)8 * D * H * W : (size_t)D * H * W;
 
     // staging duty: voxel v0 + (tid & 63), channels 8 * (tid >> 6) .. + 7 of the step
     const int sv = v0 + (tid & 63), skq = tid >> 6;
@@ -84,15 +96,26 @@ __global__ __launch_bounds__(kThreads) void neck_gemm_bf16x3_kernel(const float*
         if (MODE == 0) {
             const int d = sv / (Hv * Wv), r = sv - d * Hv * Wv, h = r / Wv, w = r - h * Wv;
             soff = ((size_t)2 * d * H + 2 * h) * W + 2 * w;
+        } else if (MODE == 3) {   // corner (2d, 2h, 2w) of the voxel's cube in grad_out
+            const int d = sv / (Hv * Wv), r = sv - d * Hv * Wv, h = r / Wv, w = r - h * Wv;
+            soff = ((size_t)2 * d * 2 * H + 2 * h) * 2 * W + 2 * w;
         } else {
             soff = (size_t)sv;
         }
     }
-    const float* xs = x + ((size_t)n * K + 8 * skq) * plane + soff;
+    // MODE 3: the 8 k of a staging duty are the 8 taps of ONE grad_out channel o = 4 ks + skq
+    const float* xs = MODE == 3 ? x + ((size_t)n * (K / 8) + skq) * plane + soff : x + ((size_t)n * K + 8 * skq) * plane + soff;
     float f[8];
     auto fetch = [&](int ks) {
+        if (MODE == 3) {
+            const size_t W2 = 2 * (size_t)W, HW2 = 4 * (size_t)H * W;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = sv_ok ? xs[(size_t)(ks * kNgBK + j) * plane] : 0.0f;
+            for (int j = 0; j < 8; ++j)
+                f[j] = sv_ok ? xs[(size_t)(4 * ks) * plane + (j >> 2) * HW2 + ((j >> 1) & 1) * W2 + (j & 1)] : 0.0f;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[j] = sv_ok ? xs[(size_t)(ks * kNgBK + j) * plane] : 0.0f;
+        }
     };
     auto put = [&](int buf) {
         ng_u32x4 hi, mid;
@@ -145,7 +168,17 @@ __global__ __launch_bounds__(kThreads) void neck_gemm_bf16x3_kernel(const float*
     for (int c = 0; c < 2; ++c) {
         const int v = v0 + 32 * c + (lane & 31);
         if (v >= V) continue;
-        if (MODE == 0) {
+        if (MODE == 2) {   // += at the even positions of the (D, H, W) input gradient: one thread per element, no atomics
+            const int d = v / (Hv * Wv), r = v - d * Hv * Wv, h = r / Wv, w = r - h * Wv;
+            const size_t vol = (size_t)D * H * W;
+            float* o = out + ((size_t)n * M + m0 + 32 * wave) * vol + ((size_t)2 * d * H + 2 * h) * W + 2 * w;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) o[(size_t)((i & 3) + 8 * (i >> 2) + 4 * half) * vol] += acc[c][i];
+        } else if (MODE == 3) {
+            float* o = out + ((size_t)n * M + m0 + 32 * wave) * V + v;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) o[(size_t)((i & 3) + 8 * (i >> 2) + 4 * half) * V] = acc[c][i];
+        } else if (MODE == 0) {
             float* o = out + ((size_t)n * M + m0 + 32 * wave) * V + v;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
@@ -170,6 +203,120 @@ __global__ __launch_bounds__(kThreads) void neck_gemm_bf16x3_kernel(const float*
                 }
             }
         }
+    }
+}
+
+// Weight gradients of the two layers: D[m][j] = sum_k A[m][k] B[j][k] over the voxels k = (n, v) of the coarse grid D x H x W,
+// both operands activations (NCDHW fp32), cut into bf16 pieces on the way into the LDS:
+//   MODE 0 (1x1x1 stride 2):  m = o, A = grad_out (N,M,D,H,W);  j = c, B = x (N,J,2D,2H,2W) at (2d, 2h, 2w)      -> dW (Cout, Cin)
+//   MODE 1 (k2 s2 transposed): m = c, A = x (N,M,D,H,W);  j = 8 o + 4 p + 2 q + r, B = grad_out (N,J/8,2D,2H,2W) at (2d+p, 2h+q, 2w+r)
+//                                                                                                                -> dW (Cin, Cout, 2,2,2)
+// Block = 64 x 64 outputs, 4 waves of one 32 x 32 accumulator each; k in steps of 32 voxels, a thread stages 8 consecutive voxels of
+// one A row and of one B row (a staging pass for both operands shares the voxel coordinates).  LDS image [row][k-group of 8] per
+// piece, the k-group XOR-swizzled by (row >> 2) & 3 so that 16 consecutive rows of one k-group fill all 64 banks.  Split-K: block
+// (tile, s) sums the steps of chunk s and writes partial[s] (or the output itself with one split); neck_gemm_dw_reduce_kernel adds
+// the chunks in order 0, 1, ...: the same bits on every run.
+constexpr int kNdT = 64, kNdBK = 32;
+
+template <int MODE>
+__global__ __launch_bounds__(kThreads) void neck_gemm_dw_bf16x3_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                                       float* __restrict__ out, int M, int J, int N, int D, int H, int W,
+                                                                       int steps_per_split) {
+    __shared__ uint4 s_t[2][2][2][kNdT][4];   // [stage][operand A/B][piece][row][k-group (swizzled)]
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tiles_j = (J + kNdT - 1) / kNdT;
+    const int m0 = (blockIdx.x / tiles_j) * kNdT, j0 = (blockIdx.x % tiles_j) * kNdT, split = blockIdx.y;
+    const int V = D * H * W;
+    const long long K = (long long)N * V;
+    const long long kbeg = (long long)split * steps_per_split * kNdBK;
+    const long long kend = kbeg + (long long)steps_per_split * kNdBK < K ? kbeg + (long long)steps_per_split * kNdBK : K;
+    const int nsteps = kend > kbeg ? (int)((kend - kbeg + kNdBK - 1) / kNdBK) : 0;
+
+    // staging duty: row r of both tiles, voxels 8 kg .. 8 kg + 7 of the step
+    const int r = tid >> 2, kg = tid & 3, kgs = kg ^ ((r >> 2) & 3);
+    const int am = min(m0 + r, M - 1), bj = min(j0 + r, J - 1);
+    const bool a_ok = m0 + r < M, b_ok = j0 + r < J;
+    const int Jc = MODE == 1 ? J / 8 : J;                      // channels of the B tensor
+    const int bc = MODE == 1 ? bj >> 3 : bj;
+    const int H2 = 2 * H, W2 = 2 * W;
+    const size_t bplane = (size_t)8 * V;
+    const size_t btap = MODE == 1 ? ((size_t)((bj >> 2) & 1) * H2 + ((bj >> 1) & 1)) * W2 + (bj & 1) : 0;
+    float fa[8], fb[8];
+    auto fetch = [&](int step) {
+        long long k = kbeg + (long long)step * kNdBK + 8 * kg;
+        int n = 0, d = 0, h = 0, w = 0;
+        if (k < kend) {
+            n = (int)(k / V);
+            int v = (int)(k - (long long)n * V);
+            d = v / (H * W);
+            v -= d * H * W;
+            h = v / W;
+            w = v - h * W;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const bool ok = k + i < kend;
+            const size_t av = ((size_t)n * M + am) * V + ((size_t)d * H + h) * W + w;
+            const size_t bv = ((size_t)n * Jc + bc) * bplane + ((size_t)2 * d * H2 + 2 * h) * W2 + 2 * w + btap;
+            fa[i] = ok && a_ok ? a[av] : 0.0f;
+            fb[i] = ok && b_ok ? b[bv] : 0.0f;
+            if (++w == W) { w = 0; if (++h == H) { h = 0; if (++d == D) { d = 0; ++n; } } }
+        }
+    };
+    auto put = [&](int buf) {
+        ng_u32x4 hi, mid;
+        ng_cut8(fa, hi, mid);
+        s_t[buf][0][0][r][kgs] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+        s_t[buf][0][1][r][kgs] = make_uint4(mid[0], mid[1], mid[2], mid[3]);
+        ng_cut8(fb, hi, mid);
+        s_t[buf][1][0][r][kgs] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+        s_t[buf][1][1][r][kgs] = make_uint4(mid[0], mid[1], mid[2], mid[3]);
+    };
+
+    ng_f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
+    const int ar = 32 * (wave >> 1) + (lane & 31), br = 32 * (wave & 1) + (lane & 31);
+    if (nsteps > 0) {
+        fetch(0);
+        put(0);
+    }
+    __syncthreads();
+    for (int st = 0; st < nsteps; ++st) {
+        const int buf = st & 1;
+        if (st + 1 < nsteps) fetch(st + 1);               // in flight under the MFMAs below
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int q = 2 * s + (lane >> 5);
+            const ng_bf16x8 Ah = __builtin_bit_cast(ng_bf16x8, s_t[buf][0][0][ar][q ^ ((ar >> 2) & 3)]);
+            const ng_bf16x8 Am = __builtin_bit_cast(ng_bf16x8, s_t[buf][0][1][ar][q ^ ((ar >> 2) & 3)]);
+            const ng_bf16x8 Bh = __builtin_bit_cast(ng_bf16x8, s_t[buf][1][0][br][q ^ ((br >> 2) & 3)]);
+            const ng_bf16x8 Bm = __builtin_bit_cast(ng_bf16x8, s_t[buf][1][1][br][q ^ ((br >> 2) & 3)]);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh, acc, 0, 0, 0);   // small terms first
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, acc, 0, 0, 0);
+        }
+        if (st + 1 < nsteps) put(buf ^ 1);
+        __syncthreads();
+    }
+    // C/D map: column = lane & 31 (j), row = (i & 3) + 8 (i >> 2) + 4 (lane >> 5) (m)
+    const int j = j0 + 32 * (wave & 1) + (lane & 31);
+    if (j >= J) return;
+    float* o = out + (size_t)split * M * J;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const int m = m0 + 32 * (wave >> 1) + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
+        if (m < M) o[(size_t)m * J + j] = acc[i];
+    }
+}
+
+// out[i] = sum_s partial[s][i], s = 0, 1, ... in order
+__global__ __launch_bounds__(kThreads) void neck_gemm_dw_reduce_kernel(const float* __restrict__ partial, float* __restrict__ out, size_t count,
+                                                                       int nsplit) {
+    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < count; i += (size_t)gridDim.x * kThreads) {
+        float s = partial[i];
+        for (int p = 1; p < nsplit; ++p) s += partial[(size_t)p * count + i];
+        out[i] = s;
     }
 }
 
@@ -226,5 +373,84 @@ extern "C" int mvsdet_convT3d_k2_s2_bf16x3(const float* x, const void* wsplit, c
     hipLaunchKernelGGL(neck_gemm_bf16x3_kernel<1>, grid, dim3(kThreads), 0, (hipStream_t)stream, x, static_cast<const uint4*>(wsplit), bias,
                        out, 8 * Cout, Cin, D, H, W, relu);
     MVS_LAUNCH_CHECK("convT3d_k2_s2_bf16x3");
+    return MVSDET_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- training: gradients
+// Input gradients: wsplit = mvsdet_gemm_split_weight of the (Cin, Cout) matrix W^T (shortcut) or of the (Cin, 8 Cout) matrix
+// W.reshape(Cin, 8 Cout) (transposed layer, columns 8 o + 4 p + 2 q + r).
+extern "C" int mvsdet_conv3d_k1_s2_dx_bf16x3(const float* grad_out, const void* wsplit, float* grad_x, int N, int Cin, int Cout, int D,
+                                             int H, int W, mvsdet_stream_t stream) {
+    const float* one = grad_out;   // the shared check asks for a bias pointer: none here
+    if (int rc = neck_gemm_check("conv3d_k1_s2_dx_bf16x3", grad_out, wsplit, one, grad_x, N, Cout, Cin, D, H, W)) return rc;
+    MVS_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, "conv3d_k1_s2_dx_bf16x3: D, H, W must be even");
+    MVS_REQUIRE(((uintptr_t)grad_out & 3u) == 0 && ((uintptr_t)grad_x & 3u) == 0, "conv3d_k1_s2_dx_bf16x3: tensors must be 4-byte aligned");
+    const int V = (D / 2) * (H / 2) * (W / 2);
+    dim3 grid((unsigned)((V + kNgBN - 1) / kNgBN), (unsigned)(Cin / kNgBM), (unsigned)N);
+    hipLaunchKernelGGL(neck_gemm_bf16x3_kernel<2>, grid, dim3(kThreads), 0, (hipStream_t)stream, grad_out, static_cast<const uint4*>(wsplit),
+                       nullptr, grad_x, Cin, Cout, D, H, W, 0);
+    MVS_LAUNCH_CHECK("conv3d_k1_s2_dx_bf16x3");
+    return MVSDET_OK;
+}
+
+extern "C" int mvsdet_convT3d_k2_s2_dx_bf16x3(const float* grad_out, const void* wsplit, float* grad_x, int N, int Cin, int Cout, int D,
+                                              int H, int W, mvsdet_stream_t stream) {
+    MVS_REQUIRE(Cout > 0 && Cout <= INT32_MAX / 8, "convT3d_k2_s2_dx_bf16x3: bad Cout");
+    const float* one = grad_out;
+    if (int rc = neck_gemm_check("convT3d_k2_s2_dx_bf16x3", grad_out, wsplit, one, grad_x, N, 8 * Cout, Cin, D, H, W)) return rc;
+    MVS_REQUIRE((long long)8 * D * H * W < INT32_MAX / 8, "convT3d_k2_s2_dx_bf16x3: volume too large");
+    const int V = D * H * W;
+    dim3 grid((unsigned)((V + kNgBN - 1) / kNgBN), (unsigned)(Cin / kNgBM), (unsigned)N);
+    hipLaunchKernelGGL(neck_gemm_bf16x3_kernel<3>, grid, dim3(kThreads), 0, (hipStream_t)stream, grad_out, static_cast<const uint4*>(wsplit),
+                       nullptr, grad_x, Cin, 8 * Cout, D, H, W, 0);
+    MVS_LAUNCH_CHECK("convT3d_k2_s2_dx_bf16x3");
+    return MVSDET_OK;
+}
+
+extern "C" size_t mvsdet_neck_gemm_dw_partial_bytes(int Cin, int Cout, int transposed, int nsplit) {
+    if (Cin <= 0 || Cout <= 0 || nsplit <= 1 || Cout > INT32_MAX / 8) return 0;
+    return (size_t)nsplit * Cin * Cout * (transposed ? 8 : 1) * sizeof(float);
+}
+
+// Weight gradients.  transposed = 0: x (N,Cin,2D,2H,2W), grad_out (N,Cout,D,H,W) -> dW (Cout, Cin) of the 1x1x1 stride-2 layer;
+// transposed = 1: x (N,Cin,D,H,W), grad_out (N,Cout,2D,2H,2W) -> dW (Cin, Cout, 2, 2, 2) of ConvTranspose3d(k=2, s=2).  (D, H, W) is
+// the coarse grid either way.  nsplit > 1: chunks of the voxels summed into `partial` (mvsdet_neck_gemm_dw_partial_bytes) and added
+// in a fixed order.
+extern "C" int mvsdet_neck_gemm_dw_bf16x3(const float* x, const float* grad_out, float* dw, float* partial, size_t partial_bytes, int nsplit,
+                                          int transposed, int N, int Cin, int Cout, int D, int H, int W, mvsdet_stream_t stream) {
+    MVS_REQUIRE(x && grad_out && dw, "neck_gemm_dw_bf16x3: NULL pointer");
+    MVS_REQUIRE(transposed == 0 || transposed == 1, "neck_gemm_dw_bf16x3: transposed must be 0 or 1");
+    MVS_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, "neck_gemm_dw_bf16x3: bad shape N=%d Cin=%d Cout=%d D=%d H=%d W=%d",
+                N, Cin, Cout, D, H, W);
+    MVS_REQUIRE(Cout <= INT32_MAX / 8 && (long long)8 * D * H * W < INT32_MAX, "neck_gemm_dw_bf16x3: too large");
+    MVS_REQUIRE(nsplit >= 1 && nsplit <= 65535, "neck_gemm_dw_bf16x3: nsplit=%d outside [1,65535]", nsplit);
+    MVS_REQUIRE(((uintptr_t)x & 3u) == 0 && ((uintptr_t)grad_out & 3u) == 0 && ((uintptr_t)dw & 3u) == 0,
+                "neck_gemm_dw_bf16x3: tensors must be 4-byte aligned");
+    if (nsplit > 1) {
+        MVS_REQUIRE(partial && ((uintptr_t)partial & 3u) == 0, "neck_gemm_dw_bf16x3: nsplit=%d needs a partial buffer", nsplit);
+        const size_t need = mvsdet_neck_gemm_dw_partial_bytes(Cin, Cout, transposed, nsplit);
+        if (partial_bytes < need) {
+            set_error("neck_gemm_dw_bf16x3: partial buffer %zu B < %zu B", partial_bytes, need);
+            return MVSDET_ERR_WORKSPACE;
+        }
+    }
+    const int M = transposed ? Cin : Cout, J = transposed ? 8 * Cout : Cin;
+    const long long tiles = (long long)((M + kNdT - 1) / kNdT) * ((J + kNdT - 1) / kNdT);
+    MVS_REQUIRE(tiles < INT32_MAX, "neck_gemm_dw_bf16x3: too many tiles");
+    const long long K = (long long)N * D * H * W;
+    const long long steps = (K + kNdBK - 1) / kNdBK;
+    const int per = (int)((steps + nsplit - 1) / nsplit);
+    float* dst = nsplit > 1 ? partial : dw;
+    dim3 grid((unsigned)tiles, (unsigned)nsplit);
+    if (transposed)
+        hipLaunchKernelGGL(neck_gemm_dw_bf16x3_kernel<1>, grid, dim3(kThreads), 0, (hipStream_t)stream, x, grad_out, dst, M, J, N, D, H, W, per);
+    else
+        hipLaunchKernelGGL(neck_gemm_dw_bf16x3_kernel<0>, grid, dim3(kThreads), 0, (hipStream_t)stream, grad_out, x, dst, M, J, N, D, H, W, per);
+    if (nsplit > 1) {
+        const size_t count = (size_t)M * J;
+        hipLaunchKernelGGL(neck_gemm_dw_reduce_kernel, dim3((unsigned)std::min<size_t>((count + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0,
+                           (hipStream_t)stream, partial, dw, count, nsplit);
+    }
+    MVS_LAUNCH_CHECK("neck_gemm_dw_bf16x3");
     return MVSDET_OK;
 }

@@ -15,6 +15,11 @@ reference's.  Parameter names equal the reference's (`conv_center.weight`, `conv
 autograd, on a ROCm device, the three convolutions of a level run as ONE 3x3x3 MFMA convolution whose 64 output channels
 are [center | reg | cls | zeros] -- the input is read once, the neck's small grids take the split over input channels of
 csrc/costreg_conv0.hip -- followed by the slices, the exponential and the bias: 5 GFLOP per scene, 13 GFLOP padded.
+
+Under autograd with `autograd_route` "hip" (initial value from MVSDET_DETECTOR_AUTOGRAD, "aten" by default; neck.py), any CUDA fp32
+call runs the same fused convolution on the bf16x3 forward / input-gradient / weight-gradient kernels (`costreg._ConvK3S1`) on
+torch.cat(conv_center.weight, conv_reg.weight, conv_cls.weight, zeros to 64 rows), concatenated per call: autograd hands the weight
+gradient back to the three parameters, and the bias, `Scale` and exp stay elementwise ATen operations.
 """
 from __future__ import annotations
 
@@ -23,7 +28,7 @@ from typing import List, Sequence, Tuple
 import torch
 from torch import Tensor, nn
 
-from .neck import DerivedTensorsMixin, _await_made, _mark_made, fp32_under_autocast
+from .neck import DerivedTensorsMixin, _await_made, _check_route, _mark_made, autograd_route_from_env, fp32_under_autocast
 
 
 class Scale(nn.Module):
@@ -55,6 +60,7 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
         self.conv_cls = nn.Conv3d(n_channels, n_classes, 3, padding=1)
         self.scales = nn.ModuleList([Scale(1.0) for _ in range(n_levels)])
         self._fused = None   # (key, permuted fused weight); dropped on train()/eval() and load_state_dict
+        self.autograd_route = autograd_route_from_env()   # "aten" | "hip": the route under autograd (module docstring)
         self._init_derived_hooks()
 
     def init_weights(self):
@@ -77,6 +83,32 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
             _mark_made(self._fused[1])
         _await_made(self._fused[1])   # computed on another stream a moment ago: this stream waits for it (neck._PENDING)
         return self._fused[1]
+
+    def _hip_autograd(self, x: Tensor) -> bool:
+        return _check_route(self) == "hip" and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled()
+
+    def _fused_weight_autograd(self) -> Tensor:
+        """[center | reg | cls | zeros] as ONE (64 m, C, 3, 3, 3) weight in the autograd graph (made per call: the weights change
+        every step)."""
+        w = torch.cat([self.conv_center.weight, self.conv_reg.weight, self.conv_cls.weight], 0)
+        pad = (-w.shape[0]) % 64
+        if pad:
+            w = torch.cat([w, w.new_zeros((pad,) + tuple(w.shape[1:]))], 0)
+        return w
+
+    def _forward_single_hip(self, x: Tensor, scale: Scale, w: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+        from .costreg import _ConvK3S1
+        if x.shape[1] % 64:
+            raise ValueError(f"NerfDetHeadConvs (autograd_route='hip'): {x.shape[1]} input channels, a multiple of 64 needed")
+        y = _ConvK3S1.apply(x, w, True)
+        r, c = self.n_reg_outs, self.n_classes
+        center = y[:, :1]
+        cls = y[:, 1 + r:1 + r + c] + self.conv_cls.bias.view(1, -1, 1, 1, 1)
+        if self.arkit_head:
+            reg = torch.cat((torch.exp(scale(y[:, 1:7])), y[:, 7:1 + r]), dim=1)
+        else:
+            reg = torch.exp(scale(y[:, 1:1 + r]))
+        return center, reg, cls
 
     def _forward_single(self, x: Tensor, scale: Scale) -> Tuple[Tensor, Tensor, Tensor]:
         if x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and not self.training:
@@ -101,7 +133,12 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
     @fp32_under_autocast
     def forward(self, x: Sequence[Tensor]) -> Tuple[List[Tensor], List[Tensor], List[Tensor]]:
         """mmdet's multi_apply(self._forward_single, x, self.scales): a tuple of three per-level lists."""
-        res = [self._forward_single(xi, s) for xi, s in zip(x, self.scales)]
+        if any(self._hip_autograd(xi) for xi in x):
+            w = self._fused_weight_autograd()
+            res = [self._forward_single_hip(xi, s, w) if self._hip_autograd(xi) else self._forward_single(xi, s)
+                   for xi, s in zip(x, self.scales)]
+        else:
+            res = [self._forward_single(xi, s) for xi, s in zip(x, self.scales)]
         return tuple(map(list, zip(*res)))
 
     @staticmethod

@@ -11,7 +11,16 @@ fp32-MFMA kernels of csrc/costreg_conv0.hip) with eval-mode BatchNorm, ReLU and 
 epilogue; the small levels split their input channels until ~768 blocks run.  The 1x1x1 stride-2 shortcut and the
 kernel-2 stride-2 transposed convolutions are one GEMM each on csrc/neck_gemm.hip (a kernel-2 stride-2 transposed
 convolution is 8 independent single-tap classes; bias, ReLU and the 2x2x2 interleave in the epilogue; no rocBLAS call).
-Training, CPU tensors and other shapes take the framework's layers.
+Training, CPU tensors and other shapes take the framework's layers -- unless `autograd_route` is "hip" (below).
+
+Training on the HIP kernels (opt-in: `IndoorImVoxelNeck.autograd_route` / `NerfDetHeadConvs.autograd_route`, initial value from the
+environment variable MVSDET_DETECTOR_AUTOGRAD, "aten" by default).  With "hip", a neck in training mode on CUDA fp32 tensors runs every
+layer on our kernels, with autograd on or off (off: the running statistics still update): the 3x3x3 convolutions on the bf16x3
+forward / input-gradient / weight-gradient kernels of the cost network (`costreg._ConvK3S1`, `_ConvK3S2`; BatchNorm statistics from
+the convolution's epilogue where the grid is not split over input channels), the 1x1x1 stride-2 shortcut and the kernel-2 stride-2
+transposed layer on csrc/neck_gemm.hip (forward, input gradient, weight gradient), BatchNorm on csrc/costreg_bn.hip -- the ResModule's
+`relu(bn(conv1) + identity)` with the residual inside the ReLU.  A neck in eval mode with autograd on stays on the framework's layers
+(whatever the route), as does everything with "aten".  Shapes the HIP route cannot take raise instead of falling back.
 """
 from __future__ import annotations
 
@@ -58,7 +67,7 @@ class _ConvModule(nn.Module):
 
     def forward(self, x):
         x = self.bn(self.conv(x))
-        return F.relu(x, inplace=True) if self.with_act else x
+        return _relu(self, x) if self.with_act else x
 
 
 _DERIVED = ("_mvs_affine", "_fused", "_mvs_wsplit", "_mvs_wmat", "_mvs_sclbuf")   # tensors computed from parameters and kept on a module
@@ -261,7 +270,23 @@ class ResModule(nn.Module):
         x = self.conv1(self.conv0(x))
         if self.stride != 1:
             identity = self.downsample(identity)
-        return F.relu(x + identity, inplace=True)
+        return _relu(self, x + identity)
+
+    def _train_hip(self, x):
+        """The training step of the block on the HIP kernels (autograd_route "hip"): relu(bn1(conv1(relu(bn0(conv0 x)))) + identity),
+        identity = x or bn_ds(downsample x); in the stride-2 block conv0 and the shortcut are one autograd node (`_DownS2`) whose
+        input gradient is conv0's with the shortcut's accumulated into its even positions."""
+        c0, c1 = self.conv0, self.conv1
+        if self.stride == 1:
+            identity = x
+            y0, parts, pivot = _conv3_train(c0.conv, x, c0.bn)
+        else:
+            y0, yd = _DownS2.apply(x, c0.conv.weight, self.downsample.conv.weight)
+            identity = _bn_train(self.downsample.bn, yd, None)
+            parts = pivot = None
+        h = _bn_train(c0.bn, y0, c0, parts, pivot)
+        y1, parts, pivot = _conv3_train(c1.conv, h, c1.bn)
+        return _bn_train(c1.bn, y1, self, parts, pivot, residual=identity)
 
 
 class _UpBlock(nn.Sequential):
@@ -287,7 +312,13 @@ class _UpBlock(nn.Sequential):
             out = torch.empty((n, cout, 2 * d, 2 * h, 2 * w), dtype=x.dtype, device=x.device)
             torch.clamp_min(y.permute(0, 4, 5, 1, 6, 2, 7, 3), 0.0, out=out.view(n, cout, d, 2, h, 2, w, 2))
             return _conv_k3(out, self[3], self[4], True)
-        return super().forward(x)
+        return super().forward(x) if RELU_MASKS is None else _seq_hooked(self, x)
+
+    def _train_hip(self, x):
+        y = _ConvT2S2.apply(x, self[0].weight)
+        h = _bn_train(self[1], y, self[2])
+        y, parts, pivot = _conv3_train(self[3], h, self[4])
+        return _bn_train(self[4], y, self[5], parts, pivot)
 
 
 class _OutBlock(nn.Sequential):
@@ -299,7 +330,11 @@ class _OutBlock(nn.Sequential):
     def forward(self, x):
         if _hip_ok(x, self) and self[0].out_channels % 64 == 0:
             return _conv_k3(x, self[0], self[1], True)
-        return super().forward(x)
+        return super().forward(x) if RELU_MASKS is None else _seq_hooked(self, x)
+
+    def _train_hip(self, x):
+        y, parts, pivot = _conv3_train(self[0], x, self[1])
+        return _bn_train(self[1], y, self[2], parts, pivot)
 
 
 class IndoorImVoxelNeck(DerivedTensorsMixin, nn.Module):
@@ -308,6 +343,8 @@ class IndoorImVoxelNeck(DerivedTensorsMixin, nn.Module):
     def __init__(self, in_channels: int, out_channels: int, n_blocks: Sequence[int]):
         super().__init__()
         self._init_derived_hooks()
+        # training route: "aten" (the framework's layers) or "hip" (our kernels in training mode on CUDA fp32; module docstring)
+        self.autograd_route = autograd_route_from_env()
         self.n_scales = len(n_blocks)
         n_channels = in_channels
         for i, nb in enumerate(n_blocks):
@@ -326,17 +363,47 @@ class IndoorImVoxelNeck(DerivedTensorsMixin, nn.Module):
 
     @fp32_under_autocast
     def forward(self, x: Tensor) -> List[Tensor]:
+        hip = _check_route(self) == "hip" and self.training and x.is_cuda and x.dtype == torch.float32
+        if hip:
+            self._check_hip_train(x)
+
+        def run(m, t):
+            return m._train_hip(t) if hip else m(t)
+
         down_outs = []
         for i in range(self.n_scales):
-            x = getattr(self, f"down_layer_{i}")(x)
+            layer = getattr(self, f"down_layer_{i}")
+            if hip:
+                for blk in layer:
+                    x = blk._train_hip(x)
+            else:
+                x = layer(x)
             down_outs.append(x)
         outs = []
         for i in range(self.n_scales - 1, -1, -1):
             if i < self.n_scales - 1:
-                x = getattr(self, f"up_block_{i + 1}")(x)
+                x = run(getattr(self, f"up_block_{i + 1}"), x)
                 x = down_outs[i] + x
-            outs.append(getattr(self, f"out_block_{i}")(x))
+            outs.append(run(getattr(self, f"out_block_{i}"), x))
         return outs[::-1]
+
+    def _check_hip_train(self, x: Tensor) -> None:
+        """The HIP training route's shape limits, checked before anything runs (no silent fall-back to the framework)."""
+        from . import ops
+        if any(s % (1 << self.n_scales) for s in x.shape[2:]):
+            raise ValueError(f"IndoorImVoxelNeck (autograd_route='hip'): the grid {tuple(x.shape[2:])} must be divisible by "
+                             f"{1 << self.n_scales}")
+        for m in self.modules():
+            if isinstance(m, (nn.Conv3d, nn.ConvTranspose3d)) and (m.in_channels % 64 or m.out_channels % 64):
+                raise ValueError(f"IndoorImVoxelNeck (autograd_route='hip'): {m} needs channel counts that are multiples of 64")
+            if isinstance(m, ResModule) and m.stride != 1:
+                cin, cout = m.downsample.conv.in_channels, m.downsample.conv.out_channels
+                if m.stride != 2 or not (ops.gemm_layer_ok(cout, cin) and ops.gemm_layer_ok(cin, cout)):
+                    raise ValueError(f"IndoorImVoxelNeck (autograd_route='hip'): stride-2 shortcut {cin} -> {cout} not supported")
+            if isinstance(m, _UpBlock):
+                cin, cout = m[0].in_channels, m[0].out_channels
+                if not (ops.gemm_layer_ok(8 * cout, cin) and ops.gemm_layer_ok(cin, 8 * cout)):
+                    raise ValueError(f"IndoorImVoxelNeck (autograd_route='hip'): up block {cin} -> {cout} not supported")
 
     @staticmethod
     def flops(n: int, grid: Sequence[int], in_channels: int = 256, out_channels: int = 128, n_scales: int = 3) -> float:
@@ -353,3 +420,164 @@ class IndoorImVoxelNeck(DerivedTensorsMixin, nn.Module):
             if i > 0:
                 total += 2 * c * (c // 2) * v[i - 1] + 54 * (c // 2) ** 2 * v[i - 1]
         return total
+
+
+# ------------------------------------------------------------------------------------------ training on the HIP kernels
+AUTOGRAD_ROUTES = ("aten", "hip")
+
+
+def autograd_route_from_env() -> str:
+    """The initial `autograd_route` of the neck and the head: MVSDET_DETECTOR_AUTOGRAD, "aten" when unset."""
+    route = os.environ.get("MVSDET_DETECTOR_AUTOGRAD", "aten")
+    if route not in AUTOGRAD_ROUTES:
+        raise ValueError(f"MVSDET_DETECTOR_AUTOGRAD must be one of {AUTOGRAD_ROUTES}, got {route!r}")
+    return route
+
+
+def _check_route(module: nn.Module) -> str:
+    route = getattr(module, "autograd_route", "aten")
+    if route not in AUTOGRAD_ROUTES:
+        raise ValueError(f"{type(module).__name__}.autograd_route must be one of {AUTOGRAD_ROUTES}, got {route!r}")
+    return route
+
+
+# Test hook of the neck (tests/test_g14_neck_head_train.py), the neck's counterpart of costreg.RELU_MASKS: the ReLU DECISIONS of a
+# training pass recorded or imposed, on either route.  None (always, outside those tests) | ("record", {}) -- filled with {module: mask
+# of the ReLU's positive side} -- | ("apply", {module: bool mask}): the layer multiplies by the mask instead of taking the ReLU.  Keys:
+# the `_ConvModule` with an activation (conv0 of a ResModule), the ResModule (its output ReLU), and the nn.ReLU modules of the
+# up / out blocks (`up_block_i[2]`, `up_block_i[5]`, `out_block_i[2]`).
+RELU_MASKS = None
+
+
+def _relu(key: nn.Module, t: Tensor) -> Tensor:
+    hook = RELU_MASKS
+    if hook is None:
+        return F.relu(t, inplace=True)
+    if hook[0] == "record":
+        t = F.relu(t, inplace=True)
+        hook[1][key] = t.detach() > 0
+        return t
+    return t * hook[1][key].to(t.dtype)
+
+
+def _seq_hooked(seq: nn.Sequential, x: Tensor) -> Tensor:
+    """nn.Sequential.forward with its ReLU modules through the hook."""
+    for m in seq:
+        x = _relu(m, x) if isinstance(m, nn.ReLU) else m(x)
+    return x
+
+
+def update_running_stats(bn: nn.BatchNorm3d, x: Tensor, mean: Tensor, invstd: Tensor) -> None:
+    """The running statistics of a training-mode BatchNorm from the batch's mean and 1/sqrt(biased var + eps), as
+    torch.nn.BatchNorm3d updates them (momentum or the cumulative average, unbiased variance, num_batches_tracked)."""
+    if bn.track_running_stats and bn.running_mean is not None:
+        with torch.no_grad():
+            m = x.numel() // x.shape[1]
+            bn.num_batches_tracked += 1
+            mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+            var = (1.0 / (invstd * invstd) - bn.eps).clamp_min_(0.0) * (m / max(m - 1, 1))
+            bn.running_mean.mul_(1.0 - mom).add_(mean, alpha=mom)
+            bn.running_var.mul_(1.0 - mom).add_(var, alpha=mom)
+
+
+def _bn_train(bn: nn.BatchNorm3d, y: Tensor, key, parts=None, pivot=None, residual=None) -> Tensor:
+    """Training-mode BatchNorm [+ residual inside the ReLU] [+ ReLU] on csrc/costreg_bn.hip; key = the hook's key of the ReLU, None =
+    no activation (the shortcut's BatchNorm)."""
+    from . import ops
+    relu = key is not None
+    hook = RELU_MASKS if relu else None
+    act = relu and (hook is None or hook[0] == "record")
+    if residual is None:
+        out, mean, invstd = ops.bn3d_relu_train(y, bn.weight, bn.bias, bn.eps, act, None, parts, pivot)
+    else:
+        out, mean, invstd = ops.bn3d_res_relu_train(y, bn.weight, bn.bias, residual, bn.eps, act, parts, pivot)
+    if hook is not None:
+        if hook[0] == "record":
+            hook[1][key] = out.detach() > 0
+        else:
+            out = out * hook[1][key].to(out.dtype)
+    update_running_stats(bn, y, mean, invstd)
+    return out
+
+
+def _stats_form_ok(x: Tensor, conv: nn.Conv3d) -> bool:
+    """Whether the stride-1 bf16x3 convolution can hand its BatchNorm the statistics from its epilogue: only where its grid is not
+    split over the input channels (the 20x20x8 and 10x10x4 levels are; the epilogue form would run them unsplit), and with the
+    kernel form that has the epilogue (costreg.FUSED_BN_STATS, 16x16x32 MFMA)."""
+    from . import _lib
+    from .costreg import FUSED_BN_STATS, ops_option
+    n, _, d, h, w = x.shape
+    return (FUSED_BN_STATS and n * d * h * w > 1 and ops_option("conv_mfma16") and ops_option("conv_subpairs") != 2
+            and int(_lib.load().mvsdet_conv3d_k3_bf16x3_workspace_bytes(n, conv.in_channels, conv.out_channels, d, h, w)) == 0)
+
+
+def _conv3_train(conv: nn.Conv3d, x: Tensor, bn: nn.BatchNorm3d):
+    """A 3x3x3 convolution (stride 1 or 2, padding 1, no bias) under autograd on the bf16x3 kernels -> (y, parts, pivot): the
+    BatchNorm statistics' partial sums from the epilogue (around the running mean) where `_stats_form_ok`, else (y, None, None)."""
+    from .costreg import _ConvK3S1, _ConvK3S2
+    if conv.stride[0] == 2:
+        return _ConvK3S2.apply(x, conv.weight, True), None, None
+    if _stats_form_ok(x, conv):
+        pivot = bn.running_mean.detach() if bn.running_mean is not None else None
+        y, parts = _ConvK3S1.apply(x, conv.weight, True, True, pivot)
+        return y, parts, pivot
+    return _ConvK3S1.apply(x, conv.weight, True), None, None
+
+
+class _DownS2(torch.autograd.Function):
+    """conv0 (3x3x3 stride 2) and the 1x1x1 stride-2 shortcut of a down-sampling ResModule, which read the same input, as one node:
+    forward on `ops.conv3d_k3_s2_bf16x3` and `ops.conv3d_k1_s2_bf16x3`; the input gradient is conv0's (the transposed convolution of its
+    grad_out, `ops.convT3d_k3_s2_bf16x3`) with the shortcut's accumulated into its even positions (`ops.conv3d_k1_s2_dx_bf16x3`: no
+    full-resolution zero tensor, no extra pass); weight gradients `ops.conv3d_k3_dw(stride 2)` and `ops.neck_gemm_dw_bf16x3`.  The
+    split weights are cut per call (the weights change every step)."""
+
+    @staticmethod
+    def forward(ctx, x, w0, wds):
+        from . import ops
+        ctx.save_for_backward(x, w0, wds)
+        cout, cin = wds.shape[:2]
+        y0 = ops.conv3d_k3_s2_bf16x3(x, ops.split_conv_weight(w0, 1), None, None, False)
+        yd = ops.conv3d_k1_s2_bf16x3(x, ops.gemm_split_weight(wds.detach().reshape(cout, cin)), x.new_zeros(cout), cout, False)
+        return y0, yd
+
+    @staticmethod
+    def backward(ctx, gy0, gyd):
+        from . import ops
+        x, w0, wds = ctx.saved_tensors
+        cout, cin = wds.shape[:2]
+        gy0, gyd = gy0.contiguous(), gyd.contiguous()
+        gx = gw0 = gwd = None
+        if ctx.needs_input_grad[0]:
+            gx = ops.convT3d_k3_s2_bf16x3(gy0, ops.split_conv_weight(w0.detach(), 2), None, None, None, False)
+            ops.conv3d_k1_s2_dx_bf16x3(gyd, ops.gemm_split_weight(wds.detach().reshape(cout, cin).t().contiguous()), gx)
+        if ctx.needs_input_grad[1]:
+            gw0 = ops.conv3d_k3_dw(x, gy0, 0, 2, x.shape[-1] % 8 == 0)
+        if ctx.needs_input_grad[2]:
+            gwd = ops.neck_gemm_dw_bf16x3(x, gyd, False)
+        return gx, gw0, gwd
+
+
+class _ConvT2S2(torch.autograd.Function):
+    """ConvTranspose3d(kernel 2, stride 2, no bias) of an up block under autograd: forward `ops.convT3d_k2_s2_bf16x3` (zero bias, no
+    ReLU: the training BatchNorm follows), input gradient `ops.convT3d_k2_s2_dx_bf16x3`, weight gradient `ops.neck_gemm_dw_bf16x3`."""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        from . import ops
+        ctx.save_for_backward(x, w)
+        cin, cout = w.shape[:2]
+        wq = ops.gemm_split_weight(w.detach().permute(1, 2, 3, 4, 0).reshape(8 * cout, cin).contiguous())
+        return ops.convT3d_k2_s2_bf16x3(x, wq, x.new_zeros(cout), cout, False)
+
+    @staticmethod
+    def backward(ctx, gy):
+        from . import ops
+        x, w = ctx.saved_tensors
+        cin, cout = w.shape[:2]
+        gy = gy.contiguous()
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            gx = ops.convT3d_k2_s2_dx_bf16x3(gy, ops.gemm_split_weight(w.detach().reshape(cin, 8 * cout)), cin)
+        if ctx.needs_input_grad[1]:
+            gw = ops.neck_gemm_dw_bf16x3(x, gy, True)
+        return gx, gw

@@ -1030,6 +1030,100 @@ def convT3d_k2_s2_bf16x3(x: Tensor, wsplit: Tensor, bias: Tensor, cout: int, rel
     return out
 
 
+
+# ---- the two GEMM-shaped layers under autograd: input and weight gradients (csrc/neck_gemm.hip MODEs 2 / 3, neck_gemm_dw_bf16x3_kernel)
+@torch.library.custom_op(f"{_NS}::conv3d_k1_s2_dx_bf16x3", mutates_args=("grad_x",), device_types="cuda")
+def conv3d_k1_s2_dx_bf16x3(grad_out: Tensor, wsplit: Tensor, grad_x: Tensor) -> None:
+    """Input gradient of Conv3d(kernel 1, stride 2, no bias) ACCUMULATED into `grad_x` (N,Cin,D,H,W) at its even positions only:
+    grad_x[:, c, 2d, 2h, 2w] += sum_o W[o, c] grad_out[:, o, d, h, w].  `wsplit` = gemm_split_weight of the (Cin, Cout) matrix W^T.
+    The other positions of grad_x are left as they are (the caller's tensor holds the gradient of the block's other branch)."""
+    _req(grad_out, "grad_out", dim=5)
+    _req(grad_x, "grad_x", dim=5)
+    if not grad_x.is_contiguous():
+        raise ValueError("conv3d_k1_s2_dx_bf16x3: grad_x must be contiguous (it is accumulated in place)")
+    grad_out = grad_out.contiguous()
+    N, Cin, D, H, W = grad_x.shape
+    Cout = grad_out.shape[1]
+    if D % 2 or H % 2 or W % 2 or tuple(grad_out.shape) != (N, Cout, D // 2, H // 2, W // 2):
+        raise ValueError(f"conv3d_k1_s2_dx_bf16x3: grad_out {tuple(grad_out.shape)} does not match grad_x {tuple(grad_x.shape)} at stride 2")
+    _check_wsplit("conv3d_k1_s2_dx_bf16x3", wsplit, Cin, Cout, grad_out)
+    with torch.cuda.device(grad_out.device):
+        _lib.check(_lib.load().mvsdet_conv3d_k1_s2_dx_bf16x3(_lib.ptr(grad_out), _lib.ptr(wsplit), _lib.ptr(grad_x), N, Cin, Cout, D, H, W,
+                                                             _stream(grad_out)), "conv3d_k1_s2_dx_bf16x3")
+
+
+@conv3d_k1_s2_dx_bf16x3.register_fake
+def _(grad_out, wsplit, grad_x):
+    return None
+
+
+@torch.library.custom_op(f"{_NS}::convT3d_k2_s2_dx_bf16x3", mutates_args=(), device_types="cuda")
+def convT3d_k2_s2_dx_bf16x3(grad_out: Tensor, wsplit: Tensor, cin: int) -> Tensor:
+    """Input gradient of ConvTranspose3d(kernel 2, stride 2, no bias): grad_out (N,Cout,2D,2H,2W) -> (N,Cin,D,H,W),
+    grad_x[:, c, v] = sum_{o,p,q,r} W[c, o, p, q, r] grad_out[:, o, 2v + (p, q, r)].  `wsplit` = gemm_split_weight of W.reshape(Cin, 8 Cout)."""
+    _req(grad_out, "grad_out", dim=5)
+    grad_out = grad_out.contiguous()
+    N, Cout, D2, H2, W2 = grad_out.shape
+    if D2 % 2 or H2 % 2 or W2 % 2:
+        raise ValueError(f"convT3d_k2_s2_dx_bf16x3: grad_out {tuple(grad_out.shape)} must have even D, H, W")
+    _check_wsplit("convT3d_k2_s2_dx_bf16x3", wsplit, int(cin), 8 * Cout, grad_out)
+    gx = torch.empty((N, int(cin), D2 // 2, H2 // 2, W2 // 2), dtype=torch.float32, device=grad_out.device)
+    with torch.cuda.device(grad_out.device):
+        _lib.check(_lib.load().mvsdet_convT3d_k2_s2_dx_bf16x3(_lib.ptr(grad_out), _lib.ptr(wsplit), _lib.ptr(gx), N, int(cin), Cout, D2 // 2,
+                                                              H2 // 2, W2 // 2, _stream(grad_out)), "convT3d_k2_s2_dx_bf16x3")
+    return gx
+
+
+@convT3d_k2_s2_dx_bf16x3.register_fake
+def _(grad_out, wsplit, cin):
+    return grad_out.new_empty((grad_out.shape[0], int(cin)) + tuple(s // 2 for s in grad_out.shape[2:]))
+
+
+def neck_gemm_dw_splits(rows: int, cols: int, voxels: int) -> int:
+    """Split-K of the weight-gradient GEMM: enough 64 x 64 tiles x chunks for two blocks per CU of the 256, no chunk under one step."""
+    tiles = -(-rows // 64) * -(-cols // 64)
+    return max(1, min(-(-512 // tiles), -(-voxels // 32)))
+
+
+@torch.library.custom_op(f"{_NS}::neck_gemm_dw_bf16x3", mutates_args=(), device_types="cuda")
+def neck_gemm_dw_bf16x3(x: Tensor, grad_out: Tensor, transposed: bool, nsplit: int = 0) -> Tensor:
+    """Weight gradient of the neck's GEMM-shaped layers on the bf16 matrix cores (three-term split operands, deterministic):
+    transposed=False: Conv3d(kernel 1, stride 2), x (N,Cin,D,H,W), grad_out (N,Cout,D/2,H/2,W/2) -> (Cout, Cin, 1, 1, 1);
+    transposed=True: ConvTranspose3d(kernel 2, stride 2), x (N,Cin,D,H,W), grad_out (N,Cout,2D,2H,2W) -> (Cin, Cout, 2, 2, 2).
+    nsplit: voxel chunks summed separately and added in order (0 = automatic, `neck_gemm_dw_splits`)."""
+    _req(x, "x", dim=5)
+    _req(grad_out, "grad_out", dim=5)
+    x, grad_out = x.contiguous(), grad_out.contiguous()
+    N, Cin = x.shape[:2]
+    Cout = grad_out.shape[1]
+    if transposed:
+        ok = tuple(grad_out.shape) == (N, Cout) + tuple(2 * s for s in x.shape[2:])
+        coarse = tuple(x.shape[2:])
+    else:
+        ok = all(s % 2 == 0 for s in x.shape[2:]) and tuple(grad_out.shape) == (N, Cout) + tuple(s // 2 for s in x.shape[2:])
+        coarse = tuple(grad_out.shape[2:])
+    if not ok:
+        raise ValueError(f"neck_gemm_dw_bf16x3: grad_out {tuple(grad_out.shape)} does not match x {tuple(x.shape)} "
+                         f"({'transposed ' if transposed else ''}stride 2)")
+    D, H, W = coarse
+    rows, cols = (Cin, 8 * Cout) if transposed else (Cout, Cin)
+    if nsplit <= 0:
+        nsplit = neck_gemm_dw_splits(rows, cols, N * D * H * W)
+    lib = _lib.load()
+    dw = torch.empty((Cin, Cout, 2, 2, 2) if transposed else (Cout, Cin, 1, 1, 1), dtype=torch.float32, device=x.device)
+    pbytes = int(lib.mvsdet_neck_gemm_dw_partial_bytes(int(Cin), int(Cout), int(transposed), int(nsplit)))
+    partial = torch.empty((pbytes // 4,), dtype=torch.float32, device=x.device) if pbytes else None
+    with torch.cuda.device(x.device):
+        _lib.check(lib.mvsdet_neck_gemm_dw_bf16x3(_lib.ptr(x), _lib.ptr(grad_out), _lib.ptr(dw), _lib.ptr(partial), pbytes, int(nsplit),
+                                                  int(transposed), N, Cin, Cout, D, H, W, _stream(x)), "neck_gemm_dw_bf16x3")
+    return dw
+
+
+@neck_gemm_dw_bf16x3.register_fake
+def _(x, grad_out, transposed, nsplit=0):
+    cin, cout = x.shape[1], grad_out.shape[1]
+    return x.new_empty((cin, cout, 2, 2, 2) if transposed else (cout, cin, 1, 1, 1))
+
 def _check_affine(name, scale, shift, Cout):
     if (scale is None) != (shift is None):
         raise ValueError(f"{name}: scale and shift come together")
@@ -1680,6 +1774,103 @@ def _bn_bwd(ctx, g_out, g_mean, g_invstd):
 
 bn3d_relu_train.register_autograd(_bn_bwd, setup_context=_bn_setup)
 
+
+
+# ---- training BatchNorm with the residual INSIDE the ReLU (the neck's ResModule: relu(bn(conv1(h)) + identity))
+@torch.library.custom_op(f"{_NS}::bn3d_res_relu_train", mutates_args=(), device_types="cuda")
+def bn3d_res_relu_train(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], residual: Tensor, eps: float, relu: bool,
+                        parts: Optional[Tensor] = None, pivot: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """Training-mode BatchNorm3d on the batch statistics of x (N,C,D,H,W) with `residual` added before the activation:
+    out = [relu](bn(x) + residual) -> (out, batch mean, invstd).  Running statistics are the caller's to update, as for
+    `bn3d_relu_train`; parts / pivot: statistics from the producing convolution's epilogue, as there."""
+    _req(x, "x", dim=5)
+    _req(residual, "residual", dim=5)
+    if residual.shape != x.shape:
+        raise ValueError(f"bn3d_res_relu_train: residual {tuple(residual.shape)} != x {tuple(x.shape)}")
+    N, C = x.shape[:2]
+    vol = x[0, 0].numel()
+    for t, name in ((weight, "weight"), (bias, "bias")):
+        if t is not None:
+            _req(t, name, dim=1)
+            if t.numel() != C:
+                raise ValueError(f"bn3d_res_relu_train: {name} must have {C} elements")
+    if parts is not None:
+        if parts.dtype != torch.float64 or parts.dim() != 3 or parts.shape[0] != C or parts.shape[2] != 2 or parts.device != x.device:
+            raise ValueError(f"bn3d_res_relu_train: parts must be float64 ({C}, n, 2) on {x.device}, got {parts.dtype} {tuple(parts.shape)}")
+        parts = parts.contiguous()
+        if pivot is not None:
+            if pivot.dtype != torch.float32 or pivot.numel() != C or pivot.device != x.device:
+                raise ValueError(f"bn3d_res_relu_train: pivot must be {C} fp32 values on {x.device}")
+            pivot = pivot.contiguous()
+    elif pivot is not None:
+        raise ValueError("bn3d_res_relu_train: a pivot belongs to partial sums")
+    x, residual = x.contiguous(), residual.contiguous()
+    weight = None if weight is None else weight.contiguous()
+    bias = None if bias is None else bias.contiguous()
+    out = torch.empty_like(x)
+    mean = torch.empty(C, dtype=torch.float32, device=x.device)
+    invstd = torch.empty_like(mean)
+    lib = _lib.load()
+    wb = lib.mvsdet_bn3d_workspace_bytes(C)
+    ws = torch.empty(wb // 8, dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.mvsdet_bn3d_res_relu_train_fwd_f32(_lib.ptr(x), _lib.ptr(parts), int(parts.shape[1]) if parts is not None else 0,
+                                                          _lib.ptr(pivot), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(residual), None, None,
+                                                          _lib.ptr(out), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(ws), wb, N, C, vol, 0.0,
+                                                          float(eps), int(relu), _stream(x)), "bn3d_res_relu_train")
+    return out, mean, invstd
+
+
+@bn3d_res_relu_train.register_fake
+def _(x, weight, bias, residual, eps, relu, parts=None, pivot=None):
+    return torch.empty_like(x), x.new_empty(x.shape[1]), x.new_empty(x.shape[1])
+
+
+@torch.library.custom_op(f"{_NS}::bn3d_res_relu_backward", mutates_args=(), device_types="cuda")
+def bn3d_res_relu_backward(x: Tensor, out: Tensor, grad_out: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], save_mean: Tensor,
+                           save_invstd: Tensor, relu: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Backward of bn3d_res_relu_train -> (grad_x, grad_weight, grad_bias, grad_residual); the ReLU mask is `out > 0`."""
+    _req(x, "x", dim=5)
+    _req(out, "out", dim=5)
+    _req(grad_out, "grad_out", dim=5)
+    if grad_out.shape != x.shape or out.shape != x.shape:
+        raise ValueError("bn3d_res_relu_backward: out / grad_out do not match x")
+    N, C = x.shape[:2]
+    vol = x[0, 0].numel()
+    x, out, grad_out = x.contiguous(), out.contiguous(), grad_out.contiguous()
+    weight = None if weight is None else weight.contiguous()
+    bias = None if bias is None else bias.contiguous()
+    gx, gres = torch.empty_like(x), torch.empty_like(x)
+    gw = torch.empty(C, dtype=torch.float32, device=x.device)
+    gb = torch.empty_like(gw)
+    lib = _lib.load()
+    wb = lib.mvsdet_bn3d_workspace_bytes(C)
+    ws = torch.empty(wb // 8, dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.mvsdet_bn3d_res_relu_bwd_f32(_lib.ptr(x), _lib.ptr(out), _lib.ptr(grad_out), _lib.ptr(weight), _lib.ptr(bias),
+                                                    _lib.ptr(save_mean), _lib.ptr(save_invstd), _lib.ptr(gx), _lib.ptr(gw), _lib.ptr(gb),
+                                                    _lib.ptr(gres), _lib.ptr(ws), wb, N, C, vol, int(relu), _stream(x)), "bn3d_res_relu_backward")
+    return gx, gw, gb, gres
+
+
+@bn3d_res_relu_backward.register_fake
+def _(x, out, grad_out, weight, bias, save_mean, save_invstd, relu):
+    return torch.empty_like(x), x.new_empty(x.shape[1]), x.new_empty(x.shape[1]), torch.empty_like(x)
+
+
+def _bn_res_setup(ctx, inputs, output):
+    x, weight, bias, _residual, _eps, relu, _parts, _pivot = inputs
+    ctx.save_for_backward(x, output[0], weight, bias, output[1], output[2])
+    ctx.relu = relu
+
+
+def _bn_res_bwd(ctx, g_out, g_mean, g_invstd):
+    x, out, weight, bias, mean, invstd = ctx.saved_tensors
+    gx, gw, gb, gres = bn3d_res_relu_backward(x, out, g_out.contiguous(), weight, bias, mean, invstd, ctx.relu)
+    return gx, (gw if weight is not None else None), (gb if bias is not None else None), gres, None, None, None, None
+
+
+bn3d_res_relu_train.register_autograd(_bn_res_bwd, setup_context=_bn_res_setup)
 
 # ------------------------------------------------------------------------------------------- --amp (tools/train.py:24-28)
 # Under torch.autocast the 2-D backbone hands out float16 / bfloat16 maps.  The hot path computes in float32 -- the rule torch's own
