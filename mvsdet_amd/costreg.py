@@ -18,181 +18,19 @@ on the GPU it, not the plane sweep, is what a scene costs.
 from __future__ import annotations
 
 import os
+import sys
 import weakref
-from typing import Optional
 
 import torch
 from torch import nn
 
-from .neck import DerivedTensorsMixin, _bn_affine, fp32_under_autocast, update_running_stats
+from . import layers, ops
+from .layers import ConvK3S1, ConvK3S2, ConvT3S2, DerivedTensorsMixin, bn_affine, bn_train, fp32_under_autocast
 from .scratch import EventPool
 
-
-class _ConvK3S1(torch.autograd.Function):
-    """Conv3d(kernel 3, stride 1, padding 1, no bias) with all three passes on the fp32 matrix cores: forward and input
-    gradient through `ops.conv3d_k3_mfma` (the input gradient is the same convolution of grad_out with the weights
-    transposed and flipped), weight gradient through `ops.conv3d_k3_dw`.  MIOpen needs 34 + 42 + 360 ms for conv0 at the
-    reference-true shape, these kernels 15 + 15 + 22 ms."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bf16x3=False, stats=False, pivot=None):
-        """stats (bf16x3 only): also return the per-channel partial sums of the output and of its squares from the kernel's
-        epilogue (`ops.conv3d_k3_bf16x3_stats`, sums of value - pivot_c), for the training-mode BatchNorm behind the layer."""
-        from . import ops
-        ctx.save_for_backward(x, weight)
-        ctx.bf16x3 = bool(bf16x3)
-        if ctx.bf16x3 and stats:
-            y, parts = ops.conv3d_k3_bf16x3_stats(x, ops.split_conv_weight(weight), pivot)
-            ctx.mark_non_differentiable(parts)
-            return y, parts
-        if ctx.bf16x3:   # forward and input gradient on the bf16 matrix cores, three-term split (csrc/costreg_bf16.hip)
-            return ops.conv3d_k3_bf16x3(x, ops.split_conv_weight(weight), None, None, False)
-        return ops.conv3d_k3_mfma(x, ops.permute_conv_weight(weight), None, None, False)
-
-    @staticmethod
-    def backward(ctx, gy, gparts=None):
-        from . import ops
-        x, weight = ctx.saved_tensors
-        gy = gy.contiguous()
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            wflip = weight.detach().transpose(0, 1).flip(2, 3, 4).contiguous()      # (Cin, Cout, 3,3,3)
-            if ctx.bf16x3 and wflip.shape[0] % 64 == 0:
-                src = gy
-                if wflip.shape[0] >= 256:
-                    # four or more blocks of output channels per tile would each cut the same grad_out values into bf16 pieces:
-                    # one packing pass and the DMA-fed form instead (conv0: 4.78 -> 4.65 ms, the same bits).  The SCL copy
-                    # (larger than grad_out itself) lives for this one convolution: it comes from the caching allocator and goes
-                    # back to it when `src` dies below -- the packing kernel writes the zero border itself, nothing is kept
-                    src = ops.scl_pack(gy)
-                gx = ops.conv3d_k3_bf16x3(src, ops.split_conv_weight(wflip), None, None, False)
-                del src
-            else:
-                gx = ops.conv3d_k3_mfma(gy, ops.permute_conv_weight(wflip), None, None, False)
-        if ctx.needs_input_grad[1]:   # bf16x3: csrc/costreg_dw_bf16.hip (rows read as float4)
-            gw = ops.conv3d_k3_dw(x, gy, 0, 1, ctx.bf16x3 and x.shape[-1] % 4 == 0)
-        return gx, gw, None, None, None
-
-
-class _ConvK3S2(torch.autograd.Function):
-    """Conv3d(kernel 3, stride 2, padding 1, no bias) of conv1 / conv3 (mvsnet.py:77,80) under autograd: forward on
-    `ops.conv3d_k3_mfma(stride=2)`; the input gradient is the transposed convolution of grad_out with the same weight
-    (`ops.convT3d_k3_s2_mfma`: the (Cout,Cin,3,3,3) tensor read as a ConvTranspose3d weight), the weight gradient
-    `ops.conv3d_k3_dw(stride=2)`.  D, H, W even (the network asks for multiples of 4)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bf16x3=False, split_skip=False):
-        """split_skip: also return x itself as a second output, for the skip connection that reads it (mvsnet.py:109-111).  The
-        input then has this one consumer, both gradients arrive here together, and the skip's is added in the epilogue of the
-        input-gradient kernel instead of by a pass of autograd's own over the full-resolution tensor."""
-        from . import ops
-        ctx.save_for_backward(x, weight)
-        ctx.bf16x3 = bool(bf16x3)
-        ctx.set_materialize_grads(False)
-        if ctx.bf16x3:
-            y = ops.conv3d_k3_s2_bf16x3(x, ops.split_conv_weight(weight, 1), None, None, False)
-        else:
-            y = ops.conv3d_k3_mfma(x, ops.permute_conv_weight(weight), None, None, False, 2)
-        return (y, x.view_as(x)) if split_skip else y
-
-    @staticmethod
-    def backward(ctx, gy, gskip=None):
-        from . import ops
-        x, weight = ctx.saved_tensors
-        gx = gw = None
-        if gy is None:   # only the skip branch reached the loss
-            return gskip, None, None, None
-        gy = gy.contiguous()
-        if ctx.needs_input_grad[0]:
-            res = None if gskip is None else gskip.contiguous()
-            if ctx.bf16x3 and weight.shape[1] % 64 == 0:   # the (Cout,Cin,3,3,3) tensor read as a ConvTranspose3d weight
-                gx = ops.convT3d_k3_s2_bf16x3(gy, ops.split_conv_weight(weight.detach(), 2), None, None, res, False)
-            else:
-                gx = ops.convT3d_k3_s2_mfma(gy, ops.permute_convT_weight(weight.detach()), None, None, res, False)
-        if ctx.needs_input_grad[1]:
-            gw = ops.conv3d_k3_dw(x, gy, 0, 2, ctx.bf16x3 and x.shape[-1] % 8 == 0)
-        return gx, gw, None, None
-
-
-class _ConvT3S2(torch.autograd.Function):
-    """ConvTranspose3d(kernel 3, stride 2, padding 1, output_padding 1, no bias) of conv9 / conv11 (mvsnet.py:92-100) under
-    autograd, the mirror image of `_ConvK3S2`: forward on `ops.convT3d_k3_s2_mfma`, input gradient = the stride-2
-    convolution of grad_out with the (Cin,Cout,3,3,3) weight read as a Conv3d weight, weight gradient = the stride-2
-    weight-gradient kernel with the two tensors exchanged."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bf16x3=False, stats=False, pivot=None):
-        """stats (bf16x3 only): also return the partial sums of the output's BatchNorm statistics from the kernel's epilogue
-        (`ops.convT3d_k3_s2_bf16x3_stats`); an empty tensor where the shape has no such form."""
-        from . import ops
-        ctx.save_for_backward(x, weight)
-        ctx.bf16x3 = bool(bf16x3)
-        if ctx.bf16x3 and stats:
-            got = ops.convT3d_k3_s2_bf16x3_stats(x, ops.split_conv_weight(weight, 2), pivot)
-            if got is None:
-                y, parts = ops.convT3d_k3_s2_bf16x3(x, ops.split_conv_weight(weight, 2), None, None, None, False), x.new_empty(0, dtype=torch.float64)
-            else:
-                y, parts = got
-            ctx.mark_non_differentiable(parts)
-            return y, parts
-        if ctx.bf16x3:
-            return ops.convT3d_k3_s2_bf16x3(x, ops.split_conv_weight(weight, 2), None, None, None, False)
-        return ops.convT3d_k3_s2_mfma(x, ops.permute_convT_weight(weight), None, None, None, False)
-
-    @staticmethod
-    def backward(ctx, gy, gparts=None):
-        from . import ops
-        x, weight = ctx.saved_tensors
-        gy = gy.contiguous()
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            if ctx.bf16x3 and weight.shape[0] % 64 == 0:   # the (Cin,Cout,3,3,3) tensor read as a Conv3d weight
-                gx = ops.conv3d_k3_s2_bf16x3(gy, ops.split_conv_weight(weight.detach(), 1), None, None, False)
-            else:
-                gx = ops.conv3d_k3_mfma(gy, ops.permute_conv_weight(weight.detach()), None, None, False, 2)
-        if ctx.needs_input_grad[1]:
-            gw = ops.conv3d_k3_dw(gy, x, 0, 2, ctx.bf16x3 and gy.shape[-1] % 8 == 0)
-        return gx, gw, None, None, None
-
-
-# Test hook (tests/test_gpu_parity.py, tests/test_f3_goldens.py G12c): the ReLU DECISIONS of a training pass recorded, or imposed.
-# None (always, outside those tests) | ("record", {}) -- filled with {BatchNorm module: mask of relu's positive side} -- |
-# ("apply", {BatchNorm module: bool mask}): the layer computes bn(x) * mask (+ residual) instead of relu(bn(x)) (+ residual).
-# With the decisions of ONE pass imposed on two routes (or the reference's on ours) no activation can fall on the other side
-# of zero, and gradients can be compared element-wise instead of by direction.
-RELU_MASKS = None
-
-
-def _bn_relu_train(bn: nn.BatchNorm3d, x: torch.Tensor, residual: Optional[torch.Tensor] = None,
-                   parts: Optional[torch.Tensor] = None, pivot: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """relu(bn(x)) with batch statistics (module.py:26-37; mvsnet.py:92-100) on the streaming kernels of
-    csrc/costreg_bn.hip -- two passes over x forward, ReLU in the second, the mask recomputed going backward -- and the
-    running statistics updated the way torch.nn.BatchNorm3d does (momentum, unbiased variance, num_batches_tracked)."""
-    from . import ops
-    hook = RELU_MASKS
-    # residual: added after the ReLU; parts: the statistics' partial sums from the convolution's epilogue (no pass over x for them)
-    if hook is None:
-        out, mean, invstd = ops.bn3d_relu_train(x, bn.weight, bn.bias, bn.eps, True, residual, parts, pivot)
-    elif hook[0] == "record":
-        out, mean, invstd = ops.bn3d_relu_train(x, bn.weight, bn.bias, bn.eps, True, None, parts, pivot)
-        hook[1][bn] = out.detach() > 0
-        out = out if residual is None else out + residual
-    else:
-        out, mean, invstd = ops.bn3d_relu_train(x, bn.weight, bn.bias, bn.eps, False, None, parts, pivot)
-        out = out * hook[1][bn].to(out.dtype)
-        out = out if residual is None else out + residual
-    update_running_stats(bn, x, mean, invstd)
-    return out
-
-
-# training: the statistics of a BatchNorm behind a stride-1 bf16x3 convolution come from that convolution's epilogue (partial sums
-# per block, finished in a fixed order) instead of a pass of their own over the tensor; MVSDET_FUSED_BN_STATS=0: the separate pass
-FUSED_BN_STATS = os.environ.get("MVSDET_FUSED_BN_STATS", "1") != "0"
-
-
-def ops_option(name: str) -> int:
-    from . import ops
-    return int(ops.get_option(name))
+# the names of this module's earlier layout, for code written against them
+sys.modules[__name__].__class__ = layers.ForwardedToggles   # costreg.RELU_MASKS / FUSED_BN_STATS set the ones in `layers`
+_ConvK3S1, _ConvK3S2, _ConvT3S2 = ConvK3S1, ConvK3S2, ConvT3S2
 
 
 def _bn_hip_ok(bn: nn.BatchNorm3d, x: torch.Tensor) -> bool:
@@ -210,14 +48,12 @@ class _HeadConv(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, bf16x3=False):
-        from . import ops
         ctx.save_for_backward(x, weight)
         ctx.bf16x3 = bool(bf16x3)   # the weight gradient on the bf16 matrix cores (three-term split operands)
         return ops.conv3d_k3_cout2(x, weight, bias)
 
     @staticmethod
     def backward(ctx, gy):
-        from . import ops
         x, weight = ctx.saved_tensors
         gx, gw = ops.conv3d_k3_cout2_backward(x, weight.detach(), gy.contiguous(), 32, ctx.bf16x3)
         gb = gy.sum(dim=(0, 2, 3, 4)) if ctx.needs_input_grad[2] else None
@@ -296,7 +132,6 @@ class CostRegNet3DGS(DerivedTensorsMixin, nn.Module):
         """The SCL / PSCL buffer a layer of the chain writes: allocated and zeroed once per (layer, shape, device) -- the kernels
         write interior voxels only, the zero border stays -- and refilled on every call.  Taken from the module's pool for the
         duration of one `_forward_chain` (`leases` collects what that call must hand back)."""
-        from . import ops
         make = ops.scl_empty if kind == "scl" else ops.pscl_empty
         lease = self._scl.acquire((name, kind, tuple(shape), str(dev)), lambda: make(shape, dev), lambda b: (b.data,), dev)
         leases.append(lease)
@@ -306,7 +141,6 @@ class CostRegNet3DGS(DerivedTensorsMixin, nn.Module):
         """mvsnet.py:104-112 with the layer-to-layer forms of include/mvsdet_hip.h: conv0 -(fp32 skip, PSCL)-> conv1 -(SCL)->
         conv2 -(fp32 skip, PSCL)-> conv3 -(SCL)-> conv4 -(SCL)-> conv9 -(SCL)-> conv11 -(fp32)-> [+ conv0] prob.  Same values as the
         fp32-handover route bit for bit (a producer cuts exactly the pieces the consumer would have cut)."""
-        from . import ops
         n, _, d, h, w = x.shape
         dev = x.device
         b = self.conv0.conv.out_channels
@@ -318,7 +152,7 @@ class CostRegNet3DGS(DerivedTensorsMixin, nn.Module):
         wsplit = dict(zip((id(m) for m, _ in layers), ops.split_conv_weights([(m.weight, o) for m, o in layers])))
 
         def cbr(layer, inp, order, outputs, name, oshape):
-            sc, sh = _bn_affine(layer.bn)
+            sc, sh = bn_affine(layer.bn)
             wq = wsplit[id(layer.conv)]
             kw = {}
             if "scl" in outputs:
@@ -329,12 +163,12 @@ class CostRegNet3DGS(DerivedTensorsMixin, nn.Module):
             return fn(inp, wq, sc, sh, True, outputs=outputs, **kw)
 
         def up(seq, inp, skip, outputs, name, oshape):
-            sc, sh = _bn_affine(seq[1])
+            sc, sh = bn_affine(seq[1])
             kw = {"scl_out": self._buf(leases, name, "scl", oshape, dev)} if "scl" in outputs else {}
             return ops.convT3d_k3_s2_bf16x3(inp, wsplit[id(seq[0])], sc, sh, skip, True, outputs=outputs, **kw)
 
         if self.conv0_precision == "fp16mx" and ops.conv3d_k3_fp16mx_ok(x):   # else bf16x3: a view beyond the kernel's 32-bit offsets
-            sc0, sh0 = _bn_affine(self.conv0.bn)
+            sc0, sh0 = bn_affine(self.conv0.bn)
             full, full_p = ops.conv3d_k3_fp16mx(x, ops.split_conv_weight_mx(self.conv0.conv.weight), sc0, sh0, True, outputs=("f32", "pscl"),
                                                 pscl_out=self._buf(leases, "conv0", "pscl", (n, b, d, h, w), dev))
         else:
@@ -388,7 +222,7 @@ class CostRegNet3DGS(DerivedTensorsMixin, nn.Module):
                 parts[i].record_stream(cur)            # allocated under a side stream, read by the concatenation on this one
             return torch.cat(parts, 0)
         full = self._cbr(self.conv0, x)                           # (N, 64, D, H, W)
-        # the stride-2 layers hand their input back as the skip tensor (`_ConvK3S2`: its gradient joins the input gradient in
+        # the stride-2 layers hand their input back as the skip tensor (`ConvK3S2`: its gradient joins the input gradient in
         # that layer's own kernel)
         h1, full = self._cbr(self.conv1, full, split_skip=True)
         half = self._cbr(self.conv2, h1)                          # (N, 128, D/2, H/2, W/2)
@@ -406,8 +240,7 @@ class CostRegNet3DGS(DerivedTensorsMixin, nn.Module):
         conv, bn = layer.conv, layer.bn
         if (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and not self.training
                 and conv.out_channels % 64 == 0 and conv.stride in ((1, 1, 1), (2, 2, 2))):
-            from . import ops
-            scale, shift = _bn_affine(bn)
+            scale, shift = bn_affine(bn)
             if self.matrix_precision == "bf16x3":
                 # the bf16 matrix cores with three-term split operands (csrc/costreg_bf16.hip): conv0 4.8 ms instead of 15.2
                 # on the fp32 MFMA; the stride-2 layers as sums over the 8 parity classes of their input
@@ -428,20 +261,20 @@ class CostRegNet3DGS(DerivedTensorsMixin, nn.Module):
             skip = x
             parts = pivot = None
             if conv.stride == (1, 1, 1):
-                # the BatchNorm's statistics from the convolution's epilogue (16x16x32 form of the kernel: the default)
-                if (FUSED_BN_STATS and self.matrix_precision == "bf16x3" and _bn_hip_ok(bn, x) and x.shape[0] * x[0, 0].numel() > 1
-                        and ops_option("conv_mfma16") and ops_option("conv_subpairs") != 2):
+                # the BatchNorm's statistics from the convolution's epilogue (16x16x32 form of the kernel: the default), also on
+                # grids split over the input channels (the neck refuses those)
+                if self.matrix_precision == "bf16x3" and _bn_hip_ok(bn, x) and layers.fused_stats_ok(x):
                     # sums around the running mean (read by the convolution and by the BatchNorm's finishing kernel before the
                     # in-place update of the buffer that follows them on the same stream)
                     pivot = bn.running_mean.detach() if bn.running_mean is not None else None
-                    y, parts = _ConvK3S1.apply(x, conv.weight, True, True, pivot)
+                    y, parts = ConvK3S1.apply(x, conv.weight, True, True, pivot)
                 else:
-                    y = _ConvK3S1.apply(x, conv.weight, self.matrix_precision == "bf16x3")
+                    y = ConvK3S1.apply(x, conv.weight, self.matrix_precision == "bf16x3")
             elif split_skip:
-                y, skip = _ConvK3S2.apply(x, conv.weight, self.matrix_precision == "bf16x3", True)
+                y, skip = ConvK3S2.apply(x, conv.weight, self.matrix_precision == "bf16x3", True)
             else:
-                y = _ConvK3S2.apply(x, conv.weight, self.matrix_precision == "bf16x3")
-            y = _bn_relu_train(bn, y, None, parts, pivot) if _bn_hip_ok(bn, y) else torch.relu_(bn(y))
+                y = ConvK3S2.apply(x, conv.weight, self.matrix_precision == "bf16x3")
+            y = bn_train(bn, y, bn, parts, pivot) if _bn_hip_ok(bn, y) else torch.relu_(bn(y))
             return (y, skip) if split_skip else y
         return (layer(x), x) if split_skip else layer(x)
 
@@ -451,8 +284,7 @@ class CostRegNet3DGS(DerivedTensorsMixin, nn.Module):
         deconv, bn = seq[0], seq[1]
         if (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and not self.training
                 and deconv.out_channels % 64 == 0):
-            from . import ops
-            scale, shift = _bn_affine(bn)
+            scale, shift = bn_affine(bn)
             if self.matrix_precision == "bf16x3":
                 # 8 output parity classes = 8 small stride-1 convolutions over the coarse input (csrc/costreg_bf16.hip)
                 # the coarse input in split channel-last form: a buffer of this call's own (the packing kernel writes its border)
@@ -462,16 +294,16 @@ class CostRegNet3DGS(DerivedTensorsMixin, nn.Module):
             return ops.convT3d_k3_s2_mfma(x, wperm, scale, shift, skip, True)
         if (self.hip_backward and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled()
                 and deconv.out_channels % 64 == 0 and deconv.in_channels % 64 == 0):
-            if FUSED_BN_STATS and self.matrix_precision == "bf16x3" and _bn_hip_ok(bn, x):
+            if layers.FUSED_BN_STATS and self.matrix_precision == "bf16x3" and _bn_hip_ok(bn, x):
                 # the BatchNorm's statistics from the transposed kernel's epilogue, around the running mean
                 pivot = bn.running_mean.detach() if bn.running_mean is not None else None
-                y, parts = _ConvT3S2.apply(x, deconv.weight, True, True, pivot)
+                y, parts = ConvT3S2.apply(x, deconv.weight, True, True, pivot)
                 if parts.numel():
-                    return _bn_relu_train(bn, y, skip, parts, pivot)
-                return _bn_relu_train(bn, y, skip)
-            y = _ConvT3S2.apply(x, deconv.weight, self.matrix_precision == "bf16x3")
+                    return bn_train(bn, y, bn, parts, pivot, skip=skip)
+                return bn_train(bn, y, bn, skip=skip)
+            y = ConvT3S2.apply(x, deconv.weight, self.matrix_precision == "bf16x3")
             if _bn_hip_ok(bn, y):
-                return _bn_relu_train(bn, y, skip)   # the skip addition in the BatchNorm's second pass
+                return bn_train(bn, y, bn, skip=skip)   # the skip addition in the BatchNorm's second pass
             return skip + torch.relu_(bn(y))
         return skip + seq(x)
 
@@ -479,8 +311,7 @@ class CostRegNet3DGS(DerivedTensorsMixin, nn.Module):
         """mvsnet.py:112.  Two output channels make a poor GEMM (MIOpen: 8.2 ms at the reference-true shape); without
         autograd the streaming HIP kernel of csrc/costreg_head.hip does it in a fraction of that."""
         if full.is_cuda and full.dtype == torch.float32 and not torch.is_grad_enabled():
-            from . import ops
-            return ops.conv3d_k3_cout2(full, self.prob.weight.detach(), self.prob.bias.detach())
+                return ops.conv3d_k3_cout2(full, self.prob.weight.detach(), self.prob.bias.detach())
         if self.hip_backward and full.is_cuda and full.dtype == torch.float32 and torch.is_grad_enabled():
             return _HeadConv.apply(full, self.prob.weight, self.prob.bias, self.matrix_precision == "bf16x3")
         return self.prob(full)

@@ -17,7 +17,7 @@ are [center | reg | cls | zeros] -- the input is read once, the neck's small gri
 csrc/costreg_conv0.hip -- followed by the slices, the exponential and the bias: 5 GFLOP per scene, 13 GFLOP padded.
 
 Under autograd with `autograd_route` "hip" (initial value from MVSDET_DETECTOR_AUTOGRAD, "aten" by default; neck.py), any CUDA fp32
-call runs the same fused convolution on the bf16x3 forward / input-gradient / weight-gradient kernels (`costreg._ConvK3S1`) on
+call runs the same fused convolution on the bf16x3 forward / input-gradient / weight-gradient kernels (`layers.ConvK3S1`) on
 torch.cat(conv_center.weight, conv_reg.weight, conv_cls.weight, zeros to 64 rows), concatenated per call: autograd hands the weight
 gradient back to the three parameters, and the bias, `Scale` and exp stay elementwise ATen operations.
 """
@@ -28,7 +28,8 @@ from typing import List, Sequence, Tuple
 import torch
 from torch import Tensor, nn
 
-from .neck import DerivedTensorsMixin, _await_made, _check_route, _mark_made, autograd_route_from_env, fp32_under_autocast
+from . import ops
+from .layers import ConvK3S1, DerivedTensorsMixin, autograd_route_from_env, await_made, check_route, fp32_under_autocast, mark_made
 
 
 class Scale(nn.Module):
@@ -70,7 +71,6 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
         nn.init.constant_(self.conv_cls.bias, float(-torch.log(torch.tensor((1 - 0.01) / 0.01))))
 
     def _fused_weight(self) -> Tensor:
-        from . import ops
         ws = (self.conv_center.weight, self.conv_reg.weight, self.conv_cls.weight)
         key = tuple((w.data_ptr(), w._version, w.device) for w in ws)
         if self._fused is None or self._fused[0] != key or self._fused[2] != HEAD_BF16X3:
@@ -80,12 +80,12 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
                 w = torch.cat([w, w.new_zeros((pad,) + tuple(w.shape[1:]))], 0)
             # cut into bf16 pieces in the bf16x3 kernel's layout (csrc/costreg_bf16.hip; HEAD_BF16X3), or permuted for the fp32 MFMA
             self._fused = (key, ops.split_conv_weight(w) if HEAD_BF16X3 else ops.permute_conv_weight(w), HEAD_BF16X3)
-            _mark_made(self._fused[1])
-        _await_made(self._fused[1])   # computed on another stream a moment ago: this stream waits for it (neck._PENDING)
+            mark_made(self._fused[1])
+        await_made(self._fused[1])   # computed on another stream a moment ago: this stream waits for it (layers._PENDING)
         return self._fused[1]
 
     def _hip_autograd(self, x: Tensor) -> bool:
-        return _check_route(self) == "hip" and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled()
+        return check_route(self) == "hip" and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled()
 
     def _fused_weight_autograd(self) -> Tensor:
         """[center | reg | cls | zeros] as ONE (64 m, C, 3, 3, 3) weight in the autograd graph (made per call: the weights change
@@ -97,10 +97,9 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
         return w
 
     def _forward_single_hip(self, x: Tensor, scale: Scale, w: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
-        from .costreg import _ConvK3S1
         if x.shape[1] % 64:
             raise ValueError(f"NerfDetHeadConvs (autograd_route='hip'): {x.shape[1]} input channels, a multiple of 64 needed")
-        y = _ConvK3S1.apply(x, w, True)
+        y = ConvK3S1.apply(x, w, True)
         r, c = self.n_reg_outs, self.n_classes
         center = y[:, :1]
         cls = y[:, 1 + r:1 + r + c] + self.conv_cls.bias.view(1, -1, 1, 1, 1)
@@ -112,7 +111,6 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
 
     def _forward_single(self, x: Tensor, scale: Scale) -> Tuple[Tensor, Tensor, Tensor]:
         if x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and not self.training:
-            from . import ops
             if HEAD_BF16X3:
                 y = ops.conv3d_k3_bf16x3(x, self._fused_weight(), None, None, False)
             else:

@@ -16,7 +16,7 @@ Training, CPU tensors and other shapes take the framework's layers -- unless `au
 Training on the HIP kernels (opt-in: `IndoorImVoxelNeck.autograd_route` / `NerfDetHeadConvs.autograd_route`, initial value from the
 environment variable MVSDET_DETECTOR_AUTOGRAD, "aten" by default).  With "hip", a neck in training mode on CUDA fp32 tensors runs every
 layer on our kernels, with autograd on or off (off: the running statistics still update): the 3x3x3 convolutions on the bf16x3
-forward / input-gradient / weight-gradient kernels of the cost network (`costreg._ConvK3S1`, `_ConvK3S2`; BatchNorm statistics from
+forward / input-gradient / weight-gradient kernels of the cost network (`layers.ConvK3S1`, `ConvK3S2`; BatchNorm statistics from
 the convolution's epilogue where the grid is not split over input channels), the 1x1x1 stride-2 shortcut and the kernel-2 stride-2
 transposed layer on csrc/neck_gemm.hip (forward, input gradient, weight gradient), BatchNorm on csrc/costreg_bn.hip -- the ResModule's
 `relu(bn(conv1) + identity)` with the residual inside the ReLU.  A neck in eval mode with autograd on stays on the framework's layers
@@ -24,35 +24,21 @@ transposed layer on csrc/neck_gemm.hip (forward, input gradient, weight gradient
 """
 from __future__ import annotations
 
-import functools
 import os
-import weakref
-
+import sys
 from typing import List, Sequence
 
 import torch
 from torch import Tensor, nn
-from torch.nn import functional as F
 
-
-def fp32_under_autocast(forward):
-    """`--amp` (tools/train.py:24-28): under torch.autocast a module of this package still computes in float32 (bf16x3 on the
-    matrix cores is fp32-equivalent; the framework's layers it falls back to would otherwise run float16 convolutions beside
-    it): low-precision inputs are cast up and autocast is off for the call.  Outside autocast the call is untouched."""
-    def _up(v):
-        if isinstance(v, Tensor):
-            return v.float() if v.is_floating_point() and v.dtype != torch.float32 else v
-        if isinstance(v, (list, tuple)):
-            return type(v)(_up(t) for t in v)
-        return v
-
-    @functools.wraps(forward)
-    def wrapped(self, x, *args, **kwargs):
-        if torch.is_autocast_enabled("cuda"):
-            with torch.autocast("cuda", enabled=False):
-                return forward(self, _up(x), *args, **kwargs)
-        return forward(self, x, *args, **kwargs)
-    return wrapped
+from . import _lib, layers, ops
+from .layers import (ConvK3S1, ConvK3S2, DerivedTensorsMixin, autograd_route_from_env, await_made, bn_affine, bn_train,
+                     check_route, fp32_under_autocast, mark_made, relu_hooked)
+# the names of this module's earlier layout, for code written against them; modules pickled whole store their load hook as
+# neck._drop_after_load
+from .layers import _drop_after_load, drop_derived_tensors  # noqa: F401
+sys.modules[__name__].__class__ = layers.ForwardedToggles   # neck.RELU_MASKS sets the one in `layers`
+_bn_affine = bn_affine
 
 
 class _ConvModule(nn.Module):
@@ -67,82 +53,7 @@ class _ConvModule(nn.Module):
 
     def forward(self, x):
         x = self.bn(self.conv(x))
-        return _relu(self, x) if self.with_act else x
-
-
-_DERIVED = ("_mvs_affine", "_fused", "_mvs_wsplit", "_mvs_wmat", "_mvs_sclbuf")   # tensors computed from parameters and kept on a module
-
-
-def drop_derived_tensors(root: nn.Module) -> None:
-    """Forget every tensor this package derived from `root`'s parameters (BatchNorm affines, fused / permuted / split
-    weights).  The caches key on (data_ptr, _version), which an in-place update through `.data` does not bump (mmengine's
-    EMAHook swaps parameters that way) -- so they are also dropped on every train()/eval() switch and after
-    load_state_dict (`DerivedTensorsMixin`); call this by hand after any other out-of-band `.data` write."""
-    for m in root.modules():
-        for name in _DERIVED:
-            if m.__dict__.get(name) is not None:
-                m.__dict__[name] = None
-
-
-def _drop_after_load(module: nn.Module, incompatible_keys) -> None:
-    # module-level (not a lambda or a closure): the hook is stored on the module and must pickle with it
-    # (torch.save(model), mp.spawn)
-    drop_derived_tensors(module)
-
-
-class DerivedTensorsMixin:
-    """nn.Module mixin of the modules that own derived-tensor caches: mode switches and state-dict loads drop them."""
-
-    def _init_derived_hooks(self):
-        self.register_load_state_dict_post_hook(_drop_after_load)
-
-    def train(self, mode: bool = True):
-        drop_derived_tensors(self)
-        return super().train(mode)
-
-
-# Derived tensors are computed by whichever stream first needs them and kept on the module; a call on ANOTHER stream shortly
-# afterwards (the two halves of CostRegNet3DGS.view_streams; a detector moved to a side stream) must not read them before the
-# kernels that fill them ran.  Every derived tensor is therefore registered with the event recorded behind its computation, and every
-# use makes the using stream wait for it while it is pending.  Kept outside the modules (events do not pickle), by the tensor.
-_PENDING: dict = {}   # id(tensor) -> (weak reference to it, event); by identity: tensors compare element-wise
-
-
-def _mark_made(*tensors: Tensor) -> None:
-    ts = [t for t in tensors if isinstance(t, Tensor) and t.is_cuda]
-    if ts:
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(ts[0].device))
-        for t in ts:
-            _PENDING[id(t)] = (weakref.ref(t), ev)
-        if len(_PENDING) > 4096:   # entries of tensors that died before anyone asked again
-            for k in [k for k, (r, e) in _PENDING.items() if r() is None or e.query()]:
-                _PENDING.pop(k, None)
-
-
-def _await_made(*tensors: Tensor) -> None:
-    for t in tensors:
-        ent = _PENDING.get(id(t)) if isinstance(t, Tensor) else None
-        if ent is not None and ent[0]() is t:
-            if ent[1].query():
-                _PENDING.pop(id(t), None)
-            else:
-                torch.cuda.current_stream(t.device).wait_event(ent[1])
-
-
-def _bn_affine(bn: nn.BatchNorm3d):
-    """Eval-mode BatchNorm as a per-channel affine; kept on the module until one of its four tensors changes (five tiny
-    kernels per layer otherwise: a twentieth of the neck's time at one scene) or `drop_derived_tensors` runs."""
-    key = tuple((t.data_ptr(), t._version) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
-    cached = getattr(bn, "_mvs_affine", None)
-    if cached is None or cached[0] != key:
-        with torch.no_grad():
-            scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
-            cached = (key, scale, bn.bias - bn.running_mean * scale)
-        _mark_made(cached[1], cached[2])
-        bn._mvs_affine = cached
-    _await_made(cached[1], cached[2])
-    return cached[1], cached[2]
+        return relu_hooked(self, x) if self.with_act else x
 
 
 def _hip_ok(x: Tensor, module: nn.Module) -> bool:
@@ -167,7 +78,6 @@ def _split_weight(conv: nn.Module, order: int | None = None) -> Tensor:
     """The weight cut into bf16 pieces in the bf16x3 kernel's layout (tap order of the layer's stride; `order` 2 = a
     ConvTranspose3d weight), kept on the module (the neck's weights are 300 MB: not re-split per call) until the weight tensor
     changes or `drop_derived_tensors` runs."""
-    from . import ops
     w = conv.weight
     if order is None:
         order = 1 if conv.stride[0] == 2 else 0
@@ -178,9 +88,9 @@ def _split_weight(conv: nn.Module, order: int | None = None) -> Tensor:
     cached = conv.__dict__.get("_mvs_wsplit")
     if cached is None or cached[0] != key:
         cached = (key, ops.split_conv_weight(w, order=order))
-        _mark_made(cached[1])
+        mark_made(cached[1])
         conv.__dict__["_mvs_wsplit"] = cached
-    _await_made(cached[1])
+    await_made(cached[1])
     return cached[1]
 
 
@@ -198,7 +108,7 @@ def _gemm_weight(conv: nn.Module, bn: nn.BatchNorm3d, split: bool = False):
     key = (w.data_ptr(), w._version, w.device, bool(split)) + tuple((t.data_ptr(), t._version) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
     cached = conv.__dict__.get("_mvs_wmat")
     if cached is None or cached[0] != key:
-        scale, shift = _bn_affine(bn)
+        scale, shift = bn_affine(bn)
         with torch.no_grad():
             if isinstance(conv, nn.ConvTranspose3d):
                 cout = conv.out_channels
@@ -211,19 +121,17 @@ def _gemm_weight(conv: nn.Module, bn: nn.BatchNorm3d, split: bool = False):
                 wmat = (w.detach().reshape(conv.out_channels, -1) * scale[:, None]).contiguous()
                 bias = shift.contiguous() if split else shift.view(1, -1, 1).contiguous()
             if split:
-                from . import ops
                 wmat = ops.gemm_split_weight(wmat)
         cached = (key, wmat, bias)
-        _mark_made(wmat, bias)
+        mark_made(wmat, bias)
         conv.__dict__["_mvs_wmat"] = cached
-    _await_made(cached[1], cached[2])
+    await_made(cached[1], cached[2])
     return cached[1], cached[2]
 
 
 def _conv_k3(x: Tensor, conv: nn.Conv3d, bn: nn.BatchNorm3d, relu: bool, residual: Tensor | None = None) -> Tensor:
     """Conv3d(k=3, p=1, stride 1|2) + BN(eval) [+ residual] [+ ReLU] in one MFMA kernel."""
-    from . import ops
-    scale, shift = _bn_affine(bn)
+    scale, shift = bn_affine(bn)
     if conv.stride[0] == 1 and BF16X3_MIN_VOXELS and x[0, 0].numel() >= BF16X3_MIN_VOXELS and conv.out_channels % 64 == 0:
         src = x
         if PACK_INPUT_FROM_COUT and conv.out_channels >= PACK_INPUT_FROM_COUT and x[0, 0].numel() >= PACK_INPUT_MIN_VOXELS:
@@ -253,7 +161,6 @@ class ResModule(nn.Module):
             identity = x
             if self.stride != 1:   # 1x1x1 stride-2 convolution + BN: one GEMM on the sub-sampled volume
                 ds = self.downsample
-                from . import ops
                 if (GEMM_BF16X3 and self.stride == 2 and ops.gemm_layer_ok(ds.conv.out_channels, ds.conv.in_channels)
                         and not any(v % 2 for v in x.shape[2:])):
                     wq, bias = _gemm_weight(ds.conv, ds.bn, split=True)      # the sub-sampling is the kernel's gather
@@ -270,7 +177,7 @@ class ResModule(nn.Module):
         x = self.conv1(self.conv0(x))
         if self.stride != 1:
             identity = self.downsample(identity)
-        return _relu(self, x + identity)
+        return relu_hooked(self, x + identity)
 
     def _train_hip(self, x):
         """The training step of the block on the HIP kernels (autograd_route "hip"): relu(bn1(conv1(relu(bn0(conv0 x)))) + identity),
@@ -282,11 +189,11 @@ class ResModule(nn.Module):
             y0, parts, pivot = _conv3_train(c0.conv, x, c0.bn)
         else:
             y0, yd = _DownS2.apply(x, c0.conv.weight, self.downsample.conv.weight)
-            identity = _bn_train(self.downsample.bn, yd, None)
+            identity = bn_train(self.downsample.bn, yd, None)
             parts = pivot = None
-        h = _bn_train(c0.bn, y0, c0, parts, pivot)
+        h = bn_train(c0.bn, y0, c0, parts, pivot)
         y1, parts, pivot = _conv3_train(c1.conv, h, c1.bn)
-        return _bn_train(c1.bn, y1, self, parts, pivot, residual=identity)
+        return bn_train(c1.bn, y1, self, parts, pivot, residual=identity)
 
 
 class _UpBlock(nn.Sequential):
@@ -303,7 +210,6 @@ class _UpBlock(nn.Sequential):
             cout = deconv.out_channels
             # out[:, o, 2i+p, 2j+q, 2k+r] = sum_c x[:, c, i, j, k] * W[c, o, p, q, r]: one (8*Cout x Cin) GEMM with the BatchNorm's
             # shift as its bias; the ReLU writes the interleaved (N, Cout, 2D, 2H, 2W) tensor directly (one pass, no copy)
-            from . import ops
             if GEMM_BF16X3 and ops.gemm_layer_ok(8 * cout, cin):
                 wq, bias = _gemm_weight(deconv, bn, split=True)      # bias, ReLU and the 2x2x2 interleave in the GEMM's epilogue
                 return _conv_k3(ops.convT3d_k2_s2_bf16x3(x, wq, bias, cout, True), self[3], self[4], True)
@@ -312,13 +218,13 @@ class _UpBlock(nn.Sequential):
             out = torch.empty((n, cout, 2 * d, 2 * h, 2 * w), dtype=x.dtype, device=x.device)
             torch.clamp_min(y.permute(0, 4, 5, 1, 6, 2, 7, 3), 0.0, out=out.view(n, cout, d, 2, h, 2, w, 2))
             return _conv_k3(out, self[3], self[4], True)
-        return super().forward(x) if RELU_MASKS is None else _seq_hooked(self, x)
+        return super().forward(x) if layers.RELU_MASKS is None else _seq_hooked(self, x)
 
     def _train_hip(self, x):
         y = _ConvT2S2.apply(x, self[0].weight)
-        h = _bn_train(self[1], y, self[2])
+        h = bn_train(self[1], y, self[2])
         y, parts, pivot = _conv3_train(self[3], h, self[4])
-        return _bn_train(self[4], y, self[5], parts, pivot)
+        return bn_train(self[4], y, self[5], parts, pivot)
 
 
 class _OutBlock(nn.Sequential):
@@ -330,11 +236,11 @@ class _OutBlock(nn.Sequential):
     def forward(self, x):
         if _hip_ok(x, self) and self[0].out_channels % 64 == 0:
             return _conv_k3(x, self[0], self[1], True)
-        return super().forward(x) if RELU_MASKS is None else _seq_hooked(self, x)
+        return super().forward(x) if layers.RELU_MASKS is None else _seq_hooked(self, x)
 
     def _train_hip(self, x):
         y, parts, pivot = _conv3_train(self[0], x, self[1])
-        return _bn_train(self[1], y, self[2], parts, pivot)
+        return bn_train(self[1], y, self[2], parts, pivot)
 
 
 class IndoorImVoxelNeck(DerivedTensorsMixin, nn.Module):
@@ -363,7 +269,7 @@ class IndoorImVoxelNeck(DerivedTensorsMixin, nn.Module):
 
     @fp32_under_autocast
     def forward(self, x: Tensor) -> List[Tensor]:
-        hip = _check_route(self) == "hip" and self.training and x.is_cuda and x.dtype == torch.float32
+        hip = check_route(self) == "hip" and self.training and x.is_cuda and x.dtype == torch.float32
         if hip:
             self._check_hip_train(x)
 
@@ -389,7 +295,6 @@ class IndoorImVoxelNeck(DerivedTensorsMixin, nn.Module):
 
     def _check_hip_train(self, x: Tensor) -> None:
         """The HIP training route's shape limits, checked before anything runs (no silent fall-back to the framework)."""
-        from . import ops
         if any(s % (1 << self.n_scales) for s in x.shape[2:]):
             raise ValueError(f"IndoorImVoxelNeck (autograd_route='hip'): the grid {tuple(x.shape[2:])} must be divisible by "
                              f"{1 << self.n_scales}")
@@ -422,106 +327,27 @@ class IndoorImVoxelNeck(DerivedTensorsMixin, nn.Module):
         return total
 
 
-# ------------------------------------------------------------------------------------------ training on the HIP kernels
-AUTOGRAD_ROUTES = ("aten", "hip")
-
-
-def autograd_route_from_env() -> str:
-    """The initial `autograd_route` of the neck and the head: MVSDET_DETECTOR_AUTOGRAD, "aten" when unset."""
-    route = os.environ.get("MVSDET_DETECTOR_AUTOGRAD", "aten")
-    if route not in AUTOGRAD_ROUTES:
-        raise ValueError(f"MVSDET_DETECTOR_AUTOGRAD must be one of {AUTOGRAD_ROUTES}, got {route!r}")
-    return route
-
-
-def _check_route(module: nn.Module) -> str:
-    route = getattr(module, "autograd_route", "aten")
-    if route not in AUTOGRAD_ROUTES:
-        raise ValueError(f"{type(module).__name__}.autograd_route must be one of {AUTOGRAD_ROUTES}, got {route!r}")
-    return route
-
-
-# Test hook of the neck (tests/test_g14_neck_head_train.py), the neck's counterpart of costreg.RELU_MASKS: the ReLU DECISIONS of a
-# training pass recorded or imposed, on either route.  None (always, outside those tests) | ("record", {}) -- filled with {module: mask
-# of the ReLU's positive side} -- | ("apply", {module: bool mask}): the layer multiplies by the mask instead of taking the ReLU.  Keys:
-# the `_ConvModule` with an activation (conv0 of a ResModule), the ResModule (its output ReLU), and the nn.ReLU modules of the
-# up / out blocks (`up_block_i[2]`, `up_block_i[5]`, `out_block_i[2]`).
-RELU_MASKS = None
-
-
-def _relu(key: nn.Module, t: Tensor) -> Tensor:
-    hook = RELU_MASKS
-    if hook is None:
-        return F.relu(t, inplace=True)
-    if hook[0] == "record":
-        t = F.relu(t, inplace=True)
-        hook[1][key] = t.detach() > 0
-        return t
-    return t * hook[1][key].to(t.dtype)
-
-
 def _seq_hooked(seq: nn.Sequential, x: Tensor) -> Tensor:
     """nn.Sequential.forward with its ReLU modules through the hook."""
     for m in seq:
-        x = _relu(m, x) if isinstance(m, nn.ReLU) else m(x)
+        x = relu_hooked(m, x) if isinstance(m, nn.ReLU) else m(x)
     return x
 
 
-def update_running_stats(bn: nn.BatchNorm3d, x: Tensor, mean: Tensor, invstd: Tensor) -> None:
-    """The running statistics of a training-mode BatchNorm from the batch's mean and 1/sqrt(biased var + eps), as
-    torch.nn.BatchNorm3d updates them (momentum or the cumulative average, unbiased variance, num_batches_tracked)."""
-    if bn.track_running_stats and bn.running_mean is not None:
-        with torch.no_grad():
-            m = x.numel() // x.shape[1]
-            bn.num_batches_tracked += 1
-            mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
-            var = (1.0 / (invstd * invstd) - bn.eps).clamp_min_(0.0) * (m / max(m - 1, 1))
-            bn.running_mean.mul_(1.0 - mom).add_(mean, alpha=mom)
-            bn.running_var.mul_(1.0 - mom).add_(var, alpha=mom)
-
-
-def _bn_train(bn: nn.BatchNorm3d, y: Tensor, key, parts=None, pivot=None, residual=None) -> Tensor:
-    """Training-mode BatchNorm [+ residual inside the ReLU] [+ ReLU] on csrc/costreg_bn.hip; key = the hook's key of the ReLU, None =
-    no activation (the shortcut's BatchNorm)."""
-    from . import ops
-    relu = key is not None
-    hook = RELU_MASKS if relu else None
-    act = relu and (hook is None or hook[0] == "record")
-    if residual is None:
-        out, mean, invstd = ops.bn3d_relu_train(y, bn.weight, bn.bias, bn.eps, act, None, parts, pivot)
-    else:
-        out, mean, invstd = ops.bn3d_res_relu_train(y, bn.weight, bn.bias, residual, bn.eps, act, parts, pivot)
-    if hook is not None:
-        if hook[0] == "record":
-            hook[1][key] = out.detach() > 0
-        else:
-            out = out * hook[1][key].to(out.dtype)
-    update_running_stats(bn, y, mean, invstd)
-    return out
-
-
-def _stats_form_ok(x: Tensor, conv: nn.Conv3d) -> bool:
-    """Whether the stride-1 bf16x3 convolution can hand its BatchNorm the statistics from its epilogue: only where its grid is not
-    split over the input channels (the 20x20x8 and 10x10x4 levels are; the epilogue form would run them unsplit), and with the
-    kernel form that has the epilogue (costreg.FUSED_BN_STATS, 16x16x32 MFMA)."""
-    from . import _lib
-    from .costreg import FUSED_BN_STATS, ops_option
-    n, _, d, h, w = x.shape
-    return (FUSED_BN_STATS and n * d * h * w > 1 and ops_option("conv_mfma16") and ops_option("conv_subpairs") != 2
-            and int(_lib.load().mvsdet_conv3d_k3_bf16x3_workspace_bytes(n, conv.in_channels, conv.out_channels, d, h, w)) == 0)
-
-
+# ------------------------------------------------------------------------------------------ training on the HIP kernels
 def _conv3_train(conv: nn.Conv3d, x: Tensor, bn: nn.BatchNorm3d):
     """A 3x3x3 convolution (stride 1 or 2, padding 1, no bias) under autograd on the bf16x3 kernels -> (y, parts, pivot): the
-    BatchNorm statistics' partial sums from the epilogue (around the running mean) where `_stats_form_ok`, else (y, None, None)."""
-    from .costreg import _ConvK3S1, _ConvK3S2
+    BatchNorm statistics' partial sums from the epilogue (around the running mean) where the stride-1 kernel may give them
+    (`layers.fused_stats_ok`) and its grid is not split over the input channels (the 20x20x8 and 10x10x4 levels are; the epilogue
+    form would run them unsplit), else (y, None, None)."""
     if conv.stride[0] == 2:
-        return _ConvK3S2.apply(x, conv.weight, True), None, None
-    if _stats_form_ok(x, conv):
+        return ConvK3S2.apply(x, conv.weight, True), None, None
+    n, _, d, h, w = x.shape
+    if layers.fused_stats_ok(x) and int(_lib.load().mvsdet_conv3d_k3_bf16x3_workspace_bytes(n, conv.in_channels, conv.out_channels, d, h, w)) == 0:
         pivot = bn.running_mean.detach() if bn.running_mean is not None else None
-        y, parts = _ConvK3S1.apply(x, conv.weight, True, True, pivot)
+        y, parts = ConvK3S1.apply(x, conv.weight, True, True, pivot)
         return y, parts, pivot
-    return _ConvK3S1.apply(x, conv.weight, True), None, None
+    return ConvK3S1.apply(x, conv.weight, True), None, None
 
 
 class _DownS2(torch.autograd.Function):
@@ -533,7 +359,6 @@ class _DownS2(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w0, wds):
-        from . import ops
         ctx.save_for_backward(x, w0, wds)
         cout, cin = wds.shape[:2]
         y0 = ops.conv3d_k3_s2_bf16x3(x, ops.split_conv_weight(w0, 1), None, None, False)
@@ -542,7 +367,6 @@ class _DownS2(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy0, gyd):
-        from . import ops
         x, w0, wds = ctx.saved_tensors
         cout, cin = wds.shape[:2]
         gy0, gyd = gy0.contiguous(), gyd.contiguous()
@@ -563,7 +387,6 @@ class _ConvT2S2(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w):
-        from . import ops
         ctx.save_for_backward(x, w)
         cin, cout = w.shape[:2]
         wq = ops.gemm_split_weight(w.detach().permute(1, 2, 3, 4, 0).reshape(8 * cout, cin).contiguous())
@@ -571,7 +394,6 @@ class _ConvT2S2(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from . import ops
         x, w = ctx.saved_tensors
         cin, cout = w.shape[:2]
         gy = gy.contiguous()

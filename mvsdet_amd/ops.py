@@ -1667,13 +1667,42 @@ def _(x, weight, grad_out, nsplit=32, bf16x3=False):
     return torch.empty_like(x), torch.empty_like(weight)
 
 
+def _bn_params(name: str, x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], parts: Optional[Tensor],
+               pivot: Optional[Tensor]):
+    """A training BatchNorm's affine and its statistics from the producing convolution's epilogue, checked against x's channels
+    and made contiguous -> (weight, bias, parts, pivot)."""
+    C = x.shape[1]
+    for t, tname in ((weight, "weight"), (bias, "bias")):
+        if t is not None:
+            _req(t, tname, dim=1)
+            if t.numel() != C:
+                raise ValueError(f"{name}: {tname} must have {C} elements")
+    if parts is not None:
+        if parts.dtype != torch.float64 or parts.dim() != 3 or parts.shape[0] != C or parts.shape[2] != 2 or parts.device != x.device:
+            raise ValueError(f"{name}: parts must be float64 ({C}, n, 2) on {x.device}, got {parts.dtype} {tuple(parts.shape)}")
+        parts = parts.contiguous()
+        if pivot is not None:
+            if pivot.dtype != torch.float32 or pivot.numel() != C or pivot.device != x.device:
+                raise ValueError(f"{name}: pivot must be {C} fp32 values on {x.device}")
+            pivot = pivot.contiguous()
+    elif pivot is not None:
+        raise ValueError(f"{name}: a pivot belongs to partial sums")
+    return (None if weight is None else weight.contiguous(), None if bias is None else bias.contiguous(), parts, pivot)
+
+
+def _bn_workspace(C: int, device) -> Tuple[Tensor, int]:
+    """The BatchNorm kernels' float64 workspace for C channels and its size in bytes."""
+    wb = _lib.load().mvsdet_bn3d_workspace_bytes(C)
+    return torch.empty(wb // 8, dtype=torch.float64, device=device), wb
+
+
 @torch.library.custom_op(f"{_NS}::bn3d_relu_train", mutates_args=(), device_types="cuda")
 def bn3d_relu_train(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], eps: float,
                     relu: bool, residual: Optional[Tensor] = None, parts: Optional[Tensor] = None,
                     pivot: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
     """Training-mode BatchNorm3d [+ ReLU] (mvs_models/module.py:26-37) on the batch statistics of x (N,C,D,H,W) fp32 ->
     (out, batch mean, 1/sqrt(biased batch variance + eps)).  The running statistics are the caller's to update (a custom
-    operator with an autograd formula must not mutate its inputs): mvsdet_amd.costreg does it from the returned vectors.
+    operator with an autograd formula must not mutate its inputs): `layers.update_running_stats` does it from the returned vectors.
     residual (same shape as x): out = [relu](bn(x)) + residual in the same pass (mvsnet.py:109-111, the skip additions).
     parts: float64 (C, n, 2) partial sums of x and of its squares per channel, left by the convolution that produced x
     (`conv3d_k3_bf16x3_stats`): the statistics pass over x is skipped; pivot: the vector that call was given (None = zeros)."""
@@ -1683,32 +1712,15 @@ def bn3d_relu_train(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor],
         if residual.shape != x.shape:
             raise ValueError(f"bn3d_relu_train: residual {tuple(residual.shape)} != x {tuple(x.shape)}")
         residual = residual.contiguous()
+    weight, bias, parts, pivot = _bn_params("bn3d_relu_train", x, weight, bias, parts, pivot)
     N, C = x.shape[:2]
     vol = x[0, 0].numel()
-    for t, name in ((weight, "weight"), (bias, "bias")):
-        if t is not None:
-            _req(t, name, dim=1)
-            if t.numel() != C:
-                raise ValueError(f"bn3d_relu_train: {name} must have {C} elements")
     x = x.contiguous()
-    weight = None if weight is None else weight.contiguous()
-    bias = None if bias is None else bias.contiguous()
     out = torch.empty_like(x)
     mean = torch.empty(C, dtype=torch.float32, device=x.device)
     invstd = torch.empty_like(mean)
     lib = _lib.load()
-    wb = lib.mvsdet_bn3d_workspace_bytes(C)
-    ws = torch.empty(wb // 8, dtype=torch.float64, device=x.device)
-    if parts is not None:
-        if parts.dtype != torch.float64 or parts.dim() != 3 or parts.shape[0] != C or parts.shape[2] != 2 or parts.device != x.device:
-            raise ValueError(f"bn3d_relu_train: parts must be float64 ({C}, n, 2) on {x.device}, got {parts.dtype} {tuple(parts.shape)}")
-        parts = parts.contiguous()
-        if pivot is not None:
-            if pivot.dtype != torch.float32 or pivot.numel() != C or pivot.device != x.device:
-                raise ValueError(f"bn3d_relu_train: pivot must be {C} fp32 values on {x.device}")
-            pivot = pivot.contiguous()
-    elif pivot is not None:
-        raise ValueError("bn3d_relu_train: a pivot belongs to partial sums")
+    ws, wb = _bn_workspace(C, x.device)
     with torch.cuda.device(x.device):
         if parts is not None:
             _lib.check(lib.mvsdet_bn3d_relu_train_fwd_parts_f32(_lib.ptr(x), _lib.ptr(parts), int(parts.shape[1]), _lib.ptr(pivot), _lib.ptr(weight), _lib.ptr(bias),
@@ -1744,8 +1756,7 @@ def bn3d_relu_backward(x: Tensor, grad_out: Tensor, weight: Optional[Tensor], bi
     gw = torch.empty(C, dtype=torch.float32, device=x.device)
     gb = torch.empty_like(gw)
     lib = _lib.load()
-    wb = lib.mvsdet_bn3d_workspace_bytes(C)
-    ws = torch.empty(wb // 8, dtype=torch.float64, device=x.device)
+    ws, wb = _bn_workspace(C, x.device)
     with torch.cuda.device(x.device):
         _lib.check(lib.mvsdet_bn3d_relu_bwd_f32(_lib.ptr(x), _lib.ptr(grad_out), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(save_mean),
                                                 _lib.ptr(save_invstd), _lib.ptr(gx), _lib.ptr(gw), _lib.ptr(gb), _lib.ptr(ws), wb, N, C,
@@ -1787,32 +1798,15 @@ def bn3d_res_relu_train(x: Tensor, weight: Optional[Tensor], bias: Optional[Tens
     _req(residual, "residual", dim=5)
     if residual.shape != x.shape:
         raise ValueError(f"bn3d_res_relu_train: residual {tuple(residual.shape)} != x {tuple(x.shape)}")
+    weight, bias, parts, pivot = _bn_params("bn3d_res_relu_train", x, weight, bias, parts, pivot)
     N, C = x.shape[:2]
     vol = x[0, 0].numel()
-    for t, name in ((weight, "weight"), (bias, "bias")):
-        if t is not None:
-            _req(t, name, dim=1)
-            if t.numel() != C:
-                raise ValueError(f"bn3d_res_relu_train: {name} must have {C} elements")
-    if parts is not None:
-        if parts.dtype != torch.float64 or parts.dim() != 3 or parts.shape[0] != C or parts.shape[2] != 2 or parts.device != x.device:
-            raise ValueError(f"bn3d_res_relu_train: parts must be float64 ({C}, n, 2) on {x.device}, got {parts.dtype} {tuple(parts.shape)}")
-        parts = parts.contiguous()
-        if pivot is not None:
-            if pivot.dtype != torch.float32 or pivot.numel() != C or pivot.device != x.device:
-                raise ValueError(f"bn3d_res_relu_train: pivot must be {C} fp32 values on {x.device}")
-            pivot = pivot.contiguous()
-    elif pivot is not None:
-        raise ValueError("bn3d_res_relu_train: a pivot belongs to partial sums")
     x, residual = x.contiguous(), residual.contiguous()
-    weight = None if weight is None else weight.contiguous()
-    bias = None if bias is None else bias.contiguous()
     out = torch.empty_like(x)
     mean = torch.empty(C, dtype=torch.float32, device=x.device)
     invstd = torch.empty_like(mean)
     lib = _lib.load()
-    wb = lib.mvsdet_bn3d_workspace_bytes(C)
-    ws = torch.empty(wb // 8, dtype=torch.float64, device=x.device)
+    ws, wb = _bn_workspace(C, x.device)
     with torch.cuda.device(x.device):
         _lib.check(lib.mvsdet_bn3d_res_relu_train_fwd_f32(_lib.ptr(x), _lib.ptr(parts), int(parts.shape[1]) if parts is not None else 0,
                                                           _lib.ptr(pivot), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(residual), None, None,
@@ -1844,8 +1838,7 @@ def bn3d_res_relu_backward(x: Tensor, out: Tensor, grad_out: Tensor, weight: Opt
     gw = torch.empty(C, dtype=torch.float32, device=x.device)
     gb = torch.empty_like(gw)
     lib = _lib.load()
-    wb = lib.mvsdet_bn3d_workspace_bytes(C)
-    ws = torch.empty(wb // 8, dtype=torch.float64, device=x.device)
+    ws, wb = _bn_workspace(C, x.device)
     with torch.cuda.device(x.device):
         _lib.check(lib.mvsdet_bn3d_res_relu_bwd_f32(_lib.ptr(x), _lib.ptr(out), _lib.ptr(grad_out), _lib.ptr(weight), _lib.ptr(bias),
                                                     _lib.ptr(save_mean), _lib.ptr(save_invstd), _lib.ptr(gx), _lib.ptr(gw), _lib.ptr(gb),

@@ -578,7 +578,7 @@ def g12c_relu_masks_grads():
     BatchNorm3d of mvsnet.py:76-100, taken by a forward hook before the in-place ReLU that follows it (bit-packed).  A route
     whose sums differ from fp32's in the last bits cannot be held element-wise on a free input (an activation within that noise
     of zero flips, and one flip among N moves a layer's gradient by sqrt(2/N) in norm: G12b needed a seed search at a smaller
-    shape to avoid it); with the reference's own decisions imposed on it (costreg.RELU_MASKS) it computes the same piecewise
+    shape to avoid it); with the reference's own decisions imposed on it (layers.RELU_MASKS) it computes the same piecewise
     linear function and its gradients can be.  Stored as in G12, plus the masks."""
     from lcg import lcg_fill_state, lcg_uniform
     mvsnet = sys.modules["refpkg.mvs_models.mvsnet"]

@@ -283,10 +283,10 @@ def test_g12c_training_step_with_the_reference_relu_decisions(gpu, fused_stats, 
     """The default training route (bf16x3, BatchNorm statistics from the producing kernels' epilogues) and its separate-pass twin
     against the REFERENCE module's gradients at (2,256,12,64,32) -- the stride-1 AND the transposed statistics forms are active
     (conv9 reads one 3 x 16 x 8 coarse tile per view, conv11 eight) -- with the reference's own seven ReLU decisions imposed
-    (costreg.RELU_MASKS): no activation can take the other branch, so every gradient is held ELEMENT-WISE (VERDICT r5 weak #1,
+    (layers.RELU_MASKS): no activation can take the other branch, so every gradient is held ELEMENT-WISE (VERDICT r5 weak #1,
     next #3).  Logits and running statistics 1e-4; gradients element-wise 1e-3 of each tensor's scale with no outliers (the
     bf16x3 bound of G12b) and 1e-4 in norm."""
-    from mvsdet_amd import costreg
+    from mvsdet_amd import layers
     from mvsdet_amd.costreg import CostRegNet3DGS
     g = load_golden("g12c_cost_regularisation_grads_masks")
     net = CostRegNet3DGS(256, 64).train()
@@ -296,7 +296,7 @@ def test_g12c_training_step_with_the_reference_relu_decisions(gpu, fused_stats, 
     net = net.to(gpu)
     shape = tuple(int(v) for v in g["in_shape"])
     x = torch.from_numpy(lcg_uniform(int(np.prod(shape)), int(g["input_seed"]))).reshape(shape).abs().to(gpu).requires_grad_(True)
-    was = costreg.FUSED_BN_STATS, costreg.RELU_MASKS
+    was = layers.FUSED_BN_STATS, layers.RELU_MASKS
     calls = {"s1": 0, "t": 0}
     from mvsdet_amd import ops
     real_s1, real_t = ops.conv3d_k3_bf16x3_stats, ops.convT3d_k3_s2_bf16x3_stats
@@ -308,14 +308,14 @@ def test_g12c_training_step_with_the_reference_relu_decisions(gpu, fused_stats, 
             return r
         return wrapped
     try:
-        costreg.FUSED_BN_STATS = fused_stats
-        costreg.RELU_MASKS = ("apply", _g12c_masks(g, net, gpu))
+        layers.FUSED_BN_STATS = fused_stats
+        layers.RELU_MASKS = ("apply", _g12c_masks(g, net, gpu))
         ops.conv3d_k3_bf16x3_stats, ops.convT3d_k3_s2_bf16x3_stats = count("s1", real_s1), count("t", real_t)
         y = net(x)
         R = torch.from_numpy(lcg_uniform(y.numel(), int(g["r_seed"]))).reshape(y.shape).to(gpu)
         (y * R).sum().backward()
     finally:
-        costreg.FUSED_BN_STATS, costreg.RELU_MASKS = was
+        layers.FUSED_BN_STATS, layers.RELU_MASKS = was
         ops.conv3d_k3_bf16x3_stats, ops.convT3d_k3_s2_bf16x3_stats = real_s1, real_t
     record_property("fused_statistics_calls", dict(calls))
     if fused_stats:   # both forms really ran: three stride-1 layers, two transposed ones

@@ -75,7 +75,7 @@ def _relu_modules(neck):
 
 
 def _check_decisions(rec, neck, g):
-    """Decisions recorded on `neck` (neck.RELU_MASKS "record") against the fixture: every `mask_stride`-th decision of each layer
+    """Decisions recorded on `neck` (layers.RELU_MASKS "record") against the fixture: every `mask_stride`-th decision of each layer
     (a flip allowed on at most 1e-5 of the samples, for another host's summation order) and each layer's count of positive ones."""
     keys = _relu_modules(neck)
     names = [str(n) for n in g["mask_names"]]
@@ -113,13 +113,13 @@ def _decisions_for(neck, by_name, device):
 
 
 def _with_hook(hook, fn):
-    from mvsdet_amd import neck as neck_mod
-    was = neck_mod.RELU_MASKS
-    neck_mod.RELU_MASKS = hook
+    from mvsdet_amd import layers
+    was = layers.RELU_MASKS
+    layers.RELU_MASKS = hook
     try:
         return fn()
     finally:
-        neck_mod.RELU_MASKS = was
+        layers.RELU_MASKS = was
 
 
 def _check_outputs(levels, heads, g, tol):
@@ -200,7 +200,7 @@ def test_autograd_route_default_and_environment(monkeypatch):
 
 def test_g14_aten_route_reproduces_the_reference_training_step():
     """The package's modules on the framework's layers (route "aten", CPU): the reference's outputs to 1e-5 and its ReLU decisions
-    (recorded through neck.RELU_MASKS, against the fixture's sampled decisions and per-layer counts); then, with those decisions imposed, every gradient element-wise to 1e-4 of its scale and the
+    (recorded through layers.RELU_MASKS, against the fixture's sampled decisions and per-layer counts); then, with those decisions imposed, every gradient element-wise to 1e-4 of its scale and the
     running statistics after the step."""
     g = load_golden(G14)
     cpu = torch.device("cpu")
@@ -272,7 +272,7 @@ def g14():
 
 @pytest.mark.gpu
 def test_g14_hip_route_with_the_reference_relu_decisions(gpu, g14):
-    """The HIP route against the REFERENCE's training step with the reference's ReLU decisions imposed (neck.RELU_MASKS; recorded
+    """The HIP route against the REFERENCE's training step with the reference's ReLU decisions imposed (layers.RELU_MASKS; recorded
     from the framework route on the CPU and checked against the fixture's sampled decisions and counts): G12c's bf16x3 bar -- outputs and running statistics 1e-4, every gradient element-wise to 1e-3 of its tensor's scale with no outlier
     and 1e-4 in norm."""
     decisions, _ = _reference_decisions(g14)

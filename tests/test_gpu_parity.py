@@ -1228,10 +1228,10 @@ def test_cost_network_training_on_bf16x3(gpu):
     layer pass is within 1e-5 of its fp32 counterpart (checked per autograd Function); through the network a forward
     difference of that size flips the ReLU decision of the few activations that sit within it of zero, so gradients are
     compared in norm: a few 1e-3, set by how many activations flip, not by the arithmetic of a layer (2.4e-3 at this shape)."""
-    from mvsdet_amd import costreg as CR
+    from mvsdet_amd import costreg as CR, layers
     torch.manual_seed(5)
-    for fn, xs, ws in ((CR._ConvK3S1, (2, 256, 8, 12, 32), (64, 256, 3, 3, 3)), (CR._ConvK3S2, (2, 64, 8, 12, 32), (128, 64, 3, 3, 3)),
-                       (CR._ConvT3S2, (2, 128, 4, 6, 16), (128, 64, 3, 3, 3))):
+    for fn, xs, ws in ((layers.ConvK3S1, (2, 256, 8, 12, 32), (64, 256, 3, 3, 3)), (layers.ConvK3S2, (2, 64, 8, 12, 32), (128, 64, 3, 3, 3)),
+                       (layers.ConvT3S2, (2, 128, 4, 6, 16), (128, 64, 3, 3, 3))):
         x, w = torch.randn(*xs, device=gpu), torch.randn(*ws, device=gpu) / 30
         res = {}
         for bf in (False, True):
@@ -1396,37 +1396,37 @@ def test_cost_network_training_mode_batchnorm(gpu):
 
 def test_cost_network_batchnorm_statistics_from_the_epilogues_or_from_their_own_pass(gpu):
     """The two training routes of the BatchNorm statistics -- partial sums left by the producing convolution's epilogue (default) and
-    the separate pass over the tensor (`costreg.FUSED_BN_STATS = False`, MVSDET_FUSED_BN_STATS=0) -- on one network at a shape whose
+    the separate pass over the tensor (`layers.FUSED_BN_STATS = False`, MVSDET_FUSED_BN_STATS=0) -- on one network at a shape whose
     stride-1 and transposed layers all have the fused form (12 x 60 x 80, as the reference-true shape), ELEMENT-WISE: statistics
     that differ in the last bits move activations by ~1e-7, and one activation of a layer's N on the other side of zero would
     move that layer's gradient by sqrt(2 / N) in norm (round 5 could only hold the gradients to their direction for that reason).
     So the ReLU decisions of ONE pass (the separate-pass route, on a copy of the network) are imposed on both routes
-    (costreg.RELU_MASKS): both then compute the same piecewise-linear function, and logits, running statistics and every parameter
+    (layers.RELU_MASKS): both then compute the same piecewise-linear function, and logits, running statistics and every parameter
     gradient must agree to 1e-5 of each tensor's scale -- a wrong term in either statistics form shows.  A second step starts from
     running means that are no longer zero (the pivots).  Against the REFERENCE's gradients the same routes are held by G12c
     (tests/test_f3_goldens.py)."""
     import copy
-    from mvsdet_amd import costreg
+    from mvsdet_amd import layers
     from mvsdet_amd.costreg import CostRegNet3DGS
     torch.manual_seed(9)
     nets = [CostRegNet3DGS(64, base=64).to(gpu).train() for _ in range(2)]
     nets[1].load_state_dict(nets[0].state_dict())
     x = torch.rand(2, 64, 12, 60, 80, device=gpu)
-    was = costreg.FUSED_BN_STATS, costreg.RELU_MASKS
+    was = layers.FUSED_BN_STATS, layers.RELU_MASKS
     try:
         for step in range(2):
             xin = x + 0.1 * step
             # the decisions of this step: one pass of the separate-pass route on a copy (its running statistics move, not the nets')
             probe = copy.deepcopy(nets[1])
-            costreg.FUSED_BN_STATS, costreg.RELU_MASKS = False, ("record", {})
+            layers.FUSED_BN_STATS, layers.RELU_MASKS = False, ("record", {})
             with torch.enable_grad():
                 probe(xin)
-            by_name = {name: costreg.RELU_MASKS[1][m] for name, m in probe.named_modules() if m in costreg.RELU_MASKS[1]}
+            by_name = {name: layers.RELU_MASKS[1][m] for name, m in probe.named_modules() if m in layers.RELU_MASKS[1]}
             assert len(by_name) == 7 and all(0.2 < float(v.float().mean()) < 0.8 for v in by_name.values())
             outs = []
             for fused, net in zip((True, False), nets):
                 mods = dict(net.named_modules())
-                costreg.FUSED_BN_STATS, costreg.RELU_MASKS = fused, ("apply", {mods[k]: v for k, v in by_name.items()})
+                layers.FUSED_BN_STATS, layers.RELU_MASKS = fused, ("apply", {mods[k]: v for k, v in by_name.items()})
                 net.zero_grad(set_to_none=True)
                 out = net(xin)
                 out.square().mean().backward()
@@ -1444,7 +1444,7 @@ def test_cost_network_batchnorm_statistics_from_the_epilogues_or_from_their_own_
                 assert err <= 1e-5 * scale, (step, name, err, scale)
             print(f"BatchNorm statistics routes, step {step}: max |d grad| / scale = {worst:.2e}")
     finally:
-        costreg.FUSED_BN_STATS, costreg.RELU_MASKS = was
+        layers.FUSED_BN_STATS, layers.RELU_MASKS = was
 
 
 def test_depth_prob_topk_reads_the_network_output_in_place(gpu):

@@ -317,7 +317,7 @@ def test_first_call_on_two_streams_waits_for_the_derived_tensors(gpu):
     the FIRST call of a fresh CostRegNet3DGS with the views on two streams that is the side stream's chain -- and the main stream's
     chain, running layers ahead or behind, read them before the kernels that fill them had run (stale small blocks recycled by the
     allocator: wrong logits by ~1e-2, found in round 5 by the 100-view test in a full-suite run; latent since the halves exist).
-    Every derived tensor now carries the event behind its computation (neck._mark_made / _await_made).  Here the allocator's small
+    Every derived tensor now carries the event behind its computation (layers.mark_made / await_made).  Here the allocator's small
     blocks are poisoned first, so that a premature read cannot go unnoticed, and a long kernel is enqueued in front, so that both
     chains are enqueued before either starts."""
     from mvsdet_amd.costreg import CostRegNet3DGS

@@ -42,12 +42,12 @@ def test_structure_and_parameter_names():
 
 def test_gemm_forms_match_aten_layers():
     """The fast route's two GEMM rewrites, evaluated on the CPU: 1x1x1 stride-2 conv + BN, ConvTranspose3d(k=2,s=2) + BN + ReLU."""
-    from mvsdet_amd import neck as NK
+    from mvsdet_amd import layers, neck as NK
     g = torch.Generator().manual_seed(3)
     ds = _randomise(NK._ConvModule(6, 10, 1, 2, 0, act=False), 1)
     x = torch.randn(2, 6, 8, 6, 4, generator=g)
     xs = x[:, :, ::2, ::2, ::2]
-    scale, shift = NK._bn_affine(ds.bn)
+    scale, shift = layers.bn_affine(ds.bn)
     wmat = ds.conv.weight.detach().reshape(10, 6) * scale[:, None]
     got = torch.baddbmm(shift.view(1, -1, 1), wmat.unsqueeze(0).expand(2, -1, -1), xs.reshape(2, 6, -1)).view(2, 10, 4, 3, 2)
     with torch.no_grad():
@@ -55,13 +55,33 @@ def test_gemm_forms_match_aten_layers():
     up = _randomise(NK._UpBlock(6, 4), 2)
     x = torch.randn(2, 6, 3, 4, 2, generator=g)
     deconv, bn = up[0], up[1]
-    scale, shift = NK._bn_affine(bn)
+    scale, shift = layers.bn_affine(bn)
     wmat = (deconv.weight.detach() * scale.view(1, -1, 1, 1, 1)).permute(2, 3, 4, 1, 0).reshape(8 * 4, 6)
     y = torch.matmul(wmat.unsqueeze(0), x.reshape(2, 6, -1)).view(2, 2, 2, 2, 4, 3, 4, 2)
     y = torch.relu(y.permute(0, 4, 5, 1, 6, 2, 7, 3).reshape(2, 4, 6, 8, 4) + shift.view(1, -1, 1, 1, 1))
     with torch.no_grad():
         ref = torch.relu(bn(deconv(x)))
     np.testing.assert_allclose(y.numpy(), ref.numpy(), rtol=1e-5, atol=1e-5)
+
+
+def test_earlier_names_reach_the_shared_layers():
+    """The names costreg and neck had before mvsdet_amd.layers: the toggles set through either module are the shared ones (the
+    neck's framework route records its ReLU decisions through neck.RELU_MASKS), and the moved functions resolve there."""
+    from mvsdet_amd import costreg, layers, neck as NK
+    was = layers.RELU_MASKS, layers.FUSED_BN_STATS
+    try:
+        costreg.FUSED_BN_STATS = not was[1]
+        assert layers.FUSED_BN_STATS is (not was[1]) and NK.FUSED_BN_STATS is layers.FUSED_BN_STATS
+        NK.RELU_MASKS = ("record", {})
+        m = NK._ConvModule(4, 4, 3, 1, 1)
+        with torch.no_grad():
+            m(torch.randn(1, 4, 4, 4, 4))
+        assert costreg.RELU_MASKS is layers.RELU_MASKS and list(layers.RELU_MASKS[1]) == [m]
+    finally:
+        layers.RELU_MASKS, layers.FUSED_BN_STATS = was
+    assert NK.RELU_MASKS is costreg.RELU_MASKS is was[0]
+    assert (costreg._ConvK3S1, costreg._ConvK3S2, costreg._ConvT3S2) == (layers.ConvK3S1, layers.ConvK3S2, layers.ConvT3S2)
+    assert NK._bn_affine is layers.bn_affine and NK._drop_after_load is layers._drop_after_load
 
 
 @pytest.mark.gpu

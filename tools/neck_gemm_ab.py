@@ -7,7 +7,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from mvsdet_amd import neck as NK  # noqa: E402
+from mvsdet_amd import layers, neck as NK  # noqa: E402
 from mvsdet_amd.head import NerfDetHeadConvs  # noqa: E402
 
 dev = torch.device("cuda:0")
@@ -35,7 +35,7 @@ with torch.no_grad():
         for rnd in range(2):
             for flag in (False, True):
                 NK.GEMM_BF16X3 = flag
-                NK.drop_derived_tensors(neck)
+                layers.drop_derived_tensors(neck)
                 tn = timed(lambda: neck(x))
                 tnh = timed(lambda: head(neck(x)))
                 print(f"batch {bsz} {'neck_gemm.hip' if flag else 'rocBLAS+ATen '}: neck {tn:.3f} ms ({tn / bsz:.3f} per scene), neck + head {tnh:.3f} ms ({tnh / bsz:.3f} per scene)", flush=True)

@@ -4,13 +4,13 @@ side stream's chain; does the main stream's chain read them too early?  Compares
 import sys
 sys.path.insert(0, ".")
 import torch
-from mvsdet_amd import neck as NK
+from mvsdet_amd import layers
 from mvsdet_amd.costreg import CostRegNet3DGS
 dev = torch.device("cuda:0")
 x = torch.rand(100, 256, 12, 60, 80, device=dev)
-real_await = NK._await_made
+real_await = layers.await_made
 for mode in ("no wait", "wait"):
-    NK._await_made = real_await if mode == "wait" else (lambda *a: None)
+    layers.await_made = real_await if mode == "wait" else (lambda *a: None)
     bad = 0
     for it in range(12):
         torch.manual_seed(it)

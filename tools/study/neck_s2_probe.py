@@ -1,6 +1,6 @@
 import os, sys, torch
 sys.path.insert(0, "/root/repo")
-from mvsdet_amd import neck as NK
+from mvsdet_amd import layers, neck as NK
 def timeit(fn, reps=20):
     fn(); torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -14,6 +14,6 @@ x = torch.randn(1, 256, 40, 40, 16, device=dev).relu()
 with torch.no_grad():
     for flag in (False, True, False, True):
         NK.S2_BF16X3 = flag
-        NK.drop_derived_tensors(net)
+        layers.drop_derived_tensors(net)
         net(x)
         print("S2_BF16X3", flag, f"{timeit(lambda: net(x)):.3f} ms", flush=True)
