@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MVSDet plane-sweep hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -16,8 +16,13 @@ roofline = algorithmic HBM bytes of the plane-sweep kernel / its mean duration f
            the timed region, against the 8 TB/s HBM3E peak.
 --dump-outputs DIR writes what the last timed step computed (cost volume, depth distribution, voxel volume and counts) as
 DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the JSON line.  --full adds
+everything that takes runs of its own (rank 0, N=1): per-stage timings, footprint split, copy and store-pattern ceilings, the
+reference-true shape, the other workloads, the chain with the cost network, the training block, the CPU baseline, and in
+--mode train the backward rooflines.
 cpu_baseline = the CPU restatement of the same stage (oracle/) timed on this box's host cores on a bounded
-           sample (rank 0, N=1 only).  It is a checker-side measurement: nothing shipped runs on it.
+           sample (--full, rank 0, N=1 only).  It is a checker-side measurement: nothing shipped runs on it.
 """
 import argparse
 import gc
@@ -1037,11 +1042,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="auto", choices=["auto"] + list(WORKLOADS))
     ap.add_argument("--scene-pool", type=int, default=2, help="distinct resident scenes cycled through")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU baseline budget (0 disables)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every measurement that takes runs of its own (see the module docstring); "
+                         "a plain run does set-up, warm-up, the timed steps and --dump-outputs only")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU baseline budget under --full (0 disables)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip stage breakdown / copy ceiling / R-shape line / other workloads / cost-network chain")
+                    help="under --full, skip stage breakdown / copy ceiling / R-shape line / other workloads / cost-network chain")
     ap.add_argument("--with-cost-network", action="store_true",
-                    help="(default on at N=1 unless --no-extras) scenes/s of a1..a10 with the real cost regularisation "
+                    help="(default on under --full at N=1 unless --no-extras) scenes/s of a1..a10 with the real cost regularisation "
                          "network in between, reference-true shape, eval mode: our kernels only")
     ap.add_argument("--mode", default="infer", choices=["infer", "train", "view-sharded"],
                     help="train = configs[2]: fwd + bwd + optimiser step with a stand-in cost network under DDP; "
@@ -1140,7 +1148,7 @@ def main():
                            "optimizer": OPTIMIZER},
                 "optimizer_ms": args.optimizer_ms,
                 **({"gradient_tolerance": BF16X3_GRADIENT_TOLERANCE} if args.with_cost_network else {}),
-                "roofline": backward_rooflines(w, device)["backward_sweep"], "ranks_seen": ranks_seen,
+                "roofline": backward_rooflines(w, device)["backward_sweep"] if args.full else None, "ranks_seen": ranks_seen,
                 "launch_env": launch_env(), "device_binding": binding, "checksum": checksum}), flush=True)
         if world > 1:
             import torch.distributed as dist
@@ -1186,7 +1194,7 @@ def main():
             line["dump_outputs"]["variance_last_chunk_first_view"] = hp.dumped_chunk_first_view
     if w.get("chunk"):
         line["config"]["views_per_launch"] = w["chunk"]
-    extras = rank == 0 and world == 1 and not args.no_extras
+    extras = args.full and rank == 0 and world == 1 and not args.no_extras
     if extras and not w.get("chunk"):
         line["stage_ms"] = stage_breakdown(w, hp, scenes[0], device)
         line["roofline"]["footprints"] = footprint_stats(w, hp, scenes[0], device)
@@ -1235,7 +1243,7 @@ def main():
                                                  ("scannet_test_80v_12d_60x80", "arkit_test_100v_12d_60x80")}
     if extras:
         line["training"] = training_block(device)   # BASELINE.json configs[2] at N = 1
-    if rank == 0 and world == 1 and args.cpu_seconds > 0 and not w.get("half"):
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0 and not w.get("half"):
         line["cpu_baseline"] = cpu_baseline(w, args.cpu_seconds)
         line["gpu_over_cpu"] = round(value / line["cpu_baseline"]["value"], 1)
     if rank == 0:

@@ -15,6 +15,10 @@ pytestmark = pytest.mark.gpu
 KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
         "dtype", "data", "config", "roofline"}
 
+# what --full adds to the line of an N=1 run at a workload other than the reference-true shape
+FULL_ONLY = {"cpu_baseline", "gpu_over_cpu", "stage_ms", "hbm_copy_ceiling_GBps", "reference_true_shape", "with_cost_network",
+             "with_cost_network_test_shapes", "training"}
+
 
 def _last_json(out):
     lines = [l for l in out.strip().splitlines() if l.startswith("{")]
@@ -25,7 +29,7 @@ def _last_json(out):
 @pytest.mark.timeout(600)
 def test_single_gpu_line(gpu):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny_3v_8d_48x64", "--steps", "3",
-                          "--warmup", "1", "--cpu-seconds", "2"], capture_output=True, text=True, timeout=500, cwd=ROOT)
+                          "--warmup", "1", "--full", "--cpu-seconds", "2"], capture_output=True, text=True, timeout=500, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json(out.stdout)
     assert KEYS <= set(d) and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0
@@ -35,6 +39,21 @@ def test_single_gpu_line(gpu):
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and "sample" in c
     assert d["config"]["workload"] == "tiny_3v_8d_48x64" and "model" not in d["config"]
+    assert FULL_ONLY <= set(d), sorted(FULL_ONLY - set(d))
+
+
+@pytest.mark.timeout(600)
+def test_plain_run_measures_the_headline_only(gpu):
+    """Without --full the line is the headline and what the timed steps themselves recorded: no measurement of its own."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny_3v_8d_48x64", "--steps", "3",
+                          "--warmup", "1"], capture_output=True, text=True, timeout=500, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = _last_json(out.stdout)
+    assert KEYS <= set(d) and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert not FULL_ONLY & set(d), sorted(FULL_ONLY & set(d))
+    r = d["roofline"]
+    assert r["kernel_ms"] > 0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
+    assert "footprints" not in r and "store_pattern_ceiling" not in r
 
 
 @pytest.mark.timeout(600)

@@ -2,11 +2,11 @@
 """One table of the numbers that matter, generated from a bench record.
 
     python tools/numbers_table.py BENCH_r05.json            # the driver's record ({"parsed": {...}} or the bare JSON line)
-    python tools/numbers_table.py gpurun_out/r05_bench.log  # a log whose last JSON line is bench.py's
+    python tools/numbers_table.py bench.log                 # a log whose last JSON line is bench.py's
 
 Prints a markdown table: workload, kernel / quantity, milliseconds, fraction of its roofline, what the fraction is of, and the
 key of the record the number was read from -- DESIGN.md section 0 pastes this output, so that every number there can be
-checked against the record by its key.
+checked against the record by its key.  Every row but the headline's and the sweep kernel's needs a `bench.py --full` record.
 """
 import json
 import sys
