@@ -581,6 +581,34 @@ size_t mvsdet_neck_gemm_dw_partial_bytes(int Cin, int Cout, int transposed, int 
 int mvsdet_neck_gemm_dw_bf16x3(const float* x, const float* grad_out, float* dw, float* partial, size_t partial_bytes, int nsplit,
                                int transposed, int N, int Cin, int Cout, int D, int H, int W, mvsdet_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Detection post-processing of the ScanNet head (NerfDetHead.predict_by_feat / _nms / aligned_3d_nms, nerfdet_head.py:301-420,
+ * 564-628) on the caller's stream, no host synchronisation (csrc/detect.hip).  fp32; labels int64.
+ *
+ * mvsdet_detect_head_f32: B scenes, L levels (HOST arrays of L device pointers: center (B,1,X,Y,Z), bbox (B,6,X,Y,Z), cls
+ *   (B,C,X,Y,Z), contiguous; level_dims HOST int[3 L]); valid (B,1,VX,VY,VZ) = the stacked view counts as float; level_geom
+ *   (B,L,6) DEVICE float = per scene and level the voxel size and get_points' new_origin.  Per level k = nms_pre if
+ *   X*Y*Z > nms_pre > 0, else X*Y*Z; ncap = the sum of k over the levels, points = the sum of X*Y*Z.  Outputs padded to Nmax >=
+ *   min(ncap, MVSDET_DETECT_MAX_CANDIDATES): out_boxes (B,Nmax,6) (cx, cy, cz, dx, dy, dz), out_scores (B,Nmax), out_labels
+ *   (B,Nmax), out_count (B) int32; rows past a scene's count are zero.  A scene with more than MVSDET_DETECT_MAX_CANDIDATES
+ *   boxes above score_thr gets out_count = -(that number) and no boxes (known on the device only).
+ *   Candidate order: score descending, ties by level, then voxel index (the reference's argsort leaves ties unordered).
+ * mvsdet_aligned_3d_nms_f32: boxes (n,6) (x1,y1,z1,x2,y2,z2), scores (n), classes (n) int64 -> out_index (n) int64 = the kept
+ *   indices in pick order, out_count (1) int32; n <= MVSDET_DETECT_MAX_CANDIDATES (else MVSDET_ERR_INVALID_ARG).
+ * mvsdet_detect_workspace_bytes(B, points, ncap): the workspace of either call (standalone NMS: B = 1, points = 0, ncap = n);
+ *   each region rounded up to 256 bytes, caps = min(ncap, limit):
+ *   B*4*4 + B*4 + 2 * B*points*4 + B*ncap*(24+4+8) (three regions) + B*caps*(24+4+8+4) (four) + B*caps*ceil(caps/64)*8.
+ * ------------------------------------------------------------------------------------------- */
+#define MVSDET_DETECT_MAX_CANDIDATES 16384 /* boxes of one scene above score_thr: one sort in 128 KiB of LDS */
+#define MVSDET_DETECT_MAX_LEVELS 4
+size_t mvsdet_detect_workspace_bytes(int B, int points, int ncap);
+int mvsdet_detect_head_f32(const float* const* center, const float* const* bbox, const float* const* cls, const int* level_dims,
+                           const float* valid, const float* level_geom, int B, int L, int n_classes, int VX, int VY, int VZ,
+                           int nms_pre, float score_thr, float iou_thr, float* out_boxes, float* out_scores, int64_t* out_labels,
+                           int* out_count, int nmax, void* workspace, size_t workspace_bytes, mvsdet_stream_t stream);
+int mvsdet_aligned_3d_nms_f32(const float* boxes, const float* scores, const int64_t* classes, int n, float thresh,
+                              int64_t* out_index, int* out_count, void* workspace, size_t workspace_bytes, mvsdet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,563 @@
+// Detection post-processing of the ScanNet head (NerfDetHead.predict_by_feat -> _predict_by_feat_single -> _nms -> aligned_3d_nms,
+// projects/NeRF-Det/nerfdet/nerfdet_head.py:301-420, 564-628): head maps -> kept boxes in four launches per batch, no host round trip.
+//
+//   detect_select_kernel  one workgroup per (level, scene): upsampled valid mask, score = sigmoid(cls) * sigmoid(center) * valid, max
+//                         over classes, top-nms_pre by a radix select on the score bits, decode, score > score_thr; survivors are
+//                         appended in voxel order to the level's own segment of the scene's candidate list
+//   detect_sort_kernel    one workgroup per scene: bitonic sort in LDS of (score descending, candidate index ascending) keys
+//   detect_mask_kernel    grid of 64-row x 64-column tiles: the class-aware IoU suppression bit of every ordered pair (i, j > i)
+//   detect_scan_kernel    one workgroup per scene: the greedy walk 64 boxes at a time, kept boxes written in pick order
+//
+// The standalone NMS (mvsdet_aligned_3d_nms_f32) replaces the first launch by detect_load_kernel.  All arithmetic that decides or
+// produces an output is written as the reference's ATen expression, op for op; the Makefile's -ffp-contract=off keeps every
+// product and sum separately rounded, and fp32 division is IEEE-rounded (hipcc's default).
+#include "common.h"
+
+#include <algorithm>
+
+namespace mvsdet {
+namespace {
+
+constexpr int kSelThreads = 1024;
+constexpr int kSortThreads = 1024;
+constexpr int kScanThreads = 1024;
+constexpr int kMaxL = MVSDET_DETECT_MAX_LEVELS;
+constexpr int kLimit = MVSDET_DETECT_MAX_CANDIDATES;
+
+struct DetLevel {
+    const float* center;   // (B,1,X,Y,Z)
+    const float* bbox;     // (B,6,X,Y,Z)
+    const float* cls;      // (B,C,X,Y,Z)
+    int X, Y, Z;
+    int k;                 // top-k size, 0 = every point
+    int seg_off;           // offset of this level's segment in a scene's candidate list
+    int pt_off;            // offset of this level's points in a scene's score workspace
+    float sx, sy, sz;      // trilinear scales of the valid upsampling: (float)in / out
+};
+
+struct Work {              // carved out of the caller's workspace (mvsdet_detect_workspace_bytes)
+    int* seg_count;        // (B, kMaxL)
+    int* n_sorted;         // (B): candidates of the scene, or -(survivors) above the limit
+    float* pscore;         // (B, points) max score per point
+    int* plabel;           // (B, points) its class
+    float* cbox;           // (B, ncap, 6)
+    float* cscore;         // (B, ncap)
+    long long* clabel;     // (B, ncap)
+    float* sbox;           // (B, caps, 6) sorted
+    float* sscore;
+    long long* slabel;
+    int* sidx;             // candidate index (standalone NMS: the input index)
+    unsigned long long* mask;  // (B, caps, words)
+    int points, ncap, caps, words;
+};
+
+struct SelectParams {
+    DetLevel lv[kMaxL];
+    const float* valid;    // (B,1,VX,VY,VZ) view counts as float
+    const float* geom;     // (B, L, 6): voxel size, new origin
+    int L, C, VX, VY, VZ;
+    float score_thr;
+};
+
+struct SortParams {
+    int L;
+    int seg_off[kMaxL];
+};
+
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// torch.maximum / torch.minimum: NaN in, NaN out
+__device__ __forceinline__ float nan_max(float a, float b) { return (a != a || b != b) ? __int_as_float(0x7fc00000) : (a > b ? a : b); }
+__device__ __forceinline__ float nan_min(float a, float b) { return (a != a || b != b) ? __int_as_float(0x7fc00000) : (a < b ? a : b); }
+
+// aten/src/ATen/native/UpSample.h: area_pixel_compute_source_index + guard_index_and_lambda (align_corners = False)
+__device__ __forceinline__ void linear_taps(float scale, int d, int in, int& i0, int& i1, float& l0, float& l1) {
+    float r = scale * ((float)d + 0.5f) - 0.5f;
+    if (r < 0.f) r = 0.f;
+    const int i = min((int)floorf(r), in - 1);
+    const float lam = fminf(fmaxf(r - (float)i, 0.f), 1.f);
+    i0 = i;
+    i1 = i + (i < in - 1 ? 1 : 0);
+    l1 = lam;
+    l0 = 1.f - lam;
+}
+
+// exclusive prefix of `flag` over the workgroup (in thread order) and the workgroup's total
+__device__ __forceinline__ int block_scan(bool flag, int* wave_cnt, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const unsigned long long m = __ballot(flag);
+    const int pre = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_cnt[wave] = __popcll(m);
+    __syncthreads();
+    int base = 0, tot = 0;
+    for (int w = 0; w < nw; ++w) {
+        const int c = wave_cnt[w];
+        base += w < wave ? c : 0;
+        tot += c;
+    }
+    __syncthreads();
+    total = tot;
+    return base + pre;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- selection
+__global__ __launch_bounds__(kSelThreads) void detect_select_kernel(SelectParams p, Work w) {
+    __shared__ int hist[256];
+    __shared__ int wave_cnt[kSelThreads / 64];
+    __shared__ int sel[2];
+    const int l = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const DetLevel lv = p.lv[l];
+    const int YZ = lv.Y * lv.Z, N = lv.X * YZ, C = p.C;
+    const float* ctr = lv.center + (size_t)b * N;
+    const float* cls = lv.cls + (size_t)b * C * N;
+    const float* box = lv.bbox + (size_t)b * 6 * N;
+    const float* valid = p.valid + (size_t)b * p.VX * p.VY * p.VZ;
+    float* ps = w.pscore + (size_t)b * w.points + lv.pt_off;
+    int* pl = w.plabel + (size_t)b * w.points + lv.pt_off;
+
+    // 1. scores: nn.Upsample(trilinear)(valid).round().bool(); sigmoid(cls) * sigmoid(center) * valid; max / first argmax
+    for (int i = tid; i < N; i += kSelThreads) {
+        const int x = i / YZ, y = (i / lv.Z) % lv.Y, z = i % lv.Z;
+        int x0, x1, y0, y1, z0, z1;
+        float ax0, ax1, ay0, ay1, az0, az1;
+        linear_taps(lv.sx, x, p.VX, x0, x1, ax0, ax1);
+        linear_taps(lv.sy, y, p.VY, y0, y1, ay0, ay1);
+        linear_taps(lv.sz, z, p.VZ, z0, z1, az0, az1);
+        auto at = [&](int xi, int yi, int zi) { return valid[((size_t)xi * p.VY + yi) * p.VZ + zi]; };
+        auto zl = [&](int xi, int yi) { float t = at(xi, yi, z0) * az0; t += at(xi, yi, z1) * az1; return t; };
+        auto yl = [&](int xi) { float t = zl(xi, y0) * ay0; t += zl(xi, y1) * ay1; return t; };
+        float v = yl(x0) * ax0;
+        v += yl(x1) * ax1;
+        const float vm = rintf(v) != 0.f ? 1.f : 0.f;
+        const float sc = sigmoidf_(ctr[i]);
+        float best = (sigmoidf_(cls[i]) * sc) * vm;
+        int arg = 0;
+        for (int c = 1; c < C; ++c) {
+            const float s = (sigmoidf_(cls[(size_t)c * N + i]) * sc) * vm;
+            if (!(best != best) && (s != s || s > best)) {
+                best = s;
+                arg = c;
+            }
+        }
+        ps[i] = best;
+        pl[i] = arg;
+    }
+    __syncthreads();
+
+    // 2. top-k threshold: the k-th largest score bits (scores are >= 0: their bits order like their values), 8 bits a pass
+    unsigned T = 0;
+    int need_eq = 0;
+    if (lv.k > 0) {
+        unsigned prefix = 0, pmask = 0;
+        int kk = lv.k;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            for (int d = tid; d < 256; d += kSelThreads) hist[d] = 0;
+            __syncthreads();
+            for (int i = tid; i < N; i += kSelThreads) {
+                const unsigned u = __float_as_uint(ps[i]);
+                if ((u & pmask) == prefix) atomicAdd(&hist[(u >> shift) & 255u], 1);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                int acc = 0, d = 255;
+                for (; d > 0; --d) {
+                    if (acc + hist[d] >= kk) break;
+                    acc += hist[d];
+                }
+                sel[0] = d;
+                sel[1] = kk - acc;
+            }
+            __syncthreads();
+            prefix |= (unsigned)sel[0] << shift;
+            pmask |= 255u << shift;
+            kk = sel[1];
+            __syncthreads();
+        }
+        T = prefix;
+        need_eq = kk;   // points with bits == T to take, lowest voxel index first
+    }
+
+    // 3. compaction in voxel order: (top-k) and score > score_thr -> decoded box, score, label
+    const float* g = p.geom + ((size_t)b * p.L + l) * 6;
+    const float vs0 = g[0], vs1 = g[1], vs2 = g[2], o0 = g[3], o1 = g[4], o2 = g[5];
+    const size_t cbase = (size_t)b * w.ncap + lv.seg_off;
+    int base = 0, eq_base = 0;
+    for (int c0 = 0; c0 < N; c0 += kSelThreads) {
+        const int i = c0 + tid;
+        const bool in = i < N;
+        const float s = in ? ps[i] : 0.f;
+        const unsigned u = __float_as_uint(s);
+        bool take = in;
+        if (lv.k > 0) {
+            int eq_tot;
+            const bool eq = in && u == T;
+            const int r = block_scan(eq, wave_cnt, eq_tot);
+            take = in && (u > T || (eq && eq_base + r < need_eq));
+            eq_base += eq_tot;
+        }
+        const bool keep = take && s > p.score_thr;
+        int tot;
+        const int r = block_scan(keep, wave_cnt, tot);
+        if (keep) {
+            const int x = i / YZ, y = (i / lv.Z) % lv.Y, z = i % lv.Z;
+            float px = (float)x * vs0, py = (float)y * vs1, pz = (float)z * vs2;
+            px = px + o0;
+            py = py + o1;
+            pz = pz + o2;
+            const size_t ci = cbase + base + r;
+            float* ob = w.cbox + ci * 6;
+            ob[0] = px - box[i];
+            ob[1] = py - box[(size_t)2 * N + i];
+            ob[2] = pz - box[(size_t)4 * N + i];
+            ob[3] = px + box[(size_t)1 * N + i];
+            ob[4] = py + box[(size_t)3 * N + i];
+            ob[5] = pz + box[(size_t)5 * N + i];
+            w.cscore[ci] = s;
+            w.clabel[ci] = pl[i];
+        }
+        base += tot;
+    }
+    if (tid == 0) w.seg_count[b * kMaxL + l] = base;
+}
+
+// standalone NMS: the caller's boxes / scores / classes as the one-level candidate list of one scene
+__global__ void detect_load_kernel(const float* __restrict__ boxes, const float* __restrict__ scores, const long long* __restrict__ classes,
+                                   int n, Work w) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) w.seg_count[0] = n;
+    if (i >= n) return;
+    for (int c = 0; c < 6; ++c) w.cbox[(size_t)i * 6 + c] = boxes[(size_t)i * 6 + c];
+    w.cscore[i] = scores[i];
+    w.clabel[i] = classes[i];
+}
+
+// ---------------------------------------------------------------------------------------------------------------- sort
+// float -> unsigned with the same order (NaN above +inf, as torch.sort places it)
+__device__ __forceinline__ unsigned order_bits(float f) {
+    const unsigned u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__global__ __launch_bounds__(kSortThreads) void detect_sort_kernel(SortParams q, Work w, int pmax) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];   // [pmax] keys, then the level counts / prefixes
+    int* cnt = reinterpret_cast<int*>(keys + pmax);
+    int* pre = cnt + kMaxL;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) {
+        int acc = 0;
+        for (int l = 0; l < q.L; ++l) {
+            cnt[l] = w.seg_count[b * kMaxL + l];
+            pre[l] = acc;
+            acc += cnt[l];
+        }
+        pre[kMaxL] = acc;
+    }
+    __syncthreads();
+    const int total = pre[kMaxL];
+    if (total > kLimit || total > w.caps) {
+        if (tid == 0) w.n_sorted[b] = -total;
+        return;
+    }
+    int P = 1;
+    while (P < total) P <<= 1;
+    auto cand = [&](int e) {   // concatenated (level-major) candidate index -> slot of the candidate buffer
+        int l = 0;
+        while (l + 1 < q.L && e >= pre[l + 1]) ++l;
+        return (size_t)b * w.ncap + q.seg_off[l] + (e - pre[l]);
+    };
+    for (int e = tid; e < P; e += kSortThreads)
+        keys[e] = e < total ? ((unsigned long long)(~order_bits(w.cscore[cand(e)])) << 32) | (unsigned)e : ~0ull;
+    __syncthreads();
+    // ascending bitonic sort: score descending, then candidate index ascending
+    for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (P >> 1); t += kSortThreads) {
+                const int i = 2 * t - (t & (j - 1));
+                const unsigned long long a = keys[i], c = keys[i + j];
+                if ((a > c) == ((i & k) == 0)) {
+                    keys[i] = c;
+                    keys[i + j] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    const size_t sb = (size_t)b * w.caps;
+    for (int r = tid; r < total; r += kSortThreads) {
+        const int e = (int)(keys[r] & 0xffffffffu);
+        const size_t ci = cand(e);
+        for (int c = 0; c < 6; ++c) w.sbox[(sb + r) * 6 + c] = w.cbox[ci * 6 + c];
+        w.sscore[sb + r] = w.cscore[ci];
+        w.slabel[sb + r] = w.clabel[ci];
+        w.sidx[sb + r] = e;
+    }
+    if (tid == 0) w.n_sorted[b] = total;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- IoU mask
+// aligned_3d_nms's suppression test of the later box j by the earlier box i, op for op:
+//   inter = max(0, min(x2) - max(x1)) * max(0, ..y..) * max(0, ..z..);  iou = inter / (area_i + area_j - inter) * (cls_i == cls_j)
+//   j goes when !(iou <= thr): NaN (zero-volume / infinite boxes) suppresses, across classes too (NaN * 0)
+__device__ __forceinline__ bool suppresses(const float* a, float area_a, long long la, const float* c, float area_c, long long lc,
+                                           float thr) {
+    const float xx1 = nan_max(a[0], c[0]), yy1 = nan_max(a[1], c[1]), zz1 = nan_max(a[2], c[2]);
+    const float xx2 = nan_min(a[3], c[3]), yy2 = nan_min(a[4], c[4]), zz2 = nan_min(a[5], c[5]);
+    const float il = nan_max(0.f, xx2 - xx1), iw = nan_max(0.f, yy2 - yy1), ih = nan_max(0.f, zz2 - zz1);
+    const float inter = (il * iw) * ih;
+    float iou = inter / ((area_a + area_c) - inter);
+    iou = iou * (la == lc ? 1.f : 0.f);
+    return !(iou <= thr);
+}
+
+__device__ __forceinline__ float box_area(const float* x) { return ((x[3] - x[0]) * (x[4] - x[1])) * (x[5] - x[2]); }
+
+__global__ __launch_bounds__(64) void detect_mask_kernel(Work w, float thr) {
+    __shared__ float cb[64][7];
+    __shared__ long long cl[64];
+    const int cbk = blockIdx.x, rb = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
+    const int n = w.n_sorted[b];
+    if (cbk < rb || rb * 64 >= n || cbk * 64 >= n) return;
+    const size_t sb = (size_t)b * w.caps;
+    const int j = cbk * 64 + t;
+    if (j < n) {
+        const float* x = w.sbox + (sb + j) * 6;
+        for (int c = 0; c < 6; ++c) cb[t][c] = x[c];
+        cb[t][6] = box_area(x);
+        cl[t] = w.slabel[sb + j];
+    }
+    __syncthreads();
+    const int i = rb * 64 + t;
+    if (i >= n) return;
+    float a[6];
+    const float* x = w.sbox + (sb + i) * 6;
+    for (int c = 0; c < 6; ++c) a[c] = x[c];
+    const float area = box_area(a);
+    const long long la = w.slabel[sb + i];
+    const int ncol = min(64, n - cbk * 64);
+    unsigned long long bits = 0;
+    for (int jj = 0; jj < ncol; ++jj)
+        if (cbk * 64 + jj > i && suppresses(a, area, la, cb[jj], cb[jj][6], cl[jj], thr)) bits |= 1ull << jj;
+    w.mask[(sb + i) * w.words + cbk] = bits;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- greedy walk
+__device__ __forceinline__ unsigned long long readlane64(unsigned long long v, int lane) {
+    const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, lane), hi = __builtin_amdgcn_readlane((unsigned)(v >> 32), lane);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// Boxes 64 at a time: every wave loads the block's diagonal mask words (lane j: row 64 w + j, word w) and walks them with the
+// block's entry of the removed set (the same decisions in every wave); the workgroup then ORs the kept rows into the removed
+// words behind the block.  Head route: converted boxes, scores, labels and the padding; standalone: the input indices.
+__global__ __launch_bounds__(kScanThreads) void detect_scan_kernel(Work w, float* out_boxes, float* out_scores, long long* out_labels,
+                                                                   long long* out_index, int* out_count, int nmax) {
+    __shared__ unsigned long long removed[kLimit / 64];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = w.n_sorted[b];
+    const size_t sb = (size_t)b * w.caps;
+    const int W = n > 0 ? (n + 63) / 64 : 0;
+    for (int q = tid; q < W; q += kScanThreads) removed[q] = 0;
+    __syncthreads();
+    int kept = 0;
+    unsigned long long diag = (W > 0 && lane < n) ? w.mask[(sb + lane) * w.words] : 0ull;
+    for (int blk = 0; blk < W; ++blk) {
+        const int nb = min(64, n - blk * 64);
+        unsigned long long rem = removed[blk];
+        if (nb < 64) rem |= ~0ull << nb;
+        const unsigned long long row = diag;
+        if (blk + 1 < W) {   // next block's diagonal words: they do not depend on this block's decisions
+            const int i = (blk + 1) * 64 + lane;
+            diag = i < n ? w.mask[(sb + i) * w.words + blk + 1] : 0ull;
+        }
+        unsigned long long keptmask = 0, todo = ~rem;
+        while (todo) {
+            const int j = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
+            keptmask |= 1ull << j;
+            rem |= readlane64(row, j);
+            todo = j == 63 ? 0ull : (~rem & (~0ull << (j + 1)));
+        }
+        const int later = W - blk - 1;
+        for (int pq = tid; pq < 64 * later; pq += kScanThreads) {
+            const int j = pq / later, qw = blk + 1 + pq % later;
+            if ((keptmask >> j) & 1ull) {
+                const unsigned long long v = w.mask[(sb + blk * 64 + j) * w.words + qw];
+                if (v) atomicOr(&removed[qw], v);
+            }
+        }
+        if (wave == 0 && ((keptmask >> lane) & 1ull)) {
+            const int k = kept + __popcll(keptmask & ((1ull << lane) - 1ull));
+            const size_t r = sb + blk * 64 + lane;
+            if (out_index) {
+                out_index[(size_t)b * nmax + k] = w.sidx[r];
+            } else {
+                const float* x = w.sbox + r * 6;
+                float* o = out_boxes + ((size_t)b * nmax + k) * 6;
+                o[0] = (x[0] + x[3]) / 2.f;
+                o[1] = (x[1] + x[4]) / 2.f;
+                o[2] = (x[2] + x[5]) / 2.f;
+                o[3] = x[3] - x[0];
+                o[4] = x[4] - x[1];
+                o[5] = x[5] - x[2];
+                out_scores[(size_t)b * nmax + k] = w.sscore[r];
+                out_labels[(size_t)b * nmax + k] = w.slabel[r];
+            }
+        }
+        kept += __popcll(keptmask);
+        __syncthreads();
+    }
+    if (!out_index) {
+        for (int k = kept + tid; k < nmax; k += kScanThreads) {
+            float* o = out_boxes + ((size_t)b * nmax + k) * 6;
+            for (int c = 0; c < 6; ++c) o[c] = 0.f;
+            out_scores[(size_t)b * nmax + k] = 0.f;
+            out_labels[(size_t)b * nmax + k] = 0;
+        }
+    }
+    if (tid == 0) out_count[b] = n < 0 ? n : kept;
+}
+
+size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// workspace layout; returns the bytes needed (Work pointers filled when base != nullptr)
+size_t carve(void* base, int B, int points, int ncap, Work* w) {
+    const int caps = std::min(ncap, kLimit), words = (caps + 63) / 64;
+    size_t off = 0;
+    char* p = static_cast<char*>(base);
+    auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += align256(bytes); return r; };
+    Work t{};
+    t.seg_count = reinterpret_cast<int*>(take((size_t)B * kMaxL * 4));
+    t.n_sorted = reinterpret_cast<int*>(take((size_t)B * 4));
+    t.pscore = reinterpret_cast<float*>(take((size_t)B * points * 4));
+    t.plabel = reinterpret_cast<int*>(take((size_t)B * points * 4));
+    t.cbox = reinterpret_cast<float*>(take((size_t)B * ncap * 24));
+    t.cscore = reinterpret_cast<float*>(take((size_t)B * ncap * 4));
+    t.clabel = reinterpret_cast<long long*>(take((size_t)B * ncap * 8));
+    t.sbox = reinterpret_cast<float*>(take((size_t)B * caps * 24));
+    t.sscore = reinterpret_cast<float*>(take((size_t)B * caps * 4));
+    t.slabel = reinterpret_cast<long long*>(take((size_t)B * caps * 8));
+    t.sidx = reinterpret_cast<int*>(take((size_t)B * caps * 4));
+    t.mask = reinterpret_cast<unsigned long long*>(take((size_t)B * caps * words * 8));
+    t.points = points;
+    t.ncap = ncap;
+    t.caps = caps;
+    t.words = words;
+    if (w) *w = t;
+    return off;
+}
+
+// sort, mask and walk of the candidate lists in `w` (segments and counts written by the first launch)
+int sort_mask_scan(const Work& w, const SortParams& q, int B, float thr, float* out_boxes, float* out_scores, long long* out_labels,
+                   long long* out_index, int* out_count, int nmax, hipStream_t stream, const char* name) {
+    int pmax = 1;
+    while (pmax < std::max(w.caps, 1)) pmax <<= 1;
+    const size_t lds = (size_t)pmax * 8 + (2 * kMaxL + 1) * 4;
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(detect_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+            hipSuccess) {
+        set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed", name);
+        return MVSDET_ERR_HIP;
+    }
+    hipLaunchKernelGGL(detect_sort_kernel, dim3(B), dim3(kSortThreads), lds, stream, q, w, pmax);
+    if (w.words > 0) hipLaunchKernelGGL(detect_mask_kernel, dim3(w.words, w.words, B), dim3(64), 0, stream, w, thr);
+    hipLaunchKernelGGL(detect_scan_kernel, dim3(B), dim3(kScanThreads), 0, stream, w, out_boxes, out_scores, out_labels, out_index,
+                       out_count, nmax);
+    MVS_LAUNCH_CHECK(name);
+    return MVSDET_OK;
+}
+
+}  // namespace
+}  // namespace mvsdet
+
+using namespace mvsdet;
+
+extern "C" size_t mvsdet_detect_workspace_bytes(int B, int points, int ncap) {
+    if (B <= 0 || points < 0 || ncap < 0) return 0;
+    return carve(nullptr, B, points, ncap, nullptr);
+}
+
+extern "C" int mvsdet_detect_head_f32(const float* const* center, const float* const* bbox, const float* const* cls,
+                                      const int* level_dims, const float* valid, const float* level_geom, int B, int L, int n_classes,
+                                      int VX, int VY, int VZ, int nms_pre, float score_thr, float iou_thr, float* out_boxes,
+                                      float* out_scores, int64_t* out_labels, int* out_count, int nmax, void* workspace,
+                                      size_t workspace_bytes, mvsdet_stream_t stream) {
+    const char* name = "detect_head";
+    MVS_REQUIRE(center && bbox && cls && level_dims && valid && level_geom && out_boxes && out_scores && out_labels && out_count,
+                "%s: NULL pointer", name);
+    MVS_REQUIRE(B >= 1 && B <= 65535, "%s: bad shape B=%d", name, B);
+    MVS_REQUIRE(L >= 1 && L <= MVSDET_DETECT_MAX_LEVELS, "%s: bad shape L=%d (1..%d levels)", name, L, MVSDET_DETECT_MAX_LEVELS);
+    MVS_REQUIRE(n_classes >= 1 && n_classes <= 1024, "%s: bad shape n_classes=%d", name, n_classes);
+    MVS_REQUIRE(VX > 0 && VY > 0 && VZ > 0 && (long long)VX * VY * VZ < (1 << 26), "%s: bad shape valid %dx%dx%d", name, VX, VY, VZ);
+    MVS_REQUIRE(nms_pre >= 0, "%s: nms_pre=%d < 0", name, nms_pre);
+    SelectParams p{};
+    SortParams q{};
+    long long points = 0, ncap = 0;
+    for (int l = 0; l < L; ++l) {
+        MVS_REQUIRE(center[l] && bbox[l] && cls[l], "%s: NULL pointer (level %d)", name, l);
+        const int X = level_dims[3 * l], Y = level_dims[3 * l + 1], Z = level_dims[3 * l + 2];
+        MVS_REQUIRE(X > 0 && Y > 0 && Z > 0 && (long long)X * Y * Z < (1 << 24), "%s: bad shape level %d: %dx%dx%d", name, l, X, Y, Z);
+        const int N = X * Y * Z;
+        DetLevel& lv = p.lv[l];
+        lv.center = center[l];
+        lv.bbox = bbox[l];
+        lv.cls = cls[l];
+        lv.X = X;
+        lv.Y = Y;
+        lv.Z = Z;
+        lv.k = (N > nms_pre && nms_pre > 0) ? nms_pre : 0;
+        lv.seg_off = (int)ncap;
+        lv.pt_off = (int)points;
+        lv.sx = (float)VX / (float)X;
+        lv.sy = (float)VY / (float)Y;
+        lv.sz = (float)VZ / (float)Z;
+        q.seg_off[l] = (int)ncap;
+        points += N;
+        ncap += lv.k > 0 ? lv.k : N;
+    }
+    MVS_REQUIRE((long long)B * points < (1ll << 31) && (long long)B * ncap < (1ll << 31), "%s: bad shape: %d scenes x %lld points", name,
+                B, points);
+    const int caps = (int)std::min<long long>(ncap, kLimit);
+    MVS_REQUIRE(nmax >= caps, "%s: Nmax=%d < %d, the most boxes a scene can keep here (min(candidates, %d))", name, nmax, caps, kLimit);
+    const size_t need = mvsdet_detect_workspace_bytes(B, (int)points, (int)ncap);
+    if (!workspace || workspace_bytes < need) {
+        set_error("%s: workspace of %zu bytes, %zu needed (mvsdet_detect_workspace_bytes)", name, workspace_bytes, need);
+        return MVSDET_ERR_WORKSPACE;
+    }
+    Work w;
+    carve(workspace, B, (int)points, (int)ncap, &w);
+    p.valid = valid;
+    p.geom = level_geom;
+    p.L = L;
+    p.C = n_classes;
+    p.VX = VX;
+    p.VY = VY;
+    p.VZ = VZ;
+    p.score_thr = score_thr;
+    q.L = L;
+    hipLaunchKernelGGL(detect_select_kernel, dim3(L, B), dim3(kSelThreads), 0, (hipStream_t)stream, p, w);
+    return sort_mask_scan(w, q, B, iou_thr, out_boxes, out_scores, reinterpret_cast<long long*>(out_labels), nullptr, out_count, nmax,
+                          (hipStream_t)stream, name);
+}
+
+extern "C" int mvsdet_aligned_3d_nms_f32(const float* boxes, const float* scores, const int64_t* classes, int n, float thresh,
+                                         int64_t* out_index, int* out_count, void* workspace, size_t workspace_bytes,
+                                         mvsdet_stream_t stream) {
+    const char* name = "aligned_3d_nms";
+    MVS_REQUIRE(out_index && out_count, "%s: NULL pointer", name);
+    MVS_REQUIRE(n >= 0, "%s: bad shape n=%d", name, n);
+    MVS_REQUIRE(n <= MVSDET_DETECT_MAX_CANDIDATES, "%s: n=%d boxes above the candidate limit MVSDET_DETECT_MAX_CANDIDATES=%d", name, n,
+                MVSDET_DETECT_MAX_CANDIDATES);
+    MVS_REQUIRE(n == 0 || (boxes && scores && classes), "%s: NULL pointer", name);
+    const size_t need = mvsdet_detect_workspace_bytes(1, 0, n);
+    if (!workspace || workspace_bytes < need) {
+        set_error("%s: workspace of %zu bytes, %zu needed (mvsdet_detect_workspace_bytes)", name, workspace_bytes, need);
+        return MVSDET_ERR_WORKSPACE;
+    }
+    Work w;
+    carve(workspace, 1, 0, n, &w);
+    SortParams q{};
+    q.L = 1;
+    hipLaunchKernelGGL(detect_load_kernel, dim3(std::max(1, (n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, boxes, scores,
+                       reinterpret_cast<const long long*>(classes), n, w);
+    return sort_mask_scan(w, q, 1, thresh, nullptr, nullptr, nullptr, reinterpret_cast<long long*>(out_index), out_count, std::max(n, 1),
+                          (hipStream_t)stream, name);
+}

@@ -7,8 +7,9 @@
                                               ImVoxelHead_ARKit: exp(scale_l(.)) on the 6 distances, the angle channel raw
     cls        = conv_cls(x)                  Conv3d(C -> n_classes,  k=3, p=1, bias)
 
-Target assignment, the losses and NMS (nerfdet_head.py:120 ff.) are detection logic outside the path and stay the
-reference's.  Parameter names equal the reference's (`conv_center.weight`, `conv_reg.weight`, `conv_cls.weight/bias`,
+Target assignment and the losses (nerfdet_head.py:120 ff.) are training logic outside the path and stay the reference's.
+`predict_by_feat` (nerfdet_head.py:301-420, 564-628: scores, top-k, decode, aligned 3-D NMS) runs on csrc/detect.hip for the
+ScanNet head (`ops.head_predict`); the ARKit head's rotated NMS is not provided.  Parameter names equal the reference's (`conv_center.weight`, `conv_reg.weight`, `conv_cls.weight/bias`,
 `scales.<l>.scale`), so a checkpoint's `bbox_head.*` entries load.
 
 1 + 6 + 18 = 25 output channels are no GEMM shape for a library (nine launches per scene).  In eval mode without
@@ -52,8 +53,9 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
     """The learnable layers of NerfDetHead and their forward pass (nerfdet_head.py:94-118)."""
 
     def __init__(self, n_classes: int = 18, n_levels: int = 3, n_channels: int = 128, n_reg_outs: int = 6,
-                 arkit_head: bool = False):
+                 arkit_head: bool = False, test_cfg=None):
         super().__init__()
+        self.test_cfg = test_cfg   # nms_pre, score_thr, iou_thr (mvsdet_res50_2x_low_res_depth.py:61): predict_by_feat
         self.n_classes, self.n_levels, self.n_reg_outs = n_classes, n_levels, n_reg_outs
         self.arkit_head = bool(arkit_head)   # ImVoxelHead_ARKit._forward_single (nerfdet_head.py:677-692)
         self.conv_center = nn.Conv3d(n_channels, 1, 3, padding=1, bias=False)
@@ -139,7 +141,77 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
             res = [self._forward_single(xi, s) for xi, s in zip(x, self.scales)]
         return tuple(map(list, zip(*res)))
 
+    def predict_by_feat(self, center_preds: List[List[Tensor]], bbox_preds: List[List[Tensor]], cls_preds: List[List[Tensor]],
+                        valid_pred: Tensor, batch_input_metas: List[dict], **kwargs) -> List["SceneDetections"]:
+        """NerfDetHead.predict_by_feat (nerfdet_head.py:301-420): boxes, scores and labels of every scene from the head's maps (per
+        level (B,...) tensors) and valid_pred = torch.stack(valids).float() (B,1,X,Y,Z), on the HIP kernels of csrc/detect.hip.
+        The selection is the reference's; equal scores are ordered by level, then voxel index (the reference's argsort leaves them
+        unordered).  One host sync per batch.  CUDA float32 maps only."""
+        if self.arkit_head:
+            raise NotImplementedError(
+                "predict_by_feat: ImVoxelHead_ARKit's 7-DoF boxes go through mmcv's rotated BEV nms3d (nerfdet_head.py:1190-1243), "
+                "whose source is not available to pin its semantics; only the ScanNet head's aligned 3-D NMS is provided")
+        pred = predict_head_maps(center_preds, bbox_preds, cls_preds, valid_pred, batch_input_metas, self.test_cfg)
+        return unpad_predictions(pred, batch_input_metas)
+
     @staticmethod
     def flops(grid: Sequence[int], n_classes: int = 18, n_levels: int = 3, n_channels: int = 128, n_reg_outs: int = 6) -> float:
         v = sum((grid[0] >> i) * (grid[1] >> i) * (grid[2] >> i) for i in range(n_levels))
         return 54.0 * n_channels * (1 + n_reg_outs + n_classes) * v
+
+
+def cfg_value(cfg, name: str):
+    """test_cfg.<name> of an mmengine ConfigDict, a dict or any object with the attribute."""
+    return cfg[name] if isinstance(cfg, dict) else getattr(cfg, name)
+
+
+def scene_origin(meta: dict):
+    """input_meta['lidar2img']['origin'] as the reference's torch.tensor(origin): float32 only (the dataset builds it so,
+    scannet_multiview_dataset.py:153-157; a float64 origin would make the reference decode the boxes in float64)."""
+    o = meta["lidar2img"]["origin"]
+    t = o if isinstance(o, Tensor) else torch.tensor(o)
+    if t.dtype != torch.float32:
+        raise ValueError(f"predict_by_feat: lidar2img['origin'] must be float32 (got {t.dtype}); the reference would decode "
+                         "the boxes in float64")
+    return t
+
+
+def predict_head_maps(center_preds, bbox_preds, cls_preds, valid_pred: Tensor, batch_input_metas, test_cfg) -> ops.HeadPrediction:
+    """The padded device result of predict_by_feat for the whole batch (no host sync): ops.head_predict with the test_cfg's values."""
+    if test_cfg is None:
+        raise ValueError("predict_by_feat: a test_cfg with nms_pre, score_thr and iou_thr is needed")
+    origins = [scene_origin(m) for m in batch_input_metas]
+    return ops.head_predict(center_preds, bbox_preds, cls_preds, valid_pred, origins, int(cfg_value(test_cfg, "nms_pre")),
+                            float(cfg_value(test_cfg, "score_thr")), float(cfg_value(test_cfg, "iou_thr")))
+
+
+class SceneDetections:
+    """mmengine's InstanceData as the reference fills it: bboxes_3d, scores_3d, labels_3d."""
+
+    def __init__(self, bboxes_3d, scores_3d: Tensor, labels_3d: Tensor):
+        self.bboxes_3d, self.scores_3d, self.labels_3d = bboxes_3d, scores_3d, labels_3d
+
+    def keys(self):
+        return ["bboxes_3d", "scores_3d", "labels_3d"]
+
+    def __len__(self):
+        return int(self.scores_3d.shape[0])
+
+    def __repr__(self):
+        return f"SceneDetections({len(self)} boxes)"
+
+
+def unpad_predictions(pred: ops.HeadPrediction, batch_input_metas) -> List[SceneDetections]:
+    """Per scene the first `count` rows (ONE host sync for the batch: the counts), boxed by meta['box_type_3d'] where given."""
+    counts = pred.counts.cpu().tolist()
+    results = []
+    for i, n in enumerate(counts):
+        if n < 0:
+            raise RuntimeError(f"predict_by_feat: scene {i} has {-n} boxes above score_thr, more than the candidate limit "
+                               f"{ops.DETECT_MAX_CANDIDATES} of one sort (MVSDET_DETECT_MAX_CANDIDATES)")
+        bboxes = pred.boxes[i, :n]
+        meta = batch_input_metas[i]
+        if "box_type_3d" in meta:
+            bboxes = meta["box_type_3d"](bboxes, box_dim=6, with_yaw=False, origin=(.5, .5, .5))
+        results.append(SceneDetections(bboxes, pred.scores[i, :n], pred.labels[i, :n]))
+    return results

@@ -227,7 +227,7 @@ class MVSDetHotPath:
                  num_monocular_samples: int, topk: int = 3,
                  cost_regularization: Optional[Callable[[Tensor], Tensor]] = None, stride: int = 4,
                  neck_3d: Optional[Callable[[Tensor], list]] = None,
-                 bbox_head: Optional[Callable[[list], tuple]] = None):
+                 bbox_head: Optional[Callable[[list], tuple]] = None, test_cfg=None):
         self.n_voxels = [int(v) for v in n_voxels]
         self.voxel_size = [float(v) for v in voxel_size]      # python floats -> torch.tensor(...) is fp32, as in the reference
         self.near_far_range = [float(v) for v in near_far_range]
@@ -242,6 +242,9 @@ class MVSDetHotPath:
         self.cost_regularization = cost_regularization
         self.neck_3d = neck_3d   # mvsdet.py:681-698: x = self.neck_3d(torch.stack(volumes)); SURVEY 8 f-3 (mvsdet_amd.neck)
         self.bbox_head = bbox_head   # nerfdet_head.py:116-118: the head's convolutions on the neck's levels (mvsdet_amd.head)
+        # opt-in: with a test_cfg (nms_pre, score_thr, iou_thr) and a ScanNet head, out["detections"] = the padded boxes of
+        # predict_by_feat (ops.HeadPrediction) made from out["head"] and out["valid"] on the stream the head ran on
+        self.test_cfg = test_cfg
         self._points_cache: dict = {}
         self._geo_streams: dict = {}
         self._geometry = _GeometryWorker(self)
@@ -602,6 +605,14 @@ class MVSDetHotPath:
             if isinstance(t, Tensor) and t.is_cuda:
                 t.record_stream(side)
 
+    def _detections(self, head_out, valid: Tensor, img_metas):
+        """predict_by_feat's padded device result (head.predict_head_maps) of the head's maps; the ARKit head has no NMS here."""
+        from .head import predict_head_maps
+        if getattr(self.bbox_head, "arkit_head", False):
+            raise NotImplementedError("MVSDetHotPath.test_cfg: detections are provided for the ScanNet head only (the ARKit head's "
+                                      "rotated BEV NMS is not)")
+        return predict_head_maps(*head_out, valid, img_metas, self.test_cfg)
+
     def forward_scene(self, feature: Tensor, img_meta: dict, cost_logits: Optional[Tensor] = None,
                       geo: Optional[SceneGeometry] = None) -> dict:
         """One scene through a1..a10.  `cost_logits` (N,2,D,Hf,Wf) stands in for the cost regularisation
@@ -625,6 +636,8 @@ class MVSDetHotPath:
                 out._put("neck", self.neck_3d(out.raw("volume").unsqueeze(0)))
                 if self.bbox_head is not None:
                     out._put("head", self.bbox_head(out.raw("neck")))   # (centerness, bbox, cls) lists over the levels
+                    if self.test_cfg is not None:
+                        out._put("detections", self._detections(out.raw("head"), out.raw("valid").unsqueeze(0), [img_meta]))
             return out
 
         if not on_side or (torch.is_grad_enabled() and cost_logits.requires_grad):
@@ -709,6 +722,8 @@ class MVSDetHotPath:
                     res._put("head", self.bbox_head(res.raw("neck")))
                     for i, o in enumerate(outs):
                         o._put("head", tuple([lvl[i:i + 1] for lvl in part] for part in res.raw("head")))
+                    if self.test_cfg is not None:
+                        res._put("detections", self._detections(res.raw("head"), res.raw("valid"), img_metas))
             return res
 
         if side is None:

@@ -116,3 +116,27 @@ def apply_on_import() -> bool:
             patch_reference(mod)
             done = True
     return done
+
+
+def patch_reference_head(head_module) -> dict:
+    """Opt-in (the import hook does not apply it): rebind `NerfDetHead.aligned_3d_nms` of an imported reference `nerfdet_head`
+    module so that its unmodified `predict` runs the NMS on the HIP kernel (ops.aligned_3d_nms) for CUDA tensors and on the
+    original static method for CPU tensors.  Returns {name: original} for `unpatch_reference_head`."""
+    from . import ops
+    cls = head_module.NerfDetHead
+    original = cls.__dict__["aligned_3d_nms"]
+    fallback = original.__func__ if isinstance(original, staticmethod) else original
+
+    def aligned_3d_nms(boxes, scores, classes, thresh):
+        if boxes.is_cuda:
+            return ops.aligned_3d_nms(boxes, scores, classes, thresh)
+        return fallback(boxes, scores, classes, thresh)
+
+    aligned_3d_nms.__doc__ = fallback.__doc__
+    cls.aligned_3d_nms = staticmethod(aligned_3d_nms)
+    return {"NerfDetHead.aligned_3d_nms": original}
+
+
+def unpatch_reference_head(head_module, originals: dict) -> None:
+    for name, fn in originals.items():
+        setattr(head_module.NerfDetHead, name.split(".", 1)[1], fn)
