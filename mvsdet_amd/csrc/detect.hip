@@ -4,7 +4,7 @@
 //   detect_select_kernel  one workgroup per (level, scene): upsampled valid mask, score = sigmoid(cls) * sigmoid(center) * valid, max
 //                         over classes, top-nms_pre by a radix select on the score bits, decode, score > score_thr; survivors are
 //                         appended in voxel order to the level's own segment of the scene's candidate list
-//   detect_sort_kernel    one workgroup per scene: bitonic sort in LDS of (score descending, candidate index ascending) keys
+//   detect_sort_kernel    one workgroup per scene: bitonic sort in LDS of (score descending, NaN first, candidate index ascending) keys
 //   detect_mask_kernel    grid of 64-row x 64-column tiles: the class-aware IoU suppression bit of every ordered pair (i, j > i)
 //   detect_scan_kernel    one workgroup per scene: the greedy walk 64 boxes at a time, kept boxes written in pick order
 //
@@ -232,9 +232,12 @@ __global__ void detect_load_kernel(const float* __restrict__ boxes, const float*
 }
 
 // ---------------------------------------------------------------------------------------------------------------- sort
-// float -> unsigned with the same order (NaN above +inf, as torch.sort places it)
+// float -> unsigned with the same order: every NaN, whatever its sign and payload, one key above +inf (torch.sort places NaN
+// last, so the reference's greedy loop visits it first); -0 the key of +0, so equal scores fall back to the index
 __device__ __forceinline__ unsigned order_bits(float f) {
-    const unsigned u = __float_as_uint(f);
+    if (f != f) return 0xffffffffu;
+    unsigned u = __float_as_uint(f);
+    if (u == 0x80000000u) u = 0u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 

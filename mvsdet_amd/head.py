@@ -145,8 +145,9 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
                         valid_pred: Tensor, batch_input_metas: List[dict], **kwargs) -> List["SceneDetections"]:
         """NerfDetHead.predict_by_feat (nerfdet_head.py:301-420): boxes, scores and labels of every scene from the head's maps (per
         level (B,...) tensors) and valid_pred = torch.stack(valids).float() (B,1,X,Y,Z), on the HIP kernels of csrc/detect.hip.
-        The selection is the reference's; equal scores are ordered by level, then voxel index (the reference's argsort leaves them
-        unordered).  One host sync per batch.  CUDA float32 maps only."""
+        The selection is the reference's; the walk visits NaN scores first whatever their sign, takes -0 and +0 as equal, and
+        orders equal scores by level, then voxel index (the reference's argsort leaves them unordered).  One host sync per batch.
+        CUDA float32 maps only."""
         if self.arkit_head:
             raise NotImplementedError(
                 "predict_by_feat: ImVoxelHead_ARKit's 7-DoF boxes go through mmcv's rotated BEV nms3d (nerfdet_head.py:1190-1243), "

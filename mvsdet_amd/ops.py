@@ -1931,7 +1931,8 @@ def head_predict(center_preds, bbox_preds, cls_preds, valid_pred: Tensor, origin
     """The ScanNet head's predict_by_feat up to the boxes, for every scene of the batch, on the current stream without a host sync.
     center_preds / bbox_preds / cls_preds: per level (B,1|6|C,X,Y,Z) float32; valid_pred (B,1,X,Y,Z): the stacked view counts (any
     dtype; taken as float, as the reference's torch.stack(valids).float()); origins: one float32 (3,) origin per scene.
-    Kept boxes of a scene in pick order; order of equal scores: level, then voxel index."""
+    Kept boxes of a scene in pick order.  Visiting order of the walk: NaN scores first, whatever their sign; -0 and +0 equal; equal
+    scores by level, then voxel index.  (The head's scores are >= +0 and a NaN never passes score_thr.)"""
     L = len(center_preds)
     if not (1 <= L <= DETECT_MAX_LEVELS) or len(bbox_preds) != L or len(cls_preds) != L:
         raise ValueError(f"head_predict: 1..{DETECT_MAX_LEVELS} levels of center / bbox / cls maps needed")
@@ -1978,7 +1979,8 @@ def head_predict(center_preds, bbox_preds, cls_preds, valid_pred: Tensor, origin
 def aligned_3d_nms(boxes: Tensor, scores: Tensor, classes: Tensor, thresh: float) -> Tensor:
     """NerfDetHead.aligned_3d_nms (nerfdet_head.py:580-628): boxes (n,6) (x1,y1,z1,x2,y2,z2), scores (n,), classes (n,) ->
     the kept indices in pick order (LongTensor).  CUDA float32 only; n <= DETECT_MAX_CANDIDATES.  Reads the kept count back
-    (one host sync, as the reference's loop syncs on every box).  Order of equal scores: lower index first."""
+    (one host sync, as the reference's loop syncs on every box).  Visiting order: NaN scores first, whatever their sign (the
+    reference's argsort puts NaN last and its loop takes from the end); -0 and +0 equal; equal scores by lower index first."""
     _req(boxes, "boxes", dim=2)
     _req(scores, "scores", dim=1)
     if not classes.is_cuda:

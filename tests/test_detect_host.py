@@ -16,7 +16,9 @@ from conftest import GOLDEN, load_golden
 
 # --------------------------------------------------------------------------------------------- the greedy walk, restated
 def nms_restated(boxes, scores, classes, thresh):
-    """aligned_3d_nms in float32 NumPy: visit the boxes by score (highest first, equal scores by lower index); keep a box that
+    """aligned_3d_nms in float32 NumPy: visit the boxes by score (highest first; NaN of either sign above +inf, as the
+    reference's argsort places it last and its loop takes from the end; NaNs equal to each other, -0 equal to +0; equal scores by
+    lower index); keep a box that
     no kept box has removed; remove every later box j with NOT (iou <= thresh), where the IoU is zeroed for another class and
     written with the reference's association: ((l * w) * h) / ((area_i + area_j) - inter).  A NaN IoU (empty or infinite boxes)
     therefore removes, also across classes.  Returns the kept indices in pick order."""
@@ -26,7 +28,8 @@ def nms_restated(boxes, scores, classes, thresh):
     t = np.float32(thresh)
     lo, hi = b[:, :3], b[:, 3:]
     area = ((hi[:, 0] - lo[:, 0]) * (hi[:, 1] - lo[:, 1])) * (hi[:, 2] - lo[:, 2])
-    order = np.lexsort((np.arange(len(s)), -s))
+    nan = np.isnan(s)
+    order = np.lexsort((np.arange(len(s)), -np.where(nan, np.float32(0), s), ~nan))
     picks = []
     with np.errstate(invalid="ignore", over="ignore"):
         while order.size:
@@ -212,6 +215,26 @@ def test_restatement_on_a_small_hand_case():
     assert nms_restated(boxes, scores, classes, .5).tolist() == [0, 1, 2, 3]
 
 
+def f32_bits(*words):
+    return np.array(words, np.uint32).view(np.float32)
+
+
+NEG_NAN, POS_NAN = f32_bits(0xffc00000)[0], f32_bits(0x7fc00000)[0]   # torch.zeros(1) / 0 on x86 is the first
+
+
+def test_restatement_orders_nan_zero_and_inf():
+    # disjoint boxes, so every box is kept and the pick order is the visiting order: NaN of either sign first (by index), +inf,
+    # the finite scores, -0 and +0 as equals (by index), -inf last
+    boxes = np.array([[3 * i, 0, 0, 3 * i + 1, 1, 1] for i in range(8)], np.float32)
+    scores = np.array([.5, NEG_NAN, 0., -0., np.inf, -np.inf, POS_NAN, .5], np.float32)
+    assert nms_restated(boxes, scores, np.zeros(8), .25).tolist() == [1, 6, 4, 0, 7, 2, 3, 5]
+    assert nms_restated(boxes, scores[::-1].copy(), np.zeros(8), .25).tolist() == [1, 6, 3, 0, 7, 4, 5, 2]
+    # the two cases of identical same-class boxes: the NaN-scored one is the reference's pick; -0 and +0 tie, index 0 first
+    same = np.array([[0, 0, 0, 1, 1, 1]] * 2, np.float32)
+    assert nms_restated(same, np.array([.5, NEG_NAN], np.float32), [0, 0], .25).tolist() == [1]
+    assert nms_restated(same, np.array([-0., 0.], np.float32), [0, 0], .25).tolist() == [0]
+
+
 # --------------------------------------------------------------------------------------------- against the reference
 @pytest.fixture(scope="module")
 def reference_predict():
@@ -246,3 +269,41 @@ def test_g15_regenerates(reference_predict):
             assert np.array_equal(rs.bboxes_3d.numpy(), gold[f"{name}:{i}:boxes"]), name
             assert np.array_equal(rs.scores_3d.numpy(), gold[f"{name}:{i}:scores"]), name
             assert np.array_equal(rs.labels_3d.numpy(), gold[f"{name}:{i}:labels"]), name
+
+
+@pytest.mark.refcheck
+@pytest.mark.parametrize("nan", ["+nan", "-nan"])
+@pytest.mark.parametrize("n,n_classes", [(2, 1), (9, 2), (16, 1), (300, 1), (300, 18)])
+def test_restatement_matches_reference_nms_with_a_nan(reference_predict, nan, n, n_classes):
+    # distinct scores but one NaN: no ties, so the reference's order does not hang on its sort being stable
+    _, RefPredict = reference_predict
+    b, s, c = nms_case(n, n_classes, 200 + n)
+    s[n // 2] = NEG_NAN if nan == "-nan" else POS_NAN
+    b[n // 2] = b[0]                      # the NaN-scored box overlaps box 0: it is picked first and removes box 0 (same class)
+    c[n // 2] = c[0]
+    for thresh in (.25, 1.0):
+        ref = RefPredict.aligned_3d_nms(torch.from_numpy(b), torch.from_numpy(s), torch.from_numpy(c), thresh)
+        want = nms_restated(b, s, c, thresh)
+        assert ref.tolist() == want.tolist()
+        assert want[0] == n // 2
+
+
+@pytest.mark.refcheck
+@pytest.mark.parametrize("name", ["l1_c18", "l4_ragged_c40_b3_pre440", "l4_ragged_c1_pre439", "l4_ragged_c2_b3_pre441",
+                                  "l2_larger_than_valid_c2_pre0", "l2_larger_than_valid_c18_b3_pre1", "l3_scannet_c40_b3_pre1000"])
+def test_head_restatement_matches_reference(reference_predict, name):
+    # tests/detect_restated.predict (the GPU tests' yardstick) against the reference's predict_by_feat, both on the CPU: counts,
+    # labels and pick order equal, boxes and scores bit for bit, at the level counts, shapes and class counts of family (a)
+    import detect_restated as R
+    g, RefPredict = reference_predict
+    (c, r, k, v, origins), nms_pre = R.case_a(name)
+    assert not R.near_decisions(c, r, k, v, origins, nms_pre, R.SCORE_THR, R.IOU_THR), name
+    cfg = types.SimpleNamespace(nms_pre=nms_pre, score_thr=R.SCORE_THR, iou_thr=R.IOU_THR)
+    with torch.no_grad():
+        ref = RefPredict(cfg).predict_by_feat(c, r, k, v, g.metas_for(origins))
+    want = R.predict(c, r, k, v, origins, nms_pre, R.SCORE_THR, R.IOU_THR)
+    for i, (rs, w) in enumerate(zip(ref, want)):
+        assert len(rs.scores_3d) == w["count"] > 0, (name, i)
+        assert np.array_equal(rs.labels_3d.numpy(), w["labels"]), (name, i)
+        assert np.array_equal(rs.bboxes_3d.numpy().view(np.uint32), w["boxes"].view(np.uint32)), (name, i)
+        assert np.array_equal(rs.scores_3d.numpy().view(np.uint32), w["scores"].view(np.uint32)), (name, i)
