@@ -609,6 +609,34 @@ int mvsdet_detect_head_f32(const float* const* center, const float* const* bbox,
 int mvsdet_aligned_3d_nms_f32(const float* boxes, const float* scores, const int64_t* classes, int n, float thresh,
                               int64_t* out_index, int* out_count, void* workspace, size_t workspace_bytes, mvsdet_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Detection post-processing of the ARKit head (ImVoxelHead_ARKit.predict_by_feat / _single_scene_multiclass_nms / mmcv's nms3d,
+ * nerfdet_head.py:902-1056, 1190-1243) on the caller's stream, no host synchronisation (csrc/detect.hip).  fp32; labels int64.
+ *
+ * mvsdet_detect_head_rotated_f32: the arguments of mvsdet_detect_head_f32, with bbox maps of 7 channels (six distances and the
+ *   angle) and n_classes <= 256, B * n_classes <= 65535.  Every top-k point is decoded into a (x, y, z, dx, dy, dz, heading) box;
+ *   each of its classes with a score > score_thr puts it into the scene's segment of that class; nms3d runs per segment (order: the
+ *   class score descending, ties by level, then voxel index).  Outputs padded to Nmax >= n_classes * min(ncap,
+ *   MVSDET_DETECT_MAX_CANDIDATES): out_boxes (B,Nmax,7), out_scores (B,Nmax), out_labels (B,Nmax), out_count (B) int32, class-major
+ *   (classes ascending, each in pick order); rows past a scene's count are zero.  A scene with more than
+ *   MVSDET_DETECT_MAX_CANDIDATES boxes above score_thr in one class gets out_count = -(the largest such number) and no boxes.
+ * mvsdet_nms3d_f32: mmcv's nms3d of one class: boxes (n,7), scores (n) -> out_index (n) int64 = the kept indices in pick order,
+ *   out_count (1) int32; suppression where iou_bev(kept, later) > thresh; n <= MVSDET_DETECT_MAX_CANDIDATES.
+ * mvsdet_bev_iou_rotated_f32: out (n,m) = iou_bev(a[i], b[j]) of boxes (n,7) and (m,7): the device function of both calls above.
+ * mvsdet_detect_rotated_workspace_bytes(B, points, ncap, n_classes): the workspace of either NMS call (standalone: B = 1,
+ *   points = 0, ncap = n, n_classes = 1); each region rounded up to 256 bytes, S = B*n_classes, caps = min(ncap, limit):
+ *   3 * S*4 + B*points*4 + B*ncap*28 + S*ncap*4 + S*caps*(4+28+4+4+56+4) (six regions) + S*caps*ceil(caps/64)*8.
+ * ------------------------------------------------------------------------------------------- */
+size_t mvsdet_detect_rotated_workspace_bytes(int B, int points, int ncap, int n_classes);
+int mvsdet_detect_head_rotated_f32(const float* const* center, const float* const* bbox, const float* const* cls,
+                                   const int* level_dims, const float* valid, const float* level_geom, int B, int L, int n_classes,
+                                   int VX, int VY, int VZ, int nms_pre, float score_thr, float iou_thr, float* out_boxes,
+                                   float* out_scores, int64_t* out_labels, int* out_count, int nmax, void* workspace,
+                                   size_t workspace_bytes, mvsdet_stream_t stream);
+int mvsdet_nms3d_f32(const float* boxes, const float* scores, int n, float thresh, int64_t* out_index, int* out_count,
+                     void* workspace, size_t workspace_bytes, mvsdet_stream_t stream);
+int mvsdet_bev_iou_rotated_f32(const float* a, int n, const float* b, int m, float* out, mvsdet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,8 +9,9 @@
 
 Target assignment and the losses (nerfdet_head.py:120 ff.) are training logic outside the path and stay the reference's.
 `predict_by_feat` (nerfdet_head.py:301-420, 564-628: scores, top-k, decode, aligned 3-D NMS) runs on csrc/detect.hip for the
-ScanNet head (`ops.head_predict`); the ARKit head's rotated NMS is not provided.  Parameter names equal the reference's (`conv_center.weight`, `conv_reg.weight`, `conv_cls.weight/bias`,
-`scales.<l>.scale`), so a checkpoint's `bbox_head.*` entries load.
+ScanNet head (`ops.head_predict`), and for the ARKit head (:902-1056, 1190-1243: all class scores of a top-k point, rotated decode,
+mmcv's nms3d per class) on its rotated kernels (`ops.head_predict_rotated`).  Parameter names equal the reference's
+(`conv_center.weight`, `conv_reg.weight`, `conv_cls.weight/bias`, `scales.<l>.scale`), so a checkpoint's `bbox_head.*` entries load.
 
 1 + 6 + 18 = 25 output channels are no GEMM shape for a library (nine launches per scene).  In eval mode without
 autograd, on a ROCm device, the three convolutions of a level run as ONE 3x3x3 MFMA convolution whose 64 output channels
@@ -147,12 +148,17 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
         level (B,...) tensors) and valid_pred = torch.stack(valids).float() (B,1,X,Y,Z), on the HIP kernels of csrc/detect.hip.
         The selection is the reference's; the walk visits NaN scores first whatever their sign, takes -0 and +0 as equal, and
         orders equal scores by level, then voxel index (the reference's argsort leaves them unordered).  One host sync per batch.
-        CUDA float32 maps only."""
-        if self.arkit_head:
+        CUDA float32 maps only.
+        ARKit head (ImVoxelHead_ARKit.predict_by_feat, nerfdet_head.py:902-1056, 1190-1243): 7-DoF boxes (x, y, z, dx, dy, dz,
+        heading), class-major, per class in mmcv nms3d's pick order (equal class scores by level, then voxel index), boxed with
+        box_dim=7, with_yaw=True.  Labels are int64 also for a scene without boxes, where the reference returns float32
+        new_zeros((0,)).  Maps that are not on a ROCm device raise NotImplementedError: mmcv's nms3d has no CPU path either."""
+        if self.arkit_head and not all(t.is_cuda for t in center_preds):
             raise NotImplementedError(
                 "predict_by_feat: ImVoxelHead_ARKit's 7-DoF boxes go through mmcv's rotated BEV nms3d (nerfdet_head.py:1190-1243), "
-                "whose source is not available to pin its semantics; only the ScanNet head's aligned 3-D NMS is provided")
-        pred = predict_head_maps(center_preds, bbox_preds, cls_preds, valid_pred, batch_input_metas, self.test_cfg)
+                "which runs on ROCm tensors only (ops.nms3d); there is no CPU path")
+        pred = predict_head_maps(center_preds, bbox_preds, cls_preds, valid_pred, batch_input_metas, self.test_cfg,
+                                 rotated=self.arkit_head)
         return unpad_predictions(pred, batch_input_metas)
 
     @staticmethod
@@ -177,12 +183,14 @@ def scene_origin(meta: dict):
     return t
 
 
-def predict_head_maps(center_preds, bbox_preds, cls_preds, valid_pred: Tensor, batch_input_metas, test_cfg) -> ops.HeadPrediction:
-    """The padded device result of predict_by_feat for the whole batch (no host sync): ops.head_predict with the test_cfg's values."""
+def predict_head_maps(center_preds, bbox_preds, cls_preds, valid_pred: Tensor, batch_input_metas, test_cfg,
+                      rotated: bool = False) -> ops.HeadPrediction:
+    """The padded device result of predict_by_feat for the whole batch (no host sync): ops.head_predict (ARKit head, `rotated`:
+    ops.head_predict_rotated) with the test_cfg's values."""
     if test_cfg is None:
         raise ValueError("predict_by_feat: a test_cfg with nms_pre, score_thr and iou_thr is needed")
     origins = [scene_origin(m) for m in batch_input_metas]
-    return ops.head_predict(center_preds, bbox_preds, cls_preds, valid_pred, origins, int(cfg_value(test_cfg, "nms_pre")),
+    return (ops.head_predict_rotated if rotated else ops.head_predict)(center_preds, bbox_preds, cls_preds, valid_pred, origins, int(cfg_value(test_cfg, "nms_pre")),
                             float(cfg_value(test_cfg, "score_thr")), float(cfg_value(test_cfg, "iou_thr")))
 
 
@@ -203,16 +211,19 @@ class SceneDetections:
 
 
 def unpad_predictions(pred: ops.HeadPrediction, batch_input_metas) -> List[SceneDetections]:
-    """Per scene the first `count` rows (ONE host sync for the batch: the counts), boxed by meta['box_type_3d'] where given."""
+    """Per scene the first `count` rows (ONE host sync for the batch: the counts), boxed by meta['box_type_3d'] where given
+    (box_dim 6 without yaw, or 7 with yaw for the ARKit head's boxes)."""
     counts = pred.counts.cpu().tolist()
     results = []
     for i, n in enumerate(counts):
         if n < 0:
-            raise RuntimeError(f"predict_by_feat: scene {i} has {-n} boxes above score_thr, more than the candidate limit "
+            raise RuntimeError(f"predict_by_feat: scene {i} has {-n} boxes above score_thr (in one class, for the ARKit head), "
+                               f"more than the candidate limit "
                                f"{ops.DETECT_MAX_CANDIDATES} of one sort (MVSDET_DETECT_MAX_CANDIDATES)")
         bboxes = pred.boxes[i, :n]
         meta = batch_input_metas[i]
         if "box_type_3d" in meta:
-            bboxes = meta["box_type_3d"](bboxes, box_dim=6, with_yaw=False, origin=(.5, .5, .5))
+            dim = int(bboxes.shape[-1])   # 7: the ARKit head's boxes with their heading
+            bboxes = meta["box_type_3d"](bboxes, box_dim=dim, with_yaw=dim == 7, origin=(.5, .5, .5))
         results.append(SceneDetections(bboxes, pred.scores[i, :n], pred.labels[i, :n]))
     return results

@@ -242,8 +242,9 @@ class MVSDetHotPath:
         self.cost_regularization = cost_regularization
         self.neck_3d = neck_3d   # mvsdet.py:681-698: x = self.neck_3d(torch.stack(volumes)); SURVEY 8 f-3 (mvsdet_amd.neck)
         self.bbox_head = bbox_head   # nerfdet_head.py:116-118: the head's convolutions on the neck's levels (mvsdet_amd.head)
-        # opt-in: with a test_cfg (nms_pre, score_thr, iou_thr) and a ScanNet head, out["detections"] = the padded boxes of
-        # predict_by_feat (ops.HeadPrediction) made from out["head"] and out["valid"] on the stream the head ran on
+        # opt-in: with a test_cfg (nms_pre, score_thr, iou_thr), out["detections"] = the padded boxes of predict_by_feat
+        # (ops.HeadPrediction; 7-wide and class-major for a head with `arkit_head`) made from out["head"] and out["valid"] on the
+        # stream the head ran on
         self.test_cfg = test_cfg
         self._points_cache: dict = {}
         self._geo_streams: dict = {}
@@ -606,12 +607,10 @@ class MVSDetHotPath:
                 t.record_stream(side)
 
     def _detections(self, head_out, valid: Tensor, img_metas):
-        """predict_by_feat's padded device result (head.predict_head_maps) of the head's maps; the ARKit head has no NMS here."""
+        """predict_by_feat's padded device result (head.predict_head_maps) of the head's maps; the ARKit head's through its
+        rotated NMS (7-wide boxes, class-major)."""
         from .head import predict_head_maps
-        if getattr(self.bbox_head, "arkit_head", False):
-            raise NotImplementedError("MVSDetHotPath.test_cfg: detections are provided for the ScanNet head only (the ARKit head's "
-                                      "rotated BEV NMS is not)")
-        return predict_head_maps(*head_out, valid, img_metas, self.test_cfg)
+        return predict_head_maps(*head_out, valid, img_metas, self.test_cfg, rotated=bool(getattr(self.bbox_head, "arkit_head", False)))
 
     def forward_scene(self, feature: Tensor, img_meta: dict, cost_logits: Optional[Tensor] = None,
                       geo: Optional[SceneGeometry] = None) -> dict:

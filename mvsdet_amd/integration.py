@@ -140,3 +140,26 @@ def patch_reference_head(head_module) -> dict:
 def unpatch_reference_head(head_module, originals: dict) -> None:
     for name, fn in originals.items():
         setattr(head_module.NerfDetHead, name.split(".", 1)[1], fn)
+
+
+def patch_reference_nms3d(head_module) -> dict:
+    """Opt-in (the import hook does not apply it): rebind the module-global `nms3d` of an imported reference `nerfdet_head` module
+    (mmcv.ops.nms3d, which ImVoxelHead_ARKit._single_scene_multiclass_nms calls) so that its unmodified predict runs the rotated
+    NMS on the HIP kernel (ops.nms3d) for CUDA tensors and the original for anything else.  Returns {name: original} for
+    `unpatch_reference_nms3d`."""
+    from . import ops
+    original = head_module.nms3d
+
+    def nms3d(boxes, scores, iou_threshold):
+        if boxes.is_cuda:
+            return ops.nms3d(boxes, scores, iou_threshold)
+        return original(boxes, scores, iou_threshold)
+
+    nms3d.__doc__ = getattr(original, "__doc__", None)
+    head_module.nms3d = nms3d
+    return {"nms3d": original}
+
+
+def unpatch_reference_nms3d(head_module, originals: dict) -> None:
+    for name, fn in originals.items():
+        setattr(head_module, name, fn)
