@@ -85,9 +85,13 @@ __global__ __launch_bounds__(kThreads) void depth_prob_topk_kernel(
         avg = avg + dep * pd;
         float cv = pd, co = od;
         int cidx = d;
+        // once the new plane is in, every entry below moves down one slot: a displaced entry is compared with nothing, or
+        // an equal value further down (a lower plane) would overtake it
+        bool moved = false;
 #pragma unroll
         for (int k = 0; k < KT; ++k) {
-            const bool gt = cv > bv[k];
+            const bool gt = moved || cv > bv[k];
+            moved = gt;
             const float tv = bv[k], to = bo[k];
             const int ti = bi[k];
             bv[k] = gt ? cv : tv;

@@ -298,7 +298,8 @@ class MVSDetHotPath:
 
     def ray_depth(self, img_meta: dict, est_depth: Tensor):
         """NVS-branch input (mvsdet.py:487-494): `cur_depth_scale` (N, h*w, 1) of compute_depth_scale[_MultiIntrin]
-        (:1158-1216) and `est_ray_depth` (N, h*w, 1, J) = est_depth / (scale + 1e-8) from the padded (N,J,Hf,Wf) candidates."""
+        (:1158-1216) and `est_ray_depth` (N, h*w, 1, J) = est_depth / (scale + 1e-8) from the padded (N,J,Hf,Wf) candidates.
+        est_ray_depth carries the reference's gradient back to est_depth (ops.ray_depth); depth_scale carries none."""
         stride = self.stride
         h, w = img_meta["img_shape"][0] // stride, img_meta["img_shape"][1] // stride
         K = torch.tensor(np.array(img_meta["lidar2img"]["intrinsic"])).clone()

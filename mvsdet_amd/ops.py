@@ -79,9 +79,8 @@ def _(src, proj, depth):
 
 
 # ------------------------------------------------------------------------------------------- a3+a4
-def ray_depth(intr: Tensor, est_depth: Optional[Tensor], h: int, w: int):
-    """mvsdet.py:1158-1216 + :494: intr (N,5) {fx,fy,cx,cy,skew} at feature level -> depth_scale (N,h*w,1) and, when
-    est_depth (N,J,H,W) is given, est_ray_depth (N,h*w,1,J) in the layout extract_feat hands to the Gaussian adapter."""
+def _ray_depth_launch(intr: Tensor, est_depth: Optional[Tensor], h: int, w: int):
+    """The kernel launch of `ray_depth` -> depth_scale (N,h*w,1), est_ray_depth (N,J,h*w) or None."""
     _req(intr, "intr", dim=2)
     N = intr.shape[0]
     intr = intr.contiguous()
@@ -98,6 +97,41 @@ def ray_depth(intr: Tensor, est_depth: Optional[Tensor], h: int, w: int):
     with torch.cuda.device(intr.device):
         _lib.check(_lib.load().mvsdet_ray_depth_f32(_lib.ptr(intr), _lib.ptr(est_depth), _lib.ptr(scale), _lib.ptr(ray), N, J, H, W,
                                                     h, w, _stream(intr)), "ray_depth")
+    return scale, ray
+
+
+class _RayDepthGrad(torch.autograd.Function):
+    """est_ray_depth under autograd: the forward is the same launch as the no-grad path; the backward is that of the
+    reference's `est_depth / (scale + 1e-8)` (mvsdet.py:494): g / (scale + 1e-8) on the cropped (h, w) window of est_depth,
+    zero on its padding.  depth_scale depends on the intrinsics alone and carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, est_depth, intr, h, w):
+        scale, ray = _ray_depth_launch(intr, est_depth, h, w)
+        ctx.mark_non_differentiable(scale)
+        ctx.save_for_backward(scale)
+        ctx.geometry = (tuple(est_depth.shape), h, w)
+        return scale, ray
+
+    @staticmethod
+    def backward(ctx, g_scale, g_ray):
+        (scale,) = ctx.saved_tensors
+        (N, J, H, W), h, w = ctx.geometry
+        grad = g_ray.new_zeros((N, J, H, W))
+        grad[:, :, :h, :w] = (g_ray / (scale.view(N, 1, h * w) + 1e-8)).view(N, J, h, w)
+        return grad, None, None, None
+
+
+def ray_depth(intr: Tensor, est_depth: Optional[Tensor], h: int, w: int):
+    """mvsdet.py:1158-1216 + :494: intr (N,5) {fx,fy,cx,cy,skew} at feature level -> depth_scale (N,h*w,1) and, when
+    est_depth (N,J,H,W) is given, est_ray_depth (N,h*w,1,J) in the layout extract_feat hands to the Gaussian adapter.
+    Differentiable in est_depth only (when it requires grad): d est_ray_depth / d est_depth = 1 / (depth_scale + 1e-8) on
+    the (h, w) window, 0 on the padding, as the reference's division; depth_scale and the intrinsics carry no gradient.
+    The forward values are those of the no-grad path, bit for bit (the same launch)."""
+    if est_depth is not None and est_depth.requires_grad and torch.is_grad_enabled():
+        scale, ray = _RayDepthGrad.apply(est_depth, intr, h, w)
+    else:
+        scale, ray = _ray_depth_launch(intr, est_depth, h, w)
     return scale, (None if ray is None else ray.transpose(2, 1).unsqueeze(2))
 
 

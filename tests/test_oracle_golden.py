@@ -197,3 +197,53 @@ def test_g8_cost_regularisation_network_cpu():
         x = torch.from_numpy(lcg_uniform(int(np.prod(shape)), int(g["input_seed"]))).reshape(shape).abs()
         y = net(x)
     np.testing.assert_allclose(y.numpy(), g["logits"], rtol=0, atol=1e-4)
+
+
+@pytest.mark.refcheck
+@pytest.mark.parametrize("J", [1, 8])
+def test_backproject_bwd_against_the_reference_autograd(oracle, J):
+    """The oracle's stage-3 backward (which the GPU tests hold the kernels to) at J = 1 and 8 against the reference's own
+    `backproject_Weigh` (mvsdet.py:1372) under torch autograd on the CPU: G6 pins it at J = 3 only."""
+    import os
+    import sys
+
+    import torch
+    from conftest import GOLDEN
+    sys.path.insert(0, GOLDEN)
+    from _ref_loader import _NERFDET, load_reference
+    if not os.path.isdir(_NERFDET):
+        pytest.skip("reference tree not mounted")
+    from mvsdet_amd import synthetic
+    ref, _ = load_reference()
+    N, C, D, hw, nv, vs = 5, 6, 12, (24, 32), [12, 10, 6], [0.4, 0.4, 0.4]
+    seed = {1: 31, 8: 39}[J]
+    meta = synthetic.make_img_meta(N, hw, seed=seed)
+    feat = synthetic.make_features(N, C, hw, seed=seed)
+    logits = synthetic.make_cost_logits(N, D, hw, seed=seed, sharp=2.0)
+    r = oracle.depth_prob_topk(logits[:, 0], logits[:, 1], 0.2, 0.4, J)
+    h, w = meta["img_shape"][0] // 4, meta["img_shape"][1] // 4
+    proj = oracle.compute_projection(meta["lidar2img"]["extrinsic"], meta["lidar2img"]["intrinsic"], meta["img_shape"],
+                                     meta["ori_shape"])
+    pts = oracle.get_points(nv, vs, meta["lidar2img"]["origin"])
+    ed = np.ascontiguousarray(r["est_depth"][:, :, :h, :w])
+    en = np.ascontiguousarray(r["est_dens"][:, :, :h, :w])
+    f = torch.from_numpy(np.ascontiguousarray(feat.numpy()[:, :, :h, :w])).requires_grad_(True)
+    dn = torch.from_numpy(en).requires_grad_(True)
+    d_r = torch.from_numpy(ed).reshape(N, J, -1).transpose(2, 1).unsqueeze(2)
+    p_r = dn.reshape(N, J, -1).transpose(2, 1).unsqueeze(2)
+    volume, valid, _, _ = ref.backproject_Weigh(f, torch.from_numpy(pts).view(3, *nv), torch.from_numpy(proj), d_r, vs, p_r)
+    V = int(np.prod(nv))
+    assert int(valid.sum()) > 20
+    R = torch.randn((N, C, V), generator=torch.Generator().manual_seed(J))
+    (volume.reshape(N, C, V) * R).sum().backward()
+    gf, gd = oracle.backproject_weigh_bwd(f.detach().numpy(), pts, proj, ed, en, vs[-1], R.numpy())
+    assert np.abs(gf).max() > 0 and (J == 1 or np.abs(gd).max() > 0)
+    np.testing.assert_allclose(gf, f.grad.numpy(), rtol=0, atol=1e-6 * float(np.abs(gf).max()))
+    if J == 1:
+        # prob_norm = dens / dens is 1: the oracle's density gradient is exactly 0, the reference's the fp32 rounding of the
+        # quotient rule, a few ulps of sum_c g_c f_c (at most C max|R| max|f|)
+        assert np.abs(gd).max() == 0.0
+        bound = C * float(R.abs().max()) * float(f.detach().abs().max())
+        assert float(dn.grad.abs().max()) <= 1e-6 * bound
+    else:
+        np.testing.assert_allclose(gd, dn.grad.numpy(), rtol=0, atol=2e-6 * float(np.abs(dn.grad.numpy()).max()))
