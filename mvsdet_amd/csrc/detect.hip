@@ -1,24 +1,33 @@
-// Detection post-processing of the ScanNet head (NerfDetHead.predict_by_feat -> _predict_by_feat_single -> _nms -> aligned_3d_nms,
-// projects/NeRF-Det/nerfdet/nerfdet_head.py:301-420, 564-628): head maps -> kept boxes in four launches per batch, no host round trip.
+// Detection post-processing of the two heads: head maps -> kept boxes on the caller's stream, no host round trip.
 //
-//   detect_select_kernel  one workgroup per (level, scene): upsampled valid mask, score = sigmoid(cls) * sigmoid(center) * valid, max
-//                         over classes, top-nms_pre by a radix select on the score bits, decode, score > score_thr; survivors are
-//                         appended in voxel order to the level's own segment of the scene's candidate list
-//   detect_sort_kernel    one workgroup per scene: bitonic sort in LDS of (score descending, NaN first, candidate index ascending) keys
-//   detect_mask_kernel    grid of 64-row x 64-column tiles: the class-aware IoU suppression bit of every ordered pair (i, j > i)
-//   detect_scan_kernel    one workgroup per scene: the greedy walk 64 boxes at a time, kept boxes written in pick order
+// The stages, each written once:
+//   detect_select_kernel<kRot>  one workgroup per (level, scene): upsampled valid mask, score = sigmoid(cls) * sigmoid(center) * valid,
+//                               max over classes, top-nms_pre by a radix select on the score bits, decode into the candidate list
+//   sort_keys                   one workgroup per list: bitonic sort in LDS of (score descending, NaN first, index ascending) keys
+//   mask_tile                   64 rows x 64 columns: the suppression bit of every ordered pair (i, j > i), one 64-bit word per row
+//   greedy_walk                 one workgroup per list: the walk 64 boxes at a time, kept rows handed to the route in pick order
+//
+// The ScanNet head (NerfDetHead.predict_by_feat -> _predict_by_feat_single -> _nms -> aligned_3d_nms,
+// projects/NeRF-Det/nerfdet/nerfdet_head.py:301-420, 564-628; mvsdet_detect_head_f32), four launches: detect_select_kernel<false>
+// keeps score > score_thr and appends the 6-DoF boxes in voxel order to the level's segment of the scene's list.
+// detect_sort_kernel sorts one list per scene over the levels' segments.  detect_mask_kernel runs the class-aware axis-aligned IoU
+// (NaN suppresses) on a (words, words, B) grid.  detect_scan_kernel writes the kept boxes converted, in pick order, then the padding.
 //
 // The ARKit head (ImVoxelHead_ARKit.predict_by_feat -> _single_scene_multiclass_nms -> mmcv's nms3d, nerfdet_head.py:902-1056,
-// 1190-1243; mvsdet_detect_head_rotated_f32): the same selection (detect_select_kernel<true>: every top-k point decoded into a
-// rotated box, its classes above score_thr appended to (scene, class) segments), then per segment rot_sort_kernel (with the IoU
-// prepass), rot_mask_kernel (mmcv's rotated BEV IoU), rot_scan_kernel, and rot_gather_kernel for the class-major output.
+// 1190-1243; mvsdet_detect_head_rotated_f32), a memset and five launches: detect_select_kernel<true> decodes every top-k point into
+// a 7-DoF box and appends each of its classes above score_thr to the (scene, class) segment.  rot_sort_kernel sorts one list per
+// segment and computes the IoU prepass of every box.  rot_mask_kernel runs mmcv's rotated BEV IoU (NaN does not suppress), its
+// workgroups striding over a segment's tiles.  rot_scan_kernel records the kept rows; rot_gather_kernel writes them class-major.
 //
-// The standalone NMS (mvsdet_aligned_3d_nms_f32) replaces the first launch by detect_load_kernel; mvsdet_nms3d_f32 by rot_load_kernel.  All arithmetic that decides or
-// produces an output is written as the reference's ATen expression, op for op; the Makefile's -ffp-contract=off keeps every
-// product and sum separately rounded, and fp32 division is IEEE-rounded (hipcc's default).
+// The standalone NMS replaces the first launch by a copy of the caller's boxes: mvsdet_aligned_3d_nms_f32 by detect_load_kernel,
+// mvsdet_nms3d_f32 by rot_load_kernel.
+//
+// All arithmetic that decides or produces an output is written as the reference's ATen expression, op for op; the Makefile's
+// -ffp-contract=off keeps every product and sum separately rounded, and fp32 division is IEEE-rounded (hipcc's default).
 #include "common.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace mvsdet {
 namespace {
@@ -40,7 +49,11 @@ struct DetLevel {
     float sx, sy, sz;      // trilinear scales of the valid upsampling: (float)in / out
 };
 
-struct Work {              // carved out of the caller's workspace (mvsdet_detect_workspace_bytes)
+struct WorkSizes {         // of either workspace; caps = min(ncap, kLimit) rows a sorted list can hold, words = ceil(caps / 64)
+    int points, ncap, caps, words;
+};
+
+struct Work : WorkSizes {  // carved out of the caller's workspace (mvsdet_detect_workspace_bytes)
     int* seg_count;        // (B, kMaxL)
     int* n_sorted;         // (B): candidates of the scene, or -(survivors) above the limit
     float* pscore;         // (B, points) max score per point
@@ -53,7 +66,6 @@ struct Work {              // carved out of the caller's workspace (mvsdet_detec
     long long* slabel;
     int* sidx;             // candidate index (standalone NMS: the input index)
     unsigned long long* mask;  // (B, caps, words)
-    int points, ncap, caps, words;
 };
 
 struct SelectParams {
@@ -116,7 +128,7 @@ struct RotBox {            // what iou_bev reads of a box: centre and size in BE
     float cn, sn;
 };
 
-struct RotWork {           // carved out of the caller's workspace (mvsdet_detect_rotated_workspace_bytes)
+struct RotWork : WorkSizes {   // carved out of the caller's workspace (mvsdet_detect_rotated_workspace_bytes)
     int* ccount;           // (B*C): pairs appended to a segment (may exceed caps: the overflow count)
     int* n_sorted;         // (B*C): boxes of the segment, or -(survivors) above the limit
     int* nkept;            // (B*C)
@@ -130,7 +142,7 @@ struct RotWork {           // carved out of the caller's workspace (mvsdet_detec
     RotBox* sgeo;          // (B*C, caps) the IoU prepass of every sorted box
     int* kept;             // (B*C, caps) sorted rows kept, in pick order
     unsigned long long* mask;  // (B*C, caps, words)
-    int points, ncap, caps, words, C;
+    int C;
 };
 
 // _bbox_pred_to_bbox (nerfdet_head.py:1030-1056) of one point: shift = half-differences of the distances, turned about z by the
@@ -324,11 +336,21 @@ __device__ __forceinline__ float valid_at(const SelectParams& p, const DetLevel&
     return rintf(v) != 0.f ? 1.f : 0.f;
 }
 
+// get_points of voxel i of a level: its (x, y, z), and the point = voxel * voxel size + new origin (g: a row of SelectParams::geom)
+__device__ __forceinline__ void voxel_point(const DetLevel& lv, const float* g, int i, int& x, int& y, int& z, float& px, float& py,
+                                            float& pz) {
+    x = i / (lv.Y * lv.Z), y = (i / lv.Z) % lv.Y, z = i % lv.Z;
+    px = (float)x * g[0], py = (float)y * g[1], pz = (float)z * g[2];
+    px = px + g[3];
+    py = py + g[4];
+    pz = pz + g[5];
+}
+
 // kRot = false: the ScanNet head (6 regression channels, Work).  kRot = true: ImVoxelHead_ARKit (7 channels, RotWork): every
 // top-k point is decoded into the scene's candidate list, and each of its (class, score > score_thr) pairs joins the (scene, class)
 // segment (rotated part below).
-template <bool kRot, class W>
-__global__ __launch_bounds__(kSelThreads) void detect_select_kernel(SelectParams p, W w) {
+template <bool kRot>
+__global__ __launch_bounds__(kSelThreads) void detect_select_kernel(SelectParams p, std::conditional_t<kRot, RotWork, Work> w) {
     __shared__ int hist[256];
     __shared__ int wave_cnt[kSelThreads / 64];
     __shared__ int sel[2];
@@ -396,8 +418,8 @@ __global__ __launch_bounds__(kSelThreads) void detect_select_kernel(SelectParams
 
     // 3. compaction in voxel order: (top-k) and score > score_thr -> decoded box, score, label
     //    (rotated: every top-k point -> decoded box; its classes with score > score_thr -> their segments)
-    const float* g = p.geom + ((size_t)b * p.L + l) * 6;
-    const float vs0 = g[0], vs1 = g[1], vs2 = g[2], o0 = g[3], o1 = g[4], o2 = g[5];
+    const float* gp = p.geom + ((size_t)b * p.L + l) * 6;
+    const float g[6] = {gp[0], gp[1], gp[2], gp[3], gp[4], gp[5]};
     const size_t cbase = (size_t)b * w.ncap + lv.seg_off;
     int base = 0, eq_base = 0;
     for (int c0 = 0; c0 < N; c0 += kSelThreads) {
@@ -418,11 +440,9 @@ __global__ __launch_bounds__(kSelThreads) void detect_select_kernel(SelectParams
             const int r = block_scan(take, wave_cnt, tot);
             float sc = 0.f, vm = 0.f;
             if (take) {
-                const int x = i / YZ, y = (i / lv.Z) % lv.Y, z = i % lv.Z;
-                float px = (float)x * vs0, py = (float)y * vs1, pz = (float)z * vs2;
-                px = px + o0;
-                py = py + o1;
-                pz = pz + o2;
+                int x, y, z;
+                float px, py, pz;
+                voxel_point(lv, g, i, x, y, z, px, py, pz);
                 float d[7];
                 for (int q = 0; q < 7; ++q) d[q] = box[(size_t)q * N + i];
                 rotated_decode(px, py, pz, d, w.cbox + (cbase + base + r) * 7);
@@ -441,11 +461,9 @@ __global__ __launch_bounds__(kSelThreads) void detect_select_kernel(SelectParams
             int tot;
             const int r = block_scan(keep, wave_cnt, tot);
             if (keep) {
-                const int x = i / YZ, y = (i / lv.Z) % lv.Y, z = i % lv.Z;
-                float px = (float)x * vs0, py = (float)y * vs1, pz = (float)z * vs2;
-                px = px + o0;
-                py = py + o1;
-                pz = pz + o2;
+                int x, y, z;
+                float px, py, pz;
+                voxel_point(lv, g, i, x, y, z, px, py, pz);
                 const size_t ci = cbase + base + r;
                 float* ob = w.cbox + ci * 6;
                 ob[0] = px - box[i];
@@ -503,6 +521,37 @@ __device__ __forceinline__ void bitonic_sort(unsigned long long* keys, int P) {
     }
 }
 
+struct ScoreIndex {
+    float score;
+    int index;
+};
+
+// One list of `total` elements by the whole workgroup: above `caps` elements n_sorted = -total and false; else the keys
+// (~order_bits(score) << 32) | index of element_of(e), e < total, sorted ascending in keys[0, total) (score descending, NaN first,
+// then index ascending; the padding up to the power of two sorts behind every element), n_sorted = total and true.
+template <class ElementOf>
+__device__ __forceinline__ bool sort_keys(unsigned long long* keys, int total, int caps, int* n_sorted, ElementOf element_of) {
+    if (total > caps) {
+        if (threadIdx.x == 0) *n_sorted = -total;
+        return false;
+    }
+    int P = 1;
+    while (P < total) P <<= 1;
+    for (int e = threadIdx.x; e < P; e += kSortThreads) {
+        unsigned long long key = ~0ull;
+        if (e < total) {
+            const ScoreIndex s = element_of(e);
+            key = ((unsigned long long)(~order_bits(s.score)) << 32) | (unsigned)s.index;
+        }
+        keys[e] = key;
+    }
+    __syncthreads();
+    bitonic_sort(keys, P);
+    if (threadIdx.x == 0) *n_sorted = total;
+    return true;
+}
+
+// one workgroup per scene: the levels' segments as one list, keyed by the level-major concatenated index
 __global__ __launch_bounds__(kSortThreads) void detect_sort_kernel(SortParams q, Work w, int pmax) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];   // [pmax] keys, then the level counts / prefixes
     int* cnt = reinterpret_cast<int*>(keys + pmax);
@@ -519,22 +568,12 @@ __global__ __launch_bounds__(kSortThreads) void detect_sort_kernel(SortParams q,
     }
     __syncthreads();
     const int total = pre[kMaxL];
-    if (total > kLimit || total > w.caps) {
-        if (tid == 0) w.n_sorted[b] = -total;
-        return;
-    }
-    int P = 1;
-    while (P < total) P <<= 1;
     auto cand = [&](int e) {   // concatenated (level-major) candidate index -> slot of the candidate buffer
         int l = 0;
         while (l + 1 < q.L && e >= pre[l + 1]) ++l;
         return (size_t)b * w.ncap + q.seg_off[l] + (e - pre[l]);
     };
-    for (int e = tid; e < P; e += kSortThreads)
-        keys[e] = e < total ? ((unsigned long long)(~order_bits(w.cscore[cand(e)])) << 32) | (unsigned)e : ~0ull;
-    __syncthreads();
-    // ascending bitonic sort: score descending, then candidate index ascending
-    bitonic_sort(keys, P);
+    if (!sort_keys(keys, total, w.caps, w.n_sorted + b, [&](int e) { return ScoreIndex{w.cscore[cand(e)], e}; })) return;
     const size_t sb = (size_t)b * w.caps;
     for (int r = tid; r < total; r += kSortThreads) {
         const int e = (int)(keys[r] & 0xffffffffu);
@@ -544,53 +583,63 @@ __global__ __launch_bounds__(kSortThreads) void detect_sort_kernel(SortParams q,
         w.slabel[sb + r] = w.clabel[ci];
         w.sidx[sb + r] = e;
     }
-    if (tid == 0) w.n_sorted[b] = total;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- IoU mask
-// aligned_3d_nms's suppression test of the later box j by the earlier box i, op for op:
-//   inter = max(0, min(x2) - max(x1)) * max(0, ..y..) * max(0, ..z..);  iou = inter / (area_i + area_j - inter) * (cls_i == cls_j)
-//   j goes when !(iou <= thr): NaN (zero-volume / infinite boxes) suppresses, across classes too (NaN * 0)
-__device__ __forceinline__ bool suppresses(const float* a, float area_a, long long la, const float* c, float area_c, long long lc,
-                                           float thr) {
-    const float xx1 = nan_max(a[0], c[0]), yy1 = nan_max(a[1], c[1]), zz1 = nan_max(a[2], c[2]);
-    const float xx2 = nan_min(a[3], c[3]), yy2 = nan_min(a[4], c[4]), zz2 = nan_min(a[5], c[5]);
-    const float il = nan_max(0.f, xx2 - xx1), iw = nan_max(0.f, yy2 - yy1), ih = nan_max(0.f, zz2 - zz1);
-    const float inter = (il * iw) * ih;
-    float iou = inter / ((area_a + area_c) - inter);
-    iou = iou * (la == lc ? 1.f : 0.f);
-    return !(iou <= thr);
-}
-
-__device__ __forceinline__ float box_area(const float* x) { return ((x[3] - x[0]) * (x[4] - x[1])) * (x[5] - x[2]); }
-
-__global__ __launch_bounds__(64) void detect_mask_kernel(Work w, float thr) {
-    __shared__ float cb[64][7];
-    __shared__ long long cl[64];
-    const int cbk = blockIdx.x, rb = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
-    const int n = w.n_sorted[b];
-    if (cbk < rb || rb * 64 >= n || cbk * 64 >= n) return;
-    const size_t sb = (size_t)b * w.caps;
+// Tile (rb, cbk) of one sorted list of n boxes by a 64-thread workgroup: the columns 64 cbk + t staged in LDS, then bit jj of word
+// cbk of row i = 64 rb + t is pair(box i, box 64 cbk + jj) for 64 cbk + jj > i (the earlier box first).  load(r) is the record of
+// sorted row r; `rows` the list's mask rows.
+template <class Box, class Load, class Pair>
+__device__ __forceinline__ void mask_tile(Box* cb, unsigned long long* rows, int words, int n, int rb, int cbk, Load load, Pair pair) {
+    const int t = threadIdx.x;
     const int j = cbk * 64 + t;
-    if (j < n) {
-        const float* x = w.sbox + (sb + j) * 6;
-        for (int c = 0; c < 6; ++c) cb[t][c] = x[c];
-        cb[t][6] = box_area(x);
-        cl[t] = w.slabel[sb + j];
-    }
+    if (j < n) cb[t] = load(j);
     __syncthreads();
     const int i = rb * 64 + t;
     if (i >= n) return;
-    float a[6];
-    const float* x = w.sbox + (sb + i) * 6;
-    for (int c = 0; c < 6; ++c) a[c] = x[c];
-    const float area = box_area(a);
-    const long long la = w.slabel[sb + i];
+    const Box a = load(i);
     const int ncol = min(64, n - cbk * 64);
     unsigned long long bits = 0;
     for (int jj = 0; jj < ncol; ++jj)
-        if (cbk * 64 + jj > i && suppresses(a, area, la, cb[jj], cb[jj][6], cl[jj], thr)) bits |= 1ull << jj;
-    w.mask[(sb + i) * w.words + cbk] = bits;
+        if (cbk * 64 + jj > i && pair(a, cb[jj])) bits |= 1ull << jj;
+    rows[(size_t)i * words + cbk] = bits;
+}
+
+struct __attribute__((packed, aligned(4))) AlignedBox {   // 36 bytes: 64 of them take the LDS the separate arrays took
+    float x[6];            // (x1, y1, z1, x2, y2, z2)
+    float area;
+    long long label;
+};
+
+// aligned_3d_nms's suppression test of the later box c by the earlier box a, op for op:
+//   inter = max(0, min(x2) - max(x1)) * max(0, ..y..) * max(0, ..z..);  iou = inter / (area_i + area_j - inter) * (cls_i == cls_j)
+//   j goes when !(iou <= thr): NaN (zero-volume / infinite boxes) suppresses, across classes too (NaN * 0)
+__device__ __forceinline__ bool suppresses(const AlignedBox& a, const AlignedBox& c, float thr) {
+    const float xx1 = nan_max(a.x[0], c.x[0]), yy1 = nan_max(a.x[1], c.x[1]), zz1 = nan_max(a.x[2], c.x[2]);
+    const float xx2 = nan_min(a.x[3], c.x[3]), yy2 = nan_min(a.x[4], c.x[4]), zz2 = nan_min(a.x[5], c.x[5]);
+    const float il = nan_max(0.f, xx2 - xx1), iw = nan_max(0.f, yy2 - yy1), ih = nan_max(0.f, zz2 - zz1);
+    const float inter = (il * iw) * ih;
+    float iou = inter / ((a.area + c.area) - inter);
+    iou = iou * (a.label == c.label ? 1.f : 0.f);
+    return !(iou <= thr);
+}
+
+// one tile per workgroup of a (words, words, B) grid; the tiles below the diagonal and behind the scene's boxes return at once
+__global__ __launch_bounds__(64) void detect_mask_kernel(Work w, float thr) {
+    __shared__ AlignedBox cb[64];
+    const int cbk = blockIdx.x, rb = blockIdx.y, b = blockIdx.z;
+    const int n = w.n_sorted[b];
+    if (cbk < rb || rb * 64 >= n || cbk * 64 >= n) return;
+    const size_t sb = (size_t)b * w.caps;
+    auto load = [&](int r) {
+        AlignedBox v;
+        for (int c = 0; c < 6; ++c) v.x[c] = w.sbox[(sb + r) * 6 + c];
+        v.area = ((v.x[3] - v.x[0]) * (v.x[4] - v.x[1])) * (v.x[5] - v.x[2]);
+        v.label = w.slabel[sb + r];
+        return v;
+    };
+    mask_tile(cb, w.mask + sb * w.words, w.words, n, rb, cbk, load,
+              [thr](const AlignedBox& a, const AlignedBox& c) { return suppresses(a, c, thr); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------- greedy walk
@@ -599,20 +648,19 @@ __device__ __forceinline__ unsigned long long readlane64(unsigned long long v, i
     return ((unsigned long long)hi << 32) | lo;
 }
 
-// Boxes 64 at a time: every wave loads the block's diagonal mask words (lane j: row 64 w + j, word w) and walks them with the
-// block's entry of the removed set (the same decisions in every wave); the workgroup then ORs the kept rows into the removed
-// words behind the block.  Head route: converted boxes, scores, labels and the padding; standalone: the input indices.
-__global__ __launch_bounds__(kScanThreads) void detect_scan_kernel(Work w, float* out_boxes, float* out_scores, long long* out_labels,
-                                                                   long long* out_index, int* out_count, int nmax) {
+// The walk over one sorted list of n boxes (n <= 0: none) by a workgroup of kScanThreads, `rows` its mask rows.  Boxes 64 at a
+// time: every wave loads the block's diagonal mask words (lane j: row 64 w + j, word w) and walks them with the block's entry of
+// the removed set (the same decisions in every wave); the workgroup then ORs the kept rows into the removed words behind the block.
+// Wave 0's lane of a kept row calls emit(k, row): the row is the k-th pick.  Returns the number kept, in every thread.
+template <class Emit>
+__device__ __forceinline__ int greedy_walk(const unsigned long long* rows, int words, int n, Emit emit) {
     __shared__ unsigned long long removed[kLimit / 64];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = w.n_sorted[b];
-    const size_t sb = (size_t)b * w.caps;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int W = n > 0 ? (n + 63) / 64 : 0;
     for (int q = tid; q < W; q += kScanThreads) removed[q] = 0;
     __syncthreads();
     int kept = 0;
-    unsigned long long diag = (W > 0 && lane < n) ? w.mask[(sb + lane) * w.words] : 0ull;
+    unsigned long long diag = (W > 0 && lane < n) ? rows[(size_t)lane * words] : 0ull;
     for (int blk = 0; blk < W; ++blk) {
         const int nb = min(64, n - blk * 64);
         unsigned long long rem = removed[blk];
@@ -620,7 +668,7 @@ __global__ __launch_bounds__(kScanThreads) void detect_scan_kernel(Work w, float
         const unsigned long long row = diag;
         if (blk + 1 < W) {   // next block's diagonal words: they do not depend on this block's decisions
             const int i = (blk + 1) * 64 + lane;
-            diag = i < n ? w.mask[(sb + i) * w.words + blk + 1] : 0ull;
+            diag = i < n ? rows[(size_t)i * words + blk + 1] : 0ull;
         }
         unsigned long long keptmask = 0, todo = ~rem;
         while (todo) {
@@ -633,31 +681,41 @@ __global__ __launch_bounds__(kScanThreads) void detect_scan_kernel(Work w, float
         for (int pq = tid; pq < 64 * later; pq += kScanThreads) {
             const int j = pq / later, qw = blk + 1 + pq % later;
             if ((keptmask >> j) & 1ull) {
-                const unsigned long long v = w.mask[(sb + blk * 64 + j) * w.words + qw];
+                const unsigned long long v = rows[(size_t)(blk * 64 + j) * words + qw];
                 if (v) atomicOr(&removed[qw], v);
             }
         }
-        if (wave == 0 && ((keptmask >> lane) & 1ull)) {
-            const int k = kept + __popcll(keptmask & ((1ull << lane) - 1ull));
-            const size_t r = sb + blk * 64 + lane;
-            if (out_index) {
-                out_index[(size_t)b * nmax + k] = w.sidx[r];
-            } else {
-                const float* x = w.sbox + r * 6;
-                float* o = out_boxes + ((size_t)b * nmax + k) * 6;
-                o[0] = (x[0] + x[3]) / 2.f;
-                o[1] = (x[1] + x[4]) / 2.f;
-                o[2] = (x[2] + x[5]) / 2.f;
-                o[3] = x[3] - x[0];
-                o[4] = x[4] - x[1];
-                o[5] = x[5] - x[2];
-                out_scores[(size_t)b * nmax + k] = w.sscore[r];
-                out_labels[(size_t)b * nmax + k] = w.slabel[r];
-            }
-        }
+        if (wave == 0 && ((keptmask >> lane) & 1ull)) emit(kept + __popcll(keptmask & ((1ull << lane) - 1ull)), blk * 64 + lane);
         kept += __popcll(keptmask);
         __syncthreads();
     }
+    return kept;
+}
+
+// one workgroup per scene.  Head route: the kept boxes converted to (centre, size), scores, labels, then the zero padding;
+// standalone: the input indices.
+__global__ __launch_bounds__(kScanThreads) void detect_scan_kernel(Work w, float* out_boxes, float* out_scores, long long* out_labels,
+                                                                   long long* out_index, int* out_count, int nmax) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = w.n_sorted[b];
+    const size_t sb = (size_t)b * w.caps;
+    const int kept = greedy_walk(w.mask + sb * w.words, w.words, n, [&](int k, int row) {
+        const size_t r = sb + row;
+        if (out_index) {
+            out_index[(size_t)b * nmax + k] = w.sidx[r];
+        } else {
+            const float* x = w.sbox + r * 6;
+            float* o = out_boxes + ((size_t)b * nmax + k) * 6;
+            o[0] = (x[0] + x[3]) / 2.f;
+            o[1] = (x[1] + x[4]) / 2.f;
+            o[2] = (x[2] + x[5]) / 2.f;
+            o[3] = x[3] - x[0];
+            o[4] = x[4] - x[1];
+            o[5] = x[5] - x[2];
+            out_scores[(size_t)b * nmax + k] = w.sscore[r];
+            out_labels[(size_t)b * nmax + k] = w.slabel[r];
+        }
+    });
     if (!out_index) {
         for (int k = kept + tid; k < nmax; k += kScanThreads) {
             float* o = out_boxes + ((size_t)b * nmax + k) * 6;
@@ -680,29 +738,18 @@ __global__ void rot_load_kernel(const float* __restrict__ boxes, const float* __
     w.eslot[i] = i;
 }
 
-// one workgroup per (scene, class) segment: bitonic sort in LDS of (score descending, NaN first, candidate index ascending), then
-// the sorted boxes, scores, candidate indices and the IoU prepass of every box
+// one workgroup per (scene, class) segment: the segment's candidates keyed by their scene-relative index (append order is sorted
+// away), then the sorted boxes, scores, candidate indices and the IoU prepass of every box
 __global__ __launch_bounds__(kSortThreads) void rot_sort_kernel(RotWork w, int pmax) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
     const int seg = blockIdx.x, b = seg / w.C, tid = threadIdx.x;
     const int total = w.ccount[seg];
-    if (total > w.caps) {
-        if (tid == 0) w.n_sorted[seg] = -total;
-        return;
-    }
-    int P = 1;
-    while (P < total) P <<= 1;
     const size_t eb = (size_t)seg * w.caps, db = (size_t)seg * w.ncap;
-    for (int e = tid; e < P; e += kSortThreads) {
-        unsigned long long key = ~0ull;
-        if (e < total) {
-            const int slot = w.eslot[eb + e];
-            key = ((unsigned long long)(~order_bits(w.dscore[db + slot])) << 32) | (unsigned)slot;
-        }
-        keys[e] = key;
-    }
-    __syncthreads();
-    bitonic_sort(keys, P);
+    auto element = [&](int e) {
+        const int slot = w.eslot[eb + e];
+        return ScoreIndex{w.dscore[db + slot], slot};
+    };
+    if (!sort_keys(keys, total, w.caps, w.n_sorted + seg, element)) return;
     for (int r = tid; r < total; r += kSortThreads) {
         const int slot = (int)(keys[r] & 0xffffffffu);
         const float* x = w.cbox + ((size_t)b * w.ncap + slot) * 7;
@@ -712,14 +759,13 @@ __global__ __launch_bounds__(kSortThreads) void rot_sort_kernel(RotWork w, int p
         w.sidx[eb + r] = slot;
         w.sgeo[eb + r] = rot_prep(x);
     }
-    if (tid == 0) w.n_sorted[seg] = total;
 }
 
-// 64 x 64 tiles of the upper triangle of every segment, gridDim.x workgroups striding over a segment's tiles: bit jj of word cbk of
-// row i is iou_bev(box i, box 64 cbk + jj) > thr for 64 cbk + jj > i (mmcv's nms3d kernel: the earlier box first)
+// 64 x 64 tiles of the upper triangle of every segment, gridDim.x workgroups striding over a segment's tiles: the pair test is
+// iou_bev(box i, box j) > thr (mmcv's nms3d kernel), on the prepass records the sort left
 __global__ __launch_bounds__(64) void rot_mask_kernel(RotWork w, float thr) {
     __shared__ RotBox cb[64];
-    const int seg = blockIdx.y, t = threadIdx.x;
+    const int seg = blockIdx.y;
     const int n = w.n_sorted[seg];
     if (n <= 0) return;
     const int W = (n + 63) / 64, T = W * (W + 1) / 2;
@@ -730,63 +776,18 @@ __global__ __launch_bounds__(64) void rot_mask_kernel(RotWork w, float thr) {
             rest -= W - rb;
             ++rb;
         }
-        const int cbk = rb + rest;
         __syncthreads();   // the previous tile's columns are read
-        const int j = cbk * 64 + t;
-        if (j < n) cb[t] = w.sgeo[sb + j];
-        __syncthreads();
-        const int i = rb * 64 + t;
-        if (i < n) {
-            const RotBox a = w.sgeo[sb + i];
-            const int ncol = min(64, n - cbk * 64);
-            unsigned long long bits = 0;
-            for (int jj = 0; jj < ncol; ++jj)
-                if (cbk * 64 + jj > i && rot_iou(a, cb[jj]) > thr) bits |= 1ull << jj;
-            w.mask[(sb + i) * w.words + cbk] = bits;
-        }
+        mask_tile(cb, w.mask + sb * w.words, w.words, n, rb, rb + rest, [&](int r) { return w.sgeo[sb + r]; },
+                  [thr](const RotBox& a, const RotBox& c) { return rot_iou(a, c) > thr; });
     }
 }
 
-// the greedy walk of detect_scan_kernel, one workgroup per segment: kept sorted rows in pick order
+// one workgroup per segment: kept sorted rows in pick order
 __global__ __launch_bounds__(kScanThreads) void rot_scan_kernel(RotWork w) {
-    __shared__ unsigned long long removed[kLimit / 64];
-    const int seg = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = w.n_sorted[seg];
+    const int seg = blockIdx.x;
     const size_t sb = (size_t)seg * w.caps;
-    const int W = n > 0 ? (n + 63) / 64 : 0;
-    for (int q = tid; q < W; q += kScanThreads) removed[q] = 0;
-    __syncthreads();
-    int kept = 0;
-    unsigned long long diag = (W > 0 && lane < n) ? w.mask[(sb + lane) * w.words] : 0ull;
-    for (int blk = 0; blk < W; ++blk) {
-        const int nb = min(64, n - blk * 64);
-        unsigned long long rem = removed[blk];
-        if (nb < 64) rem |= ~0ull << nb;
-        const unsigned long long row = diag;
-        if (blk + 1 < W) {
-            const int i = (blk + 1) * 64 + lane;
-            diag = i < n ? w.mask[(sb + i) * w.words + blk + 1] : 0ull;
-        }
-        unsigned long long keptmask = 0, todo = ~rem;
-        while (todo) {
-            const int j = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
-            keptmask |= 1ull << j;
-            rem |= readlane64(row, j);
-            todo = j == 63 ? 0ull : (~rem & (~0ull << (j + 1)));
-        }
-        const int later = W - blk - 1;
-        for (int pq = tid; pq < 64 * later; pq += kScanThreads) {
-            const int j = pq / later, qw = blk + 1 + pq % later;
-            if ((keptmask >> j) & 1ull) {
-                const unsigned long long v = w.mask[(sb + blk * 64 + j) * w.words + qw];
-                if (v) atomicOr(&removed[qw], v);
-            }
-        }
-        if (wave == 0 && ((keptmask >> lane) & 1ull)) w.kept[sb + kept + __popcll(keptmask & ((1ull << lane) - 1ull))] = blk * 64 + lane;
-        kept += __popcll(keptmask);
-        __syncthreads();
-    }
-    if (tid == 0) w.nkept[seg] = kept;
+    const int kept = greedy_walk(w.mask + sb * w.words, w.words, w.n_sorted[seg], [&](int k, int row) { w.kept[sb + k] = row; });
+    if (threadIdx.x == 0) w.nkept[seg] = kept;
 }
 
 // one workgroup per scene: the kept boxes class-major (classes ascending, each in pick order), then the zero padding.  A scene with
@@ -845,47 +846,93 @@ __global__ void rot_iou_kernel(const float* __restrict__ a, int n, const float* 
     out[q] = rot_iou(rot_prep(a + (size_t)i * 7), rot_prep(b + (size_t)j * 7));
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// workspace layout; returns the bytes needed (Work pointers filled when base != nullptr)
-size_t carve(void* base, int B, int points, int ncap, Work* w) {
-    const int caps = std::min(ncap, kLimit), words = (caps + 63) / 64;
+// Hands out the arrays of a workspace in order, each aligned to 256 bytes; `off` ends as the bytes needed.  Without a base every
+// pointer is null: the size query.
+struct Carver {
+    char* base;
     size_t off = 0;
-    char* p = static_cast<char*>(base);
-    auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += align256(bytes); return r; };
-    Work t{};
-    t.seg_count = reinterpret_cast<int*>(take((size_t)B * kMaxL * 4));
-    t.n_sorted = reinterpret_cast<int*>(take((size_t)B * 4));
-    t.pscore = reinterpret_cast<float*>(take((size_t)B * points * 4));
-    t.plabel = reinterpret_cast<int*>(take((size_t)B * points * 4));
-    t.cbox = reinterpret_cast<float*>(take((size_t)B * ncap * 24));
-    t.cscore = reinterpret_cast<float*>(take((size_t)B * ncap * 4));
-    t.clabel = reinterpret_cast<long long*>(take((size_t)B * ncap * 8));
-    t.sbox = reinterpret_cast<float*>(take((size_t)B * caps * 24));
-    t.sscore = reinterpret_cast<float*>(take((size_t)B * caps * 4));
-    t.slabel = reinterpret_cast<long long*>(take((size_t)B * caps * 8));
-    t.sidx = reinterpret_cast<int*>(take((size_t)B * caps * 4));
-    t.mask = reinterpret_cast<unsigned long long*>(take((size_t)B * caps * words * 8));
-    t.points = points;
-    t.ncap = ncap;
-    t.caps = caps;
-    t.words = words;
+    template <class T>
+    void take(T*& ptr, size_t count) {
+        ptr = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += (count * sizeof(T) + 255) & ~(size_t)255;
+    }
+};
+
+WorkSizes work_sizes(int points, int ncap) {
+    const int caps = std::min(ncap, kLimit);
+    return {points, ncap, caps, (caps + 63) / 64};
+}
+
+// workspace layout; returns the bytes needed
+size_t carve(void* base, int B, int points, int ncap, Work* w) {
+    Work t{work_sizes(points, ncap)};
+    const size_t nb = B, cand = nb * ncap, rows = nb * t.caps;
+    Carver c{static_cast<char*>(base)};
+    c.take(t.seg_count, nb * kMaxL);
+    c.take(t.n_sorted, nb);
+    c.take(t.pscore, nb * points);
+    c.take(t.plabel, nb * points);
+    c.take(t.cbox, cand * 6);
+    c.take(t.cscore, cand);
+    c.take(t.clabel, cand);
+    c.take(t.sbox, rows * 6);
+    c.take(t.sscore, rows);
+    c.take(t.slabel, rows);
+    c.take(t.sidx, rows);
+    c.take(t.mask, rows * t.words);
     if (w) *w = t;
-    return off;
+    return c.off;
+}
+
+// rotated workspace layout; returns the bytes needed
+size_t carve_rotated(void* base, int B, int points, int ncap, int C, RotWork* w) {
+    RotWork t{work_sizes(points, ncap)};
+    t.C = C;
+    const size_t nb = B, S = nb * C, rows = S * t.caps;
+    Carver c{static_cast<char*>(base)};
+    c.take(t.ccount, S);
+    c.take(t.n_sorted, S);
+    c.take(t.nkept, S);
+    c.take(t.pscore, nb * points);
+    c.take(t.cbox, nb * ncap * 7);
+    c.take(t.dscore, S * ncap);
+    c.take(t.eslot, rows);
+    c.take(t.sbox, rows * 7);
+    c.take(t.sscore, rows);
+    c.take(t.sidx, rows);
+    c.take(t.sgeo, rows);
+    c.take(t.kept, rows);
+    c.take(t.mask, rows * t.words);
+    if (w) *w = t;
+    return c.off;
+}
+
+int check_workspace(const char* name, const void* workspace, size_t bytes, size_t need, const char* query) {
+    if (workspace && bytes >= need) return MVSDET_OK;
+    set_error("%s: workspace of %zu bytes, %zu needed (%s)", name, bytes, need, query);
+    return MVSDET_ERR_WORKSPACE;
+}
+
+// LDS of a sort kernel: a power of two of keys that holds `caps`, then `extra` bytes; above 64 KiB the kernel is told so
+template <class Kernel>
+int sort_lds(Kernel kernel, int caps, size_t extra, const char* name, int* pmax, size_t* lds) {
+    *pmax = 1;
+    while (*pmax < std::max(caps, 1)) *pmax <<= 1;
+    *lds = (size_t)*pmax * 8 + extra;
+    if (*lds > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds) != hipSuccess) {
+        set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed", name);
+        return MVSDET_ERR_HIP;
+    }
+    return MVSDET_OK;
 }
 
 // sort, mask and walk of the candidate lists in `w` (segments and counts written by the first launch)
 int sort_mask_scan(const Work& w, const SortParams& q, int B, float thr, float* out_boxes, float* out_scores, long long* out_labels,
                    long long* out_index, int* out_count, int nmax, hipStream_t stream, const char* name) {
-    int pmax = 1;
-    while (pmax < std::max(w.caps, 1)) pmax <<= 1;
-    const size_t lds = (size_t)pmax * 8 + (2 * kMaxL + 1) * 4;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(detect_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-            hipSuccess) {
-        set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed", name);
-        return MVSDET_ERR_HIP;
-    }
+    int pmax;
+    size_t lds;
+    if (const int rc = sort_lds(detect_sort_kernel, w.caps, (2 * kMaxL + 1) * 4, name, &pmax, &lds)) return rc;
     hipLaunchKernelGGL(detect_sort_kernel, dim3(B), dim3(kSortThreads), lds, stream, q, w, pmax);
     if (w.words > 0) hipLaunchKernelGGL(detect_mask_kernel, dim3(w.words, w.words, B), dim3(64), 0, stream, w, thr);
     hipLaunchKernelGGL(detect_scan_kernel, dim3(B), dim3(kScanThreads), 0, stream, w, out_boxes, out_scores, out_labels, out_index,
@@ -894,49 +941,13 @@ int sort_mask_scan(const Work& w, const SortParams& q, int B, float thr, float* 
     return MVSDET_OK;
 }
 
-// rotated workspace layout; returns the bytes needed (RotWork pointers filled when base != nullptr)
-size_t carve_rotated(void* base, int B, int points, int ncap, int C, RotWork* w) {
-    const int caps = std::min(ncap, kLimit), words = (caps + 63) / 64;
-    const size_t S = (size_t)B * C;
-    size_t off = 0;
-    char* p = static_cast<char*>(base);
-    auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += align256(bytes); return r; };
-    RotWork t{};
-    t.ccount = reinterpret_cast<int*>(take(S * 4));
-    t.n_sorted = reinterpret_cast<int*>(take(S * 4));
-    t.nkept = reinterpret_cast<int*>(take(S * 4));
-    t.pscore = reinterpret_cast<float*>(take((size_t)B * points * 4));
-    t.cbox = reinterpret_cast<float*>(take((size_t)B * ncap * 28));
-    t.dscore = reinterpret_cast<float*>(take(S * ncap * 4));
-    t.eslot = reinterpret_cast<int*>(take(S * caps * 4));
-    t.sbox = reinterpret_cast<float*>(take(S * caps * 28));
-    t.sscore = reinterpret_cast<float*>(take(S * caps * 4));
-    t.sidx = reinterpret_cast<int*>(take(S * caps * 4));
-    t.sgeo = reinterpret_cast<RotBox*>(take(S * caps * sizeof(RotBox)));
-    t.kept = reinterpret_cast<int*>(take(S * caps * 4));
-    t.mask = reinterpret_cast<unsigned long long*>(take(S * caps * words * 8));
-    t.points = points;
-    t.ncap = ncap;
-    t.caps = caps;
-    t.words = words;
-    t.C = C;
-    if (w) *w = t;
-    return off;
-}
-
 // sort, mask, walk and gather of the segments in `w` (filled by the first launch; ccount zeroed before it)
 int rotated_sort_mask_scan(const RotWork& w, int B, float thr, float* out_boxes, float* out_scores, long long* out_labels,
                            long long* out_index, int* out_count, int nmax, hipStream_t stream, const char* name) {
     const int S = B * w.C;
-    int pmax = 1;
-    while (pmax < std::max(w.caps, 1)) pmax <<= 1;
-    const size_t lds = (size_t)pmax * 8;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(rot_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-            hipSuccess) {
-        set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed", name);
-        return MVSDET_ERR_HIP;
-    }
+    int pmax;
+    size_t lds;
+    if (const int rc = sort_lds(rot_sort_kernel, w.caps, 0, name, &pmax, &lds)) return rc;
     hipLaunchKernelGGL(rot_sort_kernel, dim3(S), dim3(kSortThreads), lds, stream, w, pmax);
     if (w.words > 0) {
         // tiles of the largest possible segment, at most ~4096 workgroups in all: a segment's workgroups stride over its tiles
@@ -948,6 +959,55 @@ int rotated_sort_mask_scan(const RotWork& w, int B, float thr, float* out_boxes,
     hipLaunchKernelGGL(rot_gather_kernel, dim3(B), dim3(256), 0, stream, w, out_boxes, out_scores, out_labels, out_index, out_count,
                        nmax);
     MVS_LAUNCH_CHECK(name);
+    return MVSDET_OK;
+}
+
+// What both head entry points check and derive of their arguments: the pointers, B, L, n_classes (at most max_classes, and
+// B x n_classes at most max_segments where that is not 0), the valid grid, nms_pre and every level.  Fills `p`; `points` and `ncap`
+// are a scene's points and the most candidates it can have (per level nms_pre, or all its points).
+int plan_select(const char* name, const float* const* center, const float* const* bbox, const float* const* cls, const int* level_dims,
+                const float* valid, const float* level_geom, bool outputs, int B, int L, int n_classes, int max_classes,
+                int max_segments, int VX, int VY, int VZ, int nms_pre, float score_thr, SelectParams* p, long long* points,
+                long long* ncap) {
+    MVS_REQUIRE(center && bbox && cls && level_dims && valid && level_geom && outputs, "%s: NULL pointer", name);
+    MVS_REQUIRE(B >= 1 && B <= 65535, "%s: bad shape B=%d", name, B);
+    MVS_REQUIRE(L >= 1 && L <= MVSDET_DETECT_MAX_LEVELS, "%s: bad shape L=%d (1..%d levels)", name, L, MVSDET_DETECT_MAX_LEVELS);
+    MVS_REQUIRE(n_classes >= 1 && n_classes <= max_classes, "%s: bad shape n_classes=%d (1..%d)", name, n_classes, max_classes);
+    MVS_REQUIRE(!max_segments || (long long)B * n_classes <= max_segments, "%s: bad shape: %d scenes x %d classes above %d segments",
+                name, B, n_classes, max_segments);
+    MVS_REQUIRE(VX > 0 && VY > 0 && VZ > 0 && (long long)VX * VY * VZ < (1 << 26), "%s: bad shape valid %dx%dx%d", name, VX, VY, VZ);
+    MVS_REQUIRE(nms_pre >= 0, "%s: nms_pre=%d < 0", name, nms_pre);
+    *p = SelectParams{};
+    *points = *ncap = 0;
+    for (int l = 0; l < L; ++l) {
+        MVS_REQUIRE(center[l] && bbox[l] && cls[l], "%s: NULL pointer (level %d)", name, l);
+        const int X = level_dims[3 * l], Y = level_dims[3 * l + 1], Z = level_dims[3 * l + 2];
+        MVS_REQUIRE(X > 0 && Y > 0 && Z > 0 && (long long)X * Y * Z < (1 << 24), "%s: bad shape level %d: %dx%dx%d", name, l, X, Y, Z);
+        const int N = X * Y * Z;
+        DetLevel& lv = p->lv[l];
+        lv.center = center[l];
+        lv.bbox = bbox[l];
+        lv.cls = cls[l];
+        lv.X = X;
+        lv.Y = Y;
+        lv.Z = Z;
+        lv.k = (N > nms_pre && nms_pre > 0) ? nms_pre : 0;
+        lv.seg_off = (int)*ncap;
+        lv.pt_off = (int)*points;
+        lv.sx = (float)VX / (float)X;
+        lv.sy = (float)VY / (float)Y;
+        lv.sz = (float)VZ / (float)Z;
+        *points += N;
+        *ncap += lv.k > 0 ? lv.k : N;
+    }
+    p->valid = valid;
+    p->geom = level_geom;
+    p->L = L;
+    p->C = n_classes;
+    p->VX = VX;
+    p->VY = VY;
+    p->VZ = VZ;
+    p->score_thr = score_thr;
     return MVSDET_OK;
 }
 
@@ -967,59 +1027,24 @@ extern "C" int mvsdet_detect_head_f32(const float* const* center, const float* c
                                       float* out_scores, int64_t* out_labels, int* out_count, int nmax, void* workspace,
                                       size_t workspace_bytes, mvsdet_stream_t stream) {
     const char* name = "detect_head";
-    MVS_REQUIRE(center && bbox && cls && level_dims && valid && level_geom && out_boxes && out_scores && out_labels && out_count,
-                "%s: NULL pointer", name);
-    MVS_REQUIRE(B >= 1 && B <= 65535, "%s: bad shape B=%d", name, B);
-    MVS_REQUIRE(L >= 1 && L <= MVSDET_DETECT_MAX_LEVELS, "%s: bad shape L=%d (1..%d levels)", name, L, MVSDET_DETECT_MAX_LEVELS);
-    MVS_REQUIRE(n_classes >= 1 && n_classes <= 1024, "%s: bad shape n_classes=%d", name, n_classes);
-    MVS_REQUIRE(VX > 0 && VY > 0 && VZ > 0 && (long long)VX * VY * VZ < (1 << 26), "%s: bad shape valid %dx%dx%d", name, VX, VY, VZ);
-    MVS_REQUIRE(nms_pre >= 0, "%s: nms_pre=%d < 0", name, nms_pre);
-    SelectParams p{};
-    SortParams q{};
-    long long points = 0, ncap = 0;
-    for (int l = 0; l < L; ++l) {
-        MVS_REQUIRE(center[l] && bbox[l] && cls[l], "%s: NULL pointer (level %d)", name, l);
-        const int X = level_dims[3 * l], Y = level_dims[3 * l + 1], Z = level_dims[3 * l + 2];
-        MVS_REQUIRE(X > 0 && Y > 0 && Z > 0 && (long long)X * Y * Z < (1 << 24), "%s: bad shape level %d: %dx%dx%d", name, l, X, Y, Z);
-        const int N = X * Y * Z;
-        DetLevel& lv = p.lv[l];
-        lv.center = center[l];
-        lv.bbox = bbox[l];
-        lv.cls = cls[l];
-        lv.X = X;
-        lv.Y = Y;
-        lv.Z = Z;
-        lv.k = (N > nms_pre && nms_pre > 0) ? nms_pre : 0;
-        lv.seg_off = (int)ncap;
-        lv.pt_off = (int)points;
-        lv.sx = (float)VX / (float)X;
-        lv.sy = (float)VY / (float)Y;
-        lv.sz = (float)VZ / (float)Z;
-        q.seg_off[l] = (int)ncap;
-        points += N;
-        ncap += lv.k > 0 ? lv.k : N;
-    }
+    SelectParams p;
+    long long points, ncap;
+    if (const int rc = plan_select(name, center, bbox, cls, level_dims, valid, level_geom, out_boxes && out_scores && out_labels && out_count,
+                                   B, L, n_classes, 1024, 0, VX, VY, VZ, nms_pre, score_thr, &p, &points, &ncap))
+        return rc;
     MVS_REQUIRE((long long)B * points < (1ll << 31) && (long long)B * ncap < (1ll << 31), "%s: bad shape: %d scenes x %lld points", name,
                 B, points);
     const int caps = (int)std::min<long long>(ncap, kLimit);
     MVS_REQUIRE(nmax >= caps, "%s: Nmax=%d < %d, the most boxes a scene can keep here (min(candidates, %d))", name, nmax, caps, kLimit);
-    const size_t need = mvsdet_detect_workspace_bytes(B, (int)points, (int)ncap);
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace of %zu bytes, %zu needed (mvsdet_detect_workspace_bytes)", name, workspace_bytes, need);
-        return MVSDET_ERR_WORKSPACE;
-    }
+    if (const int rc = check_workspace(name, workspace, workspace_bytes, mvsdet_detect_workspace_bytes(B, (int)points, (int)ncap),
+                                       "mvsdet_detect_workspace_bytes"))
+        return rc;
     Work w;
     carve(workspace, B, (int)points, (int)ncap, &w);
-    p.valid = valid;
-    p.geom = level_geom;
-    p.L = L;
-    p.C = n_classes;
-    p.VX = VX;
-    p.VY = VY;
-    p.VZ = VZ;
-    p.score_thr = score_thr;
+    SortParams q{};
     q.L = L;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(detect_select_kernel<false, Work>), dim3(L, B), dim3(kSelThreads), 0, (hipStream_t)stream, p, w);
+    for (int l = 0; l < L; ++l) q.seg_off[l] = p.lv[l].seg_off;
+    hipLaunchKernelGGL(detect_select_kernel<false>, dim3(L, B), dim3(kSelThreads), 0, (hipStream_t)stream, p, w);
     return sort_mask_scan(w, q, B, iou_thr, out_boxes, out_scores, reinterpret_cast<long long*>(out_labels), nullptr, out_count, nmax,
                           (hipStream_t)stream, name);
 }
@@ -1033,11 +1058,9 @@ extern "C" int mvsdet_aligned_3d_nms_f32(const float* boxes, const float* scores
     MVS_REQUIRE(n <= MVSDET_DETECT_MAX_CANDIDATES, "%s: n=%d boxes above the candidate limit MVSDET_DETECT_MAX_CANDIDATES=%d", name, n,
                 MVSDET_DETECT_MAX_CANDIDATES);
     MVS_REQUIRE(n == 0 || (boxes && scores && classes), "%s: NULL pointer", name);
-    const size_t need = mvsdet_detect_workspace_bytes(1, 0, n);
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace of %zu bytes, %zu needed (mvsdet_detect_workspace_bytes)", name, workspace_bytes, need);
-        return MVSDET_ERR_WORKSPACE;
-    }
+    if (const int rc = check_workspace(name, workspace, workspace_bytes, mvsdet_detect_workspace_bytes(1, 0, n),
+                                       "mvsdet_detect_workspace_bytes"))
+        return rc;
     Work w;
     carve(workspace, 1, 0, n, &w);
     SortParams q{};
@@ -1059,38 +1082,11 @@ extern "C" int mvsdet_detect_head_rotated_f32(const float* const* center, const 
                                               float* out_boxes, float* out_scores, int64_t* out_labels, int* out_count, int nmax,
                                               void* workspace, size_t workspace_bytes, mvsdet_stream_t stream) {
     const char* name = "detect_head_rotated";
-    MVS_REQUIRE(center && bbox && cls && level_dims && valid && level_geom && out_boxes && out_scores && out_labels && out_count,
-                "%s: NULL pointer", name);
-    MVS_REQUIRE(B >= 1 && B <= 65535, "%s: bad shape B=%d", name, B);
-    MVS_REQUIRE(L >= 1 && L <= MVSDET_DETECT_MAX_LEVELS, "%s: bad shape L=%d (1..%d levels)", name, L, MVSDET_DETECT_MAX_LEVELS);
-    MVS_REQUIRE(n_classes >= 1 && n_classes <= kRotMaxClasses, "%s: bad shape n_classes=%d (1..%d)", name, n_classes,
-                kRotMaxClasses);
-    MVS_REQUIRE((long long)B * n_classes <= 65535, "%s: bad shape: %d scenes x %d classes above 65535 segments", name, B, n_classes);
-    MVS_REQUIRE(VX > 0 && VY > 0 && VZ > 0 && (long long)VX * VY * VZ < (1 << 26), "%s: bad shape valid %dx%dx%d", name, VX, VY, VZ);
-    MVS_REQUIRE(nms_pre >= 0, "%s: nms_pre=%d < 0", name, nms_pre);
-    SelectParams p{};
-    long long points = 0, ncap = 0;
-    for (int l = 0; l < L; ++l) {
-        MVS_REQUIRE(center[l] && bbox[l] && cls[l], "%s: NULL pointer (level %d)", name, l);
-        const int X = level_dims[3 * l], Y = level_dims[3 * l + 1], Z = level_dims[3 * l + 2];
-        MVS_REQUIRE(X > 0 && Y > 0 && Z > 0 && (long long)X * Y * Z < (1 << 24), "%s: bad shape level %d: %dx%dx%d", name, l, X, Y, Z);
-        const int N = X * Y * Z;
-        DetLevel& lv = p.lv[l];
-        lv.center = center[l];
-        lv.bbox = bbox[l];
-        lv.cls = cls[l];
-        lv.X = X;
-        lv.Y = Y;
-        lv.Z = Z;
-        lv.k = (N > nms_pre && nms_pre > 0) ? nms_pre : 0;
-        lv.seg_off = (int)ncap;
-        lv.pt_off = (int)points;
-        lv.sx = (float)VX / (float)X;
-        lv.sy = (float)VY / (float)Y;
-        lv.sz = (float)VZ / (float)Z;
-        points += N;
-        ncap += lv.k > 0 ? lv.k : N;
-    }
+    SelectParams p;
+    long long points, ncap;
+    if (const int rc = plan_select(name, center, bbox, cls, level_dims, valid, level_geom, out_boxes && out_scores && out_labels && out_count,
+                                   B, L, n_classes, kRotMaxClasses, 65535, VX, VY, VZ, nms_pre, score_thr, &p, &points, &ncap))
+        return rc;
     MVS_REQUIRE((long long)B * points < (1ll << 31) && (long long)B * n_classes * ncap < (1ll << 31),
                 "%s: bad shape: %d scenes x %lld points x %d classes", name, B, points, n_classes);
     const long long caps = std::min<long long>(ncap, kLimit);
@@ -1098,27 +1094,17 @@ extern "C" int mvsdet_detect_head_rotated_f32(const float* const* center, const 
                 "%s: Nmax=%d < %lld, the most boxes a scene can keep here (n_classes x min(candidates, %d))", name, nmax,
                 n_classes * caps, kLimit);
     MVS_REQUIRE((long long)B * nmax < (1ll << 31), "%s: bad shape: %d scenes x Nmax=%d", name, B, nmax);
-    const size_t need = mvsdet_detect_rotated_workspace_bytes(B, (int)points, (int)ncap, n_classes);
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace of %zu bytes, %zu needed (mvsdet_detect_rotated_workspace_bytes)", name, workspace_bytes, need);
-        return MVSDET_ERR_WORKSPACE;
-    }
+    if (const int rc = check_workspace(name, workspace, workspace_bytes,
+                                       mvsdet_detect_rotated_workspace_bytes(B, (int)points, (int)ncap, n_classes),
+                                       "mvsdet_detect_rotated_workspace_bytes"))
+        return rc;
     RotWork w;
     carve_rotated(workspace, B, (int)points, (int)ncap, n_classes, &w);
-    p.valid = valid;
-    p.geom = level_geom;
-    p.L = L;
-    p.C = n_classes;
-    p.VX = VX;
-    p.VY = VY;
-    p.VZ = VZ;
-    p.score_thr = score_thr;
     if (hipMemsetAsync(w.ccount, 0, (size_t)B * n_classes * 4, (hipStream_t)stream) != hipSuccess) {
         set_error("%s: hipMemsetAsync failed", name);
         return MVSDET_ERR_HIP;
     }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(detect_select_kernel<true, RotWork>), dim3(L, B), dim3(kSelThreads), 0, (hipStream_t)stream,
-                       p, w);
+    hipLaunchKernelGGL(detect_select_kernel<true>, dim3(L, B), dim3(kSelThreads), 0, (hipStream_t)stream, p, w);
     return rotated_sort_mask_scan(w, B, iou_thr, out_boxes, out_scores, reinterpret_cast<long long*>(out_labels), nullptr, out_count,
                                   nmax, (hipStream_t)stream, name);
 }
@@ -1131,11 +1117,9 @@ extern "C" int mvsdet_nms3d_f32(const float* boxes, const float* scores, int n, 
     MVS_REQUIRE(n <= MVSDET_DETECT_MAX_CANDIDATES, "%s: n=%d boxes above the candidate limit MVSDET_DETECT_MAX_CANDIDATES=%d", name, n,
                 MVSDET_DETECT_MAX_CANDIDATES);
     MVS_REQUIRE(n == 0 || (boxes && scores), "%s: NULL pointer", name);
-    const size_t need = mvsdet_detect_rotated_workspace_bytes(1, 0, n, 1);
-    if (!workspace || workspace_bytes < need) {
-        set_error("%s: workspace of %zu bytes, %zu needed (mvsdet_detect_rotated_workspace_bytes)", name, workspace_bytes, need);
-        return MVSDET_ERR_WORKSPACE;
-    }
+    if (const int rc = check_workspace(name, workspace, workspace_bytes, mvsdet_detect_rotated_workspace_bytes(1, 0, n, 1),
+                                       "mvsdet_detect_rotated_workspace_bytes"))
+        return rc;
     RotWork w;
     carve_rotated(workspace, 1, 0, n, 1, &w);
     hipLaunchKernelGGL(rot_load_kernel, dim3(std::max(1, (n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, boxes, scores, n, w);

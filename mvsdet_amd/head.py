@@ -190,8 +190,9 @@ def predict_head_maps(center_preds, bbox_preds, cls_preds, valid_pred: Tensor, b
     if test_cfg is None:
         raise ValueError("predict_by_feat: a test_cfg with nms_pre, score_thr and iou_thr is needed")
     origins = [scene_origin(m) for m in batch_input_metas]
-    return (ops.head_predict_rotated if rotated else ops.head_predict)(center_preds, bbox_preds, cls_preds, valid_pred, origins, int(cfg_value(test_cfg, "nms_pre")),
-                            float(cfg_value(test_cfg, "score_thr")), float(cfg_value(test_cfg, "iou_thr")))
+    predict = ops.head_predict_rotated if rotated else ops.head_predict
+    return predict(center_preds, bbox_preds, cls_preds, valid_pred, origins, int(cfg_value(test_cfg, "nms_pre")),
+                   float(cfg_value(test_cfg, "score_thr")), float(cfg_value(test_cfg, "iou_thr")))
 
 
 class SceneDetections:
