@@ -637,6 +637,43 @@ int mvsdet_nms3d_f32(const float* boxes, const float* scores, int n, float thres
                      void* workspace, size_t workspace_bytes, mvsdet_stream_t stream);
 int mvsdet_bev_iou_rotated_f32(const float* a, int n, const float* b, int m, float* out, mvsdet_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Training of the ScanNet head (csrc/assign.hip): target assignment (NerfDetHead._get_targets, nerfdet_head.py:473-562) and the
+ * three losses of _loss_by_feat_single (:206-257) on the caller's stream, no host synchronisation, no float atomics (the same bits
+ * from run to run).  fp32; labels int64.  Levels, level_dims, level_geom and valid as in mvsdet_detect_head_f32; P = a scene's
+ * points, the levels concatenated in order, a level's voxels x-major.
+ *
+ * mvsdet_head_targets_f32: gt_boxes (B,G,6) = (gravity centre, size), gt_volumes (B,G), gt_labels (B,G) int64, padded to the
+ *   batch's largest G <= MVSDET_ASSIGN_MAX_BOXES; gt_counts (B) int32 DEVICE = boxes of every scene.  Outputs: out_labels (B,P)
+ *   int64 (-1: no box), out_box_index (B,P) int32 (-1), out_center_targets (B,P), out_bbox_targets (B,P,6) (zero where no box).
+ *   A point takes the box of least volume among those it lies inside, on the box's best level, with centerness above the box's
+ *   (pts_center_threshold + 1)-th largest (strictly); equal volumes: the lowest box index.  A scene without boxes: every label -1.
+ *   Workspace: B * G * (MVSDET_DETECT_MAX_LEVELS + 2) * 4 bytes (0 for G = 0: none needed).
+ * mvsdet_head_loss_f32: the unnormalised sums of every scene: out_sums (B,4) = (sum over positive points of the centerness BCE,
+ *   sum of centerness target * (1 - IoU), sum over valid points and classes of mmcv's sigmoid focal loss, sum of the centerness
+ *   targets), out_counts (B,2) int32 = (positive points, valid points); positive = label >= 0 and valid.
+ *   Workspace: B * ceil(P / 256) * 6 * 4 bytes.
+ * mvsdet_head_loss_backward_f32: coef (B,3) DEVICE = what a unit of a scene's centerness / box / classification sum is worth
+ *   (incoming gradient over the normaliser); d_center, d_bbox, d_cls: HOST arrays of L device pointers, written densely in the maps'
+ *   layouts (zero where a point takes no part).
+ * ------------------------------------------------------------------------------------------- */
+#define MVSDET_ASSIGN_MAX_BOXES 1024 /* ground-truth boxes of one scene: staged in 36 KiB of LDS */
+size_t mvsdet_head_targets_workspace_bytes(int B, int G);
+int mvsdet_head_targets_f32(const int* level_dims, const float* level_geom, int B, int L, const float* gt_boxes,
+                            const float* gt_volumes, const int64_t* gt_labels, const int* gt_counts, int G, int pts_assign_threshold,
+                            int pts_center_threshold, int64_t* out_labels, int* out_box_index, float* out_center_targets,
+                            float* out_bbox_targets, void* workspace, size_t workspace_bytes, mvsdet_stream_t stream);
+size_t mvsdet_head_loss_workspace_bytes(int B, int points);
+int mvsdet_head_loss_f32(const float* const* center, const float* const* bbox, const float* const* cls, const int* level_dims,
+                         const float* valid, const float* level_geom, int B, int L, int n_classes, int VX, int VY, int VZ,
+                         const int64_t* labels, const float* center_targets, const float* bbox_targets, float gamma, float alpha,
+                         float* out_sums, int* out_counts, void* workspace, size_t workspace_bytes, mvsdet_stream_t stream);
+int mvsdet_head_loss_backward_f32(const float* const* center, const float* const* bbox, const float* const* cls, const int* level_dims,
+                                  const float* valid, const float* level_geom, int B, int L, int n_classes, int VX, int VY, int VZ,
+                                  const int64_t* labels, const float* center_targets, const float* bbox_targets, float gamma,
+                                  float alpha, const float* coef, float* const* d_center, float* const* d_bbox, float* const* d_cls,
+                                  mvsdet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

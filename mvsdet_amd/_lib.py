@@ -130,11 +130,18 @@ SIGNATURES = {
                                        _vp],
     "mvsdet_nms3d_f32": [_vp, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp],
     "mvsdet_bev_iou_rotated_f32": [_vp, _i, _vp, _i, _vp, _vp],
+    "mvsdet_head_targets_workspace_bytes": [_i, _i],
+    "mvsdet_head_targets_f32": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "mvsdet_head_loss_workspace_bytes": [_i, _i],
+    "mvsdet_head_loss_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _sz, _vp],
+    "mvsdet_head_loss_backward_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp,
+                                      _vp],
 }
 _RESTYPE = {"mvsdet_last_error": ctypes.c_char_p, "mvsdet_conv3d_k3_bf16x3_stats_parts": ctypes.c_size_t, "mvsdet_convT3d_k3_s2_bf16x3_stats_parts": ctypes.c_size_t, "mvsdet_gemm_split_weight_bytes": ctypes.c_size_t, "mvsdet_neck_gemm_dw_partial_bytes": ctypes.c_size_t, "mvsdet_scl_bytes": ctypes.c_size_t, "mvsdet_pscl_bytes": ctypes.c_size_t,
             "mvsdet_split_conv_weight_bytes": ctypes.c_size_t, "mvsdet_packed_bytes": ctypes.c_size_t,
             "mvsdet_split_conv_weight_mx_bytes": ctypes.c_size_t, "mvsdet_detect_workspace_bytes": ctypes.c_size_t,
             "mvsdet_detect_rotated_workspace_bytes": ctypes.c_size_t,
+            "mvsdet_head_targets_workspace_bytes": ctypes.c_size_t, "mvsdet_head_loss_workspace_bytes": ctypes.c_size_t,
             "mvsdet_plane_sweep_scratch_bytes": ctypes.c_size_t, "mvsdet_plane_sweep_workspace_bytes": ctypes.c_size_t,
             "mvsdet_plane_sweep_bwd_workspace_bytes": ctypes.c_size_t,
             "mvsdet_conv3d_k3_dw_partial_bytes": ctypes.c_size_t,

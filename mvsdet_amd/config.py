@@ -81,3 +81,59 @@ def hotpath_from_config(cfg, cost_regularization: Optional[Callable] = None):
     if isinstance(cfg, (str, os.PathLike)):
         cfg = load_config(os.fspath(cfg))
     return MVSDetHotPath(cost_regularization=cost_regularization, **hotpath_kwargs(cfg))
+
+
+_HEAD_LOSSES = {   # the loss types NerfDetHeadConvs.loss_by_feat computes, with or without mmengine's scope prefix
+    "center_loss": ("CrossEntropyLoss", dict(type="mmdet.CrossEntropyLoss", use_sigmoid=True)),
+    "bbox_loss": ("AxisAlignedIoULoss", dict(type="RotatedIoU3DLoss")),   # NerfDetHead's default is the ARKit head's loss
+    "cls_loss": ("FocalLoss", dict(type="mmdet.FocalLoss")),
+}
+
+
+def _loss_cfg(head: Dict[str, Any], key: str) -> Dict[str, Any]:
+    want, default = _HEAD_LOSSES[key]
+    cfg = dict(head.get(key) or default)
+    kind = str(cfg.get("type", "")).split(".")[-1]
+    if kind != want:
+        raise ValueError(f"model.bbox_head.{key}.type is {cfg.get('type')!r}; loss_by_feat computes {want!r} only"
+                         + (" (RotatedIoU3DLoss, the ARKit head's loss, is not implemented)" if key == "bbox_loss" else ""))
+    if cfg.get("reduction", "mean") != "mean":
+        raise ValueError(f"model.bbox_head.{key}.reduction is {cfg['reduction']!r}; 'mean' only")
+    if key == "center_loss" and not cfg.get("use_sigmoid", False):
+        raise ValueError("model.bbox_head.center_loss needs use_sigmoid=True")
+    if key == "cls_loss" and not cfg.get("use_sigmoid", True):
+        raise ValueError("model.bbox_head.cls_loss needs use_sigmoid=True")
+    return cfg
+
+
+def head_kwargs(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The constructor arguments of `NerfDetHeadConvs` from a loaded config (or from a bare `model` dict): `model.bbox_head`
+    (classes, levels, channels, both thresholds of the target assignment, the three loss dicts) and `model.test_cfg`."""
+    model = cfg.get("model", cfg)
+    head = model.get("bbox_head")
+    if head is None:
+        raise KeyError("model config lacks bbox_head")
+    kind = head.get("type", "NerfDetHead")
+    if kind == "ImVoxelHead_ARKit":
+        raise NotImplementedError("model.bbox_head.type is 'ImVoxelHead_ARKit': its RotatedIoU3DLoss is not implemented "
+                                  "(build NerfDetHeadConvs(arkit_head=True) for inference)")
+    if kind != "NerfDetHead":
+        raise ValueError(f"model.bbox_head.type is {kind!r}; 'NerfDetHead' only")
+    missing = [k for k in ("n_classes", "n_levels", "n_channels", "pts_assign_threshold", "pts_center_threshold") if head.get(k) is None]
+    if missing:
+        raise KeyError(f"model.bbox_head lacks {missing} (nerfdet_head.py:61-75 requires them)")
+    center, bbox, cls = (_loss_cfg(head, k) for k in ("center_loss", "bbox_loss", "cls_loss"))
+    return dict(n_classes=int(head["n_classes"]), n_levels=int(head["n_levels"]), n_channels=int(head["n_channels"]),
+                n_reg_outs=int(head.get("n_reg_outs", 6)), test_cfg=model.get("test_cfg"),
+                pts_assign_threshold=int(head["pts_assign_threshold"]), pts_center_threshold=int(head["pts_center_threshold"]),
+                center_loss_weight=float(center.get("loss_weight", 1.0)), bbox_loss_weight=float(bbox.get("loss_weight", 1.0)),
+                cls_loss_weight=float(cls.get("loss_weight", 1.0)), focal_gamma=float(cls.get("gamma", 2.0)),
+                focal_alpha=float(cls.get("alpha", 0.25)))
+
+
+def head_from_config(cfg):
+    """Build the ScanNet head with its loss settings from a config path, a loaded config or a `model` dict."""
+    from .head import NerfDetHeadConvs
+    if isinstance(cfg, (str, os.PathLike)):
+        cfg = load_config(os.fspath(cfg))
+    return NerfDetHeadConvs(**head_kwargs(cfg))

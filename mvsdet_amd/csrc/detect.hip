@@ -25,6 +25,7 @@
 // All arithmetic that decides or produces an output is written as the reference's ATen expression, op for op; the Makefile's
 // -ffp-contract=off keeps every product and sum separately rounded, and fp32 division is IEEE-rounded (hipcc's default).
 #include "common.h"
+#include "head_points.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -86,18 +87,6 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf
 // torch.maximum / torch.minimum: NaN in, NaN out
 __device__ __forceinline__ float nan_max(float a, float b) { return (a != a || b != b) ? __int_as_float(0x7fc00000) : (a > b ? a : b); }
 __device__ __forceinline__ float nan_min(float a, float b) { return (a != a || b != b) ? __int_as_float(0x7fc00000) : (a < b ? a : b); }
-
-// aten/src/ATen/native/UpSample.h: area_pixel_compute_source_index + guard_index_and_lambda (align_corners = False)
-__device__ __forceinline__ void linear_taps(float scale, int d, int in, int& i0, int& i1, float& l0, float& l1) {
-    float r = scale * ((float)d + 0.5f) - 0.5f;
-    if (r < 0.f) r = 0.f;
-    const int i = min((int)floorf(r), in - 1);
-    const float lam = fminf(fmaxf(r - (float)i, 0.f), 1.f);
-    i0 = i;
-    i1 = i + (i < in - 1 ? 1 : 0);
-    l1 = lam;
-    l0 = 1.f - lam;
-}
 
 // exclusive prefix of `flag` over the workgroup (in thread order) and the workgroup's total
 __device__ __forceinline__ int block_scan(bool flag, int* wave_cnt, int& total) {
@@ -321,29 +310,16 @@ __device__ __forceinline__ float rot_iou(const RotBox& a, const RotBox& b) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- selection
-// nn.Upsample(trilinear)(valid).round().bool() at voxel (x, y, z) of level lv, as 0 / 1
+// nn.Upsample(trilinear)(valid).round().bool() at voxel (x, y, z) of level lv, as 0 / 1 (head_points.h)
 __device__ __forceinline__ float valid_at(const SelectParams& p, const DetLevel& lv, const float* valid, int x, int y, int z) {
-    int x0, x1, y0, y1, z0, z1;
-    float ax0, ax1, ay0, ay1, az0, az1;
-    linear_taps(lv.sx, x, p.VX, x0, x1, ax0, ax1);
-    linear_taps(lv.sy, y, p.VY, y0, y1, ay0, ay1);
-    linear_taps(lv.sz, z, p.VZ, z0, z1, az0, az1);
-    auto at = [&](int xi, int yi, int zi) { return valid[((size_t)xi * p.VY + yi) * p.VZ + zi]; };
-    auto zl = [&](int xi, int yi) { float t = at(xi, yi, z0) * az0; t += at(xi, yi, z1) * az1; return t; };
-    auto yl = [&](int xi) { float t = zl(xi, y0) * ay0; t += zl(xi, y1) * ay1; return t; };
-    float v = yl(x0) * ax0;
-    v += yl(x1) * ax1;
-    return rintf(v) != 0.f ? 1.f : 0.f;
+    return upsampled_valid(valid, p.VX, p.VY, p.VZ, lv.sx, lv.sy, lv.sz, x, y, z);
 }
 
 // get_points of voxel i of a level: its (x, y, z), and the point = voxel * voxel size + new origin (g: a row of SelectParams::geom)
 __device__ __forceinline__ void voxel_point(const DetLevel& lv, const float* g, int i, int& x, int& y, int& z, float& px, float& py,
                                             float& pz) {
     x = i / (lv.Y * lv.Z), y = (i / lv.Z) % lv.Y, z = i % lv.Z;
-    px = (float)x * g[0], py = (float)y * g[1], pz = (float)z * g[2];
-    px = px + g[3];
-    py = py + g[4];
-    pz = pz + g[5];
+    grid_point(g, x, y, z, px, py, pz);
 }
 
 // kRot = false: the ScanNet head (6 regression channels, Work).  kRot = true: ImVoxelHead_ARKit (7 channels, RotWork): every
@@ -386,34 +362,11 @@ __global__ __launch_bounds__(kSelThreads) void detect_select_kernel(SelectParams
     // 2. top-k threshold: the k-th largest score bits (scores are >= 0: their bits order like their values), 8 bits a pass
     unsigned T = 0;
     int need_eq = 0;
-    if (lv.k > 0) {
-        unsigned prefix = 0, pmask = 0;
-        int kk = lv.k;
-        for (int shift = 24; shift >= 0; shift -= 8) {
-            for (int d = tid; d < 256; d += kSelThreads) hist[d] = 0;
-            __syncthreads();
-            for (int i = tid; i < N; i += kSelThreads) {
-                const unsigned u = __float_as_uint(ps[i]);
-                if ((u & pmask) == prefix) atomicAdd(&hist[(u >> shift) & 255u], 1);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                int acc = 0, d = 255;
-                for (; d > 0; --d) {
-                    if (acc + hist[d] >= kk) break;
-                    acc += hist[d];
-                }
-                sel[0] = d;
-                sel[1] = kk - acc;
-            }
-            __syncthreads();
-            prefix |= (unsigned)sel[0] << shift;
-            pmask |= 255u << shift;
-            kk = sel[1];
-            __syncthreads();
-        }
-        T = prefix;
-        need_eq = kk;   // points with bits == T to take, lowest voxel index first
+    if (lv.k > 0) {   // need_eq: points with bits == T to take, lowest voxel index first
+        T = radix_select_kth(hist, sel, N, lv.k, need_eq, [&](int i, unsigned& u) {
+            u = __float_as_uint(ps[i]);
+            return true;
+        });
     }
 
     // 3. compaction in voxel order: (top-k) and score > score_thr -> decoded box, score, label

@@ -7,7 +7,9 @@
                                               ImVoxelHead_ARKit: exp(scale_l(.)) on the 6 distances, the angle channel raw
     cls        = conv_cls(x)                  Conv3d(C -> n_classes,  k=3, p=1, bias)
 
-Target assignment and the losses (nerfdet_head.py:120 ff.) are training logic outside the path and stay the reference's.
+Target assignment and the three losses (`loss_by_feat`, nerfdet_head.py:152-257, 473-562: AxisAlignedIoULoss, FocalLoss, sigmoid
+CrossEntropyLoss) run on csrc/assign.hip for the ScanNet head (`ops.head_targets`, `ops.head_loss`): six launches per batch, no host
+synchronisation, the same bits from run to run.  The ARKit head's RotatedIoU3DLoss is not implemented.
 `predict_by_feat` (nerfdet_head.py:301-420, 564-628: scores, top-k, decode, aligned 3-D NMS) runs on csrc/detect.hip for the
 ScanNet head (`ops.head_predict`), and for the ARKit head (:902-1056, 1190-1243: all class scores of a top-k point, rotated decode,
 mmcv's nms3d per class) on its rotated kernels (`ops.head_predict_rotated`).  Parameter names equal the reference's
@@ -54,8 +56,14 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
     """The learnable layers of NerfDetHead and their forward pass (nerfdet_head.py:94-118)."""
 
     def __init__(self, n_classes: int = 18, n_levels: int = 3, n_channels: int = 128, n_reg_outs: int = 6,
-                 arkit_head: bool = False, test_cfg=None):
+                 arkit_head: bool = False, test_cfg=None, pts_assign_threshold: int = 27, pts_center_threshold: int = 18,
+                 center_loss_weight: float = 1.0, bbox_loss_weight: float = 1.0, cls_loss_weight: float = 1.0,
+                 focal_gamma: float = 2.0, focal_alpha: float = 0.25):
         super().__init__()
+        # loss_by_feat: both thresholds of _get_targets, loss_weight of the three terms, FocalLoss' gamma and alpha
+        self.pts_assign_threshold, self.pts_center_threshold = int(pts_assign_threshold), int(pts_center_threshold)
+        self.center_loss_weight, self.bbox_loss_weight = float(center_loss_weight), float(bbox_loss_weight)
+        self.cls_loss_weight, self.focal_gamma, self.focal_alpha = float(cls_loss_weight), float(focal_gamma), float(focal_alpha)
         self.test_cfg = test_cfg   # nms_pre, score_thr, iou_thr (mvsdet_res50_2x_low_res_depth.py:61): predict_by_feat
         self.n_classes, self.n_levels, self.n_reg_outs = n_classes, n_levels, n_reg_outs
         self.arkit_head = bool(arkit_head)   # ImVoxelHead_ARKit._forward_single (nerfdet_head.py:677-692)
@@ -161,6 +169,49 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
                                  rotated=self.arkit_head)
         return unpad_predictions(pred, batch_input_metas)
 
+    def loss_by_feat(self, center_preds: List[Tensor], bbox_preds: List[Tensor], cls_preds: List[Tensor], valid_pred: Tensor,
+                     batch_gt_instances_3d, batch_input_metas: List[dict], batch_gt_instances_ignore=None, **kwargs) -> dict:
+        """NerfDetHead.loss_by_feat (nerfdet_head.py:152-257): dict(center_loss, bbox_loss, cls_loss), each the mean over the
+        batch's scenes, from the head's maps (per level (B,...) CUDA float32 tensors), valid_pred (B,1,X,Y,Z) and per scene anything
+        with `bboxes_3d` (`gravity_center`, `tensor`, `volume`) and `labels_3d`.  Targets and sums on csrc/assign.hip, no host
+        synchronisation.  Per scene: center_loss = BCE-with-logits over positive points / (n_pos + eps), cls_loss = mmcv's sigmoid
+        focal loss over valid points and classes / (n_pos + eps), n_pos = max(positive points, 1), averaged over the ranks of an
+        initialised process group first (mmdet's reduce_mean); bbox_loss = sum w (1 - IoU) / (sum w + eps), w = the centerness
+        target; eps = float32's machine epsilon, mmdet 3.x's weight_reduce_loss.  A scene without valid or positive points gives 0
+        with zero gradients; one without boxes has no positive point (the reference raises there).  Equal box volumes at a point:
+        the lowest box index.  batch_gt_instances_ignore is not read, as in the reference."""
+        if self.arkit_head:
+            raise NotImplementedError("loss_by_feat: ImVoxelHead_ARKit's RotatedIoU3DLoss (a differentiable rotated IoU) is not "
+                                      "implemented; the ScanNet head's AxisAlignedIoULoss is")
+        B = len(batch_input_metas)
+        if len(batch_gt_instances_3d) != B:
+            raise ValueError(f"loss_by_feat: {len(batch_gt_instances_3d)} ground-truth sets for {B} scenes")
+        ops.check_box_limit(max([len(g.labels_3d) for g in batch_gt_instances_3d], default=0))   # before anything is launched
+        for t in list(center_preds) + list(bbox_preds) + list(cls_preds) + [valid_pred]:
+            if not t.is_cuda:
+                raise RuntimeError(f"loss_by_feat: the head's maps must live on a ROCm device (got {t.device}); this package has no "
+                                   "CPU path")
+        if torch.is_autocast_enabled("cuda"):   # --amp: the loss computes in float32 (layers.fp32_under_autocast's rule)
+            with torch.autocast("cuda", enabled=False):
+                up = lambda ts: [t.float() for t in ts]
+                return self.loss_by_feat(up(center_preds), up(bbox_preds), up(cls_preds), valid_pred, batch_gt_instances_3d,
+                                         batch_input_metas, batch_gt_instances_ignore, **kwargs)
+        dev = valid_pred.device
+        gt_boxes, gt_volumes, gt_labels, gt_counts = pad_ground_truth(batch_gt_instances_3d, dev)
+        sizes = [tuple(c.shape[2:]) for c in center_preds]
+        origins = [scene_origin(m) for m in batch_input_metas]
+        targets = ops.head_targets(sizes, origins, gt_boxes, gt_volumes, gt_labels, gt_counts, self.pts_assign_threshold,
+                                   self.pts_center_threshold)
+        sums = ops.head_loss(center_preds, bbox_preds, cls_preds, valid_pred, targets, self.focal_gamma, self.focal_alpha)
+        eps = torch.finfo(torch.float32).eps
+        n_pos = sums.n_pos.float()
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            torch.distributed.all_reduce(n_pos.div_(torch.distributed.get_world_size()), op=torch.distributed.ReduceOp.SUM)
+        n_avg = n_pos.clamp(min=1.0) + eps
+        return dict(center_loss=torch.mean(sums.center / n_avg * self.center_loss_weight),
+                    bbox_loss=torch.mean(sums.bbox / (sums.weight_sum + eps) * self.bbox_loss_weight),
+                    cls_loss=torch.mean(sums.cls / n_avg * self.cls_loss_weight))
+
     @staticmethod
     def flops(grid: Sequence[int], n_classes: int = 18, n_levels: int = 3, n_channels: int = 128, n_reg_outs: int = 6) -> float:
         v = sum((grid[0] >> i) * (grid[1] >> i) * (grid[2] >> i) for i in range(n_levels))
@@ -193,6 +244,26 @@ def predict_head_maps(center_preds, bbox_preds, cls_preds, valid_pred: Tensor, b
     predict = ops.head_predict_rotated if rotated else ops.head_predict
     return predict(center_preds, bbox_preds, cls_preds, valid_pred, origins, int(cfg_value(test_cfg, "nms_pre")),
                    float(cfg_value(test_cfg, "score_thr")), float(cfg_value(test_cfg, "iou_thr")))
+
+
+def pad_ground_truth(batch_gt_instances_3d, device) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """What _get_targets reads of every scene's ground truth, by the reference's own torch expressions (nerfdet_head.py:497-500),
+    padded to the batch's largest box count: boxes (B,G,6) = cat(gravity_center, tensor[:, 3:6]), volumes (B,G), labels (B,G) int64
+    and the counts (B,) int32, made from the shapes; on `device` without a host synchronisation."""
+    rows = []
+    for gt in batch_gt_instances_3d:
+        b = gt.bboxes_3d
+        boxes = torch.cat((b.gravity_center, b.tensor[:, 3:6]), dim=1).float()
+        rows.append((boxes, b.volume.float().reshape(-1), gt.labels_3d.long().reshape(-1)))
+    G = max([int(r[0].shape[0]) for r in rows], default=0)
+    counts = torch.tensor([int(r[0].shape[0]) for r in rows], dtype=torch.int32)
+
+    def pad(ts, width, dtype):
+        out = [torch.cat([t.reshape((t.shape[0],) + width), t.new_zeros((G - t.shape[0],) + width)]) for t in ts]
+        return ops._to_device(torch.stack(out).to(dtype), device)
+
+    return (pad([r[0] for r in rows], (6,), torch.float32), pad([r[1] for r in rows], (), torch.float32),
+            pad([r[2] for r in rows], (), torch.int64), ops._to_device(counts, device))
 
 
 class SceneDetections:

@@ -2094,3 +2094,162 @@ def bev_iou_rotated(a: Tensor, b: Tensor) -> Tensor:
     with torch.cuda.device(a.device):
         _lib.check(_lib.load().mvsdet_bev_iou_rotated_f32(_lib.ptr(x), n, _lib.ptr(y), m, _lib.ptr(out), _stream(a)), "bev_iou_rotated")
     return out
+
+
+# ------------------------------------------------------------------------------------------- head training: targets and losses
+# NerfDetHead._get_targets / _loss_by_feat_single (nerfdet_head.py:206-257, 473-562) on csrc/assign.hip: three launches for the
+# targets, two for the losses' sums, one for their gradients, on the current stream, no host synchronisation, the same bits from run
+# to run.
+ASSIGN_MAX_BOXES = 1024   # MVSDET_ASSIGN_MAX_BOXES: ground-truth boxes of one scene (staged in LDS by assign_pick_kernel)
+
+
+class HeadTargets(NamedTuple):
+    """Targets of every point of a batch (P = the levels' points concatenated in order, a level's voxels x-major): labels (B,P)
+    int64 (-1: no box), box_index (B,P) int32 (-1), center_targets (B,P), bbox_targets (B,P,6) (x1, y1, z1, x2, y2, z2; zero
+    where no box), and geom (B,L,6), the device copy of detect_level_geometry the targets were made with."""
+    labels: Tensor
+    box_index: Tensor
+    center_targets: Tensor
+    bbox_targets: Tensor
+    geom: Tensor
+
+
+class HeadLossSums(NamedTuple):
+    """Unnormalised sums of every scene: center (B,) = the centerness BCE over positive points, bbox (B,) = centerness target *
+    (1 - IoU) over positive points, cls (B,) = the focal loss over valid points and classes -- these three carry gradients to the
+    nine maps -- and weight_sum (B,) = the positive points' centerness targets, n_pos, n_valid (B,) int32."""
+    center: Tensor
+    bbox: Tensor
+    cls: Tensor
+    weight_sum: Tensor
+    n_pos: Tensor
+    n_valid: Tensor
+
+
+def _to_device(t: Tensor, dev) -> Tensor:
+    """A host tensor through pinned memory (no host synchronisation); a device tensor as it is."""
+    return t.to(dev) if t.is_cuda else t.pin_memory().to(dev, non_blocking=True)
+
+
+def check_box_limit(n_boxes: int) -> None:
+    if n_boxes > ASSIGN_MAX_BOXES:
+        raise ValueError(f"head_targets: {n_boxes} ground-truth boxes in one scene, above the limit ASSIGN_MAX_BOXES = "
+                         f"{ASSIGN_MAX_BOXES} (MVSDET_ASSIGN_MAX_BOXES: the boxes of a scene are staged in LDS)")
+
+
+def head_targets(featmap_sizes, origins, gt_boxes: Tensor, gt_volumes: Tensor, gt_labels: Tensor, gt_counts: Tensor,
+                 pts_assign_threshold: int, pts_center_threshold: int) -> HeadTargets:
+    """NerfDetHead._get_targets of every scene of a batch (nerfdet_head.py:473-562).  featmap_sizes: (X, Y, Z) per level; origins:
+    one float32 (3,) origin per scene; gt_boxes (B,G,6) = cat(gravity_center, tensor[:, 3:6]), gt_volumes (B,G), gt_labels (B,G)
+    int64, padded to the batch's largest G <= ASSIGN_MAX_BOXES (checked on the shape, before any launch); gt_counts (B,) int32 =
+    the boxes of every scene.  CUDA tensors only.  Equal volumes: the lowest box index wins (torch.min on the CPU; the reference
+    leaves it to the backend).  A scene without boxes gets label -1 everywhere (the reference raises on the empty min).  A box with
+    at most pts_center_threshold points inside on its best level keeps them all."""
+    B = len(origins)
+    L = len(featmap_sizes)
+    if not (1 <= L <= DETECT_MAX_LEVELS):
+        raise ValueError(f"head_targets: 1..{DETECT_MAX_LEVELS} levels needed")
+    if gt_boxes.dim() != 3:
+        raise ValueError(f"head_targets: gt_boxes must be (B, G, 6) (got shape {tuple(gt_boxes.shape)})")
+    G = int(gt_boxes.shape[1])
+    check_box_limit(G)   # from the shape, before anything else
+    _req(gt_boxes, "gt_boxes", dim=3)
+    _req(gt_volumes, "gt_volumes", dim=2)
+    _req(gt_labels, "gt_labels", dtype=torch.int64, dim=2)
+    _req(gt_counts, "gt_counts", dtype=torch.int32, dim=1)
+    if gt_boxes.shape != (B, G, 6) or gt_volumes.shape != (B, G) or gt_labels.shape != (B, G) or gt_counts.shape != (B,):
+        raise ValueError(f"head_targets: gt_boxes {tuple(gt_boxes.shape)}, gt_volumes {tuple(gt_volumes.shape)}, gt_labels "
+                         f"{tuple(gt_labels.shape)}, gt_counts {tuple(gt_counts.shape)} for {B} scenes")
+    dev = gt_boxes.device
+    sizes = [tuple(int(v) for v in s) for s in featmap_sizes]
+    dims = [v for s in sizes for v in s]
+    P = sum(s[0] * s[1] * s[2] for s in sizes)
+    geom = _to_device(detect_level_geometry(sizes, origins), dev)
+    lib = _lib.load()
+    ws = torch.empty(int(lib.mvsdet_head_targets_workspace_bytes(B, G)), dtype=torch.uint8, device=dev)
+    labels = torch.empty((B, P), dtype=torch.int64, device=dev)
+    box_index = torch.empty((B, P), dtype=torch.int32, device=dev)
+    center_t = torch.empty((B, P), dtype=torch.float32, device=dev)
+    bbox_t = torch.empty((B, P, 6), dtype=torch.float32, device=dev)
+    boxes, volumes, glabels = gt_boxes.contiguous(), gt_volumes.contiguous(), gt_labels.contiguous()
+    with torch.cuda.device(dev):
+        _lib.check(lib.mvsdet_head_targets_f32(
+            (ctypes.c_int * len(dims))(*dims), _lib.ptr(geom), B, L, _lib.ptr(boxes) if G else None, _lib.ptr(volumes) if G else None,
+            _lib.ptr(glabels) if G else None, _lib.ptr(gt_counts.contiguous()), G, int(pts_assign_threshold), int(pts_center_threshold),
+            _lib.ptr(labels), _lib.ptr(box_index), _lib.ptr(center_t), _lib.ptr(bbox_t), _lib.ptr(ws) if ws.numel() else None,
+            ws.numel(), _stream(gt_boxes)), "head_targets")
+    return HeadTargets(labels, box_index, center_t, bbox_t, geom)
+
+
+def _loss_maps(center_preds, bbox_preds, cls_preds, valid_pred, targets: HeadTargets):
+    L = len(center_preds)
+    if not (1 <= L <= DETECT_MAX_LEVELS) or len(bbox_preds) != L or len(cls_preds) != L:
+        raise ValueError(f"head_loss: 1..{DETECT_MAX_LEVELS} levels of center / bbox / cls maps needed")
+    _req(valid_pred, "valid_pred", dtype=valid_pred.dtype, dim=5)
+    B = valid_pred.shape[0]
+    maps = []
+    for lvl, (c, r, k) in enumerate(zip(center_preds, bbox_preds, cls_preds)):
+        for t, name, ch in ((c, "center", 1), (r, "bbox", 6), (k, "cls", int(cls_preds[0].shape[1]))):
+            _req(t, f"{name}_preds[{lvl}]", dim=5)
+            if t.shape[0] != B or t.shape[1] != ch or t.shape[2:] != c.shape[2:]:
+                raise ValueError(f"head_loss: {name}_preds[{lvl}] has shape {tuple(t.shape)}")
+        maps += [c, r, k]
+    P = sum(int(c.shape[2] * c.shape[3] * c.shape[4]) for c in center_preds)
+    if targets.labels.shape != (B, P) or targets.geom.shape != (B, L, 6):
+        raise ValueError(f"head_loss: targets of shape {tuple(targets.labels.shape)} for {B} scenes of {P} points")
+    return maps
+
+
+class _HeadLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, valid, labels, center_t, bbox_t, geom, gamma, alpha, *maps):
+        L = len(maps) // 3
+        maps = [m.contiguous() for m in maps]
+        B, C = int(valid.shape[0]), int(maps[2].shape[1])
+        dims = [int(v) for l in range(L) for v in maps[3 * l].shape[2:]]
+        P = int(labels.shape[1])
+        dev = valid.device
+        lib = _lib.load()
+        ws = torch.empty(int(lib.mvsdet_head_loss_workspace_bytes(B, P)), dtype=torch.uint8, device=dev)
+        sums = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        arr = ctypes.c_void_p * L
+        ctx.args = (arr, dims, B, L, C, [int(v) for v in valid.shape[2:]], float(gamma), float(alpha))
+        with torch.cuda.device(dev):
+            _lib.check(lib.mvsdet_head_loss_f32(
+                arr(*[maps[3 * l].data_ptr() for l in range(L)]), arr(*[maps[3 * l + 1].data_ptr() for l in range(L)]),
+                arr(*[maps[3 * l + 2].data_ptr() for l in range(L)]), (ctypes.c_int * len(dims))(*dims), _lib.ptr(valid), _lib.ptr(geom),
+                B, L, C, *ctx.args[5], _lib.ptr(labels), _lib.ptr(center_t), _lib.ptr(bbox_t), float(gamma), float(alpha),
+                _lib.ptr(sums), _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _stream(valid)), "head_loss")
+        ctx.save_for_backward(valid, labels, center_t, bbox_t, geom, *maps)
+        out = (sums[:, 0], sums[:, 1], sums[:, 2], sums[:, 3], counts[:, 0], counts[:, 1])
+        ctx.mark_non_differentiable(*out[3:])
+        return out
+
+    @staticmethod
+    def backward(ctx, g_center, g_bbox, g_cls, *unused):
+        valid, labels, center_t, bbox_t, geom, *maps = ctx.saved_tensors
+        arr, dims, B, L, C, vdims, gamma, alpha = ctx.args
+        coef = torch.stack([g_center, g_bbox, g_cls], dim=1).float().contiguous()
+        grads = [torch.empty_like(m) for m in maps]
+        with torch.cuda.device(valid.device):
+            _lib.check(_lib.load().mvsdet_head_loss_backward_f32(
+                arr(*[maps[3 * l].data_ptr() for l in range(L)]), arr(*[maps[3 * l + 1].data_ptr() for l in range(L)]),
+                arr(*[maps[3 * l + 2].data_ptr() for l in range(L)]), (ctypes.c_int * len(dims))(*dims), _lib.ptr(valid), _lib.ptr(geom),
+                B, L, C, *vdims, _lib.ptr(labels), _lib.ptr(center_t), _lib.ptr(bbox_t), gamma, alpha, _lib.ptr(coef),
+                arr(*[grads[3 * l].data_ptr() for l in range(L)]), arr(*[grads[3 * l + 1].data_ptr() for l in range(L)]),
+                arr(*[grads[3 * l + 2].data_ptr() for l in range(L)]), _stream(valid)), "head_loss_backward")
+        return (None,) * 7 + tuple(grads)
+
+
+def head_loss(center_preds, bbox_preds, cls_preds, valid_pred: Tensor, targets: HeadTargets, gamma: float = 2.0,
+              alpha: float = 0.25) -> HeadLossSums:
+    """The sums of NerfDetHead._loss_by_feat_single (nerfdet_head.py:206-257) for every scene of a batch, with gradients to the nine
+    maps.  center_preds / bbox_preds / cls_preds: per level (B,1|6|C,X,Y,Z) float32 CUDA maps, read in place; valid_pred
+    (B,1,X,Y,Z): the stacked view counts; targets: ops.head_targets of the same level sizes.  Positive = label >= 0 and
+    nn.Upsample(trilinear)(valid_pred).round().bool().  The caller divides: center / n_pos', cls / n_pos' with n_pos' =
+    max(n_pos, 1) (averaged over the ranks first), bbox / weight_sum (NerfDetHeadConvs.loss_by_feat)."""
+    maps = _loss_maps(center_preds, bbox_preds, cls_preds, valid_pred, targets)
+    valid = valid_pred.float().contiguous()
+    return HeadLossSums(*_HeadLoss.apply(valid, targets.labels, targets.center_targets, targets.bbox_targets, targets.geom,
+                                         float(gamma), float(alpha), *maps))
