@@ -657,7 +657,7 @@ int mvsdet_bev_iou_rotated_f32(const float* a, int n, const float* b, int m, flo
  *   (incoming gradient over the normaliser); d_center, d_bbox, d_cls: HOST arrays of L device pointers, written densely in the maps'
  *   layouts (zero where a point takes no part).
  * ------------------------------------------------------------------------------------------- */
-#define MVSDET_ASSIGN_MAX_BOXES 1024 /* ground-truth boxes of one scene: staged in 36 KiB of LDS */
+#define MVSDET_ASSIGN_MAX_BOXES 1024 /* ground-truth boxes of one scene: staged in 36 KiB of LDS (48 KiB with headings) */
 size_t mvsdet_head_targets_workspace_bytes(int B, int G);
 int mvsdet_head_targets_f32(const int* level_dims, const float* level_geom, int B, int L, const float* gt_boxes,
                             const float* gt_volumes, const int64_t* gt_labels, const int* gt_counts, int G, int pts_assign_threshold,
@@ -673,6 +673,38 @@ int mvsdet_head_loss_backward_f32(const float* const* center, const float* const
                                   const int64_t* labels, const float* center_targets, const float* bbox_targets, float gamma,
                                   float alpha, const float* coef, float* const* d_center, float* const* d_bbox, float* const* d_cls,
                                   mvsdet_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Training of the ARKit head (csrc/assign.hip, the same kernels instantiated for 7-value boxes): ImVoxelHead_ARKit._get_targets
+ * (nerfdet_head.py:1107-1185) and _loss_by_feat_single (:779-846) with RotatedIoU3DLoss.  Everything as in the three entries above
+ * except:
+ *
+ * mvsdet_head_targets_rotated_f32: gt_boxes (B,G,7) = (gravity centre, size, yaw); gt_rot (B,G,2) = (cos(yaw), sin(yaw)) as the
+ *   caller computed them (no transcendental is evaluated on the way to a label).  Face distances are taken in the box's own frame
+ *   (:1058-1084).  The top-k takes min(pts_center_threshold + 1, P) values.  out_bbox_targets (B,P,7) = the chosen ground-truth row
+ *   itself (zero where no box); out_center_targets is -1 where no box is assigned.  Workspace: mvsdet_head_targets_workspace_bytes.
+ * mvsdet_head_loss_rotated_f32 / mvsdet_head_loss_rotated_backward_f32: bbox maps of 7 channels (six distances, heading),
+ *   bbox_targets (B,P,7); the box term is centerness target * (1 - IoU3D) of the decoded rotated box (:1029-1055) and its target,
+ *   IoU3D = A_bev * z overlap / (V_pred + V_gt - A_bev * z overlap), A_bev the exact area of the intersection of the two rotated
+ *   rectangles.  Relative headings within 1e-6 rad of a multiple of pi/2 count as that multiple; an edge shared by both rectangles
+ *   counts once; every value and gradient is finite, a target of zero size gives IoU 0.  The targets receive no gradient.
+ *   Workspace: mvsdet_head_loss_workspace_bytes.
+ * ------------------------------------------------------------------------------------------- */
+int mvsdet_head_targets_rotated_f32(const int* level_dims, const float* level_geom, int B, int L, const float* gt_boxes,
+                                    const float* gt_rot, const float* gt_volumes, const int64_t* gt_labels, const int* gt_counts, int G,
+                                    int pts_assign_threshold, int pts_center_threshold, int64_t* out_labels, int* out_box_index,
+                                    float* out_center_targets, float* out_bbox_targets, void* workspace, size_t workspace_bytes,
+                                    mvsdet_stream_t stream);
+int mvsdet_head_loss_rotated_f32(const float* const* center, const float* const* bbox, const float* const* cls, const int* level_dims,
+                                 const float* valid, const float* level_geom, int B, int L, int n_classes, int VX, int VY, int VZ,
+                                 const int64_t* labels, const float* center_targets, const float* bbox_targets, float gamma,
+                                 float alpha, float* out_sums, int* out_counts, void* workspace, size_t workspace_bytes,
+                                 mvsdet_stream_t stream);
+int mvsdet_head_loss_rotated_backward_f32(const float* const* center, const float* const* bbox, const float* const* cls,
+                                          const int* level_dims, const float* valid, const float* level_geom, int B, int L,
+                                          int n_classes, int VX, int VY, int VZ, const int64_t* labels, const float* center_targets,
+                                          const float* bbox_targets, float gamma, float alpha, const float* coef,
+                                          float* const* d_center, float* const* d_bbox, float* const* d_cls, mvsdet_stream_t stream);
 
 #ifdef __cplusplus
 }

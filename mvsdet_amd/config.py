@@ -90,13 +90,17 @@ _HEAD_LOSSES = {   # the loss types NerfDetHeadConvs.loss_by_feat computes, with
 }
 
 
-def _loss_cfg(head: Dict[str, Any], key: str) -> Dict[str, Any]:
+def _loss_cfg(head: Dict[str, Any], key: str, arkit: bool = False) -> Dict[str, Any]:
     want, default = _HEAD_LOSSES[key]
     cfg = dict(head.get(key) or default)
     kind = str(cfg.get("type", "")).split(".")[-1]
-    if kind != want:
+    if key == "bbox_loss" and arkit:
+        if kind != "RotatedIoU3DLoss":   # no axis-aligned loss of 7-value boxes exists here
+            raise NotImplementedError(f"model.bbox_head.bbox_loss.type is {cfg.get('type')!r}; for 'ImVoxelHead_ARKit' loss_by_feat "
+                                      "computes 'RotatedIoU3DLoss' only")
+    elif kind != want:
         raise ValueError(f"model.bbox_head.{key}.type is {cfg.get('type')!r}; loss_by_feat computes {want!r} only"
-                         + (" (RotatedIoU3DLoss, the ARKit head's loss, is not implemented)" if key == "bbox_loss" else ""))
+                         + (" for 'NerfDetHead' (RotatedIoU3DLoss is the loss of 'ImVoxelHead_ARKit')" if key == "bbox_loss" else ""))
     if cfg.get("reduction", "mean") != "mean":
         raise ValueError(f"model.bbox_head.{key}.reduction is {cfg['reduction']!r}; 'mean' only")
     if key == "center_loss" and not cfg.get("use_sigmoid", False):
@@ -114,17 +118,18 @@ def head_kwargs(cfg: Dict[str, Any]) -> Dict[str, Any]:
     if head is None:
         raise KeyError("model config lacks bbox_head")
     kind = head.get("type", "NerfDetHead")
-    if kind == "ImVoxelHead_ARKit":
-        raise NotImplementedError("model.bbox_head.type is 'ImVoxelHead_ARKit': its RotatedIoU3DLoss is not implemented "
-                                  "(build NerfDetHeadConvs(arkit_head=True) for inference)")
-    if kind != "NerfDetHead":
-        raise ValueError(f"model.bbox_head.type is {kind!r}; 'NerfDetHead' only")
+    if kind not in ("NerfDetHead", "ImVoxelHead_ARKit"):
+        raise ValueError(f"model.bbox_head.type is {kind!r}; 'NerfDetHead' and 'ImVoxelHead_ARKit' only")
+    arkit = kind == "ImVoxelHead_ARKit"   # 7-value boxes; bbox_loss defaults to RotatedIoU3DLoss (nerfdet_head.py:632-662)
     missing = [k for k in ("n_classes", "n_levels", "n_channels", "pts_assign_threshold", "pts_center_threshold") if head.get(k) is None]
     if missing:
         raise KeyError(f"model.bbox_head lacks {missing} (nerfdet_head.py:61-75 requires them)")
-    center, bbox, cls = (_loss_cfg(head, k) for k in ("center_loss", "bbox_loss", "cls_loss"))
+    center, bbox, cls = (_loss_cfg(head, k, arkit) for k in ("center_loss", "bbox_loss", "cls_loss"))
+    n_reg_outs = int(head.get("n_reg_outs", 7 if arkit else 6))
+    if arkit and n_reg_outs != 7:
+        raise ValueError(f"model.bbox_head.n_reg_outs is {n_reg_outs}; 'ImVoxelHead_ARKit' regresses 7 values")
     return dict(n_classes=int(head["n_classes"]), n_levels=int(head["n_levels"]), n_channels=int(head["n_channels"]),
-                n_reg_outs=int(head.get("n_reg_outs", 6)), test_cfg=model.get("test_cfg"),
+                n_reg_outs=n_reg_outs, arkit_head=arkit, test_cfg=model.get("test_cfg"),
                 pts_assign_threshold=int(head["pts_assign_threshold"]), pts_center_threshold=int(head["pts_center_threshold"]),
                 center_loss_weight=float(center.get("loss_weight", 1.0)), bbox_loss_weight=float(bbox.get("loss_weight", 1.0)),
                 cls_loss_weight=float(cls.get("loss_weight", 1.0)), focal_gamma=float(cls.get("gamma", 2.0)),
@@ -132,7 +137,8 @@ def head_kwargs(cfg: Dict[str, Any]) -> Dict[str, Any]:
 
 
 def head_from_config(cfg):
-    """Build the ScanNet head with its loss settings from a config path, a loaded config or a `model` dict."""
+    """Build the ScanNet head ('NerfDetHead') or the ARKit head ('ImVoxelHead_ARKit') with its loss settings from a config path, a
+    loaded config or a `model` dict."""
     from .head import NerfDetHeadConvs
     if isinstance(cfg, (str, os.PathLike)):
         cfg = load_config(os.fspath(cfg))

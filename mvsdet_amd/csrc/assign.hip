@@ -1,5 +1,9 @@
-// Training of the ScanNet head: target assignment (NerfDetHead._get_targets, projects/NeRF-Det/nerfdet/nerfdet_head.py:473-562)
-// and its three losses (_loss_by_feat_single, :206-257) on the caller's stream, no host round trip, no float atomics.
+// Training of the detection head on the caller's stream, no host round trip, no float atomics.  Two routes share every kernel
+// (templates on the box record and on the box loss):
+//   ScanNet head  NerfDetHead._get_targets (projects/NeRF-Det/nerfdet/nerfdet_head.py:473-562), _loss_by_feat_single (:206-257):
+//                 6-value boxes, targets rebuilt from the face distances, AxisAlignedIoULoss
+//   ARKit head    ImVoxelHead_ARKit._get_targets (:1107-1185), _loss_by_feat_single (:779-846): 7-value boxes with heading, face
+//                 distances in the box's own frame (:1058-1084), the ground-truth box itself as target, RotatedIoU3DLoss
 //
 //   assign_count_kernel        grid (box, level, scene): n[l, g] = points of level l inside box g (integer workgroup reduction)
 //   assign_select_kernel       one workgroup per (scene, box): best[g] from n[:, g]; centerness of the best level's inside points;
@@ -14,7 +18,27 @@
 // The first two visit only the sub-block of the grid that can hold a box's points (two voxels of margin; the whole level for boxes
 // with non-finite or huge coordinates); the inside test itself is the reference's expression on every visited point.  No
 // intermediate of size points x boxes exists.  All arithmetic that decides or produces a target is the reference's ATen expression,
-// op for op, under -ffp-contract=off with IEEE division and square root.
+// op for op, under -ffp-contract=off with IEEE division and square root.  The rotated route takes cos(yaw) and sin(yaw) of every
+// ground-truth box as inputs (torch.cos / torch.sin of the caller, as rotation_3d_in_axis computes them): no transcendental lies on
+// the path to a label.  The sub-block of a rotated box is that of the axis-aligned hull of its footprint.
+//
+// RotatedIoU3DLoss (rotated_iou_loss below), one thread per positive point, forward and backward, no vertex list and no sort:
+// the boundary of the intersection of two convex regions is the pieces of A's edges inside B plus the pieces of B's edges inside
+// A.  Each of the eight edges is clipped by parameter interval (Liang-Barsky) against the other rectangle in that rectangle's own
+// frame, where it is axis-aligned; the area is Green's sum 1/2 (c x t + h) * length over the pieces (c: the rectangle's centre
+// seen from B's centre, t: the edge's direction, h: its distance from c).  The gradient is the boundary integral over the pieces
+// of the predicted rectangle A: d area / d centre = sum of normal * length, / d size = half the lengths of the two edges across,
+// / d yaw = - integral of tau d tau (tau: the position along the edge from its midpoint).  That is the derivative of the area
+// itself, which is what autograd through mmcv's vertex gather yields away from degenerate pairs.
+// Convention at degenerate pairs: a relative angle within 1e-6 rad of a multiple of pi/2 is taken as that multiple (float pi and
+// pi/2 are not exact).  An edge of A that lies ON a parallel edge of B counts in full where both outward normals agree, and not
+// at all where they oppose (boxes touching from outside); an edge of B that lies on an edge of A never counts (A against closed
+// B, B against open A), so a shared edge is counted once.  With parallel axes the area is the product of the two overlaps along
+// B's axes, taken from the same sums that place A's edges: two roundings of one shared edge cannot count it twice.  Left open: a
+// relative angle between 1e-6 and about 1e-4 rad off a multiple of pi/2 together with two edges less than about 1e-7 m apart,
+// where the crossing of the two nearly coincident edges is ill-conditioned in float32 and the area can be off by a share of that
+// edge's strip (still finite; a set of vanishing measure that no test here reaches).  The area is clamped to >= 0, the union is never zero for
+// a predicted box (its sizes are sums of two exponentials); a ground-truth box of zero size gives IoU 0.  All of it is finite.
 #include "common.h"
 #include "head_points.h"
 
@@ -38,12 +62,13 @@ struct GridLevel {
 struct AssignParams {
     GridLevel lv[kMaxL];
     const float* geom;     // (B, L, 6): voxel size, new origin
-    const float* boxes;    // (B, G, 6): gravity centre, size
+    const float* boxes;    // (B, G, 6): gravity centre, size; rotated route (B, G, 7): and yaw
+    const float* rot;      // rotated route: (B, G, 2) cos(yaw), sin(yaw)
     const float* volumes;  // (B, G)
     const long long* labels;   // (B, G)
     const int* counts;     // (B): boxes of the scene
     int L, G, P;
-    int assign_thr, center_thr;
+    int assign_thr, center_k;
     int* n_inside;         // (B, G, kMaxL) workspace
     int* best;             // (B, G)
     float* thr;            // (B, G)
@@ -51,7 +76,7 @@ struct AssignParams {
 
 struct LossLevel {
     const float* center;   // (B,1,X,Y,Z)
-    const float* bbox;     // (B,6,X,Y,Z)
+    const float* bbox;     // (B,6,X,Y,Z); rotated route (B,7,X,Y,Z)
     const float* cls;      // (B,C,X,Y,Z)
     float* d_center;       // gradients in the same layouts (backward only)
     float* d_bbox;
@@ -66,10 +91,31 @@ struct LossParams {
     const float* geom;     // (B, L, 6)
     const long long* labels;   // (B, P) of the assignment, -1 = background
     const float* center_t;     // (B, P)
-    const float* bbox_t;       // (B, P, 6)
+    const float* bbox_t;       // (B, P, 6); rotated route (B, P, 7)
     int L, C, P, VX, VY, VZ;
     float gamma, alpha;
 };
+
+// The two box records.  kBox: values of a ground-truth row, kReg: channels of the bbox map and values of a target row
+struct AlignedBox {
+    static constexpr int kBox = 6, kReg = 6;
+    float b[6];            // gravity centre, size
+};
+struct RotatedBox {
+    static constexpr int kBox = 7, kReg = 7;
+    float b[6];
+    float yaw, c, s;       // heading, its cosine and sine as the caller computed them
+};
+
+__device__ __forceinline__ void load_box(const AssignParams& p, size_t r, AlignedBox& g) {
+    for (int q = 0; q < 6; ++q) g.b[q] = p.boxes[r * 6 + q];
+}
+__device__ __forceinline__ void load_box(const AssignParams& p, size_t r, RotatedBox& g) {
+    for (int q = 0; q < 6; ++q) g.b[q] = p.boxes[r * 7 + q];
+    g.yaw = p.boxes[r * 7 + 6];
+    g.c = p.rot[r * 2];
+    g.s = p.rot[r * 2 + 1];
+}
 
 // _get_face_distances of point (px, py, pz) to box b = (cx, cy, cz, dx, dy, dz), in the reference's operand order
 __device__ __forceinline__ void face_distances(float px, float py, float pz, const float* b, float* d) {
@@ -79,6 +125,26 @@ __device__ __forceinline__ void face_distances(float px, float py, float pz, con
     d[3] = (b[1] + b[4] / 2.f) - py;
     d[4] = (pz - b[2]) + b[5] / 2.f;
     d[5] = (b[2] + b[5] / 2.f) - pz;
+}
+__device__ __forceinline__ void face_distances(float px, float py, float pz, const AlignedBox& g, float* d) {
+    face_distances(px, py, pz, g.b, d);
+}
+// ImVoxelHead_ARKit._get_face_distances (:1070-1084): point - centre rotated by -yaw about z (rotation_3d_in_axis: the row
+// vector times [[cos, sin, 0], [-sin, cos, 0], [0, 0, 1]] of the angle -yaw), added to the centre again, then the six distances
+__device__ __forceinline__ void face_distances(float px, float py, float pz, const RotatedBox& g, float* d) {
+    const float sx = px - g.b[0], sy = py - g.b[1], sz = pz - g.b[2];
+    const float rs = -g.s;                                   // sin(-yaw)
+    const float cx = g.b[0] + (sx * g.c + sy * -rs);
+    const float cy = g.b[1] + (sx * rs + sy * g.c);
+    const float cz = g.b[2] + sz;
+    face_distances(cx, cy, cz, g.b, d);
+}
+
+// the extents along x and y of what bounds the box's footprint: its sizes, or the axis-aligned hull of the rotated rectangle
+__device__ __forceinline__ void footprint(const AlignedBox& g, float& ex, float& ey) { ex = g.b[3], ey = g.b[4]; }
+__device__ __forceinline__ void footprint(const RotatedBox& g, float& ex, float& ey) {
+    ex = fabsf(g.c) * g.b[3] + fabsf(g.s) * g.b[4];
+    ey = fabsf(g.s) * g.b[3] + fabsf(g.c) * g.b[4];
 }
 
 // bbox_targets[..., :6].min(-1)[0] > 0
@@ -116,12 +182,16 @@ struct SubBlock {
     }
 };
 
-__device__ __forceinline__ SubBlock box_sub_block(const float* b, const float* g, const GridLevel& lv) {
+template <class Box>
+__device__ __forceinline__ SubBlock box_sub_block(const Box& box, const float* g, const GridLevel& lv) {
     SubBlock s;
     int e;
-    axis_range(b[0], b[3], g[0], g[3], lv.X, s.x0, e);
+    float ex, ey;
+    footprint(box, ex, ey);
+    const float* b = box.b;
+    axis_range(b[0], ex, g[0], g[3], lv.X, s.x0, e);
     s.nx = e - s.x0;
-    axis_range(b[1], b[4], g[1], g[4], lv.Y, s.y0, e);
+    axis_range(b[1], ey, g[1], g[4], lv.Y, s.y0, e);
     s.ny = e - s.y0;
     axis_range(b[2], b[5], g[2], g[5], lv.Z, s.z0, e);
     s.nz = e - s.z0;
@@ -141,6 +211,7 @@ __device__ __forceinline__ T block_sum(T v, T* wave_part) {
     return s;
 }
 
+template <class Box>
 __global__ __launch_bounds__(kCountThreads) void assign_count_kernel(AssignParams p) {
     __shared__ int part[kCountThreads / 64];
     const int g = blockIdx.x, l = blockIdx.y, b = blockIdx.z;
@@ -148,8 +219,8 @@ __global__ __launch_bounds__(kCountThreads) void assign_count_kernel(AssignParam
     const GridLevel lv = p.lv[l];
     const float* gp = p.geom + ((size_t)b * p.L + l) * 6;
     const float geo[6] = {gp[0], gp[1], gp[2], gp[3], gp[4], gp[5]};
-    const float* bp = p.boxes + ((size_t)b * p.G + g) * 6;
-    const float box[6] = {bp[0], bp[1], bp[2], bp[3], bp[4], bp[5]};
+    Box box;
+    load_box(p, (size_t)b * p.G + g, box);
     const SubBlock sb = box_sub_block(box, geo, lv);
     int n = 0;
     for (int j = threadIdx.x; j < sb.size(); j += kCountThreads) {
@@ -164,6 +235,7 @@ __global__ __launch_bounds__(kCountThreads) void assign_count_kernel(AssignParam
     if (threadIdx.x == 0) p.n_inside[((size_t)b * p.G + g) * kMaxL + l] = n;
 }
 
+template <class Box>
 __global__ __launch_bounds__(kSelThreads) void assign_select_kernel(AssignParams p) {
     __shared__ int hist[256];
     __shared__ int sel[2];
@@ -182,8 +254,8 @@ __global__ __launch_bounds__(kSelThreads) void assign_select_kernel(AssignParams
     const GridLevel lv = p.lv[best];
     const float* gp = p.geom + ((size_t)b * p.L + best) * 6;
     const float geo[6] = {gp[0], gp[1], gp[2], gp[3], gp[4], gp[5]};
-    const float* bp = p.boxes + ((size_t)b * p.G + g) * 6;
-    const float box[6] = {bp[0], bp[1], bp[2], bp[3], bp[4], bp[5]};
+    Box box;
+    load_box(p, (size_t)b * p.G + g, box);
     const SubBlock sb = box_sub_block(box, geo, lv);
     // the candidates' centerness bits (an inside point's ratios are positive: bits order like values)
     auto bits_of = [&](int j, unsigned& u) {
@@ -196,7 +268,7 @@ __global__ __launch_bounds__(kSelThreads) void assign_select_kernel(AssignParams
         u = __float_as_uint(centerness(d));
         return true;
     };
-    const int k = p.center_thr + 1;
+    const int k = p.center_k;   // pts_center_threshold + 1; the ARKit head: at most all points (:1167-1170)
     float t = -1.f;   // at most pts_center_threshold candidates: the (k+1)-th largest is a -1 of the masked points
     if (n[best] >= k) {   // uniform over the workgroup
         int need_eq;
@@ -208,21 +280,39 @@ __global__ __launch_bounds__(kSelThreads) void assign_select_kernel(AssignParams
     }
 }
 
+template <class Box>
 struct StagedBox {
-    float b[6];
+    Box box;
     float volume, thr;
     int best;
 };
 
-__global__ __launch_bounds__(kPointThreads) void assign_pick_kernel(AssignParams p, long long* out_labels, int* out_box,
-                                                                    float* out_center, float* out_bbox) {
+// the targets of a point at its chosen box: the ScanNet head rebuilds the box from the face distances (:556-561), the ARKit head
+// hands out the ground-truth row itself (:1180)
+__device__ __forceinline__ void box_target(const AlignedBox&, float px, float py, float pz, const float* d, float* bt) {
+    bt[0] = px - d[0];
+    bt[1] = py - d[2];
+    bt[2] = pz - d[4];
+    bt[3] = px + d[1];
+    bt[4] = py + d[3];
+    bt[5] = pz + d[5];
+}
+__device__ __forceinline__ void box_target(const RotatedBox& g, float, float, float, const float*, float* bt) {
+    for (int q = 0; q < 6; ++q) bt[q] = g.b[q];
+    bt[6] = g.yaw;
+}
+
+// none_center: the centerness target of a point without a box (0 for the ScanNet head, the masked -1 for the ARKit head)
+template <class Box>
+__global__ __launch_bounds__(kPointThreads) void assign_pick_kernel(AssignParams p, float none_center, long long* out_labels,
+                                                                    int* out_box, float* out_center, float* out_bbox) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    StagedBox* sb = reinterpret_cast<StagedBox*>(smem);
+    StagedBox<Box>* sb = reinterpret_cast<StagedBox<Box>*>(smem);
     const int b = blockIdx.y;
     const int G = min(p.counts[b], p.G);
     for (int g = threadIdx.x; g < G; g += kPointThreads) {
         const size_t r = (size_t)b * p.G + g;
-        for (int q = 0; q < 6; ++q) sb[g].b[q] = p.boxes[r * 6 + q];
+        load_box(p, r, sb[g].box);
         sb[g].volume = p.volumes[r];
         sb[g].thr = p.thr[r];
         sb[g].best = p.best[r];
@@ -245,7 +335,7 @@ __global__ __launch_bounds__(kPointThreads) void assign_pick_kernel(AssignParams
     for (int g = 0; g < G; ++g) {
         if (sb[g].best != l) continue;
         float d[6];
-        face_distances(px, py, pz, sb[g].b, d);
+        face_distances(px, py, pz, sb[g].box, d);
         if (!inside_box(d)) continue;
         if (!(centerness(d) > sb[g].thr)) continue;
         if (sb[g].volume < vmin) {
@@ -254,24 +344,20 @@ __global__ __launch_bounds__(kPointThreads) void assign_pick_kernel(AssignParams
         }
     }
     const size_t o = (size_t)b * p.P + i;
-    float ct = 0.f, bt[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float ct = none_center, bt[Box::kReg];
+    for (int q = 0; q < Box::kReg; ++q) bt[q] = 0.f;
     long long label = -1;
     if (arg >= 0) {
         float d[6];
-        face_distances(px, py, pz, sb[arg].b, d);
+        face_distances(px, py, pz, sb[arg].box, d);
         ct = centerness(d);
-        bt[0] = px - d[0];
-        bt[1] = py - d[2];
-        bt[2] = pz - d[4];
-        bt[3] = px + d[1];
-        bt[4] = py + d[3];
-        bt[5] = pz + d[5];
+        box_target(sb[arg].box, px, py, pz, d, bt);
         label = p.labels[(size_t)b * p.G + arg];
     }
     out_labels[o] = label;
     out_box[o] = arg;
     out_center[o] = ct;
-    for (int q = 0; q < 6; ++q) out_bbox[o * 6 + q] = bt[q];
+    for (int q = 0; q < Box::kReg; ++q) out_bbox[o * Box::kReg + q] = bt[q];
 }
 
 // ---------------------------------------------------------------------------------------------------------------- losses
@@ -359,13 +445,138 @@ __device__ __forceinline__ float iou_loss(float px, float py, float pz, const fl
     return 1.f - iou;
 }
 
+__device__ __forceinline__ float box_loss(const AlignedBox&, float px, float py, float pz, const float* d, const float* t, float* gd) {
+    return iou_loss(px, py, pz, d, t, gd);
+}
+
+// The part [t0, t1] of the segment m + tau * t, |tau| <= half, inside one axis of an axis-aligned rectangle (|coordinate| <= w).
+// m, t, n: that coordinate of the segment's midpoint, direction and outward normal.  A segment along the axis' boundary (t == 0,
+// |m| == w) counts where on_edge and the two outward normals agree (file header).
+__device__ __forceinline__ void clip_axis(float m, float t, float n, float w, bool on_edge, float& t0, float& t1) {
+    if (t == 0.f) {
+        const bool in = fabsf(m) < w || (on_edge && fabsf(m) == w && m * n > 0.f);
+        if (!in) t1 = t0;
+    } else {
+        const float a = (-w - m) / t, b = (w - m) / t;
+        t0 = fmaxf(t0, fminf(a, b));
+        t1 = fminf(t1, fmaxf(a, b));
+    }
+}
+
+// Edge k (0..3, counter-clockwise: normals +x, +y, -x, -y of its own frame) of a rectangle with half sizes (hw, hl), centre
+// (rx, ry) and axes rotated by (c, s) in the frame of an axis-aligned rectangle with half sizes (ow, ol): its inside part
+// [t0, t1] along the edge from its midpoint (t1 <= t0: none), and tx, ty its direction there
+template <int k>
+__device__ __forceinline__ void clip_edge(float rx, float ry, float c, float s, float hw, float hl, float ow, float ol, bool on_edge,
+                                          float& t0, float& t1, float& tx, float& ty) {
+    constexpr float nxl = k == 0 ? 1.f : k == 2 ? -1.f : 0.f, nyl = k == 1 ? 1.f : k == 3 ? -1.f : 0.f;
+    const float nx = nxl * c - nyl * s, ny = nxl * s + nyl * c;
+    const float h = (k & 1) ? hl : hw, half = (k & 1) ? hw : hl;
+    tx = -ny, ty = nx;
+    t0 = -half, t1 = half;
+    clip_axis(rx + h * nx, tx, nx, ow, on_edge, t0, t1);
+    clip_axis(ry + h * ny, ty, ny, ol, on_edge, t0, t1);
+    t1 = fmaxf(t1, t0);
+}
+
+// RotatedIoU3DLoss of one point: ImVoxelHead_ARKit._bbox_pred_to_bbox (:1045-1055) of the point and its seven channels d (six
+// distances, heading) against the target box t = (centre, size, yaw); 1 - IoU3D, IoU3D = A_bev * z overlap / (V_pred + V_gt -
+// A_bev * z overlap) as mmcv's diff_iou_rotated_3d composes it, and where gd != nullptr its gradient by d.  File header: method
+// and the convention at degenerate pairs.
+__device__ __forceinline__ float rotated_iou_loss(float px, float py, float pz, const float* d, const float* t, float* gd) {
+    const float ca = cosf(d[6]), sa = sinf(d[6]);
+    const float sx = (d[1] - d[0]) / 2.f, sy = (d[3] - d[2]) / 2.f, sz = (d[5] - d[4]) / 2.f;
+    const float ax = px + (sx * ca - sy * sa), ay = py + (sx * sa + sy * ca), az = pz + sz;
+    const float aw = d[0] + d[1], al = d[2] + d[3], ah = d[4] + d[5];
+    const float hw = aw / 2.f, hl = al / 2.f, ow = t[3] / 2.f, ol = t[4] / 2.f;
+    // A in B's frame: centre r, axes turned by theta = yaw_a - yaw_b (snapped at multiples of pi / 2)
+    const float cb = cosf(t[6]), sb = sinf(t[6]);
+    const float ex = ax - t[0], ey = ay - t[1];
+    const float rx = ex * cb + ey * sb, ry = ey * cb - ex * sb;
+    const float theta = d[6] - t[6];
+    float c = cosf(theta), s = sinf(theta);
+    if (fabsf(s) < 1e-6f) {
+        s = 0.f;
+        c = c < 0.f ? -1.f : 1.f;
+    } else if (fabsf(c) < 1e-6f) {
+        c = 0.f;
+        s = s < 0.f ? -1.f : 1.f;
+    }
+    // B in A's frame
+    const float qx = -(rx * c + ry * s), qy = -(ry * c - rx * s);
+    float t0, t1, tx, ty, twice = 0.f, len[4], gyaw = 0.f;
+    // A's edges against B: Green's term (r x t + h) * length, and what the gradient needs
+    clip_edge<0>(rx, ry, c, s, hw, hl, ow, ol, true, t0, t1, tx, ty);
+    len[0] = t1 - t0, twice += (rx * ty - ry * tx + hw) * len[0], gyaw -= (t1 * t1 - t0 * t0) / 2.f;
+    clip_edge<1>(rx, ry, c, s, hw, hl, ow, ol, true, t0, t1, tx, ty);
+    len[1] = t1 - t0, twice += (rx * ty - ry * tx + hl) * len[1], gyaw -= (t1 * t1 - t0 * t0) / 2.f;
+    clip_edge<2>(rx, ry, c, s, hw, hl, ow, ol, true, t0, t1, tx, ty);
+    len[2] = t1 - t0, twice += (rx * ty - ry * tx + hw) * len[2], gyaw -= (t1 * t1 - t0 * t0) / 2.f;
+    clip_edge<3>(rx, ry, c, s, hw, hl, ow, ol, true, t0, t1, tx, ty);
+    len[3] = t1 - t0, twice += (rx * ty - ry * tx + hl) * len[3], gyaw -= (t1 * t1 - t0 * t0) / 2.f;
+    if (s == 0.f || c == 0.f) {
+        // parallel axes: the product of the two overlaps along B's axes, from the very sums A's edges were placed with above, so
+        // that an edge the two rectangles share (to the last bit or not) is never counted for both
+        const float hx = s == 0.f ? hw : hl, hy = s == 0.f ? hl : hw;
+        const float ox = fminf(rx + hx, ow) - fmaxf(rx - hx, -ow), oy = fminf(ry + hy, ol) - fmaxf(ry - hy, -ol);
+        twice = 2.f * fmaxf(ox, 0.f) * fmaxf(oy, 0.f);
+    } else {
+        // B's edges against A (B's centre is the origin of Green's sum: h * length)
+        clip_edge<0>(qx, qy, c, -s, ow, ol, hw, hl, false, t0, t1, tx, ty);
+        twice += ow * (t1 - t0);
+        clip_edge<1>(qx, qy, c, -s, ow, ol, hw, hl, false, t0, t1, tx, ty);
+        twice += ol * (t1 - t0);
+        clip_edge<2>(qx, qy, c, -s, ow, ol, hw, hl, false, t0, t1, tx, ty);
+        twice += ow * (t1 - t0);
+        clip_edge<3>(qx, qy, c, -s, ow, ol, hw, hl, false, t0, t1, tx, ty);
+        twice += ol * (t1 - t0);
+    }
+    const float area0 = twice / 2.f;
+    const float area = fmaxf(area0, 0.f);
+    const float zhi_a = az + ah * 0.5f, zlo_a = az - ah * 0.5f, zhi_b = t[2] + t[5] * 0.5f, zlo_b = t[2] - t[5] * 0.5f;
+    const float zo0 = fminf(zhi_a, zhi_b) - fmaxf(zlo_a, zlo_b);
+    const float zo = fmaxf(zo0, 0.f);
+    const float inter = area * zo;
+    const float vol_a = aw * al * ah, vol_b = t[3] * t[4] * t[5];
+    const float uni = vol_a + vol_b - inter;
+    const bool ok = uni > 0.f;
+    const float iou = ok ? inter / uni : 0.f;
+    if (gd) {
+        // d iou = k_i d inter + k_v d vol_a; d inter = zo d area + area d zo
+        const float k_i = ok ? (uni + inter) / (uni * uni) : 0.f, k_v = ok ? -inter / (uni * uni) : 0.f;
+        const float k_a = area0 > 0.f ? k_i * zo : 0.f, k_z = zo0 > 0.f ? k_i * area : 0.f;
+        // by the shift (A's own axes), the sizes and the heading; the centre turns with the heading about the point
+        const float gxl = len[0] - len[2], gyl = len[1] - len[3];
+        const float g_sx = k_a * gxl, g_sy = k_a * gyl;
+        const float g_zhi = zhi_a < zhi_b ? k_z : 0.f, g_zlo = zlo_a > zlo_b ? -k_z : 0.f;
+        const float g_sz = g_zhi + g_zlo;
+        const float g_w = k_a * (len[0] + len[2]) / 2.f + k_v * al * ah;
+        const float g_l = k_a * (len[1] + len[3]) / 2.f + k_v * aw * ah;
+        const float g_h = (g_zhi - g_zlo) * 0.5f + k_v * aw * al;
+        // loss = 1 - iou
+        gd[0] = -(g_w - g_sx / 2.f);
+        gd[1] = -(g_w + g_sx / 2.f);
+        gd[2] = -(g_l - g_sy / 2.f);
+        gd[3] = -(g_l + g_sy / 2.f);
+        gd[4] = -(g_h - g_sz / 2.f);
+        gd[5] = -(g_h + g_sz / 2.f);
+        gd[6] = -(k_a * (gyaw + gyl * sx - gxl * sy));
+    }
+    return 1.f - iou;
+}
+__device__ __forceinline__ float box_loss(const RotatedBox&, float px, float py, float pz, const float* d, const float* t, float* gd) {
+    return rotated_iou_loss(px, py, pz, d, t, gd);
+}
+
 // binary_cross_entropy_with_logits(x, t): (1 - t) x + max(-x, 0) + log(exp(-max(-x, 0)) + exp(-x - max(-x, 0)))
 __device__ __forceinline__ float bce_logits(float x, float t) {
     const float m = fmaxf(-x, 0.f);
     return (1.f - t) * x + m + logf(expf(-m) + expf(-x - m));
 }
 
+template <class Box>
 __global__ __launch_bounds__(kPointThreads) void head_loss_kernel(LossParams p, float* part_f, int* part_i) {
+    constexpr int R = Box::kReg;
     __shared__ float fpart[kPointThreads / 64];
     __shared__ int ipart[kPointThreads / 64];
     const int b = blockIdx.y, i = blockIdx.x * kPointThreads + threadIdx.x;
@@ -382,10 +593,10 @@ __global__ __launch_bounds__(kPointThreads) void head_loss_kernel(LossParams p, 
                 const size_t o = (size_t)b * p.P + i;
                 const float ct = p.center_t[o];
                 s.center = bce_logits(lm.center[(size_t)b * r.N + r.v], ct);
-                float d[6];
-                for (int q = 0; q < 6; ++q) d[q] = lm.bbox[((size_t)b * 6 + q) * r.N + r.v];
+                float d[R];
+                for (int q = 0; q < R; ++q) d[q] = lm.bbox[((size_t)b * R + q) * r.N + r.v];
                 s.w = ct;
-                s.bbox = iou_loss(r.px, r.py, r.pz, d, p.bbox_t + o * 6, nullptr) * ct;
+                s.bbox = box_loss(Box{}, r.px, r.py, r.pz, d, p.bbox_t + o * R, nullptr) * ct;
             }
         }
     }
@@ -417,7 +628,9 @@ __global__ void head_loss_finish_kernel(const float* part_f, const int* part_i, 
 }
 
 // coef (B, 3): what a unit of the scene's center / bbox / cls sum is worth (incoming gradient / normaliser), on the device
+template <class Box>
 __global__ __launch_bounds__(kPointThreads) void head_loss_backward_kernel(LossParams p, const float* coef) {
+    constexpr int R = Box::kReg;
     const int b = blockIdx.y, i = blockIdx.x * kPointThreads + threadIdx.x;
     if (i >= p.P) return;
     const PointRef r = locate(p, b, i);
@@ -427,21 +640,22 @@ __global__ __launch_bounds__(kPointThreads) void head_loss_backward_kernel(LossP
     float* d_cls = lm.d_cls + (size_t)b * p.C * r.N + r.v;
     for (int c = 0; c < p.C; ++c)
         d_cls[(size_t)c * r.N] = r.valid ? k_cls * focal_grad(cls[(size_t)c * r.N], r.label == c, p.gamma, p.alpha) : 0.f;
-    float gc = 0.f, gd[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float gc = 0.f, gd[R];
+    for (int q = 0; q < R; ++q) gd[q] = 0.f;
     if (r.valid && r.label >= 0) {
         const size_t o = (size_t)b * p.P + i;
         const float ct = p.center_t[o];
         gc = k_center * (sigmoidf_(lm.center[(size_t)b * r.N + r.v]) - ct);
-        float d[6];
-        for (int q = 0; q < 6; ++q) d[q] = lm.bbox[((size_t)b * 6 + q) * r.N + r.v];
-        iou_loss(r.px, r.py, r.pz, d, p.bbox_t + o * 6, gd);
-        for (int q = 0; q < 6; ++q) gd[q] *= k_bbox * ct;
+        float d[R];
+        for (int q = 0; q < R; ++q) d[q] = lm.bbox[((size_t)b * R + q) * r.N + r.v];
+        box_loss(Box{}, r.px, r.py, r.pz, d, p.bbox_t + o * R, gd);
+        for (int q = 0; q < R; ++q) gd[q] *= k_bbox * ct;
     }
     lm.d_center[(size_t)b * r.N + r.v] = gc;
-    for (int q = 0; q < 6; ++q) lm.d_bbox[((size_t)b * 6 + q) * r.N + r.v] = gd[q];
+    for (int q = 0; q < R; ++q) lm.d_bbox[((size_t)b * R + q) * r.N + r.v] = gd[q];
 }
 
-int plan_levels(const char* name, const int* level_dims, int B, int L, GridLevel* lv, long long* points) {
+int plan_levels(const char* name, const int* level_dims, int B, int L, int nreg, GridLevel* lv, long long* points) {
     MVS_REQUIRE(level_dims, "%s: NULL pointer", name);
     MVS_REQUIRE(B >= 1 && B <= 65535, "%s: bad shape B=%d", name, B);
     MVS_REQUIRE(L >= 1 && L <= kMaxL, "%s: bad shape L=%d (1..%d levels)", name, L, kMaxL);
@@ -452,19 +666,19 @@ int plan_levels(const char* name, const int* level_dims, int B, int L, GridLevel
         lv[l] = GridLevel{X, Y, Z, (int)*points};
         *points += (long long)X * Y * Z;
     }
-    MVS_REQUIRE((long long)B * *points * 6 < (1ll << 31), "%s: bad shape: %d scenes x %lld points", name, B, *points);
+    MVS_REQUIRE((long long)B * *points * nreg < (1ll << 31), "%s: bad shape: %d scenes x %lld points", name, B, *points);
     return MVSDET_OK;
 }
 
 int plan_loss(const char* name, const float* const* center, const float* const* bbox, const float* const* cls, float* const* d_center,
               float* const* d_bbox, float* const* d_cls, bool backward, const int* level_dims, const float* valid,
               const float* level_geom, const int64_t* labels, const float* center_t, const float* bbox_t, int B, int L, int C, int VX,
-              int VY, int VZ, float gamma, float alpha, LossParams* p) {
+              int VY, int VZ, float gamma, float alpha, int nreg, LossParams* p) {
     MVS_REQUIRE(center && bbox && cls && valid && level_geom && labels && center_t && bbox_t, "%s: NULL pointer", name);
     MVS_REQUIRE(!backward || (d_center && d_bbox && d_cls), "%s: NULL pointer", name);
     *p = LossParams{};
     long long points;
-    if (const int rc = plan_levels(name, level_dims, B, L, p->lv, &points)) return rc;
+    if (const int rc = plan_levels(name, level_dims, B, L, nreg, p->lv, &points)) return rc;
     MVS_REQUIRE(C >= 1 && C <= 1024, "%s: bad shape n_classes=%d (1..1024)", name, C);
     MVS_REQUIRE(VX > 0 && VY > 0 && VZ > 0 && (long long)VX * VY * VZ < (1 << 26), "%s: bad shape valid %dx%dx%d", name, VX, VY, VZ);
     MVS_REQUIRE(gamma >= 0.f && alpha >= 0.f && alpha <= 1.f, "%s: gamma=%g, alpha=%g", name, (double)gamma, (double)alpha);
@@ -508,6 +722,86 @@ int need_workspace(const char* name, const void* workspace, size_t bytes, size_t
 
 inline int point_blocks(long long points) { return (int)((points + kPointThreads - 1) / kPointThreads); }
 
+// the three launches of the target assignment; rot == nullptr: the ScanNet route
+template <class Box>
+int launch_targets(const char* name, const int* level_dims, const float* level_geom, int B, int L, const float* gt_boxes,
+                   const float* gt_rot, const float* gt_volumes, const int64_t* gt_labels, const int* gt_counts, int G,
+                   int pts_assign_threshold, int pts_center_threshold, float none_center, int64_t* out_labels, int* out_box_index,
+                   float* out_center_targets, float* out_bbox_targets, void* workspace, size_t workspace_bytes, size_t need,
+                   mvsdet_stream_t stream) {
+    constexpr bool rotated = Box::kBox == 7;
+    AssignParams p{};
+    long long points;
+    if (const int rc = plan_levels(name, level_dims, B, L, Box::kReg, p.lv, &points)) return rc;
+    MVS_REQUIRE(level_geom && gt_counts && out_labels && out_box_index && out_center_targets && out_bbox_targets, "%s: NULL pointer", name);
+    MVS_REQUIRE(G >= 0 && G <= kMaxBoxes, "%s: G=%d boxes per scene above the limit MVSDET_ASSIGN_MAX_BOXES=%d", name, G, kMaxBoxes);
+    MVS_REQUIRE(G == 0 || (gt_boxes && gt_volumes && gt_labels && (gt_rot || !rotated)), "%s: NULL pointer", name);
+    MVS_REQUIRE(pts_assign_threshold >= 0 && pts_center_threshold >= 0, "%s: pts_assign_threshold=%d, pts_center_threshold=%d", name,
+                pts_assign_threshold, pts_center_threshold);
+    if (const int rc = need_workspace(name, workspace, workspace_bytes, need, "mvsdet_head_targets_workspace_bytes")) return rc;
+    p.geom = level_geom;
+    p.boxes = gt_boxes;
+    p.rot = gt_rot;
+    p.volumes = gt_volumes;
+    p.labels = reinterpret_cast<const long long*>(gt_labels);
+    p.counts = gt_counts;
+    p.L = L;
+    p.G = G;
+    p.P = (int)points;
+    p.assign_thr = pts_assign_threshold;
+    // torch.topk(centerness, pts_center_threshold + 1); the ARKit head: min(pts_center_threshold + 1, points) (:1167-1170)
+    p.center_k = rotated ? (int)std::min<long long>((long long)pts_center_threshold + 1, points) : pts_center_threshold + 1;
+    p.n_inside = static_cast<int*>(workspace);
+    p.best = p.n_inside + (size_t)B * G * kMaxL;
+    p.thr = reinterpret_cast<float*>(p.best + (size_t)B * G);
+    hipStream_t s = (hipStream_t)stream;
+    if (G > 0) {
+        hipLaunchKernelGGL(assign_count_kernel<Box>, dim3(G, L, B), dim3(kCountThreads), 0, s, p);
+        hipLaunchKernelGGL(assign_select_kernel<Box>, dim3(G, B), dim3(kSelThreads), 0, s, p);
+    }
+    hipLaunchKernelGGL(assign_pick_kernel<Box>, dim3(point_blocks(points), B), dim3(kPointThreads),
+                       (size_t)std::max(G, 1) * sizeof(StagedBox<Box>), s, p, none_center, reinterpret_cast<long long*>(out_labels),
+                       out_box_index, out_center_targets, out_bbox_targets);
+    MVS_LAUNCH_CHECK(name);
+    return MVSDET_OK;
+}
+
+template <class Box>
+int launch_loss(const char* name, const float* const* center, const float* const* bbox, const float* const* cls, const int* level_dims,
+                const float* valid, const float* level_geom, int B, int L, int n_classes, int VX, int VY, int VZ, const int64_t* labels,
+                const float* center_targets, const float* bbox_targets, float gamma, float alpha, float* out_sums, int* out_counts,
+                void* workspace, size_t workspace_bytes, mvsdet_stream_t stream) {
+    LossParams p;
+    if (const int rc = plan_loss(name, center, bbox, cls, nullptr, nullptr, nullptr, false, level_dims, valid, level_geom, labels,
+                                 center_targets, bbox_targets, B, L, n_classes, VX, VY, VZ, gamma, alpha, Box::kReg, &p))
+        return rc;
+    MVS_REQUIRE(out_sums && out_counts, "%s: NULL pointer", name);
+    const int nblk = point_blocks(p.P);
+    if (const int rc = need_workspace(name, workspace, workspace_bytes, (size_t)B * nblk * 6 * 4, "mvsdet_head_loss_workspace_bytes"))
+        return rc;
+    float* part_f = static_cast<float*>(workspace);
+    int* part_i = reinterpret_cast<int*>(part_f + (size_t)B * nblk * 4);
+    hipLaunchKernelGGL(head_loss_kernel<Box>, dim3(nblk, B), dim3(kPointThreads), 0, (hipStream_t)stream, p, part_f, part_i);
+    hipLaunchKernelGGL(head_loss_finish_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, part_f, part_i, nblk, out_sums, out_counts);
+    MVS_LAUNCH_CHECK(name);
+    return MVSDET_OK;
+}
+
+template <class Box>
+int launch_loss_backward(const char* name, const float* const* center, const float* const* bbox, const float* const* cls,
+                         const int* level_dims, const float* valid, const float* level_geom, int B, int L, int n_classes, int VX, int VY,
+                         int VZ, const int64_t* labels, const float* center_targets, const float* bbox_targets, float gamma, float alpha,
+                         const float* coef, float* const* d_center, float* const* d_bbox, float* const* d_cls, mvsdet_stream_t stream) {
+    LossParams p;
+    if (const int rc = plan_loss(name, center, bbox, cls, d_center, d_bbox, d_cls, true, level_dims, valid, level_geom, labels,
+                                 center_targets, bbox_targets, B, L, n_classes, VX, VY, VZ, gamma, alpha, Box::kReg, &p))
+        return rc;
+    MVS_REQUIRE(coef, "%s: NULL pointer", name);
+    hipLaunchKernelGGL(head_loss_backward_kernel<Box>, dim3(point_blocks(p.P), B), dim3(kPointThreads), 0, (hipStream_t)stream, p, coef);
+    MVS_LAUNCH_CHECK(name);
+    return MVSDET_OK;
+}
+
 }  // namespace
 }  // namespace mvsdet
 
@@ -523,40 +817,20 @@ extern "C" int mvsdet_head_targets_f32(const int* level_dims, const float* level
                                        int pts_assign_threshold, int pts_center_threshold, int64_t* out_labels, int* out_box_index,
                                        float* out_center_targets, float* out_bbox_targets, void* workspace, size_t workspace_bytes,
                                        mvsdet_stream_t stream) {
-    const char* name = "head_targets";
-    AssignParams p{};
-    long long points;
-    if (const int rc = plan_levels(name, level_dims, B, L, p.lv, &points)) return rc;
-    MVS_REQUIRE(level_geom && gt_counts && out_labels && out_box_index && out_center_targets && out_bbox_targets, "%s: NULL pointer", name);
-    MVS_REQUIRE(G >= 0 && G <= kMaxBoxes, "%s: G=%d boxes per scene above the limit MVSDET_ASSIGN_MAX_BOXES=%d", name, G, kMaxBoxes);
-    MVS_REQUIRE(G == 0 || (gt_boxes && gt_volumes && gt_labels), "%s: NULL pointer", name);
-    MVS_REQUIRE(pts_assign_threshold >= 0 && pts_center_threshold >= 0, "%s: pts_assign_threshold=%d, pts_center_threshold=%d", name,
-                pts_assign_threshold, pts_center_threshold);
-    if (const int rc = need_workspace(name, workspace, workspace_bytes, mvsdet_head_targets_workspace_bytes(B, G),
-                                      "mvsdet_head_targets_workspace_bytes"))
-        return rc;
-    p.geom = level_geom;
-    p.boxes = gt_boxes;
-    p.volumes = gt_volumes;
-    p.labels = reinterpret_cast<const long long*>(gt_labels);
-    p.counts = gt_counts;
-    p.L = L;
-    p.G = G;
-    p.P = (int)points;
-    p.assign_thr = pts_assign_threshold;
-    p.center_thr = pts_center_threshold;
-    p.n_inside = static_cast<int*>(workspace);
-    p.best = p.n_inside + (size_t)B * G * kMaxL;
-    p.thr = reinterpret_cast<float*>(p.best + (size_t)B * G);
-    hipStream_t s = (hipStream_t)stream;
-    if (G > 0) {
-        hipLaunchKernelGGL(assign_count_kernel, dim3(G, L, B), dim3(kCountThreads), 0, s, p);
-        hipLaunchKernelGGL(assign_select_kernel, dim3(G, B), dim3(kSelThreads), 0, s, p);
-    }
-    hipLaunchKernelGGL(assign_pick_kernel, dim3(point_blocks(points), B), dim3(kPointThreads), (size_t)std::max(G, 1) * sizeof(StagedBox),
-                       s, p, reinterpret_cast<long long*>(out_labels), out_box_index, out_center_targets, out_bbox_targets);
-    MVS_LAUNCH_CHECK(name);
-    return MVSDET_OK;
+    return launch_targets<AlignedBox>("head_targets", level_dims, level_geom, B, L, gt_boxes, nullptr, gt_volumes, gt_labels, gt_counts, G,
+                                      pts_assign_threshold, pts_center_threshold, 0.f, out_labels, out_box_index, out_center_targets,
+                                      out_bbox_targets, workspace, workspace_bytes, mvsdet_head_targets_workspace_bytes(B, G), stream);
+}
+
+extern "C" int mvsdet_head_targets_rotated_f32(const int* level_dims, const float* level_geom, int B, int L, const float* gt_boxes,
+                                               const float* gt_rot, const float* gt_volumes, const int64_t* gt_labels,
+                                               const int* gt_counts, int G, int pts_assign_threshold, int pts_center_threshold,
+                                               int64_t* out_labels, int* out_box_index, float* out_center_targets,
+                                               float* out_bbox_targets, void* workspace, size_t workspace_bytes, mvsdet_stream_t stream) {
+    return launch_targets<RotatedBox>("head_targets_rotated", level_dims, level_geom, B, L, gt_boxes, gt_rot, gt_volumes, gt_labels,
+                                      gt_counts, G, pts_assign_threshold, pts_center_threshold, -1.f, out_labels, out_box_index,
+                                      out_center_targets, out_bbox_targets, workspace, workspace_bytes,
+                                      mvsdet_head_targets_workspace_bytes(B, G), stream);
 }
 
 extern "C" size_t mvsdet_head_loss_workspace_bytes(int B, int points) {
@@ -569,22 +843,18 @@ extern "C" int mvsdet_head_loss_f32(const float* const* center, const float* con
                                     const int64_t* labels, const float* center_targets, const float* bbox_targets, float gamma,
                                     float alpha, float* out_sums, int* out_counts, void* workspace, size_t workspace_bytes,
                                     mvsdet_stream_t stream) {
-    const char* name = "head_loss";
-    LossParams p;
-    if (const int rc = plan_loss(name, center, bbox, cls, nullptr, nullptr, nullptr, false, level_dims, valid, level_geom, labels,
-                                 center_targets, bbox_targets, B, L, n_classes, VX, VY, VZ, gamma, alpha, &p))
-        return rc;
-    MVS_REQUIRE(out_sums && out_counts, "%s: NULL pointer", name);
-    if (const int rc = need_workspace(name, workspace, workspace_bytes, mvsdet_head_loss_workspace_bytes(B, p.P),
-                                      "mvsdet_head_loss_workspace_bytes"))
-        return rc;
-    const int nblk = point_blocks(p.P);
-    float* part_f = static_cast<float*>(workspace);
-    int* part_i = reinterpret_cast<int*>(part_f + (size_t)B * nblk * 4);
-    hipLaunchKernelGGL(head_loss_kernel, dim3(nblk, B), dim3(kPointThreads), 0, (hipStream_t)stream, p, part_f, part_i);
-    hipLaunchKernelGGL(head_loss_finish_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, part_f, part_i, nblk, out_sums, out_counts);
-    MVS_LAUNCH_CHECK(name);
-    return MVSDET_OK;
+    return launch_loss<AlignedBox>("head_loss", center, bbox, cls, level_dims, valid, level_geom, B, L, n_classes, VX, VY, VZ, labels,
+                                   center_targets, bbox_targets, gamma, alpha, out_sums, out_counts, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mvsdet_head_loss_rotated_f32(const float* const* center, const float* const* bbox, const float* const* cls,
+                                            const int* level_dims, const float* valid, const float* level_geom, int B, int L,
+                                            int n_classes, int VX, int VY, int VZ, const int64_t* labels, const float* center_targets,
+                                            const float* bbox_targets, float gamma, float alpha, float* out_sums, int* out_counts,
+                                            void* workspace, size_t workspace_bytes, mvsdet_stream_t stream) {
+    return launch_loss<RotatedBox>("head_loss_rotated", center, bbox, cls, level_dims, valid, level_geom, B, L, n_classes, VX, VY, VZ,
+                                   labels, center_targets, bbox_targets, gamma, alpha, out_sums, out_counts, workspace, workspace_bytes,
+                                   stream);
 }
 
 extern "C" int mvsdet_head_loss_backward_f32(const float* const* center, const float* const* bbox, const float* const* cls,
@@ -592,13 +862,18 @@ extern "C" int mvsdet_head_loss_backward_f32(const float* const* center, const f
                                              int n_classes, int VX, int VY, int VZ, const int64_t* labels, const float* center_targets,
                                              const float* bbox_targets, float gamma, float alpha, const float* coef,
                                              float* const* d_center, float* const* d_bbox, float* const* d_cls, mvsdet_stream_t stream) {
-    const char* name = "head_loss_backward";
-    LossParams p;
-    if (const int rc = plan_loss(name, center, bbox, cls, d_center, d_bbox, d_cls, true, level_dims, valid, level_geom, labels,
-                                 center_targets, bbox_targets, B, L, n_classes, VX, VY, VZ, gamma, alpha, &p))
-        return rc;
-    MVS_REQUIRE(coef, "%s: NULL pointer", name);
-    hipLaunchKernelGGL(head_loss_backward_kernel, dim3(point_blocks(p.P), B), dim3(kPointThreads), 0, (hipStream_t)stream, p, coef);
-    MVS_LAUNCH_CHECK(name);
-    return MVSDET_OK;
+    return launch_loss_backward<AlignedBox>("head_loss_backward", center, bbox, cls, level_dims, valid, level_geom, B, L, n_classes, VX,
+                                            VY, VZ, labels, center_targets, bbox_targets, gamma, alpha, coef, d_center, d_bbox, d_cls,
+                                            stream);
+}
+
+extern "C" int mvsdet_head_loss_rotated_backward_f32(const float* const* center, const float* const* bbox, const float* const* cls,
+                                                     const int* level_dims, const float* valid, const float* level_geom, int B, int L,
+                                                     int n_classes, int VX, int VY, int VZ, const int64_t* labels,
+                                                     const float* center_targets, const float* bbox_targets, float gamma, float alpha,
+                                                     const float* coef, float* const* d_center, float* const* d_bbox,
+                                                     float* const* d_cls, mvsdet_stream_t stream) {
+    return launch_loss_backward<RotatedBox>("head_loss_rotated_backward", center, bbox, cls, level_dims, valid, level_geom, B, L,
+                                            n_classes, VX, VY, VZ, labels, center_targets, bbox_targets, gamma, alpha, coef, d_center,
+                                            d_bbox, d_cls, stream);
 }

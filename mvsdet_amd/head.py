@@ -9,7 +9,9 @@
 
 Target assignment and the three losses (`loss_by_feat`, nerfdet_head.py:152-257, 473-562: AxisAlignedIoULoss, FocalLoss, sigmoid
 CrossEntropyLoss) run on csrc/assign.hip for the ScanNet head (`ops.head_targets`, `ops.head_loss`): six launches per batch, no host
-synchronisation, the same bits from run to run.  The ARKit head's RotatedIoU3DLoss is not implemented.
+synchronisation, the same bits from run to run.  The ARKit head's objective (:779-846, 1029-1185: targets in each box's rotated
+frame, RotatedIoU3DLoss) runs on the same kernels instantiated for 7-value boxes (`ops.head_targets_rotated`,
+`ops.head_loss_rotated`), on ROCm tensors only.
 `predict_by_feat` (nerfdet_head.py:301-420, 564-628: scores, top-k, decode, aligned 3-D NMS) runs on csrc/detect.hip for the
 ScanNet head (`ops.head_predict`), and for the ARKit head (:902-1056, 1190-1243: all class scores of a top-k point, rotated decode,
 mmcv's nms3d per class) on its rotated kernels (`ops.head_predict_rotated`).  Parameter names equal the reference's
@@ -179,10 +181,16 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
         initialised process group first (mmdet's reduce_mean); bbox_loss = sum w (1 - IoU) / (sum w + eps), w = the centerness
         target; eps = float32's machine epsilon, mmdet 3.x's weight_reduce_loss.  A scene without valid or positive points gives 0
         with zero gradients; one without boxes has no positive point (the reference raises there).  Equal box volumes at a point:
-        the lowest box index.  batch_gt_instances_ignore is not read, as in the reference."""
-        if self.arkit_head:
-            raise NotImplementedError("loss_by_feat: ImVoxelHead_ARKit's RotatedIoU3DLoss (a differentiable rotated IoU) is not "
-                                      "implemented; the ScanNet head's AxisAlignedIoULoss is")
+        the lowest box index.  batch_gt_instances_ignore is not read, as in the reference.
+        ARKit head (ImVoxelHead_ARKit.loss_by_feat, nerfdet_head.py:779-900, 1029-1185): bbox maps of 7 channels, ground truth with
+        yaw (`tensor[:, 3:7]`, with_yaw boxes), face distances and centerness in each box's own frame, the ground-truth row as box
+        target, IoU = the rotated 3-D IoU of RotatedIoU3DLoss (mmcv's diff_iou_rotated_3d: the true intersection of the two
+        rectangles times the z overlap).  Maps that are not on a ROCm device raise NotImplementedError: the rotated IoU has no CPU
+        path here, as mmcv's own op has none."""
+        if self.arkit_head and not all(t.is_cuda for t in center_preds):
+            raise NotImplementedError(
+                "loss_by_feat: ImVoxelHead_ARKit's RotatedIoU3DLoss (nerfdet_head.py:779-846, mmcv's diff_iou_rotated_3d) runs on "
+                "ROCm tensors only (ops.head_loss_rotated); there is no CPU path")
         B = len(batch_input_metas)
         if len(batch_gt_instances_3d) != B:
             raise ValueError(f"loss_by_feat: {len(batch_gt_instances_3d)} ground-truth sets for {B} scenes")
@@ -197,12 +205,18 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
                 return self.loss_by_feat(up(center_preds), up(bbox_preds), up(cls_preds), valid_pred, batch_gt_instances_3d,
                                          batch_input_metas, batch_gt_instances_ignore, **kwargs)
         dev = valid_pred.device
-        gt_boxes, gt_volumes, gt_labels, gt_counts = pad_ground_truth(batch_gt_instances_3d, dev)
         sizes = [tuple(c.shape[2:]) for c in center_preds]
         origins = [scene_origin(m) for m in batch_input_metas]
-        targets = ops.head_targets(sizes, origins, gt_boxes, gt_volumes, gt_labels, gt_counts, self.pts_assign_threshold,
-                                   self.pts_center_threshold)
-        sums = ops.head_loss(center_preds, bbox_preds, cls_preds, valid_pred, targets, self.focal_gamma, self.focal_alpha)
+        if self.arkit_head:
+            gt_boxes, gt_rot, gt_volumes, gt_labels, gt_counts = pad_ground_truth_rotated(batch_gt_instances_3d, dev)
+            targets = ops.head_targets_rotated(sizes, origins, gt_boxes, gt_rot, gt_volumes, gt_labels, gt_counts,
+                                               self.pts_assign_threshold, self.pts_center_threshold)
+            sums = ops.head_loss_rotated(center_preds, bbox_preds, cls_preds, valid_pred, targets, self.focal_gamma, self.focal_alpha)
+        else:
+            gt_boxes, gt_volumes, gt_labels, gt_counts = pad_ground_truth(batch_gt_instances_3d, dev)
+            targets = ops.head_targets(sizes, origins, gt_boxes, gt_volumes, gt_labels, gt_counts, self.pts_assign_threshold,
+                                       self.pts_center_threshold)
+            sums = ops.head_loss(center_preds, bbox_preds, cls_preds, valid_pred, targets, self.focal_gamma, self.focal_alpha)
         eps = torch.finfo(torch.float32).eps
         n_pos = sums.n_pos.float()
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
@@ -250,11 +264,28 @@ def pad_ground_truth(batch_gt_instances_3d, device) -> Tuple[Tensor, Tensor, Ten
     """What _get_targets reads of every scene's ground truth, by the reference's own torch expressions (nerfdet_head.py:497-500),
     padded to the batch's largest box count: boxes (B,G,6) = cat(gravity_center, tensor[:, 3:6]), volumes (B,G), labels (B,G) int64
     and the counts (B,) int32, made from the shapes; on `device` without a host synchronisation."""
+    boxes, _, volumes, labels, counts = _pad_ground_truth(batch_gt_instances_3d, device, 6)
+    return boxes, volumes, labels, counts
+
+
+def pad_ground_truth_rotated(batch_gt_instances_3d, device) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """pad_ground_truth for ImVoxelHead_ARKit._get_targets (nerfdet_head.py:1133-1134): boxes (B,G,7) = cat(gravity_center,
+    tensor[:, 3:7]), rot (B,G,2) = (cos(yaw), sin(yaw)) by torch.cos / torch.sin on the ground truth's own tensors where they
+    live (what rotation_3d_in_axis calls), volumes, labels, counts."""
+    return _pad_ground_truth(batch_gt_instances_3d, device, 7)
+
+
+def _pad_ground_truth(batch_gt_instances_3d, device, nbox: int):
     rows = []
     for gt in batch_gt_instances_3d:
         b = gt.bboxes_3d
-        boxes = torch.cat((b.gravity_center, b.tensor[:, 3:6]), dim=1).float()
-        rows.append((boxes, b.volume.float().reshape(-1), gt.labels_3d.long().reshape(-1)))
+        if nbox == 7 and b.tensor.shape[1] < 7:
+            raise ValueError(f"loss_by_feat: the ARKit head needs ground-truth boxes with yaw (tensor of 7 values, got "
+                             f"{tuple(b.tensor.shape)})")
+        boxes = torch.cat((b.gravity_center, b.tensor[:, 3:nbox]), dim=1).float()
+        yaw = boxes[:, 6] if nbox == 7 else boxes[:, :0].reshape(-1)
+        rot = torch.stack((torch.cos(yaw), torch.sin(yaw)), dim=-1) if nbox == 7 else boxes[:, :0]
+        rows.append((boxes, b.volume.float().reshape(-1), gt.labels_3d.long().reshape(-1), rot))
     G = max([int(r[0].shape[0]) for r in rows], default=0)
     counts = torch.tensor([int(r[0].shape[0]) for r in rows], dtype=torch.int32)
 
@@ -262,8 +293,8 @@ def pad_ground_truth(batch_gt_instances_3d, device) -> Tuple[Tensor, Tensor, Ten
         out = [torch.cat([t.reshape((t.shape[0],) + width), t.new_zeros((G - t.shape[0],) + width)]) for t in ts]
         return ops._to_device(torch.stack(out).to(dtype), device)
 
-    return (pad([r[0] for r in rows], (6,), torch.float32), pad([r[1] for r in rows], (), torch.float32),
-            pad([r[2] for r in rows], (), torch.int64), ops._to_device(counts, device))
+    return (pad([r[0] for r in rows], (nbox,), torch.float32), pad([r[3] for r in rows], (2,), torch.float32) if nbox == 7 else None,
+            pad([r[1] for r in rows], (), torch.float32), pad([r[2] for r in rows], (), torch.int64), ops._to_device(counts, device))
 
 
 class SceneDetections:
