@@ -13,6 +13,12 @@ namespace mvsdet {
 
 // KT = length of the candidate list kept per pixel (3 for the reference's topk = 3, MVSDET_MAX_TOPK otherwise): the
 // insertion is 7 VALU instructions per entry and plane, and the kernel is VALU-bound (r02_stage_kernels_pmc.txt).
+//
+// Non-finite inputs follow torch.topk, which ranks NaN above every number: descending value, NaN
+// first, the lower plane first among equals and among NaNs.  From logits, one NaN / +Inf logit (or all -Inf) makes the
+// normaliser and with it every probability of the pixel NaN, so the ranking is planes 0 .. topk-1: one test of the
+// normaliser after the loop, nothing per plane.  From ready-made probabilities (sample_depth_prob) single planes can be
+// NaN, and the insertion itself compares NaN-aware.
 template <bool kFromLogits, int DREG, int KT>
 __global__ __launch_bounds__(kThreads) void depth_prob_topk_kernel(
     const float* __restrict__ cost_reg, const float* __restrict__ off_logit, float* __restrict__ prob,
@@ -90,7 +96,7 @@ __global__ __launch_bounds__(kThreads) void depth_prob_topk_kernel(
         bool moved = false;
 #pragma unroll
         for (int k = 0; k < KT; ++k) {
-            const bool gt = moved || cv > bv[k];
+            const bool gt = kFromLogits ? (moved || cv > bv[k]) : (moved || cv > bv[k] || (cv != cv && bv[k] == bv[k]));
             moved = gt;
             const float tv = bv[k], to = bo[k];
             const int ti = bi[k];
@@ -111,6 +117,16 @@ __global__ __launch_bounds__(kThreads) void depth_prob_topk_kernel(
         for (int d = 0; d < D; ++d) plane(d, 0.0f);
     }
     avg_depth[(size_t)n * HW + pix] = avg;
+    if (kFromLogits && s != s) {
+        // every probability is NaN and none was inserted (NaN > x is false): all planes tie as NaN, the lowest come first
+#pragma unroll
+        for (int k = 0; k < KT; ++k)
+            if (k < topk) {   // topk <= D: plane k exists, and this thread wrote its offset above
+                bv[k] = s;
+                bo[k] = off[base + (size_t)k * HW];
+                bi[k] = k;
+            }
+    }
 #pragma unroll
     for (int k = 0; k < KT; ++k) {
         if (k < topk) {

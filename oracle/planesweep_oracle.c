@@ -299,7 +299,9 @@ ORC_API int orc_depth_prob_topk(const float* cost_reg, const float* off_logit, f
                     int used = 0;
                     for (int q = 0; q < k; ++q) used |= (chosen[q] == d);
                     if (used) continue;
-                    if (best < 0 || e[d] > e[best]) best = d;
+                    /* descending value, NaN above every number (torch.topk), the lower plane first among equals and
+                     * among NaNs */
+                    if (best < 0 || e[d] > e[best] || (e[d] != e[d] && e[best] == e[best])) best = d;
                 }
                 chosen[k] = best;
                 float od = off[(size_t)n * D * HW + best * HW + p];

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Randomised soak of stages 2 and 3 (depth distribution + top-k; depth-weighted lifting with the view mean) against the
 oracle (not collected by pytest; run on the GPU box):  python tests/fuzz_stages.py [cases] [first_seed]
-Stage 2: prob / off / depth expectation to 2e-6, candidates exact where the probabilities are separated by more than 1e-6.
+Stage 2: prob / off to 2e-6 and the depth expectation to 2e-5 of far, D up to 512 and topk up to 8, candidates exact where the probabilities are separated by more than 1e-6.
 Stage 3: voxel volume and valid counts bit for bit."""
 import os
 import sys
@@ -23,9 +23,11 @@ def main():
     bad = 0
     for seed in range(first, first + cases):
         rng = np.random.default_rng(70000 + seed)
-        N, D = int(rng.integers(1, 7)), int(rng.integers(3, 70))
+        # D across all three forward specialisations (<= 16, <= 64, up to MVSDET_MAX_DEPTH = 512), topk across both candidate
+        # lists (<= 3, up to MVSDET_MAX_TOPK = 8)
+        N, D = int(rng.integers(1, 7)), int(rng.choice([rng.integers(3, 17), rng.integers(17, 70), rng.integers(70, 513)]))
         H, W = int(rng.integers(4, 33)), int(rng.integers(4, 49))
-        topk = int(rng.integers(1, min(3, D) + 1))
+        topk = int(rng.integers(1, min(8, D) + 1))
         near, far = 0.2, float(rng.uniform(2.0, 6.0))
         interval = (far - near) / D
         cost = (rng.standard_normal((N, D, H, W)) * rng.uniform(0.5, 4.0)).astype(np.float32)

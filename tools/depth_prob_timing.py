@@ -1,16 +1,26 @@
-"""depth_prob_topk at the headline shape (GPU box).  The register-resident form (D <= 64) takes 0.27 ms, the form that re-reads
-the logits from L2 0.30."""
+"""depth_prob_topk at the reference-true shape (40 views, 12 planes, 60x80) and at the headline 64-plane shape (GPU box).  The
+register-resident form (D <= 64) takes 0.27 ms at the latter, the form that re-reads the logits from L2 0.30.  Prints the median
+and the minimum of 7 rounds of 50 calls; for an A/B run, point MVSDET_HIP_LIB at the other build of the library and run again
+on the same box."""
+import os
+import statistics
+import sys
+
 import torch
-from mvsdet_amd import ops
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from mvsdet_amd import ops  # noqa: E402
 dev = torch.device("cuda:0")
-N, D, H, W = 40, 64, 120, 160
-lg = torch.randn(N, 2, D, H, W, device=dev)
-lg[:, 0] *= 3
-def run(): return ops.depth_prob_topk(lg[:, 0], lg[:, 1], 0.2, 0.075, 3)
-for _ in range(3): run()
-torch.cuda.synchronize()
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-e0.record()
-for _ in range(20): run()
-e1.record(); torch.cuda.synchronize()
-print(f"depth_prob_topk {N}x{D}x{H}x{W}: {e0.elapsed_time(e1) / 20:.3f} ms")
+for N, D, H, W in ((40, 12, 60, 80), (40, 64, 120, 160)):
+    lg = torch.randn(N, 2, D, H, W, device=dev)
+    lg[:, 0] *= 3
+    def run(): return ops.depth_prob_topk(lg[:, 0], lg[:, 1], 0.2, 4.8 / D, 3)
+    for _ in range(10): run()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(7):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(50): run()
+        e1.record(); torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1) / 50)
+    print(f"depth_prob_topk {N}x{D}x{H}x{W}: median {statistics.median(ms):.4f} ms, min {min(ms):.4f} ms")
