@@ -49,9 +49,8 @@ const char* mvsdet_last_error(void);
  *   "sweep_boxcap"  texels of one LDS footprint box (default: what fits, 312 / 200 by the tile shape; 0 = gather every tap
  *                   from global memory)
  *   "sweep_xcd"     0 | 1   XCD-aware block map for fewer than 8 channel slabs
- *   "sweep_dsplit", "sweep_groups", "conv_*", "convT_cg", "convT_persist"   schedules of the sweep's plane split, of the bf16x3
- *                   convolutions and of the fp16 + MX convolution ("conv_mx_th") (csrc/common.h: struct Options);
- *                   "probe_f16_pair" shapes mvsdet_store_pattern_probe_f16 only
+ *   "sweep_dsplit", "sweep_groups", "bwd_groups", "conv_*"   schedules of the sweep's plane split, of the bf16x3
+ *                   convolutions and of the fp16 + MX convolution ("conv_mx_th") (csrc/common.h: struct Options)
  * "sweep_tw" decides the layout of the sweep geometry: consume one (mvsdet_plane_sweep_variance_tabled_f32) under the
  * "sweep_tw" it was built with (mvsdet_plane_sweep_table_f32).  "sweep_boxcap" is baked into the geometry (union boxes,
  * staged / refill flags); the consuming call sizes its LDS slots for the largest capacity a geometry of that tile shape
@@ -407,10 +406,12 @@ int mvsdet_backproject_weigh_mean_bwd_f32(const float* feat, const int64_t* feat
  * reads the form) and the size in bytes come from mvsdet_scl_bytes.
  * mvsdet_scl_pack_f32 cuts an (N,C,D,H,W) fp32 tensor (possibly row-pitched: mvsdet_plane_sweep_variance_tabled_pitched_f32; zero_border 1: clear the buffer first -- a buffer reused for the
  * same shape needs that once; 2: the packing kernel runs over the padded volume and writes the border's zeros itself -- for a
- * buffer fresh from an allocator on every call, no clearing pass).  weight_split: [Cout/64][c8][14 tap pairs][2 groups of 32 outputs][2 pieces][64 lanes][8]
- * bf16, lane = 32 * (tap parity) + MFMA row m, row m carrying output channel 8*((m>>4)*2 + ((m>>2)&1)) + (m&3) + 4*((m>>3)&1)
- * of its group (so that a lane's accumulator registers 8q..8q+7 are eight consecutive channels = one SCL unit), tap 27 and
- * channels >= Cin zero (mvsdet_amd.ops.split_conv_weight).
+ * buffer fresh from an allocator on every call, no clearing pass).  weight_split (stride 1, for v_mfma_f32_16x16x32_bf16):
+ * [Cout/64][c8][7 k-steps of 4 taps][4 groups of 16 outputs][2 pieces][64 lanes][8] bf16, lane = 16 * (tap of the k-step) + MFMA row m,
+ * row m of group rg carrying output channel 32*(rg>>1) + 8*(m>>2) + 4*(rg&1) + (m&3) of the 64 (so that groups 2q, 2q+1 give a lane
+ * eight consecutive channels = one SCL unit), tap 27 and channels >= Cin zero.  Stride 2 / transposed (v_mfma_f32_32x32x16_bf16): the same
+ * bytes as [14 tap pairs][2 groups of 32 outputs][2 pieces][64 lanes][8], lane = 32 * (tap of the pair) + MFMA row m, row m carrying output
+ * channel 8*((m>>4)*2 + ((m>>2)&1)) + (m&3) + 4*((m>>3)&1) of its group (mvsdet_amd.ops.split_conv_weight).
  * out (N,Cout,D,H,W) fp32 = [relu]([scale *] conv [+ shift] [+ residual]).  Stride 1, Cout % 64 == 0.
  * ------------------------------------------------------------------------------------------- */
 size_t mvsdet_scl_bytes(int N, int C, int D, int H, int W, int* Dp /*HOST, may be NULL*/, int* Hp, int* Wp);
@@ -543,8 +544,7 @@ int mvsdet_copy_f32(const float* src, float* dst, size_t n_floats, mvsdet_stream
 int mvsdet_store_pattern_probe_f32(float* var, int N, int C, int D, int H, int W, int out_w_pitch, int tile_w,
                                    int planes_per_block, mvsdet_stream_t stream);
 /* The same for fp16 storage (BASELINE configs[4]): a lane's four pixels are 8 bytes, a wave-instruction writes 8 channel rows of
- * 64 bytes -- half a 128-byte line per row.  Option "probe_f16_pair" = 1: lanes of adjacent pixel quads store 16 bytes of two
- * channel rows instead (an experiment; the sweep's own flush is the unpaired pattern). */
+ * 64 bytes -- half a 128-byte line per row. */
 int mvsdet_store_pattern_probe_f16(void* var, int N, int C, int D, int H, int W, int out_w_pitch, int tile_w,
                                    int planes_per_block, mvsdet_stream_t stream);
 

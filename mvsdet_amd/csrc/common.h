@@ -12,7 +12,7 @@ namespace mvsdet {
 
 void set_error(const char* fmt, ...);
 
-// Tuning options of the library: initialised ONCE from the environment (MVSDET_SWEEP_TW, _BOXCAP, _XCD) the
+// Tuning options of the library: initialised ONCE from the environment (MVSDET_SWEEP_TW, _BOXCAP, _XCD, ...) the
 // first time they are needed, afterwards changed only through mvsdet_set_option() -- no getenv on the launch path.
 struct Options {
     int sweep_tw;      // 0 = by the map width, 16 / 32 force the tile shape (16x8 / 32x4)
@@ -21,16 +21,7 @@ struct Options {
     int sweep_dsplit;  // 0 = by the grid size; n > 0: every block sweeps ceil(D / n) consecutive planes
     int sweep_groups;  // -1 = by the plane count; 0 / 1 = off; g in [2, kSweepGroups]: a tile's planes are dealt to up to g blocks,
                        // cut where its footprint boxes are refilled (the near planes)
-    int conv_subpairs; // bf16x3 stride-1 convolution on 3x16x8 tiles: tap pairs per weight sub-stage; 0 = by the grid, 2 / 5 force
     int conv_nsplit;   // bf16x3 convolutions: splits of the input channels; 0 = by the grid, n > 0 force (needs the workspace)
-    int conv_cgn;      // stride-1 bf16x3 convolution (16x16x32 form) on 3x16x8 tiles: 0 / 2 = 12 waves of 32 voxels, 4 = 6 waves of 64
-    int conv_s2_cg;    // stride-2 bf16x3 convolution fed by PSCL on 3x16x8 tiles: 0 / 1 = 12 waves of one column group, 2 = 6 of two
-    int conv_s2_ob;    // stride-2 bf16x3 convolution fed by PSCL: 1 = 64 output channels per block, else 128 where Cout allows
-    int convT_cg;      // transposed bf16x3 convolution on 3x16x8 tiles: 0 / 3 = all eight output parity classes in one block of 32 output
-                       // channels (12 waves); 1 = one block per (PD, PH), 12 waves of one column group; 2 = 6 waves of two
-    int probe_f16_pair; // mvsdet_store_pattern_probe_f16 only: 1 = lanes of adjacent pixel quads own the octet between them and store
-                       // 16 bytes of two channel rows instead of 8 of four (what a paired flush of the fp16 sweep WOULD reach: +12 %,
-                       // not built -- the fp16 sweep is bound by its vector work); 0 (default) = the kernel's own pattern
     int conv_xcd;      // stride-1 bf16x3 convolution: 1 (default) = an XCD takes a contiguous eighth of the grid (neighbouring tiles share
                        // their halo voxels in one L2); 0 = blocks round-robin over the XCDs
     int conv_split_blocks; // bf16x3 convolutions on small grids: the input channels are split until about this many blocks run (768 =
@@ -40,11 +31,6 @@ struct Options {
                        // count (2 from 32 planes), 1 / 2 force
     int conv_mx_th;    // fp16 + MX convolution (costreg_mx.h): 0 (default) = wave-specialised kernel (8 multiplying + 4 staging waves, 4 x 8 x 16 tiles);
                        // 8 / 12 = every wave does everything on 4 x 8 x 16 (8 waves) / 4 x 12 x 16 (12 waves) tiles
-    int conv_mfma16;   // 1 (default): the bf16x3 stride-1 convolution on v_mfma_f32_16x16x32_bf16 (conv0 of the cost network 5.37 -> 4.91 ms:
-                       // the chip holds a higher clock on this shape); 0: 32x32x16.  Weights must be split under the same setting.
-    int convT_persist; // transposed bf16x3 convolution, all-classes form with a skip tensor: 0 (default) = one block per (tile, 32 channels);
-                       // 1 = the persistent kernel (convt_persist.h: one block per CU, an item's stores behind the next item's
-                       // multiplications; the same bits, not faster: profiles/r06_convt_persist.txt); n >= 8: persistent on n blocks
 };
 Options& options();
 

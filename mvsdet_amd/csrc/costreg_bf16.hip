@@ -3,7 +3,7 @@
 //
 //     x = x_hi + x_mid (+ 2^-16 |x|),  w = w_hi + w_mid (+ ...),   x*w ~ x_hi*w_hi + x_hi*w_mid + x_mid*w_hi
 //
-// Every product of two bf16 pieces is exact in fp32 and v_mfma_f32_32x32x16_bf16 accumulates in fp32, so the three
+// Every product of two bf16 pieces is exact in fp32 and the bf16 MFMAs accumulate in fp32, so the three
 // MFMAs leave out only the terms of relative size 2^-16 (x_mid*w_mid, x_lo*w_hi, x_hi*w_lo): measured on the network
 // (tools/study/split_bf16_emulation.py, G8 fixture) 2e-6 .. 4e-6 on the logits, 5e-7 on the depth probabilities -- the
 // north_star bar is 1e-4 -- where plain bf16 operands give 1e-3.  Three bf16 MFMAs cost 3/16 of the fp32 MFMA
@@ -22,8 +22,9 @@
 //            5 tiles, three waves on every SIMD); the fp32-input form also 3x16x8 (6) and 8x8x8 (8), the stride-2 and transposed
 //            kernels 3x16x8 -- whichever pads the volume least (6x30x40 and 3x15x20 are padded 1.7x and 2.3x by 4x8x16)
 //   wave   = 64 voxels (two column groups of 32 = 2 h-rows x 16 or 4 h-rows x 8) x 64 channels (two row groups) = 4 accumulators 32x32
-//   LDS    = input halo tile of 8 channels, both pieces, double buffered  +  the weights of 5 tap pairs x 64 x 8,
-//            both pieces, double buffered (three weight sub-stages per 8 channels); all of it filled by LDS-DMA
+//            (stride 2, transposed); the stride-1 kernel holds the same outputs as 4 x 4 accumulators 16x16 (see there)
+//   LDS    = input halo tile of 8 channels, both pieces, double buffered  +  the weights of 6 - 8 tap pairs x 64 x 8,
+//            both pieces, double buffered (two or three weight sub-stages per 8 channels); all of it filled by LDS-DMA
 //   per tap pair and wave: 4 A + 4 B ds_read_b128 feed 12 MFMAs (2 x 2 accumulators x 3 terms)
 // One barrier per weight sub-stage: wait for the own DMAs of the stage, barrier, issue the DMAs of the next stage into
 // the buffers the barrier has just freed, compute.
@@ -38,14 +39,12 @@ typedef float f32x16b __attribute__((ext_vector_type(16)));
 
 constexpr int kBfW = 16;             // tile width (voxels along w): one MFMA column group = 2 h-rows of 16
 constexpr int kBfPairs = 14;         // tap pairs (27 taps + 1 empty)
-constexpr int kBfSubPairs = 5;       // tap pairs per weight sub-stage (5 + 5 + 4); the kernels take it as a template parameter:
-                                     // 2 (seven sub-stages) makes the LDS of a 3x16x8 tile 77 KiB, so that two blocks share a CU
 __host__ __device__ constexpr int bf_w_slots(int subp) { return subp * 2 * 2 * 64; }   // 16-byte slots of one weight buffer: [pair][row group][piece][lane]
 
 __host__ __device__ constexpr int bf_in_slots(int TD, int TH, int TW = kBfW) {   // 16-byte slots of one piece of one input buffer
     return ((TD + 2) * (TH + 2) * (TW + 2) + 63) / 64 * 64;
 }
-__host__ __device__ constexpr size_t bf_lds_bytes(int TD, int TH, int TW = kBfW, int subp = kBfSubPairs) {
+__host__ __device__ constexpr size_t bf_lds_bytes(int TD, int TH, int TW, int subp) {
     return (size_t)(2 * 2 * bf_in_slots(TD, TH, TW) + 2 * bf_w_slots(subp)) * 16;
 }
 
@@ -200,8 +199,10 @@ __global__ __launch_bounds__(kThreads) void scl_pack_padded_kernel(const float* 
 // copy of weights that were updated in place.
 struct TapTable { signed char t[2 * kBfPairs]; };   // the 3x3x3 tap (0..26) of every half of the 14 tap pairs; -1 = empty half
 
-// 16x16x32 layout (order 3): [Cout/64][c8][k-step 7][row group 4][piece 2][64 lanes][8]: lane = 16 * (tap of the k-step) + row m,
-// row m of row group rg = channel 32*(rg >> 1) + 8*(m >> 2) + 4*(rg & 1) + (m & 3), tap = 4*ks + (lane >> 4) (27: empty)
+// Stride-1 layout (order 0, for v_mfma_f32_16x16x32_bf16): [Cout/64][c8][k-step 7][row group 4][piece 2][64 lanes][8]: lane = 16 * (tap
+// of the k-step) + row m, row m of row group rg = channel 32*(rg >> 1) + 8*(m >> 2) + 4*(rg & 1) + (m & 3), tap = 4*ks + (lane >> 4)
+// (27: empty).  The stride-2 and transposed layouts (orders 1, 2, 32x32x16) are pair-major with their taps from a TapTable.
+constexpr int kSplitKStep = 3;   // SplitBatch::order of a stride-1 tensor (order 0 of the entry points): the k-step-major layout
 __device__ __forceinline__ void bf_m16_unit(size_t u, int C8, int& o, int& t, int& c8) {
     const int lane = (int)(u & 63), rg = (int)((u >> 7) & 3), m = lane & 15;
     const size_t r = u >> 9;
@@ -214,14 +215,14 @@ __device__ __forceinline__ void bf_m16_unit(size_t u, int C8, int& o, int& t, in
 
 __global__ __launch_bounds__(kThreads) void split_conv_weight_kernel(const float* __restrict__ w, uint4* __restrict__ out, int Cin,
                                                                      int C8, size_t units, TapTable taps, long long so, long long sc,
-                                                                     int m16) {
+                                                                     int kstep_major) {
     const size_t u = (size_t)blockIdx.x * kThreads + threadIdx.x;
     if (u >= units) return;
     int lane = (int)(u & 63), piece = (int)((u >> 6) & 1), a = (int)((u >> 7) & 1);
     const size_t r = u >> 8;
     int p = (int)(r % kBfPairs), c8 = (int)((r / kBfPairs) % C8), ob = (int)(r / ((size_t)kBfPairs * C8));
     int o = ob * 64 + a * 32 + bf_mfma_row_channel(lane & 31), t = taps.t[2 * p + (lane >> 5)];
-    if (m16) bf_m16_unit(u, C8, o, t, c8);
+    if (kstep_major) bf_m16_unit(u, C8, o, t, c8);
     unsigned short b[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -261,8 +262,8 @@ __global__ __launch_bounds__(kThreads) void split_conv_weight_batched_kernel(Spl
     const size_t r = u >> 8;
     const int p = (int)(r % kBfPairs), ob = (int)(r / ((size_t)kBfPairs * C8));
     int c8 = (int)((r / kBfPairs) % C8);
-    int o = ob * 64 + a * 32 + bf_mfma_row_channel(lane & 31), t = b.taps[order == 3 ? 0 : order].t[2 * p + (lane >> 5)];
-    if (order == 3) bf_m16_unit(u, C8, o, t, c8);
+    int o = ob * 64 + a * 32 + bf_mfma_row_channel(lane & 31), t = b.taps[order == kSplitKStep ? 0 : order].t[2 * p + (lane >> 5)];
+    if (order == kSplitKStep) bf_m16_unit(u, C8, o, t, c8);
     const float* w = b.w[i];
     unsigned short bb[8];
 #pragma unroll
@@ -292,15 +293,17 @@ __host__ __device__ constexpr int bf_tap_off(int t) {
 // TW: tile width.  16: an MFMA column group (32 voxels) = 2 h-rows of 16; 8 (fp32-input form only): 4 h-rows of 8 -- the tiles
 // 3 x 16 x 8 and 8 x 8 x 8 fit the half- and quarter-resolution volumes of the cost network (6 x 30 x 40, 3 x 15 x 20) and the
 // neck's 40 x 40 x 16 level, which 4 x 8 x 16 tiles pad 1.7x, 2.3x and 1.2x.
-// M16: v_mfma_f32_16x16x32_bf16 instead of v_mfma_f32_32x32x16_bf16.  The 32 k of one instruction are FOUR taps of 8 channels
-// (lane group lane >> 4 = tap 4*ks + group of k-step ks; 27 taps = 7 k-steps, one slot empty), a wave's 64 voxels x 64 channels
-// are 4 x 4 accumulators of 16 x 16, per k-step 8 A + 8 B fragments feed 48 instructions: the same LDS reads, matrix cycles and
-// sums per output as the 32 x 32 form, but MFMA-dense loops hold a higher clock on this shape (MI355X_MICROARCH.md, DVFS
-// give-back item 7: ~1.12 - 1.15 x the FLOP/s at equal cycles per FLOP).  Weights: split order 3 (k-step-major, SUBP = 6 "pairs"
-// = 3 k-steps per sub-stage: 3 + 3 + 1).
-// CGN (16x16x32 form): column groups of 16 voxels per wave.  4: a wave = 64 voxels; 2: 32 voxels, twice the waves -- the
-// 3 x 16 x 8 tile then runs on 12 waves (three on every SIMD) instead of 6 (2/2/1/1 on the one block a CU holds).
-template <int TD, int TH, bool F32IN, int TW = kBfW, int SUBP = kBfSubPairs, bool M16 = false, int CGN = 4>
+// The stride-1 kernel multiplies on v_mfma_f32_16x16x32_bf16 (the stride-2 and transposed kernels on v_mfma_f32_32x32x16_bf16).  The
+// 32 k of one instruction are FOUR taps of 8 channels (lane group lane >> 4 = tap 4*ks + group of k-step ks; 27 taps = 7 k-steps,
+// one slot empty), a wave's 64 voxels x 64 channels are 4 x 4 accumulators of 16 x 16, per k-step 8 A + 8 B fragments feed 48
+// instructions: the same LDS reads, matrix cycles and sums per output as the 32 x 32 shape, but MFMA-dense loops hold a higher
+// clock on this one (MI355X_MICROARCH.md, DVFS give-back item 7: ~1.12 - 1.15 x the FLOP/s at equal cycles per FLOP; conv0 of the
+// cost network 5.37 -> 4.91 ms).  Weights: split order 0 (k-step-major).
+// SUBP: pair slots of weights per sub-stage, two per k-step: 6 = 3 k-steps (3 + 3 + 1), 8 = 4 (4 + 3: one barrier less per
+// channel group, all 160 KiB of LDS on the 4 x 12 x 16 tile).
+// CGN: column groups of 16 voxels per wave.  4: a wave = 64 voxels; 2: 32 voxels, twice the waves -- the 3 x 16 x 8 tile then
+// runs on 12 waves (three on every SIMD) instead of 6 (2/2/1/1 on the one block a CU holds).
+template <int TD, int TH, bool F32IN, int TW, int SUBP, int CGN>
 __global__ __launch_bounds__(TD * TH * TW * 4 / CGN) void conv3d_k3_bf16x3_kernel(
     const uint4* __restrict__ xs, const float* __restrict__ xf, long long sN, long long sC, long long sD, long long sH, int Cin,
     const uint4* __restrict__ wq, const float* __restrict__ scale, const float* __restrict__ shift,
@@ -308,9 +311,9 @@ __global__ __launch_bounds__(TD * TH * TW * 4 / CGN) void conv3d_k3_bf16x3_kerne
     size_t piece_stride, int tiles_w, int relu, int nsplit, float* __restrict__ partial, size_t total, int xcd_map,
     double2* __restrict__ stats, const float* __restrict__ stats_pivot) {
     float* __restrict__ out = dst.f32;
-    constexpr int RG = 32 / TW;                           // h-rows of one column group
-    static_assert(TH % RG == 0 && (TD * TH * TW) % 64 == 0, "whole column groups, two per wave");
-    static_assert(CGN == 4 || (M16 && CGN == 2), "half-size waves: 16x16x32 form only");
+    constexpr int RG = 16 / TW > 0 ? 16 / TW : 1;         // h-rows of one column group of 16 voxels
+    static_assert(CGN == 4 || CGN == 2, "a wave = 64 or 32 voxels");
+    static_assert(TH % RG == 0 && (TD * TH * TW) % (16 * CGN) == 0, "whole column groups, CGN per wave");
     constexpr int NW = TD * TH * TW / (16 * CGN);         // waves
     constexpr int NT = 64 * NW;                           // threads
     constexpr int HD = TD + 2, HH = TH + 2, HW = TW + 2;
@@ -321,7 +324,7 @@ __global__ __launch_bounds__(TD * TH * TW * 4 / CGN) void conv3d_k3_bf16x3_kerne
     constexpr int NSUB = (kBfPairs + SUBP - 1) / SUBP;    // weight sub-stages per channel group
     constexpr int kBfWSlots = bf_w_slots(SUBP);
     static_assert(NSUB >= 2, "the fp32 fetch / cut needs two sub-stages");
-    static_assert(!M16 || SUBP % 2 == 0, "16x16x32: a k-step is two pair slots of weights");
+    static_assert(SUBP % 2 == 0, "a k-step is two pair slots of weights");
     extern __shared__ uint4 s_bf[];   // [2 stages][2 pieces][INS] input, then [2 stages][kBfWSlots] weights
     uint4* s_in = s_bf;
     uint4* s_w = s_bf + 2 * 2 * INS;
@@ -339,7 +342,6 @@ __global__ __launch_bounds__(TD * TH * TW * 4 / CGN) void conv3d_k3_bf16x3_kerne
     const int n = zo / nob, ob64 = zo % nob;
     const int c8_begin = (int)((long long)C8 * split / nsplit), c8_end = (int)((long long)C8 * (split + 1) / nsplit);
     const int w0 = bw * TW, h0 = bh * TH, d0 = by * TD;
-    const int col = lane & 31, hh = lane >> 5;
 
     // ---- DMA plans.  Input: wave-instruction i of a stage = (piece i / IN_DMA, slots 64*(i % IN_DMA) ..); the lane's slot
     // is a halo voxel (dz, hy, wx) -> its address in the padded volume (slots beyond the halo re-read voxel 0).
@@ -422,7 +424,8 @@ __global__ __launch_bounds__(TD * TH * TW * 4 / CGN) void conv3d_k3_bf16x3_kerne
             }
         }
     };
-    // Weights: wq[ob64][c8][pair 14][row group 2][piece 2][lane 64] in 16-byte units; sub-stage s = pairs 5s .. 5s+4
+    // Weights: wq[ob64][c8][k-step 7][row group 4][piece 2][lane 64] in 16-byte units = 14 pair slots of 4 x 64; sub-stage s = slots
+    // SUBP * s .. SUBP * s + SUBP - 1
     const uint4* wn = wq + (size_t)ob64 * C8 * (kBfPairs * 4 * 64);
     auto dma_weights = [&](int c8, int s, int buf) {
         const int ninstr = min(SUBP, kBfPairs - s * SUBP) * 4;
@@ -434,45 +437,39 @@ __global__ __launch_bounds__(TD * TH * TW * 4 / CGN) void conv3d_k3_bf16x3_kerne
         }
     };
 
-    // ---- the wave's two column groups: g = 2*wave + b, plane g / (TH/RG), h-rows RG*(g % (TH/RG)) + {0..RG-1}; column c of a
-    // group = voxel (row c / TW, w = c % TW)
-    int vb[2];
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        const int g = 2 * wave + b;
-        const int dz = g / (TH / RG), hy = RG * (g % (TH / RG)) + col / TW;
-        vb[b] = (dz * HH + hy) * HW + col % TW;
-    }
-    // M16: four column groups of 16 voxels, g16 = 4*wave + cg: RG16 = 16 / TW h-rows each; lane = (voxel lane & 15, tap group lane >> 4)
-    constexpr int RG16 = 16 / TW > 0 ? 16 / TW : 1;
-    const int col16 = lane & 15, kg = lane >> 4;
-    int vb16[CGN], toffs[7];
+    // ---- the wave's CGN column groups of 16 voxels: g = CGN*wave + cg, plane g / (TH/RG), h-rows RG*(g % (TH/RG)) + {0..RG-1}; column c
+    // of a group = voxel (row c / TW, w = c % TW); lane = (voxel lane & 15, tap group lane >> 4)
+    const int col = lane & 15, kg = lane >> 4;
+    int vb[CGN], toffs[7];
 #pragma unroll
     for (int cg = 0; cg < CGN; ++cg) {
         const int g = CGN * wave + cg;
-        const int dz = g / (TH / RG16), hy = RG16 * (g % (TH / RG16)) + col16 / TW;
-        vb16[cg] = (dz * HH + hy) * HW + col16 % TW;
+        const int dz = g / (TH / RG), hy = RG * (g % (TH / RG)) + col / TW;
+        vb[cg] = (dz * HH + hy) * HW + col % TW;
     }
 #pragma unroll
     for (int ks = 0; ks < 7; ++ks)
         toffs[ks] = kg == 0 ? bf_tap_off<HH, HW>(4 * ks) : kg == 1 ? bf_tap_off<HH, HW>(4 * ks + 1)
                   : kg == 2 ? bf_tap_off<HH, HW>(4 * ks + 2) : bf_tap_off<HH, HW>(4 * ks + 3);
 
-    f32x16b acc[2][2];   // [row group (32 output channels)][column group]
-    typedef float f32x4b __attribute__((ext_vector_type(4)));
-    f32x4b acc16[4][CGN];  // M16: [row group (16 output channels)][column group (16 voxels)]
+    // Never read.  Four zeroed 32x32 accumulators ahead of the real ones are what the 32x32x16 form of this kernel left behind when it
+    // was removed: without them hipcc allocates the registers of six of the nine instantiations differently (same instruction count,
+    // tools/isa_compare.py), and the kernels that were measured are the ones to ship.  Drop them with the next change that re-measures.
+    f32x16b acc32[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+            for (int r = 0; r < 16; ++r) acc32[a][b][r] = 0.0f;
+    typedef float f32x4b __attribute__((ext_vector_type(4)));
+    f32x4b acc[4][CGN];  // [row group (16 output channels)][column group (16 voxels)]
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
         for (int b = 0; b < CGN; ++b)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc16[a][b][r] = 0.0f;
+            for (int r = 0; r < 4; ++r) acc[a][b][r] = 0.0f;
 
     const bf16x8* s_in8 = reinterpret_cast<const bf16x8*>(s_in);
     const bf16x8* s_w8 = reinterpret_cast<const bf16x8*>(s_w);
@@ -482,51 +479,26 @@ __global__ __launch_bounds__(TD * TH * TW * 4 / CGN) void conv3d_k3_bf16x3_kerne
         constexpr int np = (kBfPairs - s * SUBP < SUBP ? kBfPairs - s * SUBP : SUBP);
         const bf16x8* bin = s_in8 + (size_t)(ibuf * 2) * INS;
         const bf16x8* ain = s_w8 + (size_t)wbuf * kBfWSlots + lane;
-        if constexpr (M16) {
 #pragma unroll
-            for (int kl = 0; kl < np / 2; ++kl) {
-                const int toff = toffs[s * (SUBP / 2) + kl];
-                bf16x8 A[4][2], B[CGN][2];   // [row / column group][piece]
+        for (int kl = 0; kl < np / 2; ++kl) {
+            const int toff = toffs[s * (SUBP / 2) + kl];
+            bf16x8 A[4][2], B[CGN][2];   // [row / column group][piece]
 #pragma unroll
-                for (int a = 0; a < 4; ++a)
+            for (int a = 0; a < 4; ++a)
 #pragma unroll
-                    for (int q = 0; q < 2; ++q) A[a][q] = ain[((kl * 4 + a) * 2 + q) * 64];
+                for (int q = 0; q < 2; ++q) A[a][q] = ain[((kl * 4 + a) * 2 + q) * 64];
 #pragma unroll
-                for (int b = 0; b < CGN; ++b)
+            for (int b = 0; b < CGN; ++b)
 #pragma unroll
-                    for (int q = 0; q < 2; ++q) B[b][q] = bin[(size_t)q * INS + vb16[b] + toff];
+                for (int q = 0; q < 2; ++q) B[b][q] = bin[(size_t)q * INS + vb[b] + toff];
 #pragma unroll
-                for (int a = 0; a < 4; ++a)
+            for (int a = 0; a < 4; ++a)
 #pragma unroll
-                    for (int b = 0; b < CGN; ++b) {
-                        acc16[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[a][1], B[b][0], acc16[a][b], 0, 0, 0);   // w_mid * x_hi
-                        acc16[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[a][0], B[b][1], acc16[a][b], 0, 0, 0);   // w_hi * x_mid
-                        acc16[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[a][0], B[b][0], acc16[a][b], 0, 0, 0);   // w_hi * x_hi
-                    }
-            }
-        } else {
-#pragma unroll
-            for (int pl = 0; pl < np; ++pl) {
-                const int p = s * SUBP + pl;
-                const int toff = hh ? bf_tap_off<HH, HW>(2 * p + 1) : bf_tap_off<HH, HW>(2 * p);
-                bf16x8 A[2][2], B[2][2];   // [row / column group][piece]
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) A[a][q] = ain[((pl * 2 + a) * 2 + q) * 64];
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) B[b][q] = bin[(size_t)q * INS + vb[b] + toff];
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) {
-                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[a][1], B[b][0], acc[a][b], 0, 0, 0);   // w_mid * x_hi
-                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[a][0], B[b][1], acc[a][b], 0, 0, 0);   // w_hi * x_mid
-                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[a][0], B[b][0], acc[a][b], 0, 0, 0);   // w_hi * x_hi
-                    }
-            }
+                for (int b = 0; b < CGN; ++b) {
+                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[a][1], B[b][0], acc[a][b], 0, 0, 0);   // w_mid * x_hi
+                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[a][0], B[b][1], acc[a][b], 0, 0, 0);   // w_hi * x_mid
+                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[a][0], B[b][0], acc[a][b], 0, 0, 0);   // w_hi * x_hi
+                }
         }
     };
 
@@ -579,133 +551,90 @@ __global__ __launch_bounds__(TD * TH * TW * 4 / CGN) void conv3d_k3_bf16x3_kerne
         substage(std::integral_constant<int, 6>{}, c8, ibuf, q0 + 6);
     }
 
-    // ---- epilogue: C/D map of the 32x32 MFMA: column = lane & 31 (voxel), register r of lane half hh = channel bf_row_channel(r, hh)
     const size_t plane = (size_t)H * W, vol = (size_t)D * plane;
-    if constexpr (M16) {
-        // 16x16: column = lane & 15 (voxel), register r of lane group kg = row 4*kg + r of the row group; the weights are laid out
-        // so that row m of row group rg carries channel 32*(rg >> 1) + 8*(m >> 2) + 4*(rg & 1) + (m & 3): row groups 2q and 2q+1
-        // together give a lane the eight consecutive channels 32q + 8kg .. + 7
-        // stats (training-mode BatchNorm behind this layer, costreg_bn.hip): the lane's sums of its outputs and of their squares,
-        // per channel, over its CGN voxels -- reduced over the block below, so that the BatchNorm needs no pass of its own over the
-        // tensor for its statistics
-        // (sums of v - pivot_c: E[v^2] - mean^2 on raw values cancels in fp32 when |mean| >> spread; the pivot is any value near the
-        // channel's mean -- the BatchNorm's running mean -- and is requested here, ahead of the stores)
-        float st_s[2][8], st_q[2][8], st_p[2][8];
+    // ---- epilogue: C/D map of the 16x16 MFMA: column = lane & 15 (voxel), register r of lane group kg = row 4*kg + r of the row group; the weights are laid out
+    // so that row m of row group rg carries channel 32*(rg >> 1) + 8*(m >> 2) + 4*(rg & 1) + (m & 3): row groups 2q and 2q+1
+    // together give a lane the eight consecutive channels 32q + 8kg .. + 7
+    // stats (training-mode BatchNorm behind this layer, costreg_bn.hip): the lane's sums of its outputs and of their squares,
+    // per channel, over its CGN voxels -- reduced over the block below, so that the BatchNorm needs no pass of its own over the
+    // tensor for its statistics
+    // (sums of v - pivot_c: E[v^2] - mean^2 on raw values cancels in fp32 when |mean| >> spread; the pivot is any value near the
+    // channel's mean -- the BatchNorm's running mean -- and is requested here, ahead of the stores)
+    float st_s[2][8], st_q[2][8], st_p[2][8];
 #pragma unroll
-        for (int q = 0; q < 2; ++q)
+    for (int q = 0; q < 2; ++q)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                st_s[q][j] = st_q[q][j] = 0.0f;
-                st_p[q][j] = (stats && stats_pivot) ? stats_pivot[ob64 * 64 + 32 * q + 8 * kg + j] : 0.0f;
-            }
-#pragma unroll
-        for (int cg = 0; cg < CGN; ++cg) {
-            const int g = CGN * wave + cg;
-            const int d = d0 + g / (TH / RG16), h = h0 + RG16 * (g % (TH / RG16)) + col16 / TW, w = w0 + col16 % TW;
-            if (d >= D || h >= H || w >= W) continue;
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                float sc[8], sh[8], rv[8], v[8];
-                const int o0 = ob64 * 64 + 32 * q + 8 * kg;
-                const size_t idx0 = ((size_t)n * Cout + o0) * vol + (size_t)d * plane + (size_t)h * W + w;
-                const bool fin = nsplit == 1;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    sc[j] = (fin && scale) ? scale[o0 + j] : 1.0f;
-                    sh[j] = (fin && scale) ? shift[o0 + j] : 0.0f;
-                    rv[j] = (fin && residual) ? residual[idx0 + (size_t)j * vol] : 0.0f;
-                }
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    v[j] = j < 4 ? acc16[2 * q][cg][j & 3] : acc16[2 * q + 1][cg][j & 3];
-                    if (nsplit > 1) {
-                        partial[(size_t)split * total + idx0 + (size_t)j * vol] = v[j];
-                        continue;
-                    }
-                    if (scale) v[j] = fmaf(v[j], sc[j], sh[j]);
-                    if (residual) v[j] = v[j] + rv[j];
-                    if (relu) v[j] = fmaxf(v[j], 0.0f);
-                    if (out) out[idx0 + (size_t)j * vol] = v[j];
-                }
-                if (nsplit == 1 && (dst.scl || dst.pscl)) bf_store_units(dst, v, n, Cout / 8, ob64 * 8 + 4 * q + kg, d, h, w);
-                if (stats) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float dv = v[j] - st_p[q][j];
-                        st_s[q][j] += dv;
-                        st_q[q][j] = fmaf(dv, dv, st_q[q][j]);
-                    }
-                }
-            }
+        for (int j = 0; j < 8; ++j) {
+            st_s[q][j] = st_q[q][j] = 0.0f;
+            st_p[q][j] = (stats && stats_pivot) ? stats_pivot[ob64 * 64 + 32 * q + 8 * kg + j] : 0.0f;
         }
-        if (stats) {   // block-uniform; the launcher allows it with nsplit == 1 and a raw fp32 output only
-            // channel 32q + 8kg + j of the block has NW * 16 contributors (wave, voxel lane): all of them into the LDS the loop has
-            // left, then four threads per channel add theirs up in double, in a fixed order (the same bits on every run)
-            constexpr int NCON = NW * 16;
-            static_assert(NT >= 256 && (size_t)64 * NCON * sizeof(float2) <= bf_lds_bytes(TD, TH, TW, SUBP), "the reduction's LDS image");
-            float2* red = reinterpret_cast<float2*>(s_bf);
-            __syncthreads();   // every wave is past its last read of the stage buffers
 #pragma unroll
-            for (int q = 0; q < 2; ++q)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) red[(32 * q + 8 * kg + j) * NCON + wave * 16 + col16] = make_float2(st_s[q][j], st_q[q][j]);
-            __syncthreads();
-            if (tid < 256) {
-                const int ch = tid >> 2, part = tid & 3;
-                double a = 0.0, b = 0.0;
-                for (int i = part * (NCON / 4); i < (part + 1) * (NCON / 4); ++i) {
-                    const float2 e = red[ch * NCON + i];
-                    a += (double)e.x;
-                    b += (double)e.y;
-                }
-                a += __shfl_xor(a, 1, 64); b += __shfl_xor(b, 1, 64);
-                a += __shfl_xor(a, 2, 64); b += __shfl_xor(b, 2, 64);
-                if (part == 0) {
-                    // partial sums of channel c: [c][view][tile]: one entry per block that holds outputs of the channel
-                    const size_t tiles = (size_t)gridDim.x * gridDim.y;
-                    const size_t bidx = ((size_t)n * gridDim.y + by) * gridDim.x + bx;
-                    stats[(size_t)(ob64 * 64 + ch) * ((size_t)(gridDim.z / nob) * tiles) + bidx] = make_double2(a, b);
-                }
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        const int g = 2 * wave + b;
+    for (int cg = 0; cg < CGN; ++cg) {
+        const int g = CGN * wave + cg;
         const int d = d0 + g / (TH / RG), h = h0 + RG * (g % (TH / RG)) + col / TW, w = w0 + col % TW;
         if (d >= D || h >= H || w >= W) continue;
 #pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            // affine and residual of 8 outputs (registers 8q .. 8q+7 = eight consecutive channels) are requested together, ahead
-            // of the stores: loads and stores share one in-order counter, so a load issued behind a store waits for the store's
-            // round trip as well (one element at a time this epilogue was a chain of 64 memory round trips per lane)
+        for (int q = 0; q < 2; ++q) {
+            float sc[8], sh[8], rv[8], v[8];
+            const int o0 = ob64 * 64 + 32 * q + 8 * kg;
+            const size_t idx0 = ((size_t)n * Cout + o0) * vol + (size_t)d * plane + (size_t)h * W + w;
+            const bool fin = nsplit == 1;
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                float sc[8], sh[8], rv[8], v[8];
-                const int o0 = ob64 * 64 + a * 32 + bf_row_channel(8 * q, hh);   // channels o0 .. o0 + 7
-                const size_t idx0 = ((size_t)n * Cout + o0) * vol + (size_t)d * plane + (size_t)h * W + w;
-                const bool fin = nsplit == 1;
+            for (int j = 0; j < 8; ++j) {
+                sc[j] = (fin && scale) ? scale[o0 + j] : 1.0f;
+                sh[j] = (fin && scale) ? shift[o0 + j] : 0.0f;
+                rv[j] = (fin && residual) ? residual[idx0 + (size_t)j * vol] : 0.0f;
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                v[j] = j < 4 ? acc[2 * q][cg][j & 3] : acc[2 * q + 1][cg][j & 3];
+                if (nsplit > 1) {
+                    partial[(size_t)split * total + idx0 + (size_t)j * vol] = v[j];
+                    continue;
+                }
+                if (scale) v[j] = fmaf(v[j], sc[j], sh[j]);
+                if (residual) v[j] = v[j] + rv[j];
+                if (relu) v[j] = fmaxf(v[j], 0.0f);
+                if (out) out[idx0 + (size_t)j * vol] = v[j];
+            }
+            if (nsplit == 1 && (dst.scl || dst.pscl)) bf_store_units(dst, v, n, Cout / 8, ob64 * 8 + 4 * q + kg, d, h, w);
+            if (stats) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    sc[j] = (fin && scale) ? scale[o0 + j] : 1.0f;
-                    sh[j] = (fin && scale) ? shift[o0 + j] : 0.0f;
-                    rv[j] = (fin && residual) ? residual[idx0 + (size_t)j * vol] : 0.0f;
+                    const float dv = v[j] - st_p[q][j];
+                    st_s[q][j] += dv;
+                    st_q[q][j] = fmaf(dv, dv, st_q[q][j]);
                 }
+            }
+        }
+    }
+    if (stats) {   // block-uniform; the launcher allows it with nsplit == 1 and a raw fp32 output only
+        // channel 32q + 8kg + j of the block has NW * 16 contributors (wave, voxel lane): all of them into the LDS the loop has
+        // left, then four threads per channel add theirs up in double, in a fixed order (the same bits on every run)
+        constexpr int NCON = NW * 16;
+        static_assert(NT >= 256 && (size_t)64 * NCON * sizeof(float2) <= bf_lds_bytes(TD, TH, TW, SUBP), "the reduction's LDS image");
+        float2* red = reinterpret_cast<float2*>(s_bf);
+        __syncthreads();   // every wave is past its last read of the stage buffers
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    v[j] = acc[a][b][8 * q + j];
-                    if (nsplit > 1) {
-                        partial[(size_t)split * total + idx0 + (size_t)j * vol] = v[j];
-                        continue;
-                    }
-                    if (scale) v[j] = fmaf(v[j], sc[j], sh[j]);
-                    if (residual) v[j] = v[j] + rv[j];
-                    if (relu) v[j] = fmaxf(v[j], 0.0f);
-                    if (out) out[idx0 + (size_t)j * vol] = v[j];
-                }
-                // the same values cut into bf16 pieces: one 16-byte unit per piece
-                if (nsplit == 1 && (dst.scl || dst.pscl)) bf_store_units(dst, v, n, Cout / 8, ob64 * 8 + a * 4 + 2 * q + hh, d, h, w);
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) red[(32 * q + 8 * kg + j) * NCON + wave * 16 + col] = make_float2(st_s[q][j], st_q[q][j]);
+        __syncthreads();
+        if (tid < 256) {
+            const int ch = tid >> 2, part = tid & 3;
+            double a = 0.0, b = 0.0;
+            for (int i = part * (NCON / 4); i < (part + 1) * (NCON / 4); ++i) {
+                const float2 e = red[ch * NCON + i];
+                a += (double)e.x;
+                b += (double)e.y;
+            }
+            a += __shfl_xor(a, 1, 64); b += __shfl_xor(b, 1, 64);
+            a += __shfl_xor(a, 2, 64); b += __shfl_xor(b, 2, 64);
+            if (part == 0) {
+                // partial sums of channel c: [c][view][tile]: one entry per block that holds outputs of the channel
+                const size_t tiles = (size_t)gridDim.x * gridDim.y;
+                const size_t bidx = ((size_t)n * gridDim.y + by) * gridDim.x + bx;
+                stats[(size_t)(ob64 * 64 + ch) * ((size_t)(gridDim.z / nob) * tiles) + bidx] = make_double2(a, b);
             }
         }
     }
@@ -725,7 +654,7 @@ constexpr int kS2TD = 4, kS2TH = 8;
 constexpr int kS2HH = kS2TH + 1, kS2HW = kBfW + 1;
 constexpr int kS2WSlots = 4 * 2 * 2 * 64;                    // up to 4 tap pairs per stage
 __host__ __device__ constexpr int s2_ins(int TD, int TH, int TW) { return ((TD + 1) * (TH + 1) * (TW + 1) + 63) / 64 * 64; }
-__host__ __device__ constexpr size_t s2_lds_bytes(int TD = kS2TD, int TH = kS2TH, int TW = kBfW, int OB = 1) {
+__host__ __device__ constexpr size_t s2_lds_bytes(int TD, int TH, int TW, int OB) {
     return (size_t)(2 * 2 * s2_ins(TD, TH, TW) + 2 * OB * kS2WSlots) * 16;
 }
 __host__ __device__ constexpr int s2_pairs(int pi) { return (1 << ((pi >> 2) + ((pi >> 1) & 1) + (pi & 1))) / 2 == 0 ? 1 : (1 << ((pi >> 2) + ((pi >> 1) & 1) + (pi & 1))) / 2; }
@@ -752,7 +681,7 @@ __host__ __device__ constexpr int s2_tap_off(int pi, int j) {
 // (the 3 x 16 x 8 tile: 12 waves, three on every SIMD, instead of 6).
 // OB: groups of 64 output channels per block.  2: a block's staged class tile feeds twice the MFMAs (this layer reads 8 x the
 // voxels it writes: its input DMAs, not its matrix work, set its time) and a wave's B fragment serves 4 row groups.
-template <int TD, int TH, int TW, bool PIN = false, int CG = 2, int OB = 1>
+template <int TD, int TH, int TW, bool PIN, int CG, int OB>
 __global__ __launch_bounds__(TD * TH * TW * 2 / CG) void conv3d_k3_s2_bf16x3_kernel(
     const float* __restrict__ xf, long long sN, long long sC, long long sD, long long sH, int Cin, const uint4* __restrict__ xp,
     int cDp, int cHp, int cWp, size_t cpiece, int Nviews, const uint4* __restrict__ wq,
@@ -1047,9 +976,8 @@ __host__ __device__ constexpr int ct_tap_off(int pi, int j) {
     return (od * HH + oh) * HW + ow;
 }
 
-// CG: column groups (32 coarse voxels each) per wave.  2: a wave = 64 voxels x 64 channels x 2 w parities = 8 accumulators, the
-// 3 x 16 x 8 tile = 6 waves, which sit 2/2/1/1 on the four SIMDs of the one block a CU holds; 1: 4 accumulators, 12 waves, three
-// on every SIMD (each A fragment then feeds half the MFMAs: 6 LDS reads per 6 instead of 8 per 12).
+// CG: column groups (32 coarse voxels each) per wave.  2 (the one form built, for the 4 x 8 x 16 tile): a wave = 64 voxels x 64
+// channels x 2 w parities = 8 accumulators.
 template <int PD, int PH, int TD, int TH, int TW, int CG>
 __device__ __forceinline__ void convT3d_k3_s2_bf16x3_body(
     const uint4* __restrict__ xs, const uint4* __restrict__ wq, const float* __restrict__ scale, const float* __restrict__ shift,
@@ -1259,7 +1187,7 @@ __device__ __forceinline__ void convT3d_k3_s2_bf16x3_body(
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The transposed layer with ALL EIGHT output parity classes in one block (option "convT_fused"): block = (coarse tile of
+// The transposed layer with ALL EIGHT output parity classes in one block (the 3 x 16 x 8 tile's kernel): block = (coarse tile of
 // 3 x 16 x 8 input voxels, 32 output channels), 12 waves of one column group; a wave holds 8 accumulators = the 8 outputs
 // 2i + (pd, ph, pw) of its 32 coarse voxels x 32 channels.  Against one block per (PD, PH): the halo tile of a stage is staged
 // once for all classes (Cout / 32 times per tile instead of 4 x Cout / 64), and a stage is the 14 tap pairs of all classes =
@@ -1275,7 +1203,7 @@ __host__ __device__ constexpr size_t ctf_lds_bytes(int TD, int TH, int TW) {
 // stride-1 kernel's statistics epilogue leaves them.  The epilogue has no registers to spare (168 + spills), so a lane keeps its 16
 // channels' running sums in LDS slots of its own (the stage buffers are free by then): read - add - write per group of 8 values, no
 // atomics, then four threads per channel add the 384 contributors in double, in a fixed order.
-template <int TD, int TH, int TW, bool STATS = false>
+template <int TD, int TH, int TW, bool STATS>
 __global__ __launch_bounds__(TD * TH * TW * 2) void convT3d_k3_s2_bf16x3_fused_kernel(
     const uint4* __restrict__ xs, const uint4* __restrict__ wq, const float* __restrict__ scale, const float* __restrict__ shift,
     const float* __restrict__ residual, BfOut dst, int C8, int Cout, int Di, int Hi, int Wi, int Dp, int Hp, int Wp,
@@ -1474,8 +1402,6 @@ __global__ __launch_bounds__(TD * TH * TW * 2) void convT3d_k3_s2_bf16x3_fused_k
     }
 }
 
-#include "convt_persist.h"   // the same layer as a persistent kernel: the stores of item i behind the multiplications of item i + 1
-
 // ONE launch for the four (PD, PH) classes: class = blockIdx.x & 3, so the four blocks that read the same input tile are
 // dispatched together (the tile's second to fourth reads hit L2) and the grid has one tail instead of four.
 template <int TD, int TH, int TW, int CG>
@@ -1625,7 +1551,7 @@ extern "C" size_t mvsdet_split_conv_weight_bytes(int Cout, int Cin) {
     if (Cout <= 0 || Cout % 64 || Cin <= 0) return 0;
     return (size_t)(Cout / 64) * ((Cin + 7) / 8) * kBfPairs * 2 * 2 * 64 * 16;
 }
-// order: 0 = stride-1 convolution (pair p = taps 2p, 2p+1), 1 = stride-2 convolution (taps grouped by the parity class of the
+// order: 0 = stride-1 convolution (k-step-major: bf_m16_unit), 1 = stride-2 convolution (taps grouped by the parity class of the
 // input voxel they read: conv3d_k3_s2_bf16x3_kernel), 2 = transposed convolution (ConvTranspose3d weight (Cin,Cout,3,3,3);
 // taps grouped by the parity class of the OUTPUT voxel: convT3d_k3_s2_bf16x3_kernel)
 static TapTable tap_table(int order) {
@@ -1656,14 +1582,13 @@ extern "C" int mvsdet_split_conv_weight_ordered(const float* weight, void* weigh
                                                 mvsdet_stream_t stream) {
     MVS_REQUIRE(weight && weight_split, "split_conv_weight: NULL pointer");
     MVS_REQUIRE(Cout > 0 && Cout % 64 == 0 && Cin > 0, "split_conv_weight: Cout=%d must be a positive multiple of 64, Cin=%d > 0", Cout, Cin);
-    MVS_REQUIRE(order >= 0 && order <= 3, "split_conv_weight: order %d not in {0,1,2,3}", order);
-    if (order == 0 && options().conv_mfma16) order = 3;   // the stride-1 kernels then run their 16x16x32 form: its layout
+    MVS_REQUIRE(order >= 0 && order <= 2, "split_conv_weight: order %d not in {0,1,2}", order);
     MVS_REQUIRE(((uintptr_t)weight_split & 15u) == 0, "split_conv_weight: output must be 16-byte aligned");
     const size_t units = mvsdet_split_conv_weight_bytes(Cout, Cin) / 16;
     const long long so = order == 2 ? 27 : (long long)Cin * 27, sc = order == 2 ? (long long)Cout * 27 : 27;
     hipLaunchKernelGGL(split_conv_weight_kernel, dim3((unsigned)((units + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                        (hipStream_t)stream, weight, static_cast<uint4*>(weight_split), Cin, (Cin + 7) / 8, units,
-                       tap_table(order == 3 ? 0 : order), so, sc, order == 3 ? 1 : 0);
+                       tap_table(order), so, sc, order == 0 ? 1 : 0);
     MVS_LAUNCH_CHECK("split_conv_weight");
     return MVSDET_OK;
 }
@@ -1683,7 +1608,7 @@ extern "C" int mvsdet_split_conv_weights_batched(const float* const* weights, vo
         const bool live = i < count;
         if (live) {
             MVS_REQUIRE(weights[i] && splits[i], "split_conv_weights_batched: NULL tensor %d", i);
-            MVS_REQUIRE(Cout[i] > 0 && Cout[i] % 64 == 0 && Cin[i] > 0 && orders[i] >= 0 && orders[i] <= 3,
+            MVS_REQUIRE(Cout[i] > 0 && Cout[i] % 64 == 0 && Cin[i] > 0 && orders[i] >= 0 && orders[i] <= 2,
                         "split_conv_weights_batched: tensor %d: Cout=%d (multiple of 64), Cin=%d, order=%d", i, Cout[i], Cin[i], orders[i]);
             MVS_REQUIRE(((uintptr_t)splits[i] & 15u) == 0, "split_conv_weights_batched: outputs must be 16-byte aligned");
         }
@@ -1691,7 +1616,7 @@ extern "C" int mvsdet_split_conv_weights_batched(const float* const* weights, vo
         b.out[i] = live ? static_cast<uint4*>(splits[i]) : nullptr;
         b.Cin[i] = live ? Cin[i] : 1;
         b.Cout[i] = live ? Cout[i] : 64;
-        b.order[i] = live ? ((orders[i] == 0 && options().conv_mfma16) ? 3 : orders[i]) : 0;
+        b.order[i] = live ? (orders[i] == 0 ? kSplitKStep : orders[i]) : 0;
         b.first[i + 1] = b.first[i] + (live ? mvsdet_split_conv_weight_bytes(Cout[i], Cin[i]) / 16 : 0);
     }
     const size_t units = b.first[count];
@@ -1751,7 +1676,6 @@ static int launch_bf16x3(const char* name, const void* xs, const float* xf, cons
     if (!workspace || workspace_bytes < (size_t)nsplit * total * sizeof(float) || out_scl || out_pscl || stats) nsplit = 1;
     MVS_REQUIRE(nsplit == 1 || out, "%s: the split form needs the fp32 output", name);
     if (stats) {
-        MVS_REQUIRE(options().conv_mfma16 != 0 && options().conv_subpairs != 2, "%s: the statistics epilogue exists in the 16x16x32 form only", name);
         MVS_REQUIRE(!scale && !residual && !relu && out && !out_scl && !out_pscl, "%s: statistics are those of the raw fp32 output", name);
         MVS_REQUIRE(stats_bytes >= (size_t)Cout * N * p.tiles_w * p.tiles_h * p.tiles_d * sizeof(double2) && ((uintptr_t)stats & 15u) == 0,
                     "%s: the statistics buffer holds Cout x mvsdet_conv3d_k3_bf16x3_stats_parts double2", name);
@@ -1768,10 +1692,9 @@ static int launch_bf16x3(const char* name, const void* xs, const float* xf, cons
     dim3 grid((unsigned)(p.tiles_w * p.tiles_h), (unsigned)p.tiles_d, (unsigned)(N * (Cout / 64) * nsplit));
     const int xcd_map = options().conv_xcd != 0 && ((long long)grid.x * grid.y * grid.z) % 8 == 0 && (long long)grid.x * grid.y * grid.z >= 64;
     hipStream_t st = (hipStream_t)stream;
-#define MVS_BF_CASE(TD_, TH_, F32_, TW_, SUBP_, M16_, ...)                                                                  \
+#define MVS_BF_CASE(TD_, TH_, F32_, TW_, SUBP_, CGN_)                                                                       \
     {                                                                                                                       \
-        constexpr int CGN_ = (0, ##__VA_ARGS__) ? (0, ##__VA_ARGS__) : 4;                                                   \
-        auto* k = conv3d_k3_bf16x3_kernel<TD_, TH_, F32_, TW_, SUBP_, M16_, CGN_>;                                          \
+        auto* k = conv3d_k3_bf16x3_kernel<TD_, TH_, F32_, TW_, SUBP_, CGN_>;                                                \
         const size_t lds = bf_lds_bytes(TD_, TH_, TW_, SUBP_);                                                              \
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=  \
             hipSuccess) {                                                                                                   \
@@ -1783,28 +1706,24 @@ static int launch_bf16x3(const char* name, const void* xs, const float* xf, cons
                            p.Dp, p.Hp, p.Wp, piece, p.tiles_w, relu, nsplit, static_cast<float*>(workspace), total, xcd_map,         \
                            static_cast<double2*>(stats), stats_pivot);                                                      \
     }
-#define MVS_BF_TILE(TD_, TH_, F32_, TW_) { if (m16) MVS_BF_CASE(TD_, TH_, F32_, TW_, 6, true) else MVS_BF_CASE(TD_, TH_, F32_, TW_, 5, false) }
-    // option "conv_subpairs" = 2: weight sub-stages of 2 tap pairs (instead of 5) bring the 3 x 16 x 8 tile's LDS to 77 KiB, two
-    // 6-wave blocks per CU.  Measured at the cost network's 6 x 30 x 40 layer: 1.00 against 0.97 ms -- seven barriers per
-    // channel group cost what the second block wins; kept as a knob, off by default.
-    // option "conv_mfma16": the 16x16x32 form of the kernel (the weights must have been split while the option was set).
-    const bool sub2 = options().conv_subpairs == 2, m16 = options().conv_mfma16 != 0;
+    // One kernel per (input form, tile): weight sub-stages of 3 k-steps (SUBP 6) and waves of 64 voxels (CGN 4), except
+    //   * the 3 x 16 x 8 tile on 12 waves of 32 voxels (CGN 2) instead of 6 of 64, which sit 2/2/1/1 on the four SIMDs;
+    //   * the fp32-input 4 x 12 x 16 tile (the cost network's first layer) with two sub-stages of 4 + 3 k-steps (SUBP 8) instead of
+    //     3 + 3 + 1: one barrier less per channel group, all 160 KiB of LDS.
+    // (Sub-stages of one k-step, 77 KiB of LDS and two 6-wave blocks per CU, were measured at the cost network's 6 x 30 x 40 layer:
+    // 1.00 against 0.97 ms -- seven barriers per channel group cost what the second block wins.)
     if (xf) {
-        // the 3 x 16 x 8 tile on 12 waves of 32 voxels (16x16x32 form; option "conv_cgn" = 4: 6 waves of 64)
-        if (p.tw == 8 && p.td == 3) { if (sub2 && !m16) MVS_BF_CASE(3, 16, true, 8, 2, false) else if (m16 && options().conv_cgn != 4) MVS_BF_CASE(3, 16, true, 8, 6, true, 2) else MVS_BF_TILE(3, 16, true, 8) }
-        else if (p.tw == 8 && p.td == 6) MVS_BF_TILE(6, 16, true, 8)
-        else if (p.tw == 8) MVS_BF_TILE(8, 8, true, 8)
-        // (the cost network's first layer: two weight sub-stages of 4 + 3 k-steps instead of 3 + 3 + 1 -- one barrier less per
-        // channel group, all 160 KiB of LDS; "conv_subpairs" = 6 keeps three)
-        else if (p.th == 12) { if (m16 && options().conv_subpairs != 6) MVS_BF_CASE(4, 12, true, kBfW, 8, true) else MVS_BF_TILE(4, 12, true, kBfW) }
-        else MVS_BF_TILE(4, 8, true, kBfW)
+        if (p.tw == 8 && p.td == 3) MVS_BF_CASE(3, 16, true, 8, 6, 2)
+        else if (p.tw == 8 && p.td == 6) MVS_BF_CASE(6, 16, true, 8, 6, 4)
+        else if (p.tw == 8) MVS_BF_CASE(8, 8, true, 8, 6, 4)
+        else if (p.th == 12) MVS_BF_CASE(4, 12, true, kBfW, 8, 4)
+        else MVS_BF_CASE(4, 8, true, kBfW, 6, 4)
     } else {
-        if (p.tw == 8 && p.td == 3) { if (m16 && options().conv_cgn != 4) MVS_BF_CASE(3, 16, false, 8, 6, true, 2) else MVS_BF_TILE(3, 16, false, 8) }
-        else if (p.tw == 8) MVS_BF_TILE(6, 16, false, 8)
-        else if (p.th == 12) MVS_BF_TILE(4, 12, false, kBfW)
-        else MVS_BF_TILE(4, 8, false, kBfW)
+        if (p.tw == 8 && p.td == 3) MVS_BF_CASE(3, 16, false, 8, 6, 2)
+        else if (p.tw == 8) MVS_BF_CASE(6, 16, false, 8, 6, 4)
+        else if (p.th == 12) MVS_BF_CASE(4, 12, false, kBfW, 6, 4)
+        else MVS_BF_CASE(4, 8, false, kBfW, 6, 4)
     }
-#undef MVS_BF_TILE
 #undef MVS_BF_CASE
     MVS_LAUNCH_CHECK(name);
     if (nsplit > 1) {
@@ -1930,9 +1849,8 @@ static int launch_s2_bf16x3(const float* x, const int64_t* x_strides, const void
     const size_t cpiece = (size_t)8 * N * C8 * cDp * cHp * cWp;
     const BfOut dst = make_out(out, out_scl, nullptr, N, Cout, D, H, W);
     dim3 grid((unsigned)(tiles_w * tiles_h), (unsigned)tiles_d, (unsigned)(N * (Cout / 64) * nsplit));
-#define MVS_S2_CASE(TD_, TH_, TW_, PIN_, CG_, ...)                                                                           \
+#define MVS_S2_CASE(TD_, TH_, TW_, PIN_, CG_, OB_)                                                                           \
     {                                                                                                                        \
-        constexpr int OB_ = (0, ##__VA_ARGS__) ? (0, ##__VA_ARGS__) : 1;                                                     \
         auto* k = conv3d_k3_s2_bf16x3_kernel<TD_, TH_, TW_, PIN_, CG_, OB_>;                                                 \
         const size_t lds = s2_lds_bytes(TD_, TH_, TW_, OB_);                                                                 \
         grid.z = (unsigned)(N * (Cout / (64 * OB_)) * nsplit);                                                               \
@@ -1948,21 +1866,17 @@ static int launch_s2_bf16x3(const float* x, const int64_t* x_strides, const void
                            (int)(options().conv_xcd != 0 && ((long long)grid.x * grid.y * grid.z) % 8 == 0 &&                \
                                  (long long)grid.x * grid.y * grid.z >= 64));                                                \
     }
-    // the PSCL-fed 3 x 16 x 8 tile on 12 waves of one column group (conv1 0.573 -> 0.563, conv3 0.304 -> 0.291 ms: two 6-wave
-    // blocks already share a CU here; option "conv_s2_cg" = 2: the 6-wave form)
-    // ("conv_s2_ob" = 1: 64 output channels per block; default: 128 where the layer has them)
-    if (x_pscl) {
-        if (t38) {
-            if (options().conv_s2_cg == 2) MVS_S2_CASE(3, 16, 8, true, 2)
-            else if (Cout % 128 == 0 && nsplit == 1 && options().conv_s2_ob != 1) MVS_S2_CASE(3, 16, 8, true, 1, 2)
-            else MVS_S2_CASE(3, 16, 8, true, 1)
-        } else MVS_S2_CASE(kS2TD, kS2TH, kBfW, true, 2)
+    // The 3 x 16 x 8 tile runs on 12 waves of one column group (against 6 waves of two: conv1 0.573 -> 0.563, conv3 0.304 -> 0.291 ms;
+    // two 6-wave blocks already share a CU here), with 128 output channels per block where the layer has them and is not split;
+    // the 4 x 8 x 16 tile on 8 waves of two column groups.  The PSCL-fed and the fp32-fed (training, the neck) kernels alike.
+#define MVS_S2_TILE(PIN_)                                                                                                    \
+    {                                                                                                                        \
+        if (t38 && Cout % 128 == 0 && nsplit == 1) MVS_S2_CASE(3, 16, 8, PIN_, 1, 2)                                         \
+        else if (t38) MVS_S2_CASE(3, 16, 8, PIN_, 1, 1)                                                                      \
+        else MVS_S2_CASE(kS2TD, kS2TH, kBfW, PIN_, 2, 1)                                                                     \
     }
-    else if (t38) {   // fp32 input (the training route, the neck): the same 12 waves of one column group
-        if (options().conv_s2_cg == 2) MVS_S2_CASE(3, 16, 8, false, 2)
-        else if (Cout % 128 == 0 && nsplit == 1 && options().conv_s2_ob != 1) MVS_S2_CASE(3, 16, 8, false, 1, 2)
-        else MVS_S2_CASE(3, 16, 8, false, 1)
-    } else MVS_S2_CASE(kS2TD, kS2TH, kBfW, false, 2)
+    if (x_pscl) MVS_S2_TILE(true) else MVS_S2_TILE(false)
+#undef MVS_S2_TILE
 #undef MVS_S2_CASE
     MVS_LAUNCH_CHECK(name);
     if (nsplit > 1) {
@@ -2047,16 +1961,17 @@ static int launch_convT(const void* xs, const void* weight_split, const float* s
                            static_cast<const uint4*>(weight_split), scale, shift, residual, dst, C8, Cout, D, H, W, p.Dp, p.Hp, \
                            p.Wp, piece, tiles_w, relu);                                                                      \
     }
-    // the 3 x 16 x 8 tile: all eight output parity classes in one block of 32 output channels (conv9 0.40 -> 0.30, conv11 0.66 ->
-    // 0.48 ms, the same bits); option "convT_cg" = 1: one block per (PD, PH) on 12 waves of one column group, 2: on 6 waves of two
+    // the 3 x 16 x 8 tile: all eight output parity classes in one block of 32 output channels (against one block per (PD, PH):
+    // conv9 0.40 -> 0.30, conv11 0.66 -> 0.48 ms, the same bits); the 4 x 8 x 16 tile: one block per (PD, PH), 8 waves of two column groups
     if (stats) {
-        MVS_REQUIRE(t38 && options().convT_cg != 1 && options().convT_cg != 2,
-                    "%s: the statistics epilogue exists in the all-classes kernel on 3 x 16 x 8 tiles only (mvsdet_convT3d_k3_s2_bf16x3_stats_parts = 0 otherwise)", name);
+        MVS_REQUIRE(t38, "%s: the statistics epilogue exists in the all-classes kernel on 3 x 16 x 8 tiles only (mvsdet_convT3d_k3_s2_bf16x3_stats_parts = 0 otherwise)", name);
         MVS_REQUIRE(!scale && !residual && !relu && out && !out_scl, "%s: statistics are those of the raw fp32 output", name);
         MVS_REQUIRE(stats_bytes >= (size_t)Cout * N * tiles_w * tiles_h * tiles_d * sizeof(double2) && ((uintptr_t)stats & 15u) == 0,
                     "%s: the statistics buffer holds Cout x mvsdet_convT3d_k3_s2_bf16x3_stats_parts double2", name);
+    }
+    if (t38) {
         const size_t lds = ctf_lds_bytes(3, 16, 8);
-        auto* k = convT3d_k3_s2_bf16x3_fused_kernel<3, 16, 8, true>;
+        auto* k = stats ? convT3d_k3_s2_bf16x3_fused_kernel<3, 16, 8, true> : convT3d_k3_s2_bf16x3_fused_kernel<3, 16, 8, false>;
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
             set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed", name);
             return MVSDET_ERR_HIP;
@@ -2068,55 +1983,7 @@ static int launch_convT(const void* xs, const void* weight_split, const float* s
                            (int)(options().conv_xcd != 0 && ((long long)fgrid.x * fgrid.y * fgrid.z) % 8 == 0 &&
                                  (long long)fgrid.x * fgrid.y * fgrid.z >= 64),
                            static_cast<double2*>(stats), stats_pivot);
-    } else
-    if (t38 && residual && options().convT_cg == 0 && options().convT_persist != 0 && C8 % 4 == 0 && C8 >= 12 && Cout <= kCtpMaxCout && !(out && out_scl) &&
-        (unsigned long long)N * Cout * 8ull * D * H * W * 4ull < 0x7ffffff0ull && (!out_scl || 2ull * dst.piece * 16ull < 0x7ffffff0ull)) {
-        // persistent form (convt_persist.h): one block per CU, the epilogue of an item behind the loop of the next
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) {
-            set_error("%s: cannot read the device's CU count", name);
-            return MVSDET_ERR_HIP;
-        }
-        const unsigned G = (unsigned)(options().convT_persist > 1 ? options().convT_persist : cus) & ~7u;
-        const size_t lds = ctp_lds_bytes();
-        const unsigned out_bytes = out_scl ? (unsigned)(2ull * dst.piece * 16ull) : (unsigned)((unsigned long long)N * Cout * 8ull * D * H * W * 4ull);
-        const unsigned res_bytes = (unsigned)((unsigned long long)N * Cout * 8ull * D * H * W * 4ull);
-#ifndef MVS_CONVT_WHATIF
-#define MVS_CONVT_WHATIF 0   // what-if BUILDS only (-DMVS_CONVT_WHATIF=n, wrong results: convt_persist.h, profiles/r06_convt_persist.txt)
-#endif
-#define MVS_CTP_CASE(SCL_, RES_)                                                                                             \
-    {                                                                                                                        \
-        auto* k = convT3d_k3_s2_bf16x3_persist_kernel<SCL_, RES_>;                                                           \
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=   \
-            hipSuccess) {                                                                                                    \
-            set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed", name);                                   \
-            return MVSDET_ERR_HIP;                                                                                           \
-        }                                                                                                                    \
-        hipLaunchKernelGGL(k, dim3(G), dim3(768), lds, st, static_cast<const uint4*>(xs), static_cast<const uint4*>(weight_split), \
-                           scale, shift, residual, dst, C8, Cout, D, H, W, p.Dp, p.Hp, p.Wp, piece, tiles_w, tiles_h, tiles_d, N, relu, \
-                           out_bytes, res_bytes, (int)(options().conv_xcd != 0), MVS_CONVT_WHATIF);                                            \
-    }
-        if (out_scl) MVS_CTP_CASE(true, true)
-        else MVS_CTP_CASE(false, true)
-#undef MVS_CTP_CASE
-    } else
-    if (t38 && options().convT_cg != 1 && options().convT_cg != 2) {
-        const size_t lds = ctf_lds_bytes(3, 16, 8);
-        auto* k = convT3d_k3_s2_bf16x3_fused_kernel<3, 16, 8>;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed", name);
-            return MVSDET_ERR_HIP;
-        }
-        MVS_REQUIRE((long long)N * (Cout / 32) <= 65535, "%s: N*Cout/32 too large", name);
-        dim3 fgrid((unsigned)(tiles_w * tiles_h), (unsigned)tiles_d, (unsigned)(N * (Cout / 32)));
-        hipLaunchKernelGGL(k, fgrid, dim3(3 * 16 * 8 * 2), lds, st, static_cast<const uint4*>(xs), static_cast<const uint4*>(weight_split),
-                           scale, shift, residual, dst, C8, Cout, D, H, W, p.Dp, p.Hp, p.Wp, piece, tiles_w, relu,
-                           (int)(options().conv_xcd != 0 && ((long long)fgrid.x * fgrid.y * fgrid.z) % 8 == 0 &&
-                                 (long long)fgrid.x * fgrid.y * fgrid.z >= 64),
-                           static_cast<double2*>(nullptr), static_cast<const float*>(nullptr));
-    } else
-    if (t38) { if (options().convT_cg == 2) MVS_CT_CASE(3, 16, 8, 2) else MVS_CT_CASE(3, 16, 8, 1) }
-    else MVS_CT_CASE(kS2TD, kS2TH, kBfW, 2)
+    } else MVS_CT_CASE(kS2TD, kS2TH, kBfW, 2)
 #undef MVS_CT_CASE
     MVS_LAUNCH_CHECK(name);
     return MVSDET_OK;
@@ -2133,7 +2000,7 @@ extern "C" int mvsdet_convT3d_k3_s2_bf16x3(const void* xs, const void* weight_sp
 // block; parts = mvsdet_convT3d_k3_s2_bf16x3_stats_parts(N, D, H, W) of the COARSE input extents, 0 = this shape has no such form).
 extern "C" size_t mvsdet_convT3d_k3_s2_bf16x3_stats_parts(int N, int D, int H, int W) {
     if (N <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-    if (!convT_tile38(D, H, W) || options().convT_cg == 1 || options().convT_cg == 2) return 0;
+    if (!convT_tile38(D, H, W)) return 0;
     return (size_t)N * ((W + 7) / 8) * ((H + 15) / 16) * ((D + 2) / 3);
 }
 

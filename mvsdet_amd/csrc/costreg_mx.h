@@ -13,7 +13,7 @@
 //
 // Included by costreg_bf16.hip (it shares that file's BfOut, block map and epilogue conventions).
 //
-// Data flow = conv3d_k3_bf16x3_kernel's 16x16x32 form with the fp32 input cut in the kernel:
+// Data flow = conv3d_k3_bf16x3_kernel's with the fp32 input cut in the kernel:
 //   k-step  = 4 taps x 8 channels (lane group kg = lane >> 4 takes tap 4 ks + kg); 27 taps = 7 k-steps, the 28th slot empty
 //   stage   = 8 channels: halo tile in LDS as  hi[slot] = 8 fp16 (16 B)  and  q[slot] = 16 e2m3 codes (12 B in a 16-B slot):
 //             element 2c = Q(xh_c * 2^-E1), element 2c + 1 = Q(xr_c * 2^-(E1 - 11)) -- what ONE v_cvt_scalef32_2xpk16_fp6_f32 makes of
@@ -464,9 +464,6 @@ __global__ __launch_bounds__(TD * TH * 16) void conv3d_k3_fp16mx_kernel(
 //   consumers: products of k-steps 0..3 + MX groups 0, 1              products of k-steps 4..6 + MX groups 2, 3
 //   producers: DMA weights (c, 1); the values of c + 1 have           DMA weights (c + 1, 0); stage exponent of c + 1; cut and write
 //              arrived: wave maxima -> the spare slots                its stage buffer; request the values of c + 2
-// What-if builds (-DMX_WS_WHATIF=n, WRONG results, measurement only: profiles/r06_conv0_mx_whatif.txt): 1 = producers idle (DMAs and
-// barriers only), 2 = consumers idle, 4 = no global fetch, 5 = no weight DMAs inside the loop, 6 = every block fetches one L2-resident tile,
-// 7 = no epilogue.
 template <int TD, int TH>
 __global__ __launch_bounds__(TD * TH * 16 + 256) void conv3d_k3_fp16mx_ws_kernel(
     const float* __restrict__ xf, long long sN, long long sC, long long sD, long long sH, int Cin, const uint4* __restrict__ wq,
@@ -513,11 +510,7 @@ __global__ __launch_bounds__(TD * TH * 16 + 256) void conv3d_k3_fp16mx_ws_kernel
         const int ptid = tid - 64 * NCW, pwave = wave - NCW;
         unsigned f_off[NV];
         float f_reg[2][NV][8];   // two sets: the values of channel group c + 2 are requested while those of c + 1 are still being cut
-#if defined(MX_WS_WHATIF) && MX_WS_WHATIF == 6
-        const float* xfn = xf;
-#else
         const float* xfn = xf + (size_t)n * sN;
-#endif
         const unsigned long long span = ((unsigned long long)(Cin - 1) * (unsigned long long)sC + (unsigned long long)(D - 1) * sD +
                                          (unsigned long long)(H - 1) * sH + W) * 4ull;
         const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xfn), 0, (int)(unsigned)span, 0x00020000);
@@ -525,20 +518,13 @@ __global__ __launch_bounds__(TD * TH * 16 + 256) void conv3d_k3_fp16mx_ws_kernel
         for (int k = 0; k < NV; ++k) {
             const int slot = ptid + k * NPT;
             const int dz = slot / (HH * HW), r = slot - dz * (HH * HW), hy = r / HW, wx = r - hy * HW;
-#if defined(MX_WS_WHATIF) && MX_WS_WHATIF == 6
-            const int d = dz + 1, h = hy + 1, w = wx + 1;
-#else
             const int d = d0 + dz - 1, h = h0 + hy - 1, w = w0 + wx - 1;
-#endif
             const bool ok = slot < NVOX && d >= 0 && d < D && h >= 0 && h < H && w >= 0 && w < W;
             f_off[k] = ok ? (unsigned)(((long long)d * sD + (long long)h * sH + w) * 4) : 0xfffffff0u;
         }
         const unsigned sC4 = (unsigned)(sC * 4);
         auto fetch_f32 = [&](auto Ptag, int c8) __attribute__((always_inline)) {
             constexpr int P = decltype(Ptag)::value;
-#if defined(MX_WS_WHATIF) && (MX_WS_WHATIF == 1 || MX_WS_WHATIF == 4)
-            return;
-#endif
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int c = c8 * 8 + j;
@@ -563,9 +549,6 @@ __global__ __launch_bounds__(TD * TH * 16 + 256) void conv3d_k3_fp16mx_ws_kernel
         // voxel pairs [kp0, kp1) of the thread's NVP
         auto stage_cut = [&](auto Ptag, int buf, int e1, int kp0, int kp1) __attribute__((always_inline)) {
             constexpr int P = decltype(Ptag)::value;
-#if defined(MX_WS_WHATIF) && MX_WS_WHATIF == 1
-            return;
-#endif
             uint4* hi_s = s_in + (size_t)buf * STAGE;
             uint4* q_s = hi_s + INS;
             const int S = stage_shift(e1);
@@ -608,9 +591,6 @@ __global__ __launch_bounds__(TD * TH * 16 + 256) void conv3d_k3_fp16mx_ws_kernel
         const uint4* wn = wq + (size_t)ob64 * C8 * (2 * kWSlots);
         auto dma_weights = [&](int c8, int s, int buf) __attribute__((always_inline)) {
             const uint4* src0 = wn + ((size_t)c8 * 2 + s) * kWSlots + lane;
-#if defined(MX_WS_WHATIF) && MX_WS_WHATIF == 5
-            if (c8 > 1) return;
-#endif
             for (int i = pwave; i < kMxSlots; i += NPW) {
                 uint4* dstp = s_w + (size_t)buf * kWSlots + i * 64;
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src0 + i * 64),
@@ -704,9 +684,6 @@ __global__ __launch_bounds__(TD * TH * 16 + 256) void conv3d_k3_fp16mx_ws_kernel
     // pipe was 0.39 busy.  The fences keep the compiler from re-ordering the requests behind the products; the accumulation order of
     // every accumulator is unchanged (fp16 steps, then the MX groups): the same bits.
     auto compute = [&](auto sc, int ibuf, int wbuf, int e1) {
-#if defined(MX_WS_WHATIF) && MX_WS_WHATIF == 2
-        return;
-#endif
         constexpr int s = decltype(sc)::value;
         constexpr int nks = s == 0 ? 4 : 3;
         const char* const sbase = reinterpret_cast<const char*>(s_in + (size_t)ibuf * STAGE);
@@ -814,9 +791,6 @@ __global__ __launch_bounds__(TD * TH * 16 + 256) void conv3d_k3_fp16mx_ws_kernel
 
     const size_t plane = (size_t)H * W, vol = (size_t)D * plane;
     const float up = __builtin_bit_cast(float, (unsigned)(127 + s_acc) << 23);
-#if defined(MX_WS_WHATIF) && MX_WS_WHATIF == 7
-    if (acc[0][0][0] != 12345.678f) return;   // (what-if: no epilogue)
-#endif
 #pragma unroll
     for (int cg = 0; cg < CGN; ++cg) {
         const int g = CGN * wave + cg;

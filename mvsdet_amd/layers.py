@@ -264,10 +264,9 @@ FUSED_BN_STATS = os.environ.get("MVSDET_FUSED_BN_STATS", "1") != "0"
 
 def fused_stats_ok(x: Tensor) -> bool:
     """Whether a stride-1 bf16x3 convolution of x may hand its BatchNorm the statistics from its epilogue: FUSED_BN_STATS, more
-    than one output voxel, and the kernel form that has that epilogue (16x16x32 MFMA, not the sub-pair form).  Callers add their
-    own conditions (the neck refuses grids split over the input channels; the cost network does not)."""
+    than one output voxel.  Callers add their own conditions (the neck refuses grids split over the input channels; the cost network does not)."""
     n, _, d, h, w = x.shape
-    return FUSED_BN_STATS and n * d * h * w > 1 and bool(ops.get_option("conv_mfma16")) and ops.get_option("conv_subpairs") != 2
+    return FUSED_BN_STATS and n * d * h * w > 1
 
 
 # ------------------------------------------------------------------------------------------ training BatchNorm and its test hook

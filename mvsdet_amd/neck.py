@@ -81,10 +81,7 @@ def _split_weight(conv: nn.Module, order: int | None = None) -> Tensor:
     w = conv.weight
     if order is None:
         order = 1 if conv.stride[0] == 2 else 0
-    # the layout of an order-0 split follows the library option `conv_mfma16` (16x16x32 or 32x32x16 row order), and the launcher
-    # picks the kernel form from the same option at launch time: the option is part of the key, so weights cut under one setting
-    # are never fed to the other form after `mvsdet_set_option` / an A/B run in one process
-    key = (w.data_ptr(), w._version, w.device, order, ops.get_option("conv_mfma16") if order == 0 and w.is_cuda else 0)
+    key = (w.data_ptr(), w._version, w.device, order)
     cached = conv.__dict__.get("_mvs_wsplit")
     if cached is None or cached[0] != key:
         cached = (key, ops.split_conv_weight(w, order=order))
@@ -92,11 +89,6 @@ def _split_weight(conv: nn.Module, order: int | None = None) -> Tensor:
         conv.__dict__["_mvs_wsplit"] = cached
     await_made(cached[1])
     return cached[1]
-
-
-# the 1x1x1 stride-2 shortcut and the kernel-2 stride-2 transposed layers on our GEMM kernel (csrc/neck_gemm.hip: bf16x3, bias, ReLU
-# and the 2x2x2 interleave in the epilogue) where their shapes allow; False: one rocBLAS fp32 GEMM + ATen glue each (rounds 2-4)
-GEMM_BF16X3 = os.environ.get("MVSDET_NECK_GEMM", "bf16x3") == "bf16x3"
 
 
 def _gemm_weight(conv: nn.Module, bn: nn.BatchNorm3d, split: bool = False):
@@ -161,11 +153,11 @@ class ResModule(nn.Module):
             identity = x
             if self.stride != 1:   # 1x1x1 stride-2 convolution + BN: one GEMM on the sub-sampled volume
                 ds = self.downsample
-                if (GEMM_BF16X3 and self.stride == 2 and ops.gemm_layer_ok(ds.conv.out_channels, ds.conv.in_channels)
+                if (self.stride == 2 and ops.gemm_layer_ok(ds.conv.out_channels, ds.conv.in_channels)
                         and not any(v % 2 for v in x.shape[2:])):
                     wq, bias = _gemm_weight(ds.conv, ds.bn, split=True)      # the sub-sampling is the kernel's gather
                     identity = ops.conv3d_k1_s2_bf16x3(x, wq, bias, ds.conv.out_channels)
-                else:
+                else:   # a shape the GEMM kernel refuses (odd extents, channel counts outside `gemm_layer_ok`): torch.baddbmm
                     xs = x[:, :, ::self.stride, ::self.stride, ::self.stride]
                     n, c, d, h, w = xs.shape
                     wmat, bias = _gemm_weight(ds.conv, ds.bn)
@@ -210,9 +202,10 @@ class _UpBlock(nn.Sequential):
             cout = deconv.out_channels
             # out[:, o, 2i+p, 2j+q, 2k+r] = sum_c x[:, c, i, j, k] * W[c, o, p, q, r]: one (8*Cout x Cin) GEMM with the BatchNorm's
             # shift as its bias; the ReLU writes the interleaved (N, Cout, 2D, 2H, 2W) tensor directly (one pass, no copy)
-            if GEMM_BF16X3 and ops.gemm_layer_ok(8 * cout, cin):
+            if ops.gemm_layer_ok(8 * cout, cin):
                 wq, bias = _gemm_weight(deconv, bn, split=True)      # bias, ReLU and the 2x2x2 interleave in the GEMM's epilogue
                 return _conv_k3(ops.convT3d_k2_s2_bf16x3(x, wq, bias, cout, True), self[3], self[4], True)
+            # channel counts the GEMM kernel refuses (`gemm_layer_ok` false): torch.baddbmm, then the ReLU interleaves
             wmat, bias = _gemm_weight(deconv, bn)
             y = torch.baddbmm(bias, wmat.unsqueeze(0).expand(n, -1, -1), x.reshape(n, cin, -1)).view(n, 2, 2, 2, cout, d, h, w)
             out = torch.empty((n, cout, 2 * d, 2 * h, 2 * w), dtype=x.dtype, device=x.device)

@@ -822,7 +822,8 @@ def split_conv_weight(weight: Tensor, order: int = 0) -> Tensor:
     """Conv3d weight (Cout = 64*m, Cin, 3,3,3) fp32 -> the layout the bf16x3 kernels stream into LDS (include/mvsdet_hip.h):
     [Cout/64][ceil(Cin/8)][14 tap pairs][2 row groups][2 pieces][64 lanes][8 channels] bf16, lane = 32*(half of the pair) +
     MFMA row m (which carries output ROW_CHANNEL[m] of its group of 32); empty halves and the channels beyond Cin are zero.
-    order 0: stride-1 convolution (pair p = taps 2p, 2p+1);
+    order 0: stride-1 convolution, the same bytes as [7 k-steps][4 row groups of 16][2 pieces][64 lanes][8 channels], lane =
+    16*(tap of the k-step) + MFMA row (the 16x16x32 instruction's fragments);
     1: stride-2 convolution (pairs grouped by the parity class of the input voxel); 2: `weight` is a ConvTranspose3d weight
     (Cin, Cout = 64*m, 3,3,3), pairs grouped by the parity class of the output voxel.  On a ROCm device this is ONE small
     kernel (run per call: in-place weight updates are always seen); on the CPU the same layout from torch ops (tests)."""
@@ -830,7 +831,7 @@ def split_conv_weight(weight: Tensor, order: int = 0) -> Tensor:
         cin, cout = weight.shape[:2]
     else:
         cout, cin = weight.shape[:2]
-    if cout % 64 or tuple(weight.shape[2:]) != (3, 3, 3) or order not in (0, 1, 2, 3):
+    if cout % 64 or tuple(weight.shape[2:]) != (3, 3, 3) or order not in (0, 1, 2):
         raise ValueError(f"split_conv_weight: weight {tuple(weight.shape)} (order {order}) has no 64*m output channels / 3x3x3 taps")
     c8 = (cin + 7) // 8
     if weight.is_cuda:
@@ -842,12 +843,12 @@ def split_conv_weight(weight: Tensor, order: int = 0) -> Tensor:
         return out
     w = weight.detach().to(torch.float32)
     w = (w.transpose(0, 1) if order == 2 else w).reshape(cout, cin, 27)
-    taps = torch.tensor(_tap_table(0 if order == 3 else order))
+    taps = torch.tensor(_tap_table(order))
     w = torch.where(taps.view(1, 1, 28) >= 0, w[:, :, taps.clamp(min=0)], torch.zeros(()))   # (Cout, Cin, 28) in pair order
     w = torch.nn.functional.pad(w, (0, 0, 0, c8 * 8 - cin))                                  # channels -> 8*c8
     pieces = torch.stack(split_bf16(w), 0)                                                  # (piece, Cout, C, 28)
-    if order == 3 or (order == 0 and get_option("conv_mfma16")):
-        # the 16x16x32 form: channel = ob*64 + 32q + 8mh + 4b + ml (row group rg = 2q + b, row m = 4mh + ml), tap = 4ks + kg
+    if order == 0:
+        # channel = ob*64 + 32q + 8mh + 4b + ml (row group rg = 2q + b, row m = 4mh + ml), tap = 4ks + kg
         # (piece, ob, q, mh, b, ml, c8, j, ks, kg) -> (ob, c8, ks, q, b, piece, kg, mh, ml, j)
         pieces = pieces.reshape(2, cout // 64, 2, 4, 2, 4, c8, 8, 7, 4).permute(1, 6, 8, 2, 4, 0, 9, 3, 5, 7)
         return pieces.contiguous().reshape(cout // 64, c8, 14, 2, 2, 64, 8)
@@ -1309,8 +1310,7 @@ def conv3d_k3_bf16x3_stats(x, weight_split: Tensor, pivot: Optional[Tensor] = No
     fp32 output and, from the kernel's epilogue, the per-channel partial sums of the outputs and of their squares -- a float64
     tensor (Cout, parts, 2), one entry per block of the grid -- that `bn3d_relu_train(..., parts=)` finishes: the BatchNorm then
     reads the tensor once.  pivot (Cout floats, e.g. the BatchNorm's running mean): the sums are those of (value - pivot_c), which
-    keeps fp32 lane sums from cancelling when a channel's mean is far from zero; pass the same vector to `bn3d_relu_train`.
-    Needs the 16x16x32 form of the kernel (library option conv_mfma16, the default)."""
+    keeps fp32 lane sums from cancelling when a channel's mean is far from zero; pass the same vector to `bn3d_relu_train`."""
     import ctypes
     scl = isinstance(x, SclTensor)
     if scl:
