@@ -218,30 +218,20 @@ int mvsdet_depth_prob_topk_bwd_f32(const float* prob, const float* off, const in
  * x (N,Cin,D,H,W) dense fp32, weight (2,Cin,3,3,3), bias (2) or NULL -> out (N,2,D,H,W): the (cost, offset)
  * logits that mvsdet_depth_prob_topk_f32 consumes.  Forward only (training keeps the framework's convolution).
  * ------------------------------------------------------------------------------------------- */
-/* The stride-1 ConvBnReLU3D layers of the same network, mvs_models/mvsnet.py:76,79,82 (Conv3d k=3, padding 1, no bias;
- * conv0 256->64, conv2 128->128, conv4 256->256):
- *   x (N,Cin,D,H,W) dense fp32 -> out (N,Cout,D,H,W), Cout a multiple of 64, on the fp32 matrix cores (exact fp32 FMA sums).
- *   weight_perm: the (Cout,Cin,3,3,3) weight permuted to [c][kd][kh][kw][o] (Cin rounded up to even, zero padded),
- *   16-byte aligned.  scale / shift (Cout each, or both NULL): out = v*scale[o] + shift[o] -- eval-mode BatchNorm folded;
- *   relu != 0 clamps at 0.  Forward only. */
-int mvsdet_conv3d_k3_mfma_f32(const float* x, const float* weight_perm, const float* scale, const float* shift, float* out,
-                              int N, int Cin, int Cout, int D, int H, int W, int relu, mvsdet_stream_t stream);
-/* The same convolution with a residual added between the affine and the ReLU: out = act(v*scale[o] + shift[o] + residual)
- * -- the tail of the 3-D neck's ResModule, mmdet3d/models/necks/imvoxel_neck.py:219-230 (x = conv1(conv0(x)); x = x +
- * identity; x = relu(x)).  residual: shape of out, or NULL. */
-int mvsdet_conv3d_k3_res_mfma_f32(const float* x, const float* weight_perm, const float* scale, const float* shift,
-                                  const float* residual, float* out, int N, int Cin, int Cout, int D, int H, int W, int relu,
-                                  mvsdet_stream_t stream);
-/* The stride-2 layers (mvsnet.py:78,81: conv1 64->128, conv3 128->256): same arguments, x (N,Cin,D,H,W) ->
- * out (N,Cout,(D-1)/2+1,(H-1)/2+1,(W-1)/2+1). */
-int mvsdet_conv3d_k3_s2_mfma_f32(const float* x, const float* weight_perm, const float* scale, const float* shift,
-                                 float* out, int N, int Cin, int Cout, int D, int H, int W, int relu, mvsdet_stream_t stream);
-/* The general form of the three entry points above, for small volumes (mmdet3d/models/necks/imvoxel_neck.py:183-231, the
- * 3-D neck's residual blocks at one scene, and nerfdet_head.py:96-101, the head's convolutions: 400 / 50 / 8 tiles of
- * 256 voxels): with a workspace of mvsdet_conv3d_k3_mfma_workspace_bytes(...) bytes (0 = the grid fills the chip unsplit)
- * the input-channel loop is split over several blocks per tile, which write raw partial sums; a second kernel adds them in
- * ascending split order and applies affine, residual (stride 1 only, NULL = none) and ReLU.  workspace NULL or too small:
- * unsplit.  stride 1 or 2. */
+/* The ConvBnReLU3D layers of the same network on the fp32 matrix cores (exact fp32 FMA sums): Conv3d k=3, padding 1, no bias,
+ *   stride 1 (mvs_models/mvsnet.py:76,79,82: conv0 256->64, conv2 128->128, conv4 256->256): x (N,Cin,D,H,W) dense fp32 ->
+ *            out (N,Cout,D,H,W);
+ *   stride 2 (mvsnet.py:78,81: conv1 64->128, conv3 128->256): -> out (N,Cout,(D-1)/2+1,(H-1)/2+1,(W-1)/2+1).
+ * Cout a multiple of 64.  weight_perm: the (Cout,Cin,3,3,3) weight permuted to [c][kd][kh][kw][o] (Cin rounded up to even, zero
+ * padded), 16-byte aligned.  scale / shift (Cout each, or both NULL): out = v*scale[o] + shift[o] -- eval-mode BatchNorm folded;
+ * relu != 0 clamps at 0.  residual (shape of out, or NULL; stride 1 only) is added between the affine and the ReLU:
+ * out = act(v*scale[o] + shift[o] + residual) -- the tail of the 3-D neck's ResModule, mmdet3d/models/necks/imvoxel_neck.py:219-230
+ * (x = conv1(conv0(x)); x = x + identity; x = relu(x)).  Forward only.
+ * Small volumes (imvoxel_neck.py:183-231, the 3-D neck's residual blocks at one scene, and nerfdet_head.py:96-101, the head's
+ * convolutions: 400 / 50 / 8 tiles of 256 voxels): with a workspace of mvsdet_conv3d_k3_mfma_workspace_bytes(...) bytes (0 = the
+ * grid fills the chip unsplit) the input-channel loop is split over several blocks per tile, which write raw partial sums; a
+ * second kernel adds them in ascending split order and applies affine, residual and ReLU.  workspace NULL or too small (0
+ * bytes): unsplit. */
 size_t mvsdet_conv3d_k3_mfma_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W, int stride);
 int mvsdet_conv3d_k3_mfma_ws_f32(const float* x, const float* weight_perm, const float* scale, const float* shift,
                                  const float* residual, float* out, void* workspace, size_t workspace_bytes, int N, int Cin,
@@ -257,11 +247,11 @@ int mvsdet_convT3d_k3_s2_mfma_f32(const float* x, const float* weight_perm, cons
 /* Weight gradient of the stride-1 layers (training): dW[o][c][tap] = sum_voxels grad_out[n][o][v] * x[n][c][v + tap - 1]
  * on the fp32 matrix cores.  partial (nsplit,Cout,Cin,27) fp32 receives one partial sum per voxel split
  * (mvsdet_conv3d_k3_dw_partial_bytes); the caller adds them up (deterministic, no atomics).  The input gradient of
- * these layers is mvsdet_conv3d_k3_mfma_f32 on grad_out with the weights transposed and flipped. */
+ * these layers is mvsdet_conv3d_k3_mfma_ws_f32 on grad_out with the weights transposed and flipped. */
 size_t mvsdet_conv3d_k3_dw_partial_bytes(int Cin, int Cout, int nsplit);
 int mvsdet_conv3d_k3_dw_mfma_f32(const float* x, const float* grad_out, float* partial, size_t partial_bytes, int nsplit,
                                  int N, int Cin, int Cout, int D, int H, int W, mvsdet_stream_t stream);
-/* The same sum on the bf16 matrix cores with three-term split operands (the arithmetic of mvsdet_conv3d_k3_bf16x3: both
+/* The same sum on the bf16 matrix cores with three-term split operands (the arithmetic of mvsdet_conv3d_k3_bf16x3_io: both
  * fp32 tensors are cut into bf16 pieces on the way into the LDS, products accumulate in fp32; relative error of a product
  * 2^-16).  Same arguments and partial layout. */
 int mvsdet_conv3d_k3_dw_bf16x3(const float* x, const float* grad_out, float* partial, size_t partial_bytes, int nsplit,
@@ -271,7 +261,7 @@ int mvsdet_conv3d_k3_dw_bf16x3(const float* x, const float* grad_out, float* par
  * x := the layer's grad_out (fine), grad_out := the layer's input (coarse) -- the result is the (Cin,Cout,3,3,3) weight
  * gradient of the transposed layers (mvsnet.py:92-100: conv9, conv11).  Their input gradients are each other's forward:
  * dX of a stride-2 layer = mvsdet_convT3d_k3_s2_mfma_f32 on grad_out with the layer's own (Cout,Cin,3,3,3) weight read
- * as a transposed-convolution weight, dX of a transposed layer = mvsdet_conv3d_k3_s2_mfma_f32 likewise. */
+ * as a transposed-convolution weight, dX of a transposed layer = mvsdet_conv3d_k3_mfma_ws_f32 (stride 2) likewise. */
 int mvsdet_conv3d_k3_s2_dw_mfma_f32(const float* x, const float* grad_out, float* partial, size_t partial_bytes, int nsplit,
                                     int N, int Cin, int Cout, int D, int H, int W, mvsdet_stream_t stream);
 /* The same sum (either orientation) on the bf16 matrix cores with three-term split operands (csrc/costreg_dw_s2_bf16.hip:
@@ -285,16 +275,11 @@ int mvsdet_conv3d_k3_s2_dw_bf16x3(const float* x, const float* grad_out, float* 
  * running statistics updated in place with `momentum` (unbiased variance, as torch.nn.BatchNorm3d; NULL = not tracked),
  * out = [relu](gamma * (x - mean) * invstd + beta) (gamma / beta NULL = 1 / 0); save_mean / save_invstd (C floats) are what
  * the backward needs.  x and out are (N, C, vol) contiguous, vol = D*H*W.  workspace: mvsdet_bn3d_workspace_bytes(C).
+ * A residual tensor (N, C, vol; NULL = none) is added AFTER the activation: out = [relu](bn(x)) + residual, the
+ * `skip + Sequential(ConvTranspose3d, BatchNorm3d, ReLU)(x)` of mvsnet.py:109-111 without a pass of its own.
  * Backward: grad_x, grad_gamma, grad_beta (the last two may be NULL) from x, grad_out and the saved statistics; the ReLU
- * mask is recomputed from x with the forward's arithmetic. */
+ * mask is recomputed from x with the forward's arithmetic (the residual's gradient is grad_out itself). */
 size_t mvsdet_bn3d_workspace_bytes(int C);
-int mvsdet_bn3d_relu_train_fwd_f32(const float* x, const float* gamma, const float* beta, float* running_mean,
-                                   float* running_var, float* out, float* save_mean, float* save_invstd, void* workspace,
-                                   size_t workspace_bytes, int N, int C, long long vol, float momentum, float eps, int relu,
-                                   mvsdet_stream_t stream);
-/* The same with a residual tensor (N, C, vol; NULL = none) added AFTER the activation: out = [relu](bn(x)) + residual, the
- * `skip + Sequential(ConvTranspose3d, BatchNorm3d, ReLU)(x)` of mvsnet.py:109-111 without a pass of its own.  The backward is
- * unchanged (the residual's gradient is grad_out itself). */
 int mvsdet_bn3d_relu_train_fwd_res_f32(const float* x, const float* gamma, const float* beta, const float* residual,
                                        float* running_mean, float* running_var, float* out, float* save_mean, float* save_invstd,
                                        void* workspace, size_t workspace_bytes, int N, int C, long long vol, float momentum, float eps,
@@ -398,7 +383,7 @@ int mvsdet_backproject_weigh_mean_bwd_f32(const float* feat, const int64_t* feat
 /* ---------------------------------------------------------------------------------------------
  * The cost network's 3x3x3 convolutions on the bf16 matrix cores, fp32 operands cut into bf16 pieces ("bf16x3":
  * x*w ~ x_hi*w_hi + x_hi*w_mid + x_mid*w_hi, fp32 accumulation; csrc/costreg_bf16.hip).  Replaces the same layers of
- * mvs_models/mvsnet.py:76-82,104-108 as mvsdet_conv3d_k3_mfma_f32 does, at 3/16 of the fp32 matrix-core time; results
+ * mvs_models/mvsnet.py:76-82,104-108 as mvsdet_conv3d_k3_mfma_ws_f32 does, at 3/16 of the fp32 matrix-core time; results
  * differ from an fp32 convolution by ~2^-16 of the products' size (logits of the network: 2e-6 .. 4e-6, bar 1e-4).
  *
  * "SCL" (split channel-last) activations: xs[piece 2][n][c8 = ceil(C/8)][Dp][Hp][Wp][8] bf16, piece = hi | mid,
@@ -415,12 +400,11 @@ int mvsdet_backproject_weigh_mean_bwd_f32(const float* feat, const int64_t* feat
  * out (N,Cout,D,H,W) fp32 = [relu]([scale *] conv [+ shift] [+ residual]).  Stride 1, Cout % 64 == 0.
  * ------------------------------------------------------------------------------------------- */
 size_t mvsdet_scl_bytes(int N, int C, int D, int H, int W, int* Dp /*HOST, may be NULL*/, int* Hp, int* Wp);
-/* weight (Cout = 64*m, Cin, 3,3,3) fp32 -> weight_split (mvsdet_split_conv_weight_bytes) on the device: one small launch */
-size_t mvsdet_split_conv_weight_bytes(int Cout, int Cin);
-int mvsdet_split_conv_weight(const float* weight, void* weight_split, int Cout, int Cin, mvsdet_stream_t stream);
-/* order 0 = the stride-1 layout above; 1 = for mvsdet_conv3d_k3_s2_bf16x3_f32in (tap pairs grouped by the parity class of the
+/* weight (Cout = 64*m, Cin, 3,3,3) fp32 -> weight_split (mvsdet_split_conv_weight_bytes) on the device: one small launch.
+ * order 0 = the stride-1 layout above; 1 = for mvsdet_conv3d_k3_s2_bf16x3_io (tap pairs grouped by the parity class of the
  * input voxel); 2 = for the transposed convolution: `weight` is a ConvTranspose3d weight (Cin,Cout,3,3,3), pairs grouped by the
  * parity class of the output voxel. */
+size_t mvsdet_split_conv_weight_bytes(int Cout, int Cin);
 int mvsdet_split_conv_weight_ordered(const float* weight, void* weight_split, int Cout, int Cin, int order, mvsdet_stream_t stream);
 /* up to 8 weight tensors in ONE launch (a network's layers: run per forward call, so in-place weight updates are always seen);
  * weights / weight_splits: HOST arrays of `count` device pointers; Cout / Cin / orders: HOST arrays */
@@ -428,44 +412,12 @@ int mvsdet_split_conv_weights_batched(const float* const* weights, void* const* 
                                       const int* orders, int count, mvsdet_stream_t stream);
 int mvsdet_scl_pack_f32(const float* x, const int64_t* x_strides /*HOST[4] = element strides of n, c, d, h; w stride 1; NULL = contiguous*/,
                         void* xs, int N, int C, int D, int H, int W, int zero_border, mvsdet_stream_t stream);
-int mvsdet_conv3d_k3_bf16x3(const void* xs, const void* weight_split, const float* scale, const float* shift,
-                            const float* residual, float* out, int N, int Cin, int Cout, int D, int H, int W, int relu,
-                            mvsdet_stream_t stream);
-/* The same convolution on the fp32 tensor itself (x_strides as for mvsdet_scl_pack_f32): the pieces are cut inside the
- * kernel while the previous channel group is multiplied -- no packing pass, no SCL copy; results identical bit for bit. */
-int mvsdet_conv3d_k3_bf16x3_f32in(const float* x, const int64_t* x_strides /*HOST[4], NULL = contiguous*/, const void* weight_split,
-                                  const float* scale, const float* shift, const float* residual, float* out, int N, int Cin,
-                                  int Cout, int D, int H, int W, int relu, mvsdet_stream_t stream);
-/* Small volumes (the 3-D neck's 20x20x8 and 10x10x4 levels: a handful of tiles): the input channels are split over blocks so
- * that the grid fills the chip, raw partial sums go to `workspace` and a second kernel adds them (ascending split order)
- * before the affine, the residual and the ReLU.  workspace_bytes from mvsdet_conv3d_k3_bf16x3_workspace_bytes (0: the grid
- * is large enough unsplit); NULL or too small a workspace: unsplit, same results up to the order of the fp32 sums. */
+/* Workspace of the stride-1 / stride-2 convolution below (0: the grid is large enough unsplit).  Small volumes (the 3-D neck's
+ * 20x20x8 and 10x10x4 levels: a handful of tiles): the input channels are split over blocks so that the grid fills the chip, raw
+ * partial sums go to `workspace` and a second kernel adds them (ascending split order) before the affine, the residual and the
+ * ReLU.  NULL or too small a workspace: unsplit, same results up to the order of the fp32 sums. */
 size_t mvsdet_conv3d_k3_bf16x3_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W);
-int mvsdet_conv3d_k3_bf16x3_ws(const void* xs, const void* weight_split, const float* scale, const float* shift,
-                               const float* residual, float* out, void* workspace, size_t workspace_bytes, int N, int Cin, int Cout,
-                               int D, int H, int W, int relu, mvsdet_stream_t stream);
-int mvsdet_conv3d_k3_bf16x3_f32in_ws(const float* x, const int64_t* x_strides /*HOST[4], NULL = contiguous*/, const void* weight_split,
-                                     const float* scale, const float* shift, const float* residual, float* out, void* workspace,
-                                     size_t workspace_bytes, int N, int Cin, int Cout, int D, int H, int W, int relu,
-                                     mvsdet_stream_t stream);
-
-/* Conv3d(kernel 3, stride 2, padding 1, no bias) [+ affine] [+ ReLU] (mvsnet.py:77,79) on the bf16 matrix cores, three-term
- * split: x (N,Cin,D,H,W) fp32 -> out (N,Cout,(D-1)/2+1,(H-1)/2+1,(W-1)/2+1); weight_split of order 1. */
-int mvsdet_conv3d_k3_s2_bf16x3_f32in(const float* x, const int64_t* x_strides /*HOST[4], NULL = contiguous*/, const void* weight_split,
-                                     const float* scale, const float* shift, float* out, int N, int Cin, int Cout, int D, int H,
-                                     int W, int relu, mvsdet_stream_t stream);
-/* The stride-2 layer with a workspace for small volumes (as mvsdet_conv3d_k3_bf16x3_f32in_ws). */
 size_t mvsdet_conv3d_k3_s2_bf16x3_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W);
-int mvsdet_conv3d_k3_s2_bf16x3_f32in_ws(const float* x, const int64_t* x_strides /*HOST[4], NULL = contiguous*/, const void* weight_split,
-                                        const float* scale, const float* shift, float* out, void* workspace, size_t workspace_bytes,
-                                        int N, int Cin, int Cout, int D, int H, int W, int relu, mvsdet_stream_t stream);
-
-/* ConvTranspose3d(kernel 3, stride 2, padding 1, output_padding 1, no bias) [+ affine] [+ ReLU] [+ residual, added last]
- * (mvsnet.py:92-100,110-111) on the bf16 matrix cores, three-term split: xs = SCL form of x (N,Cin,D,H,W); weight_split of
- * order 2 from the (Cin,Cout,3,3,3) weight; out / residual (N,Cout,2D,2H,2W) fp32, 8-byte aligned. */
-int mvsdet_convT3d_k3_s2_bf16x3(const void* xs, const void* weight_split, const float* scale, const float* shift,
-                                const float* residual, float* out, int N, int Cin, int Cout, int D, int H, int W, int relu,
-                                mvsdet_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Layer-to-layer forms (round 4): a convolution can leave its result ALREADY CUT into bf16 pieces for the next one -- no fp32
@@ -479,8 +431,10 @@ int mvsdet_convT3d_k3_s2_bf16x3(const void* xs, const void* weight_split, const 
  * buffer: the kernels write interior voxels only); any of out_f32 / out_scl / out_pscl may be NULL.
  * ------------------------------------------------------------------------------------------- */
 size_t mvsdet_pscl_bytes(int N, int C, int D, int H, int W, int* cDp /*HOST, may be NULL*/, int* cHp, int* cWp);
-/* stride 1: input = xs (SCL) or x (fp32 + x_strides), exactly one of them; workspace as mvsdet_conv3d_k3_bf16x3_ws, used
- * only when out_f32 is the sole output */
+/* stride 1: input = xs (SCL) or x (the fp32 tensor itself, x_strides as for mvsdet_scl_pack_f32: the pieces are cut inside the
+ * kernel while the previous channel group is multiplied -- no packing pass, no SCL copy; results identical bit for bit), exactly
+ * one of them; weight_split of order 0; workspace (mvsdet_conv3d_k3_bf16x3_workspace_bytes) used only when out_f32 is the sole
+ * output */
 int mvsdet_conv3d_k3_bf16x3_io(const void* xs, const float* x, const int64_t* x_strides /*HOST[4], NULL = contiguous*/,
                                const void* weight_split, const float* scale, const float* shift, const float* residual,
                                float* out_f32, void* out_scl, void* out_pscl, void* workspace, size_t workspace_bytes, int N,
@@ -520,12 +474,17 @@ int mvsdet_conv3d_k3_bf16x3_stats(const void* xs, const float* x, const int64_t*
 size_t mvsdet_convT3d_k3_s2_bf16x3_stats_parts(int N, int D, int H, int W);
 int mvsdet_convT3d_k3_s2_bf16x3_stats(const void* xs, const void* weight_split, float* out_f32, void* stats, size_t stats_bytes,
                                       const float* pivot, int N, int Cin, int Cout, int D, int H, int W, mvsdet_stream_t stream);
-/* stride 2: input = x (fp32 + x_strides) or x_pscl (the PSCL form of the (N,Cin,D,H,W) input), exactly one of them */
+/* stride 2: Conv3d(kernel 3, stride 2, padding 1, no bias) [+ affine] [+ ReLU] (mvsnet.py:77,79), x (N,Cin,D,H,W) -> out
+ * (N,Cout,(D-1)/2+1,(H-1)/2+1,(W-1)/2+1), Cout % 64 == 0; input = x (fp32 + x_strides) or x_pscl (the PSCL form of the input),
+ * exactly one of them; weight_split of order 1; out_scl = SCL form of the result; workspace
+ * (mvsdet_conv3d_k3_s2_bf16x3_workspace_bytes) used only when out_f32 is the sole output */
 int mvsdet_conv3d_k3_s2_bf16x3_io(const float* x, const int64_t* x_strides /*HOST[4], NULL = contiguous*/, const void* x_pscl,
                                   const void* weight_split, const float* scale, const float* shift, float* out_f32,
                                   void* out_scl, void* workspace, size_t workspace_bytes, int N, int Cin, int Cout, int D, int H,
                                   int W, int relu, mvsdet_stream_t stream);
-/* transposed: out_scl = SCL form of the (N,Cout,2D,2H,2W) result */
+/* transposed: ConvTranspose3d(kernel 3, stride 2, padding 1, output_padding 1, no bias) [+ affine] [+ ReLU] [+ residual, added
+ * last] (mvsnet.py:92-100,110-111): xs = SCL form of x (N,Cin,D,H,W); weight_split of order 2 from the (Cin,Cout,3,3,3) weight,
+ * Cout % 64 == 0; out_f32 / residual (N,Cout,2D,2H,2W) fp32, 8-byte aligned; out_scl = SCL form of the result */
 int mvsdet_convT3d_k3_s2_bf16x3_io(const void* xs, const void* weight_split, const float* scale, const float* shift,
                                    const float* residual, float* out_f32, void* out_scl, int N, int Cin, int Cout, int D, int H,
                                    int W, int relu, mvsdet_stream_t stream);

@@ -47,14 +47,10 @@ SIGNATURES = {
     "mvsdet_sample_depth_prob_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp],
     "mvsdet_ray_depth_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_depth_prob_topk_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp],
-    "mvsdet_conv3d_k3_mfma_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "mvsdet_conv3d_k3_res_mfma_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_convT3d_k3_s2_mfma_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "mvsdet_conv3d_k3_s2_mfma_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_plane_sweep_tile_shape": [_i, _i, _i, _i, _vp, _vp, _vp],
     "mvsdet_conv3d_k3_mfma_workspace_bytes": [_i, _i, _i, _i, _i, _i, _i],
     "mvsdet_bn3d_workspace_bytes": [_i],
-    "mvsdet_bn3d_relu_train_fwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, ctypes.c_longlong, _f, _f, _i, _vp],
     "mvsdet_bn3d_relu_train_fwd_res_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, ctypes.c_longlong, _f, _f, _i, _vp],
     "mvsdet_bn3d_relu_train_fwd_parts_f32": [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, ctypes.c_longlong, _f, _f, _i, _vp],
     "mvsdet_bn3d_relu_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, ctypes.c_longlong, _i, _vp],
@@ -103,21 +99,13 @@ SIGNATURES = {
     "mvsdet_conv3d_k3_s2_bf16x3_io": [_vp, _i64p, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_convT3d_k3_s2_bf16x3_io": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_split_conv_weight_bytes": [_i, _i],
-    "mvsdet_split_conv_weight": [_vp, _vp, _i, _i, _vp],
     "mvsdet_split_conv_weight_ordered": [_vp, _vp, _i, _i, _i, _vp],
     "mvsdet_split_conv_weights_batched": [_vp, _vp, _vp, _vp, _vp, _i, _vp],
-    "mvsdet_convT3d_k3_s2_bf16x3": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "mvsdet_conv3d_k3_s2_bf16x3_f32in": [_vp, _i64p, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_scl_pack_f32": [_vp, _i64p, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_plane_sweep_table_pitched_f32": [_vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_plane_sweep_variance_tabled_pitched_f32": [_vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "mvsdet_conv3d_k3_bf16x3": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "mvsdet_conv3d_k3_bf16x3_f32in": [_vp, _i64p, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_conv3d_k3_bf16x3_workspace_bytes": [_i, _i, _i, _i, _i, _i],
     "mvsdet_conv3d_k3_s2_bf16x3_workspace_bytes": [_i, _i, _i, _i, _i, _i],
-    "mvsdet_conv3d_k3_s2_bf16x3_f32in_ws": [_vp, _i64p, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "mvsdet_conv3d_k3_bf16x3_ws": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "mvsdet_conv3d_k3_bf16x3_f32in_ws": [_vp, _i64p, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_split_conv_weight_mx_bytes": [_i, _i],
     "mvsdet_split_conv_weight_mx": [_vp, _vp, _i, _i, _vp],
     "mvsdet_conv3d_k3_fp16mx_f32in": [_vp, _i64p, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
@@ -202,6 +190,12 @@ def strides4(t) -> ctypes.Array:
     """HOST int64[4] with the element strides of a 4-D tensor."""
     assert t.dim() == 4
     return (ctypes.c_int64 * 4)(*[int(s) for s in t.stride()])
+
+
+def strides4_of5(t) -> ctypes.Array:
+    """HOST int64[4] with the element strides of n, c, d, h of a 5-D tensor (the kernels want w stride 1)."""
+    assert t.dim() == 5
+    return (ctypes.c_int64 * 4)(*t.stride()[:4])
 
 
 def ptr(t):

@@ -1626,10 +1626,6 @@ extern "C" int mvsdet_split_conv_weights_batched(const float* const* weights, vo
     return MVSDET_OK;
 }
 
-extern "C" int mvsdet_split_conv_weight(const float* weight, void* weight_split, int Cout, int Cin, mvsdet_stream_t stream) {
-    return mvsdet_split_conv_weight_ordered(weight, weight_split, Cout, Cin, 0, stream);
-}
-
 namespace mvsdet {
 void launch_splitk_epilogue(const float* partial, int nsplit, size_t total, const float* scale, const float* shift,
                             const float* residual, float* out, int Cout, size_t vol, int relu, hipStream_t st);   // costreg_conv0.hip
@@ -1736,7 +1732,7 @@ static int launch_bf16x3(const char* name, const void* xs, const float* xf, cons
 // Conv3d(Cin -> Cout = 64*m, kernel 3, stride 1, padding 1, no bias) [+ per-channel affine] [+ residual] [+ ReLU] on the
 // bf16 matrix cores, three-term split (file header).  Input: xs = SCL form (mvsdet_scl_pack_f32 or a producing layer's
 // out_scl), or x = the fp32 tensor itself (x_strides = element strides of n, c, d, h; w stride 1; NULL = contiguous), cut
-// inside the kernel -- same results bit for bit.  weight_split: mvsdet_split_conv_weight.  Outputs, any combination (NULL =
+// inside the kernel -- same results bit for bit.  weight_split: mvsdet_split_conv_weight_ordered(order = 0).  Outputs, any combination (NULL =
 // not wanted): out_f32 (N,Cout,D,H,W); out_scl = its SCL form; out_pscl = its parity-split SCL form (their buffers'
 // borders must be zero: the kernel writes interior voxels only).  workspace (mvsdet_conv3d_k3_bf16x3_workspace_bytes; NULL
 // or too small: unsplit) is only used when out_f32 is the sole output.
@@ -1747,20 +1743,6 @@ extern "C" int mvsdet_conv3d_k3_bf16x3_io(const void* xs, const float* x, const 
     MVS_REQUIRE((xs == nullptr) != (x == nullptr), "conv3d_k3_bf16x3_io: exactly one of xs (SCL) and x (fp32)");
     return launch_bf16x3("conv3d_k3_bf16x3_io", xs, x, x_strides, weight_split, scale, shift, residual, out_f32, out_scl, out_pscl, N,
                          Cin, Cout, D, H, W, relu, stream, workspace, workspace_bytes);
-}
-
-extern "C" int mvsdet_conv3d_k3_bf16x3(const void* xs, const void* weight_split, const float* scale, const float* shift,
-                                       const float* residual, float* out, int N, int Cin, int Cout, int D, int H, int W, int relu,
-                                       mvsdet_stream_t stream) {
-    return launch_bf16x3("conv3d_k3_bf16x3", xs, nullptr, nullptr, weight_split, scale, shift, residual, out, nullptr, nullptr, N, Cin,
-                         Cout, D, H, W, relu, stream);
-}
-
-extern "C" int mvsdet_conv3d_k3_bf16x3_f32in(const float* x, const int64_t* x_strides, const void* weight_split,
-                                             const float* scale, const float* shift, const float* residual, float* out, int N,
-                                             int Cin, int Cout, int D, int H, int W, int relu, mvsdet_stream_t stream) {
-    return launch_bf16x3("conv3d_k3_bf16x3_f32in", nullptr, x, x_strides, weight_split, scale, shift, residual, out, nullptr, nullptr,
-                         N, Cin, Cout, D, H, W, relu, stream);
 }
 
 // The convolution in front of a training-mode BatchNorm (module.py:26-37): raw fp32 output + per-channel partial sums of the
@@ -1782,22 +1764,6 @@ extern "C" int mvsdet_conv3d_k3_bf16x3_stats(const void* xs, const float* x, con
     MVS_REQUIRE(stats != nullptr, "conv3d_k3_bf16x3_stats: NULL statistics buffer");
     return launch_bf16x3("conv3d_k3_bf16x3_stats", xs, x, x_strides, weight_split, nullptr, nullptr, nullptr, out_f32, nullptr, nullptr, N,
                          Cin, Cout, D, H, W, 0, stream, nullptr, 0, stats, stats_bytes, pivot);
-}
-
-// The two forms with a workspace (mvsdet_conv3d_k3_bf16x3_workspace_bytes; NULL or too small: unsplit) for small volumes.
-extern "C" int mvsdet_conv3d_k3_bf16x3_ws(const void* xs, const void* weight_split, const float* scale, const float* shift,
-                                          const float* residual, float* out, void* workspace, size_t workspace_bytes, int N, int Cin,
-                                          int Cout, int D, int H, int W, int relu, mvsdet_stream_t stream) {
-    return launch_bf16x3("conv3d_k3_bf16x3", xs, nullptr, nullptr, weight_split, scale, shift, residual, out, nullptr, nullptr, N, Cin,
-                         Cout, D, H, W, relu, stream, workspace, workspace_bytes);
-}
-
-extern "C" int mvsdet_conv3d_k3_bf16x3_f32in_ws(const float* x, const int64_t* x_strides, const void* weight_split,
-                                                const float* scale, const float* shift, const float* residual, float* out,
-                                                void* workspace, size_t workspace_bytes, int N, int Cin, int Cout, int D, int H,
-                                                int W, int relu, mvsdet_stream_t stream) {
-    return launch_bf16x3("conv3d_k3_bf16x3_f32in", nullptr, x, x_strides, weight_split, scale, shift, residual, out, nullptr, nullptr,
-                         N, Cin, Cout, D, H, W, relu, stream, workspace, workspace_bytes);
 }
 
 // Conv3d(Cin -> Cout = 64*m, kernel 3, stride 2, padding 1, no bias) [+ affine] [+ ReLU] of mvsnet.py:77,79 on the bf16 matrix
@@ -1887,24 +1853,9 @@ static int launch_s2_bf16x3(const float* x, const int64_t* x_strides, const void
     return MVSDET_OK;
 }
 
-extern "C" int mvsdet_conv3d_k3_s2_bf16x3_f32in(const float* x, const int64_t* x_strides, const void* weight_split,
-                                                const float* scale, const float* shift, float* out, int N, int Cin, int Cout,
-                                                int Di, int Hi, int Wi, int relu, mvsdet_stream_t stream) {
-    return launch_s2_bf16x3(x, x_strides, nullptr, weight_split, scale, shift, out, nullptr, nullptr, 0, N, Cin, Cout, Di, Hi, Wi, relu,
-                            stream);
-}
-
-// with a workspace (mvsdet_conv3d_k3_s2_bf16x3_workspace_bytes; NULL or too small: unsplit) for small volumes
-extern "C" int mvsdet_conv3d_k3_s2_bf16x3_f32in_ws(const float* x, const int64_t* x_strides, const void* weight_split,
-                                                   const float* scale, const float* shift, float* out, void* workspace,
-                                                   size_t workspace_bytes, int N, int Cin, int Cout, int Di, int Hi, int Wi, int relu,
-                                                   mvsdet_stream_t stream) {
-    return launch_s2_bf16x3(x, x_strides, nullptr, weight_split, scale, shift, out, nullptr, workspace, workspace_bytes, N, Cin, Cout, Di,
-                            Hi, Wi, relu, stream);
-}
-
-// The general form: input = the fp32 tensor x (x_strides) or its parity-split SCL form x_pscl (a producing layer's out_pscl:
-// the class tiles then arrive by LDS-DMA); outputs out_f32 and / or out_scl (SCL form of the (N,Cout,D,H,W) result, zero border).
+// Input = the fp32 tensor x (x_strides) or its parity-split SCL form x_pscl (a producing layer's out_pscl: the class tiles
+// then arrive by LDS-DMA); outputs out_f32 and / or out_scl (SCL form of the (N,Cout,D,H,W) result, zero border); workspace
+// (mvsdet_conv3d_k3_s2_bf16x3_workspace_bytes; NULL or too small: unsplit) for small volumes.
 extern "C" int mvsdet_conv3d_k3_s2_bf16x3_io(const float* x, const int64_t* x_strides, const void* x_pscl, const void* weight_split,
                                              const float* scale, const float* shift, float* out_f32, void* out_scl, void* workspace,
                                              size_t workspace_bytes, int N, int Cin, int Cout, int Di, int Hi, int Wi, int relu,
@@ -1989,12 +1940,6 @@ static int launch_convT(const void* xs, const void* weight_split, const float* s
     return MVSDET_OK;
 }
 
-extern "C" int mvsdet_convT3d_k3_s2_bf16x3(const void* xs, const void* weight_split, const float* scale, const float* shift,
-                                           const float* residual, float* out, int N, int Cin, int Cout, int D, int H, int W,
-                                           int relu, mvsdet_stream_t stream) {
-    return launch_convT(xs, weight_split, scale, shift, residual, out, nullptr, N, Cin, Cout, D, H, W, relu, stream);
-}
-
 // The transposed layer in front of a training-mode BatchNorm (mvsnet.py:92-100 under model.train()): raw fp32 output + per-channel
 // partial sums as mvsdet_conv3d_k3_bf16x3_stats leaves them (sums of value - pivot_c and of its square, one double2 per channel and
 // block; parts = mvsdet_convT3d_k3_s2_bf16x3_stats_parts(N, D, H, W) of the COARSE input extents, 0 = this shape has no such form).
@@ -2018,7 +1963,7 @@ extern "C" int mvsdet_convT3d_k3_s2_bf16x3_io(const void* xs, const void* weight
 
 // ---------------------------------------------------------------------------------------------------------------
 // conv0 on ONE fp16 and TWO block-scaled FP6 (OCP MX e2m3) products per fp32-equivalent product (costreg_mx.h): the fp32
-// (N,Cin,D,H,W) tensor read in place (x_strides as for mvsdet_conv3d_k3_bf16x3_f32in), weights from mvsdet_split_conv_weight_mx,
+// (N,Cin,D,H,W) tensor read in place (x_strides as for mvsdet_conv3d_k3_bf16x3_io), weights from mvsdet_split_conv_weight_mx,
 // outputs as for mvsdet_conv3d_k3_bf16x3_io.  Values within ~2^-15 relative of the exact convolution (bf16x3: 2^-16).
 // ---------------------------------------------------------------------------------------------------------------
 extern "C" size_t mvsdet_split_conv_weight_mx_bytes(int Cout, int Cin) {

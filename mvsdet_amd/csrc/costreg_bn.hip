@@ -352,14 +352,6 @@ extern "C" int mvsdet_bn3d_relu_train_fwd_parts_f32(const float* x, const void* 
     return MVSDET_OK;
 }
 
-extern "C" int mvsdet_bn3d_relu_train_fwd_f32(const float* x, const float* gamma, const float* beta, float* running_mean,
-                                              float* running_var, float* out, float* save_mean, float* save_invstd,
-                                              void* workspace, size_t workspace_bytes, int N, int C, long long vol, float momentum,
-                                              float eps, int relu, mvsdet_stream_t stream) {
-    return mvsdet_bn3d_relu_train_fwd_res_f32(x, gamma, beta, nullptr, running_mean, running_var, out, save_mean, save_invstd, workspace,
-                                              workspace_bytes, N, C, vol, momentum, eps, relu, stream);
-}
-
 extern "C" int mvsdet_bn3d_relu_bwd_f32(const float* x, const float* grad_out, const float* gamma, const float* beta,
                                         const float* save_mean, const float* save_invstd, float* grad_x, float* grad_gamma,
                                         float* grad_beta, void* workspace, size_t workspace_bytes, int N, int C, long long vol,

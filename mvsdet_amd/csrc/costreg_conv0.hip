@@ -268,8 +268,7 @@ extern "C" size_t mvsdet_conv3d_k3_mfma_workspace_bytes(int N, int Cin, int Cout
 
 static int launch_conv_mfma(const char* name, const float* x, const float* weight_perm, const float* scale,
                             const float* shift, float* out, int N, int Cin, int Cout, int Di, int Hi, int Wi, int stride,
-                            int relu, mvsdet_stream_t stream, const float* residual = nullptr, float* workspace = nullptr,
-                            size_t workspace_bytes = 0) {
+                            int relu, mvsdet_stream_t stream, const float* residual, float* workspace, size_t workspace_bytes) {
     MVS_REQUIRE(x && weight_perm && out, "%s: NULL pointer", name);
     MVS_REQUIRE((scale == nullptr) == (shift == nullptr), "%s: scale and shift come together", name);
     MVS_REQUIRE(N > 0 && Cin > 0 && Di > 0 && Hi > 0 && Wi > 0, "%s: bad shape N=%d Cin=%d D=%d H=%d W=%d", name, N, Cin, Di, Hi,
@@ -323,24 +322,6 @@ extern "C" int mvsdet_conv3d_k3_mfma_ws_f32(const float* x, const float* weight_
     MVS_REQUIRE(residual == nullptr || stride == 1, "conv3d_k3_mfma_ws: a residual needs stride 1");
     return launch_conv_mfma("conv3d_k3_mfma_ws", x, weight_perm, scale, shift, out, N, Cin, Cout, D, H, W, stride, relu, stream,
                             residual, (float*)workspace, workspace_bytes);
-}
-
-extern "C" int mvsdet_conv3d_k3_mfma_f32(const float* x, const float* weight_perm, const float* scale, const float* shift,
-                                         float* out, int N, int Cin, int Cout, int D, int H, int W, int relu,
-                                         mvsdet_stream_t stream) {
-    return launch_conv_mfma("conv3d_k3_mfma", x, weight_perm, scale, shift, out, N, Cin, Cout, D, H, W, 1, relu, stream);
-}
-
-extern "C" int mvsdet_conv3d_k3_res_mfma_f32(const float* x, const float* weight_perm, const float* scale, const float* shift,
-                                             const float* residual, float* out, int N, int Cin, int Cout, int D, int H, int W,
-                                             int relu, mvsdet_stream_t stream) {
-    return launch_conv_mfma("conv3d_k3_res_mfma", x, weight_perm, scale, shift, out, N, Cin, Cout, D, H, W, 1, relu, stream, residual);
-}
-
-extern "C" int mvsdet_conv3d_k3_s2_mfma_f32(const float* x, const float* weight_perm, const float* scale,
-                                            const float* shift, float* out, int N, int Cin, int Cout, int D, int H, int W,
-                                            int relu, mvsdet_stream_t stream) {
-    return launch_conv_mfma("conv3d_k3_s2_mfma", x, weight_perm, scale, shift, out, N, Cin, Cout, D, H, W, 2, relu, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -142,7 +142,6 @@ def validate_neighbors(nbr: Tensor, n_src: int) -> None:
         raise ValueError("validate_neighbors: the ids are checked on their host copy")
     t = nbr.to(torch.int64).contiguous()
     m, k = (t.shape[0], t.shape[1]) if t.dim() == 2 else (t.numel(), 1)
-    import ctypes
     p = ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_int64)) if t.numel() else None
     _lib.check(_lib.load().mvsdet_validate_neighbors(p, int(m), int(k), int(n_src)), "validate_neighbors")
 
@@ -812,7 +811,6 @@ ROW_CHANNEL = [8 * ((m >> 4) * 2 + ((m >> 2) & 1)) + (m & 3) + 4 * ((m >> 3) & 1
 
 def get_option(name: str) -> int:
     """A tuning option of the library (mvsdet_get_option)."""
-    import ctypes
     v = ctypes.c_int(0)
     _lib.check(_lib.load().mvsdet_get_option(name.encode(), ctypes.byref(v)), "get_option")
     return int(v.value)
@@ -860,7 +858,6 @@ def split_conv_weight(weight: Tensor, order: int = 0) -> Tensor:
 def split_conv_weights(items) -> list:
     """`split_conv_weight` of several (weight, order) pairs in ONE launch (up to 8 per launch): a network's layers, cut anew on
     every forward call so that an in-place weight update -- also one through `.data`, which bumps no version counter -- is seen."""
-    import ctypes
     items = list(items)
     outs = []
     lib = _lib.load()
@@ -936,7 +933,6 @@ class PsclTensor:
 
 def scl_geometry(N: int, C: int, D: int, H: int, W: int):
     """(bytes, (Dp, Hp, Wp)) of the SCL form of an (N,C,D,H,W) activation."""
-    import ctypes
     dp, hp, wp = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
     nbytes = _lib.load().mvsdet_scl_bytes(N, C, D, H, W, ctypes.byref(dp), ctypes.byref(hp), ctypes.byref(wp))
     return int(nbytes), (dp.value, hp.value, wp.value)
@@ -944,7 +940,6 @@ def scl_geometry(N: int, C: int, D: int, H: int, W: int):
 
 def pscl_geometry(N: int, C: int, D: int, H: int, W: int):
     """(bytes, (cDp, cHp, cWp)) of the parity-split SCL form of an (N,C,D,H,W) activation."""
-    import ctypes
     dp, hp, wp = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
     nbytes = _lib.load().mvsdet_pscl_bytes(N, C, D, H, W, ctypes.byref(dp), ctypes.byref(hp), ctypes.byref(wp))
     return int(nbytes), (dp.value, hp.value, wp.value)
@@ -983,7 +978,6 @@ def scl_pack(x: Tensor, out: Optional[SclTensor] = None) -> SclTensor:
     """(N,C,D,H,W) fp32 -> SclTensor.  x may be any view whose last dimension has stride 1 (a row-pitched cost volume is
     read in place).  `out`: a buffer of the same shape to refill (its border is already zero); without one the result is a
     new buffer from the caching allocator whose border the packing kernel writes itself (no clearing pass, nothing kept)."""
-    import ctypes
     _req(x, "x", dim=5)
     if x.stride(4) != 1 or min(x.stride()) < 0:
         x = x.contiguous()
@@ -1160,6 +1154,34 @@ def _(x, grad_out, transposed, nsplit=0):
     cin, cout = x.shape[1], grad_out.shape[1]
     return x.new_empty((cin, cout, 2, 2, 2) if transposed else (cout, cin, 1, 1, 1))
 
+
+def _conv_input(x, form=()):
+    """A convolution's input: an object of the pre-cut `form` (SclTensor / PsclTensor), or the fp32 (N,Cin,D,H,W) tensor itself --
+    any view with w stride 1 and no negative stride, else its contiguous copy.
+    -> (x, whether it is the pre-cut form, N, Cin, D, H, W, device, HOST strides of n, c, d, h or None for the pre-cut form)."""
+    if isinstance(x, form):
+        return (x, True, *x.shape, x.data.device, None)
+    _req(x, "x", dim=5)
+    if x.stride(4) != 1 or min(x.stride()) < 0:
+        x = x.contiguous()
+    return (x, False, *x.shape, x.device, _lib.strides4_of5(x))
+
+
+def _check_weight_split(name, weight_split, Cin):
+    """Cout of a `split_conv_weight` result cut for Cin input channels."""
+    if weight_split.dtype != torch.bfloat16 or weight_split.dim() != 7 or tuple(weight_split.shape[1:]) != ((Cin + 7) // 8, 14, 2, 2, 64, 8):
+        raise ValueError(f"{name}: weight_split {tuple(weight_split.shape)} does not match Cin={Cin}")
+    return weight_split.shape[0] * 64
+
+
+def _check_pivot(name, pivot, Cout, dev):
+    if pivot is None:
+        return None
+    if pivot.dtype != torch.float32 or pivot.numel() != Cout or pivot.device != dev:
+        raise ValueError(f"{name}: pivot must be {Cout} fp32 values on {dev}")
+    return pivot.detach().contiguous()
+
+
 def _check_affine(name, scale, shift, Cout):
     if (scale is None) != (shift is None):
         raise ValueError(f"{name}: scale and shift come together")
@@ -1206,20 +1228,8 @@ def conv3d_k3_bf16x3(x, weight_split: Tensor, scale: Optional[Tensor], shift: Op
     its SclTensor form (scl_pack, or a producing layer's "scl" output) -- identical results.
     outputs: any of "f32" (the (N,Cout,D,H,W) tensor), "scl" (SclTensor: already cut for a stride-1 / transposed consumer),
     "pscl" (PsclTensor: for a stride-2 consumer); one value or a tuple in that order is returned."""
-    import ctypes
-    scl = isinstance(x, SclTensor)
-    if scl:
-        N, Cin, D, H, W = x.shape
-        dev = x.data.device
-    else:
-        _req(x, "x", dim=5)
-        if x.stride(4) != 1 or min(x.stride()) < 0:
-            x = x.contiguous()
-        N, Cin, D, H, W = x.shape
-        dev = x.device
-    if weight_split.dtype != torch.bfloat16 or weight_split.dim() != 7 or tuple(weight_split.shape[1:]) != ((Cin + 7) // 8, 14, 2, 2, 64, 8):
-        raise ValueError(f"conv3d_k3_bf16x3: weight_split {tuple(weight_split.shape)} does not match Cin={Cin}")
-    Cout = weight_split.shape[0] * 64
+    x, scl, N, Cin, D, H, W, dev, xstr = _conv_input(x, SclTensor)
+    Cout = _check_weight_split("conv3d_k3_bf16x3", weight_split, Cin)
     scale, shift = _check_affine("conv3d_k3_bf16x3", scale, shift, Cout)
     outputs, res = _conv_outputs("conv3d_k3_bf16x3", outputs, (N, Cout, D, H, W), dev, scl_out, pscl_out)
     if residual is not None:
@@ -1232,7 +1242,6 @@ def conv3d_k3_bf16x3(x, weight_split: Tensor, scale: Optional[Tensor], shift: Op
     # small volumes: partial sums of the input-channel splits (0 bytes: the grid fills the chip unsplit); fp32 output only
     wbytes = lib.mvsdet_conv3d_k3_bf16x3_workspace_bytes(N, Cin, Cout, D, H, W) if tuple(outputs) == ("f32",) else 0
     ws = torch.empty((wbytes // 4,), dtype=torch.float32, device=dev) if wbytes else None
-    xstr = None if scl else (ctypes.c_int64 * 4)(*[int(v) for v in x.stride()[:4]])
     with torch.cuda.device(dev):
         _lib.check(lib.mvsdet_conv3d_k3_bf16x3_io(_lib.ptr(x.data) if scl else None, None if scl else _lib.ptr(x), xstr,
                                                   _lib.ptr(weight_split), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual),
@@ -1263,9 +1272,8 @@ def conv3d_k3_fp16mx_ok(x: Tensor) -> bool:
     """Whether `conv3d_k3_fp16mx` runs this view of x on the fp16 + MX kernel: its 32-bit buffer offsets must cover the view
     (include/mvsdet_hip.h mvsdet_conv3d_k3_fp16mx_ok: a batch element's Cin channels below 4 GiB of span, and with Cin % 8 != 0 no
     channels interleaved with the planes)."""
-    import ctypes
     copied = x.stride(4) != 1 or min(x.stride()) < 0          # `conv3d_k3_fp16mx` reads a contiguous copy of such a view
-    xstr = None if copied else (ctypes.c_int64 * 4)(*[int(v) for v in x.stride()[:4]])
+    xstr = None if copied else _lib.strides4_of5(x)
     return bool(_lib.load().mvsdet_conv3d_k3_fp16mx_ok(*[int(v) for v in x.shape], xstr))
 
 
@@ -1279,24 +1287,18 @@ def conv3d_k3_fp16mx(x: Tensor, weight_split_mx: Tensor, scale: Optional[Tensor]
     (2^-14 of the products' block maxima; ~2^-15 of the output's scale on data of uniform magnitude).
     A view the kernel cannot address (`conv3d_k3_fp16mx_ok` False: 4 GiB or more of span per batch element, or interleaved channels) runs on
     `conv3d_k3_bf16x3` instead, cut from `weight` -- the fp32 (Cout, Cin, 3, 3, 3) weight the split was made from, required then."""
-    import ctypes
-    _req(x, "x", dim=5)
-    if x.stride(4) != 1 or min(x.stride()) < 0:
-        x = x.contiguous()
+    x, _, N, Cin, D, H, W, dev, xstr = _conv_input(x)
     if not conv3d_k3_fp16mx_ok(x):
         if weight is None:
             raise ValueError(f"conv3d_k3_fp16mx: the view {tuple(x.shape)} / {tuple(x.stride())} is beyond the fp16 + MX kernel's "
                              "addressing (conv3d_k3_fp16mx_ok): pass weight= for the bf16x3 kernel")
         return conv3d_k3_bf16x3(x, split_conv_weight(weight), scale, shift, relu, outputs=outputs, scl_out=scl_out, pscl_out=pscl_out)
-    N, Cin, D, H, W = x.shape
-    dev = x.device
     if (weight_split_mx.dtype != torch.int32 or weight_split_mx.dim() != 6 or not weight_split_mx.is_contiguous()
             or tuple(weight_split_mx.shape[1:]) != ((Cin + 7) // 8, 2, 32, 64, 4) or weight_split_mx.device != dev):
         raise ValueError(f"conv3d_k3_fp16mx: weight_split_mx {tuple(weight_split_mx.shape)} {weight_split_mx.dtype} does not match Cin={Cin}")
     Cout = weight_split_mx.shape[0] * 64
     scale, shift = _check_affine("conv3d_k3_fp16mx", scale, shift, Cout)
     outputs, res = _conv_outputs("conv3d_k3_fp16mx", outputs, (N, Cout, D, H, W), dev, scl_out, pscl_out)
-    xstr = (ctypes.c_int64 * 4)(*[int(v) for v in x.stride()[:4]])
     with torch.cuda.device(dev):
         _lib.check(_lib.load().mvsdet_conv3d_k3_fp16mx_f32in(_lib.ptr(x), xstr, _lib.ptr(weight_split_mx), _lib.ptr(scale), _lib.ptr(shift),
                                                              _lib.ptr(res.get("f32")), _lib.ptr(res["scl"].data) if "scl" in res else None,
@@ -1311,30 +1313,14 @@ def conv3d_k3_bf16x3_stats(x, weight_split: Tensor, pivot: Optional[Tensor] = No
     tensor (Cout, parts, 2), one entry per block of the grid -- that `bn3d_relu_train(..., parts=)` finishes: the BatchNorm then
     reads the tensor once.  pivot (Cout floats, e.g. the BatchNorm's running mean): the sums are those of (value - pivot_c), which
     keeps fp32 lane sums from cancelling when a channel's mean is far from zero; pass the same vector to `bn3d_relu_train`."""
-    import ctypes
-    scl = isinstance(x, SclTensor)
-    if scl:
-        N, Cin, D, H, W = x.shape
-        dev = x.data.device
-    else:
-        _req(x, "x", dim=5)
-        if x.stride(4) != 1 or min(x.stride()) < 0:
-            x = x.contiguous()
-        N, Cin, D, H, W = x.shape
-        dev = x.device
-    if weight_split.dtype != torch.bfloat16 or weight_split.dim() != 7 or tuple(weight_split.shape[1:]) != ((Cin + 7) // 8, 14, 2, 2, 64, 8):
-        raise ValueError(f"conv3d_k3_bf16x3_stats: weight_split {tuple(weight_split.shape)} does not match Cin={Cin}")
-    Cout = weight_split.shape[0] * 64
+    x, scl, N, Cin, D, H, W, dev, xstr = _conv_input(x, SclTensor)
+    Cout = _check_weight_split("conv3d_k3_bf16x3_stats", weight_split, Cin)
     weight_split = weight_split.contiguous()
-    if pivot is not None:
-        if pivot.dtype != torch.float32 or pivot.numel() != Cout or pivot.device != dev:
-            raise ValueError(f"conv3d_k3_bf16x3_stats: pivot must be {Cout} fp32 values on {dev}")
-        pivot = pivot.detach().contiguous()
+    pivot = _check_pivot("conv3d_k3_bf16x3_stats", pivot, Cout, dev)
     lib = _lib.load()
     parts = int(lib.mvsdet_conv3d_k3_bf16x3_stats_parts(N, D, H, W, 0 if scl else 1))
     out = torch.empty((N, Cout, D, H, W), dtype=torch.float32, device=dev)
     stats = torch.empty((Cout, parts, 2), dtype=torch.float64, device=dev)
-    xstr = None if scl else (ctypes.c_int64 * 4)(*[int(v) for v in x.stride()[:4]])
     with torch.cuda.device(dev):
         _lib.check(lib.mvsdet_conv3d_k3_bf16x3_stats(_lib.ptr(x.data) if scl else None, None if scl else _lib.ptr(x), xstr,
                                                      _lib.ptr(weight_split), _lib.ptr(out), _lib.ptr(stats), stats.numel() * 8,
@@ -1349,25 +1335,12 @@ def conv3d_k3_s2_bf16x3(x, weight_split: Tensor, scale: Optional[Tensor], shift:
     matrix cores, three-term split: x (N,Cin,D,H,W) fp32 (w stride 1) or its PsclTensor form (a producing layer's "pscl"
     output: the class tiles then arrive by LDS-DMA) -> (N,Cout,(D-1)//2+1,(H-1)//2+1,(W-1)//2+1) as "f32" and / or "scl";
     weight_split = split_conv_weight(weight, order=1)."""
-    import ctypes
-    pin = isinstance(x, PsclTensor)
-    if pin:
-        N, Cin, D, H, W = x.shape
-        dev = x.data.device
-    else:
-        _req(x, "x", dim=5)
-        if x.stride(4) != 1 or min(x.stride()) < 0:
-            x = x.contiguous()
-        N, Cin, D, H, W = x.shape
-        dev = x.device
-    if weight_split.dtype != torch.bfloat16 or weight_split.dim() != 7 or tuple(weight_split.shape[1:]) != ((Cin + 7) // 8, 14, 2, 2, 64, 8):
-        raise ValueError(f"conv3d_k3_s2_bf16x3: weight_split {tuple(weight_split.shape)} does not match Cin={Cin}")
-    Cout = weight_split.shape[0] * 64
+    x, pin, N, Cin, D, H, W, dev, xstr = _conv_input(x, PsclTensor)
+    Cout = _check_weight_split("conv3d_k3_s2_bf16x3", weight_split, Cin)
     scale, shift = _check_affine("conv3d_k3_s2_bf16x3", scale, shift, Cout)
     oshape = (N, Cout, (D - 1) // 2 + 1, (H - 1) // 2 + 1, (W - 1) // 2 + 1)
     outputs, res = _conv_outputs("conv3d_k3_s2_bf16x3", outputs, oshape, dev, scl_out, None, allow_pscl=False)
     weight_split = weight_split.contiguous()
-    xstr = None if pin else (ctypes.c_int64 * 4)(*[int(v) for v in x.stride()[:4]])
     lib = _lib.load()
     wbytes = lib.mvsdet_conv3d_k3_s2_bf16x3_workspace_bytes(N, Cin, Cout, D, H, W) if tuple(outputs) == ("f32",) else 0   # small volumes
     ws = torch.empty((wbytes // 4,), dtype=torch.float32, device=dev) if wbytes else None
@@ -1386,9 +1359,7 @@ def convT3d_k3_s2_bf16x3(x, weight_split: Tensor, scale: Optional[Tensor], shift
     its SclTensor) -> (N,Cout,2D,2H,2W) as "f32" and / or "scl"; weight_split = split_conv_weight(weight (Cin,Cout,3,3,3), order=2)."""
     xs = x if isinstance(x, SclTensor) else scl_pack(x)
     N, Cin, D, H, W = xs.shape
-    if weight_split.dtype != torch.bfloat16 or weight_split.dim() != 7 or tuple(weight_split.shape[1:]) != ((Cin + 7) // 8, 14, 2, 2, 64, 8):
-        raise ValueError(f"convT3d_k3_s2_bf16x3: weight_split {tuple(weight_split.shape)} does not match Cin={Cin}")
-    Cout = weight_split.shape[0] * 64
+    Cout = _check_weight_split("convT3d_k3_s2_bf16x3", weight_split, Cin)
     dev = xs.data.device
     scale, shift = _check_affine("convT3d_k3_s2_bf16x3", scale, shift, Cout)
     oshape = (N, Cout, 2 * D, 2 * H, 2 * W)
@@ -1413,18 +1384,13 @@ def convT3d_k3_s2_bf16x3_stats(x, weight_split: Tensor, pivot: Optional[Tensor] 
     `bn3d_relu_train(..., parts=, pivot=)` finishes.  None where the shape has no statistics form (the plain call applies)."""
     xs = x if isinstance(x, SclTensor) else scl_pack(x)
     N, Cin, D, H, W = xs.shape
-    if weight_split.dtype != torch.bfloat16 or weight_split.dim() != 7 or tuple(weight_split.shape[1:]) != ((Cin + 7) // 8, 14, 2, 2, 64, 8):
-        raise ValueError(f"convT3d_k3_s2_bf16x3_stats: weight_split {tuple(weight_split.shape)} does not match Cin={Cin}")
-    Cout = weight_split.shape[0] * 64
+    Cout = _check_weight_split("convT3d_k3_s2_bf16x3_stats", weight_split, Cin)
     dev = xs.data.device
     lib = _lib.load()
     parts = int(lib.mvsdet_convT3d_k3_s2_bf16x3_stats_parts(N, D, H, W))
     if parts == 0:
         return None
-    if pivot is not None:
-        if pivot.dtype != torch.float32 or pivot.numel() != Cout or pivot.device != dev:
-            raise ValueError(f"convT3d_k3_s2_bf16x3_stats: pivot must be {Cout} fp32 values on {dev}")
-        pivot = pivot.detach().contiguous()
+    pivot = _check_pivot("convT3d_k3_s2_bf16x3_stats", pivot, Cout, dev)
     weight_split = weight_split.contiguous()
     out = torch.empty((N, Cout, 2 * D, 2 * H, 2 * W), dtype=torch.float32, device=dev)
     stats = torch.empty((Cout, parts, 2), dtype=torch.float64, device=dev)

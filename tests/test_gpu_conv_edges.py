@@ -177,8 +177,8 @@ def test_conv3d_k3_bf16x3_in_canvases(gpu, N, Cin, Cout, D, H, W):
     wbytes = int(lib.mvsdet_conv3d_k3_bf16x3_workspace_bytes(N, Cin, Cout, D, H, W))
     gw = Guarded(max(wbytes, 4) // 4, gpu)
     gf2, out2 = guarded_f32(shape, gpu)
-    ok(lib.mvsdet_conv3d_k3_bf16x3_f32in_ws(_lib.ptr(xv), strides(xv), _lib.ptr(wq), None, None, None, _lib.ptr(out2), gw.ptr(),
-                                            wbytes, N, Cin, Cout, D, H, W, 0, st))
+    ok(lib.mvsdet_conv3d_k3_bf16x3_io(None, _lib.ptr(xv), strides(xv), _lib.ptr(wq), None, None, None, _lib.ptr(out2), None, None, gw.ptr(),
+                                      wbytes, N, Cin, Cout, D, H, W, 0, st))
     assert gf2.guards_intact() and gw.guards_intact()
     assert torch.equal(out2, ops.conv3d_k3_bf16x3(x.to(gpu), wq, None, None, False))
     b3_check(out2, x, w, padding=1)
@@ -454,8 +454,9 @@ def test_bn3d_train_in_canvases(gpu, N, C, D, H, W, relu):
     wb = int(lib.mvsdet_bn3d_workspace_bytes(C))
 
     def run(xp, gyp, gam, bet, outs):
-        ok(lib.mvsdet_bn3d_relu_train_fwd_f32(_lib.ptr(xp), _lib.ptr(gam), _lib.ptr(bet), outs["rm"], outs["rv"], outs["out"], outs["mean"],
-                                              outs["invstd"], outs["ws"], wb, N, C, vol, ctypes.c_float(mom), ctypes.c_float(eps), relu, st))
+        ok(lib.mvsdet_bn3d_relu_train_fwd_res_f32(_lib.ptr(xp), _lib.ptr(gam), _lib.ptr(bet), None, outs["rm"], outs["rv"], outs["out"],
+                                                  outs["mean"], outs["invstd"], outs["ws"], wb, N, C, vol, ctypes.c_float(mom),
+                                                  ctypes.c_float(eps), relu, st))
         ok(lib.mvsdet_bn3d_relu_bwd_f32(_lib.ptr(xp), _lib.ptr(gyp), _lib.ptr(gam), _lib.ptr(bet), outs["mean"], outs["invstd"], outs["gx"],
                                         outs["gg"], outs["gb"], outs["ws"], wb, N, C, vol, relu, st))
 

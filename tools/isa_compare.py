@@ -22,10 +22,9 @@ FLAGS = "-O3 --offload-arch=gfx950 -std=c++17 -fPIC -ffp-contract=off -fno-math-
 
 # Template parameters that a kernel had in --before and no longer has in --after: (index, the value every kept instantiation had).
 # A --before instantiation with another value there has no counterpart and is listed as removed.
-DROPPED_PARAMS = {
-    "mvsdet::conv3d_k3_bf16x3_kernel": (5, "true"),   # M16: the 16x16x32 form is the only one
-    "mvsdet::store_pattern_kernel": (2, "false"),     # PAIR
-}
+# Filled in for the comparison at hand -- {"mvsdet::store_pattern_kernel": (2, "false")} when its PAIR parameter went, for
+# profiles/retired_forms_isa.txt -- and empty when the kernels of both trees have the same template parameters.
+DROPPED_PARAMS = {}
 
 
 def assemble(src: str, out: str) -> None:
