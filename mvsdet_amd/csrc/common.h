@@ -29,6 +29,8 @@ struct Options {
     int conv_split_min_groups; // ... and a split keeps at least this many groups of 8 input channels (default 2: neck + head 2.39 -> 2.35 ms against 4)
     int bwd_groups;    // backward sweep: wave groups of a block that share its gradient images and split its planes; 0 = by the plane
                        // count (2 from 32 planes), 1 / 2 force
+    int sweep_inside;  // 1 (default) = planes whose taps all lie inside the image and the resident box (kFlagInside) take the slab kernel's
+                       // lean decode; 0 = every plane takes the general decode (A/B runs, tests)
     int conv_mx_th;    // fp16 + MX convolution (costreg_mx.h): 0 (default) = wave-specialised kernel (8 multiplying + 4 staging waves, 4 x 8 x 16 tiles);
                        // 8 / 12 = every wave does everything on 4 x 8 x 16 (8 waves) / 4 x 12 x 16 (12 waves) tiles
 };

@@ -198,10 +198,12 @@ template <int KV, int TW, bool FAST, typename OutT>
 int launch_slab(dim3 grid, hipStream_t stream, size_t lds, const float* packed, const float* ref_packed, const int64_t* nbr,
                 const SweepGeometry& geo, const unsigned short* groups, OutT* var, int n_src, int C, int S, int D, int H, int W,
                 int Wo, int tiles_x, int tiles, int d_per_block, int box_cap, int n_bt, int xcd_parts) {
+    // option "sweep_inside": 0 hides kFlagInside from the slab kernel, whose every plane then takes the general form
+    const unsigned fl_keep = options().sweep_inside != 0 ? ~0u : ~kFlagAllInside;
     auto* k = plane_sweep_variance_kernel<KV, TW, FAST, OutT>;
     if (int rc = allow_dynamic_lds(k, lds)) return rc;
     hipLaunchKernelGGL(k, grid, dim3(kThreads), lds, stream, packed, ref_packed, nbr, geo.header, geo.proj, geo.depth, geo.boxes, geo.flags,
-                       groups, var, n_src, C, S, D, H, W, Wo, tiles_x, tiles, d_per_block, box_cap, n_bt, xcd_parts);
+                       groups, var, n_src, C, S, D, H, W, Wo, tiles_x, tiles, d_per_block, box_cap, n_bt, xcd_parts, fl_keep);
     return MVSDET_OK;
 }
 

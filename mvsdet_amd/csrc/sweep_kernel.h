@@ -101,6 +101,13 @@ __device__ __forceinline__ float4 tap_weights(const SampleTaps& t) {
 }
 
 constexpr unsigned kFlagLive = 1u, kFlagStaged = 2u, kFlagRefill = 4u;  // per-neighbour nibble of a plane's flags word
+// kFlagInside: every one of the tile's 128 pixels exists, every tap of every pixel lies inside the source image and inside the
+// resident box -- all range tests of decode_sample / tap_weights are true and all clamps of the tap offsets are no-ops, so
+// the slab kernel may take its lean decode (taps at o, o+128, o+pitch*128, o+pitch*128+128 of the resident box).  Set by the
+// geometry kernel on staged planes of its corner fast path only; the backward kernel tests kFlagLive, kFlagStaged and kFlagRefill
+// bit by bit and so never looks at this one.
+constexpr unsigned kFlagInside = 8u;
+constexpr unsigned kFlagAllInside = kFlagInside | (kFlagInside << 4) | (kFlagInside << 8) | (kFlagInside << 12);
 constexpr int kBoxPad = 8;                // texels of slack per LDS slot (the bank swizzle may use slot index ntex)
 constexpr int kBoxSkip = INT32_MIN;       // boxes[].w of an empty footprint whose positions are all finite
 constexpr int kBoxEmpty = INT32_MIN + 1;  // empty footprint with a non-finite position: taps run and give NaN
@@ -174,6 +181,7 @@ __global__ __launch_bounds__(kThreads) void plane_sweep_coords_kernel(const floa
     constexpr int kSlowMark = INT32_MIN + 2;   // boxes[].w of a (plane, neighbour) that needs the exact scan
     {
         const int xa = tx0, xb = min(tx0 + TW, W) - 1, ya = ty0, yb = min(ty0 + TH, H) - 1;
+        const bool tile_full = tx0 + TW <= W && ty0 + TH <= H;   // no pixel of the 128 outside the map
         for (int task = tid; task < K * D; task += kThreads) {
             const int j = task / D, d = task - j * D;
             const float* P = proj + ((size_t)n * K + j) * 16;
@@ -197,10 +205,15 @@ __global__ __launch_bounds__(kThreads) void plane_sweep_coords_kernel(const floa
             int4 bx = make_int4(0, 0, 0, kSlowMark);
             if (ok) {
                 // taps of a position ix are floor(ix), floor(ix) + 1; clipped to the image (and clamped before the conversion)
-                const float fx0 = fmaxf(floorf(ixmin - 1e-3f), 0.0f), fx1 = fminf(floorf(ixmax + 1e-3f) + 1.0f, (float)(W - 1));
-                const float fy0 = fmaxf(floorf(iymin - 1e-3f), 0.0f), fy1 = fminf(floorf(iymax + 1e-3f) + 1.0f, (float)(H - 1));
+                const float ux0 = floorf(ixmin - 1e-3f), ux1 = floorf(ixmax + 1e-3f) + 1.0f;   // the footprint before clipping
+                const float uy0 = floorf(iymin - 1e-3f), uy1 = floorf(iymax + 1e-3f) + 1.0f;
+                const float fx0 = fmaxf(ux0, 0.0f), fx1 = fminf(ux1, (float)(W - 1));
+                const float fy0 = fmaxf(uy0, 0.0f), fy1 = fminf(uy1, (float)(H - 1));
                 if (fx1 < fx0 || fy1 < fy0) bx = make_int4(INT32_MAX, INT32_MIN, INT32_MAX, kBoxSkip);   // all taps outside, all finite
                 else bx = make_int4((int)fx0, (int)fx1, (int)fy0, (int)fy1);
+                // nothing was clipped and every pixel exists: a candidate for kFlagInside (kept below only where the plane is staged)
+                if (tile_full && ux0 >= 0.0f && ux1 <= (float)(W - 1) && uy0 >= 0.0f && uy1 <= (float)(H - 1))
+                    atomicOr(s_fl + d, kFlagInside << (4 * j));
             }
             s_pb[(size_t)j * D + d] = bx;
         }
@@ -318,7 +331,11 @@ __global__ __launch_bounds__(kThreads) void plane_sweep_coords_kernel(const floa
     }
     __syncthreads();
     for (int i = tid; i < D * K; i += kThreads) boxes[(size_t)bt * D * K + i] = s_pb[(size_t)(i % K) * D + i / K];
-    for (int d = tid; d < D; d += kThreads) flags[(size_t)bt * D + d] = s_fl[d];
+    // kFlagInside survives only beside kFlagStaged (the run's union box contains the plane's own box by construction)
+    for (int d = tid; d < D; d += kThreads) {
+        const unsigned f = s_fl[d];
+        flags[(size_t)bt * D + d] = f & (~kFlagAllInside | ((f << 2) & kFlagAllInside));
+    }
     // Plane groups: the slab kernel deals a tile's planes to up to gmax blocks, cut in front of a plane that refills a box.
     // The near planes' footprints jump by many texels per plane (12 planes over 0.2-5 m: every one of the first few is a
     // refill -- a block-wide stall of two barriers and a DMA round trip); as the first plane of its own block a refill is
@@ -420,7 +437,7 @@ __global__ __launch_bounds__(kThreads, (TW == 16 && K <= 2) ? 3 : 2) void plane_
     const float* __restrict__ packed, const float* __restrict__ ref_packed, const int64_t* __restrict__ nbr,
     const int4* __restrict__ header, const float* __restrict__ proj, const float* __restrict__ depth, const int4* __restrict__ boxes,
     const unsigned* __restrict__ flags, const unsigned short* __restrict__ groups, OutT* __restrict__ var, int N, int C, int S,
-    int D, int H, int W, int Wo, int tiles_x, int tiles, int d_per_block, int box_cap, int n_bt, int xcd_parts) {
+    int D, int H, int W, int Wo, int tiles_x, int tiles, int d_per_block, int box_cap, int n_bt, int xcd_parts, unsigned fl_keep) {
     constexpr int KK = K > 0 ? K : 1;
     constexpr bool kTapsAhead = TW == 32 && K <= 2;   // all four steps' taps of a neighbour requested ahead of their arithmetic (two blocks per CU: registers to spare)
     constexpr int NP = (K + 1) / 2;             // decode passes: a lane decodes ONE (pixel-step, neighbour) pair per pass
@@ -626,7 +643,7 @@ __global__ __launch_bounds__(kThreads, (TW == 16 && K <= 2) ? 3 : 2) void plane_
     for (int d = d_begin; d < d_end; ++d) {
         // ---- this plane's flags and depth (scalars, requested a plane ahead); every wave follows every plane so that all
         //      of them take the same refill decisions, whichever planes they compute
-        const unsigned fl = __builtin_amdgcn_readfirstlane(fl_next);
+        const unsigned fl = __builtin_amdgcn_readfirstlane(fl_next) & fl_keep;   // fl_keep: option "sweep_inside" 0 masks kFlagInside away
         const float dval = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(dv_next)));
         if (K > 0 && d + 1 < d_end) { fl_next = fl_bt[d + 1]; dv_next = depth_n[d + 1]; }
         bool refill = false;
@@ -741,25 +758,46 @@ __global__ __launch_bounds__(kThreads, (TW == 16 && K <= 2) ? 3 : 2) void plane_
         auto pass = [&](auto pc) {
             constexpr int p = decltype(pc)::value;
             const unsigned fp = fl >> (8 * p);
-            if (!(fp & (kFlagLive | (kFlagLive << 4)))) return;  // nothing of these neighbours is visible: warped values all zero
-            const unsigned fq = qd ? ((2 * p + 1 < K) ? (fp >> 4) : fp) : fp;   // the nibble of the lane's neighbour
-            const bool l_staged = (fq & kFlagStaged) != 0;
-            float2 e = make_float2(kNoSample, kNoSample);  // pixel outside the image: no tap inside, all weights +0
-            if (d_inside) e = sample_at(ray[p], tr0[p], tr1[p], tr2[p], dval, H, W);
-            const SampleTaps tp = decode_sample(e.x, e.y, H, W);
-            const float4 dw = tap_weights(tp);
-            // tap offsets: inside the resident box of the lane's neighbour (slot index with the bank swizzle), or inside
-            // its slab image for a gathered footprint (too large for the box, or empty with non-finite positions)
-            const int lox = l_staged ? lx0[p] : 0, hix = l_staged ? lx1[p] : W - 1;
-            const int loy = l_staged ? ly0[p] : 0, hiy = l_staged ? ly1[p] : H - 1;
-            const int pitch = hix - lox + 1;
-            const int xa = clampi(tp.x0, lox, hix) - lox, xb = clampi(tp.x0 + 1, lox, hix) - lox;
-            const int ya = (clampi(tp.y0, loy, hiy) - loy) * pitch, yb = (clampi(tp.y0 + 1, loy, hiy) - loy) * pitch;
+            constexpr unsigned kLive2 = kFlagLive | (kFlagLive << 4);
+            if (!(fp & kLive2)) return;  // nothing of these neighbours is visible: warped values all zero
             const int sbase = min(2 * p + qd, K - 1) * slot_f4 * 16;
-            const int do0 = l_staged ? fwd_box_slot(ya + xa) * 128 + sbase : (ya + xa) * 128;   // bytes: a texel of a slab is 128
-            const int do1 = l_staged ? fwd_box_slot(ya + xb) * 128 + sbase : (ya + xb) * 128;
-            const int do2 = l_staged ? fwd_box_slot(yb + xa) * 128 + sbase : (yb + xa) * 128;
-            const int do3 = l_staged ? fwd_box_slot(yb + xb) * 128 + sbase : (yb + xb) * 128;
+            // the position of every lane's pixel, inside the map or not (no memory is touched on its account)
+            const float2 e_any = sample_at(ray[p], tr0[p], tr1[p], tr2[p], dval, H, W);
+            int do0, do1, do2, do3;   // byte offsets of the four taps of the lane's decoded pixel
+            float4 dw;                // their weights
+            if ((fp & kLive2 & ~(fp >> 3)) == 0u) {
+                // LEAN (scalar decision): every live neighbour of the pass carries kFlagInside -- all 128 pixels exist, every
+                // range test of decode_sample / tap_weights is true and every clamp below is a no-op, so neither is evaluated.
+                // The lanes of a neighbour that is out of view decode a position nobody fetches.
+                const float x0 = floorf(e_any.x), y0 = floorf(e_any.y);
+                const float wx = e_any.x - x0, wy = e_any.y - y0;
+                const float ex = 1.0f - wx, sy = 1.0f - wy;
+                dw = make_float4(sy * ex, sy * wx, wy * ex, wy * wx);
+                const int row = (lx1[p] - lx0[p] + 1) * 128;   // bytes of one row of the resident box
+                do0 = ((int)y0 - ly0[p]) * row + ((int)x0 - lx0[p]) * 128 + sbase;
+                // The four offsets still travel to the tap steps one by one.  Steps of their own for this form (one offset over the
+                // quads, taps 1-3 from the LDS read's immediate offset and a scalar row pitch) were built and measured: slower,
+                // docs/KERNEL_NOTES.md 4.1.
+                do1 = do0 + 128; do2 = do0 + row; do3 = do2 + 128;
+            } else {
+                const unsigned fq = qd ? ((2 * p + 1 < K) ? (fp >> 4) : fp) : fp;   // the nibble of the lane's neighbour
+                const bool l_staged = (fq & kFlagStaged) != 0;
+                // pixel outside the image: no tap inside, all weights +0
+                const float2 e = d_inside ? e_any : make_float2(kNoSample, kNoSample);
+                const SampleTaps tp = decode_sample(e.x, e.y, H, W);
+                dw = tap_weights(tp);
+                // tap offsets: inside the resident box of the lane's neighbour (slot index with the bank swizzle), or inside
+                // its slab image for a gathered footprint (too large for the box, or empty with non-finite positions)
+                const int lox = l_staged ? lx0[p] : 0, hix = l_staged ? lx1[p] : W - 1;
+                const int loy = l_staged ? ly0[p] : 0, hiy = l_staged ? ly1[p] : H - 1;
+                const int pitch = hix - lox + 1;
+                const int xa = clampi(tp.x0, lox, hix) - lox, xb = clampi(tp.x0 + 1, lox, hix) - lox;
+                const int ya = (clampi(tp.y0, loy, hiy) - loy) * pitch, yb = (clampi(tp.y0 + 1, loy, hiy) - loy) * pitch;
+                do0 = l_staged ? fwd_box_slot(ya + xa) * 128 + sbase : (ya + xa) * 128;   // bytes: a texel of a slab is 128
+                do1 = l_staged ? fwd_box_slot(ya + xb) * 128 + sbase : (ya + xb) * 128;
+                do2 = l_staged ? fwd_box_slot(yb + xa) * 128 + sbase : (yb + xa) * 128;
+                do3 = l_staged ? fwd_box_slot(yb + xb) * 128 + sbase : (yb + xb) * 128;
+            }
             MVS_TAPS_OF(0)
             MVS_TAPS_OF(1)
         };

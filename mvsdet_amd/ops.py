@@ -276,6 +276,34 @@ def _(packed, nbr, table, C, D, H, W):
     return packed.new_empty((nbr.shape[0], C, D, H, W))
 
 
+def sweep_flags(table: Tensor, N: int, K: int, D: int, H: int, W: int) -> Tensor:
+    """The flags words of a geometry table (plane_sweep_table / plane_sweep_table_pitched) as an (N, tiles, D) int64 tensor:
+    one nibble per neighbour -- 1 live, 2 staged, 4 refill, 8 inside (csrc/sweep_kernel.h).  Layout of the table: header int4
+    {magic, tile width | box capacity << 8, W, D << 8 | K}, boxes [N*tiles*D*K] int4, then the flags."""
+    words = table.view(torch.int32)
+    hd = [int(v) for v in words[:4].cpu()]
+    if hd[0] != 0x4d565347 or hd[2] != W or hd[3] != ((D << 8) | K):
+        raise ValueError("sweep_flags: not a geometry table of this (K, D, W)")
+    tw = hd[1] & 0xff
+    tiles = ((W + tw - 1) // tw) * ((H + 128 // tw - 1) // (128 // tw))
+    first = 4 + N * tiles * D * K * 4
+    return (words[first:first + N * tiles * D].to(torch.int64) & 0xffff).view(N, tiles, D)
+
+
+def sweep_inside_count(table: Tensor, N: int, K: int, D: int, H: int, W: int) -> Tuple[int, int]:
+    """(live, lean) of a geometry table: the (tile, plane, pass) triples whose pass has a visible neighbour, and how many of
+    them the geometry kernel flagged for the slab kernel's lean decode -- every visible neighbour of the pass carries
+    kFlagInside.  What the table says, whatever "sweep_inside" is set to."""
+    fl = sweep_flags(table, N, K, D, H, W)
+    live = lean = 0
+    for p in range((K + 1) // 2):
+        fp = (fl >> (8 * p)) & 0xff
+        vis = fp & 0x11                      # kFlagLive of the pass's two neighbours
+        live += int((vis != 0).sum())
+        lean += int(((vis != 0) & ((vis & ~(fp >> 3)) == 0)).sum())
+    return live, lean
+
+
 def sweep_row_pitch(W: int) -> int:
     """Row pitch (elements) of a cost volume whose rows start on 128-byte lines: W rounded up to a multiple of 32."""
     return (int(W) + 31) // 32 * 32
