@@ -39,6 +39,14 @@
 // where the crossing of the two nearly coincident edges is ill-conditioned in float32 and the area can be off by a share of that
 // edge's strip (still finite; a set of vanishing measure that no test here reaches).  The area is clamped to >= 0, the union is never zero for
 // a predicted box (its sizes are sums of two exponentials); a ground-truth box of zero size gives IoU 0.  All of it is finite.
+//
+// Ties of the axis-aligned IoU (iou_loss) and of the z faces of the rotated one follow ATen's autograd, which is what the reference
+// trains with: torch.max / torch.min of two tensors give each operand half the gradient where the two are equal, and
+// clamp(min=0) passes the gradient on where its argument is >= 0, at 0 itself too.  So a predicted corner (a z face) that equals
+// the target's takes half the overlap's gradient, and boxes that touch (rb - lt == 0 on an axis, z ranges end to end) keep the
+// overlap's gradient on that axis: identical boxes do not lose half their pull and touching boxes are still drawn together.  The
+// forward values do not depend on any of this.  Left as it is: the exact tie un0 == 1e-6 of the axis-aligned union with its floor,
+// where the floor's side is taken (no gradient through the union; ATen would halve it).  The BEV conventions above are unchanged.
 #include "common.h"
 #include "head_points.h"
 
@@ -390,31 +398,42 @@ __device__ __forceinline__ PointRef locate(const LossParams& p, int b, int i) {
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// the floor under the focal loss' logarithms as torch's clamp(min=FLT_MIN) sets it: a NaN stays a NaN (fmaxf would drop it, and with
+// gamma = 0, where pow(NaN, 0) = 1, a NaN logit would come out as a finite term)
+__device__ __forceinline__ float log_floor(float v) { return v < 1.17549435e-38f ? 1.17549435e-38f : v; }
+
 // mmcv's sigmoid focal loss of one (point, class) logit: the positive term where the point's label is the class, else the
 // negative one (a label of -1 is background in every class)
 __device__ __forceinline__ float focal_term(float x, bool positive, float gamma, float alpha) {
     const float pr = sigmoidf_(x);
-    if (positive) return -alpha * powf(1.f - pr, gamma) * logf(fmaxf(pr, 1.17549435e-38f));
-    return -(1.f - alpha) * powf(pr, gamma) * logf(fmaxf(1.f - pr, 1.17549435e-38f));
+    if (positive) return -alpha * powf(1.f - pr, gamma) * logf(log_floor(pr));
+    return -(1.f - alpha) * powf(pr, gamma) * logf(log_floor(1.f - pr));
 }
 
 __device__ __forceinline__ float focal_grad(float x, bool positive, float gamma, float alpha) {
     const float pr = sigmoidf_(x);
-    if (positive) return -alpha * powf(1.f - pr, gamma) * (1.f - pr - gamma * pr * logf(fmaxf(pr, 1.17549435e-38f)));
-    return -(1.f - alpha) * powf(pr, gamma) * (gamma * (1.f - pr) * logf(fmaxf(1.f - pr, 1.17549435e-38f)) - pr);
+    if (positive) return -alpha * powf(1.f - pr, gamma) * (1.f - pr - gamma * pr * logf(log_floor(pr)));
+    return -(1.f - alpha) * powf(pr, gamma) * (gamma * (1.f - pr) * logf(log_floor(1.f - pr)) - pr);
 }
 
+// the first operand's share of the gradient of torch.max / torch.min of two tensors: all of it where it is the chosen one, half at
+// an exact tie, none otherwise (file header: ties)
+__device__ __forceinline__ float tie_share(bool chosen, bool tie) { return chosen ? 1.f : tie ? 0.5f : 0.f; }
+
 // _bbox_pred_to_bbox of the point and its six distances d, against the target box t: 1 - IoU of
-// axis_aligned_bbox_overlaps_3d(is_aligned=True) (iou3d_calculator.py:281-323), and where gd != nullptr its gradient by d
+// axis_aligned_bbox_overlaps_3d(is_aligned=True) (iou3d_calculator.py:281-323), and where gd != nullptr its gradient by d.
+// Ties and touches as ATen's autograd routes them (file header); the forward value does not depend on them.
 __device__ __forceinline__ float iou_loss(float px, float py, float pz, const float* d, const float* t, float* gd) {
     const float a[6] = {px - d[0], py - d[2], pz - d[4], px + d[1], py + d[3], pz + d[5]};
     float e[3], wh[3], ga[6];
-    bool lt_a[3], rb_a[3];
+    float lt_a[3], rb_a[3];   // the predicted corner's share of d max / d min: all, half at an exact tie (ATen), none
+    bool open[3];             // clamp(min=0) passes the gradient on where its argument is >= 0, at 0 itself too (ATen)
     for (int q = 0; q < 3; ++q) {
         e[q] = a[q + 3] - a[q];
         const float lt = fmaxf(a[q], t[q]), rb = fminf(a[q + 3], t[q + 3]);
-        lt_a[q] = a[q] > t[q];
-        rb_a[q] = a[q + 3] < t[q + 3];
+        lt_a[q] = tie_share(a[q] > t[q], a[q] == t[q]);
+        rb_a[q] = tie_share(a[q + 3] < t[q + 3], a[q + 3] == t[q + 3]);
+        open[q] = rb - lt >= 0.f;
         wh[q] = fmaxf(rb - lt, 0.f);
     }
     const float area1 = e[0] * e[1] * e[2];
@@ -429,10 +448,10 @@ __device__ __forceinline__ float iou_loss(float px, float py, float pz, const fl
         const float k_ar = un0 > 1e-6f ? -ov / (un * un) : 0.f;
         for (int q = 0; q < 3; ++q) {
             const float oth_e = e[(q + 1) % 3] * e[(q + 2) % 3];
-            const float oth_w = wh[q] > 0.f ? wh[(q + 1) % 3] * wh[(q + 2) % 3] : 0.f;
+            const float oth_w = open[q] ? wh[(q + 1) % 3] * wh[(q + 2) % 3] : 0.f;
             // lower corner a[q]: area1 falls with it; the overlap falls with it where it is the larger lower corner
-            ga[q] = k_ar * -oth_e + (lt_a[q] ? k_ov * -oth_w : 0.f);
-            ga[q + 3] = k_ar * oth_e + (rb_a[q] ? k_ov * oth_w : 0.f);
+            ga[q] = k_ar * -oth_e + lt_a[q] * (k_ov * -oth_w);
+            ga[q + 3] = k_ar * oth_e + rb_a[q] * (k_ov * oth_w);
         }
         // loss = 1 - iou; a = (p - d0, p - d2, p - d4, p + d1, p + d3, p + d5)
         gd[0] = ga[0];
@@ -544,11 +563,11 @@ __device__ __forceinline__ float rotated_iou_loss(float px, float py, float pz, 
     if (gd) {
         // d iou = k_i d inter + k_v d vol_a; d inter = zo d area + area d zo
         const float k_i = ok ? (uni + inter) / (uni * uni) : 0.f, k_v = ok ? -inter / (uni * uni) : 0.f;
-        const float k_a = area0 > 0.f ? k_i * zo : 0.f, k_z = zo0 > 0.f ? k_i * area : 0.f;
+        const float k_a = area0 > 0.f ? k_i * zo : 0.f, k_z = zo0 >= 0.f ? k_i * area : 0.f;
         // by the shift (A's own axes), the sizes and the heading; the centre turns with the heading about the point
         const float gxl = len[0] - len[2], gyl = len[1] - len[3];
         const float g_sx = k_a * gxl, g_sy = k_a * gyl;
-        const float g_zhi = zhi_a < zhi_b ? k_z : 0.f, g_zlo = zlo_a > zlo_b ? -k_z : 0.f;
+        const float g_zhi = tie_share(zhi_a < zhi_b, zhi_a == zhi_b) * k_z, g_zlo = tie_share(zlo_a > zlo_b, zlo_a == zlo_b) * -k_z;
         const float g_sz = g_zhi + g_zlo;
         const float g_w = k_a * (len[0] + len[2]) / 2.f + k_v * al * ah;
         const float g_l = k_a * (len[1] + len[3]) / 2.f + k_v * aw * ah;
@@ -568,10 +587,10 @@ __device__ __forceinline__ float box_loss(const RotatedBox&, float px, float py,
     return rotated_iou_loss(px, py, pz, d, t, gd);
 }
 
-// binary_cross_entropy_with_logits(x, t): (1 - t) x + max(-x, 0) + log(exp(-max(-x, 0)) + exp(-x - max(-x, 0)))
+// binary_cross_entropy_with_logits(x, t) as ATen evaluates it: (1 - t) x - log_sigmoid(x), log_sigmoid(x) = min(x, 0) -
+// log1p(exp(-|x|)).  The log1p keeps the term of a confident logit (log(1 + exp(-30)) = 9.4e-14), which log(1 + ...) rounds to 0
 __device__ __forceinline__ float bce_logits(float x, float t) {
-    const float m = fmaxf(-x, 0.f);
-    return (1.f - t) * x + m + logf(expf(-m) + expf(-x - m));
+    return (1.f - t) * x - (fminf(x, 0.f) - log1pf(expf(-fabsf(x))));
 }
 
 template <class Box>

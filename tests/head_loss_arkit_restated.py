@@ -24,18 +24,22 @@ EPS = R.EPS
 DEGENERATE_MARGIN = 1e-5   # |sin(2 (yaw_p - yaw_t))|, and metres between a corner of one rectangle and an edge of the other
 
 
-def face_distances(p, b):
-    """ImVoxelHead_ARKit._get_face_distances of points (N, 3) to ONE box (7,) = (cx, cy, cz, dx, dy, dz, yaw): (N, 6)."""
-    c, s = torch.cos(-b[6]), torch.sin(-b[6])
+def face_distances(p, b, rot=None):
+    """ImVoxelHead_ARKit._get_face_distances of points (N, 3) to ONE box (7,) = (cx, cy, cz, dx, dy, dz, yaw): (N, 6).
+    rot = (cos(yaw), sin(yaw)) handed in (as the kernels take them) instead of torch.cos / torch.sin of -yaw."""
+    c, s = (torch.cos(-b[6]), torch.sin(-b[6])) if rot is None else (rot[0], -rot[1])
     sx, sy, sz = p[:, 0] - b[0], p[:, 1] - b[1], p[:, 2] - b[2]
     q = torch.stack((b[0] + (sx * c + sy * -s), b[1] + (sx * s + sy * c), b[2] + sz), dim=-1)
     return R.face_distances(q, b)
 
 
-def assign(sizes, origin, boxes, volumes, labels, pts_assign_threshold=27, pts_center_threshold=18, details=False):
+def assign(sizes, origin, boxes, volumes, labels, pts_assign_threshold=27, pts_center_threshold=18, details=False, points=None,
+           rot=None):
     """Targets of one scene: labels (P,) int64 (-1: none), box_index (P,) int64 (-1), center_targets (P,) (-1 where no box),
-    bbox_targets (P, 7) = the chosen box (zero where no box).  boxes (G, 7) = cat(gravity_center, size, yaw)."""
-    pts = [R.level_points(s, l, origin) for l, s in enumerate(sizes)]
+    bbox_targets (P, 7) = the chosen box (zero where no box).  boxes (G, 7) = cat(gravity_center, size, yaw).
+    points: the levels' (N, 3) points handed in instead of level_points; rot (G, 2): every box's (cos, sin) handed in."""
+    pts = [R.level_points(s, l, origin) for l, s in enumerate(sizes)] if points is None else list(points)
+    fd = lambda p, g: face_distances(p, boxes[g], None if rot is None else rot[g])  # noqa: E731
     offs = np.cumsum([0] + [len(p) for p in pts])
     P, L, G = int(offs[-1]), len(sizes), int(boxes.shape[0])
     vmin = torch.full((P,), FLOAT_MAX)
@@ -44,7 +48,7 @@ def assign(sizes, origin, boxes, volumes, labels, pts_assign_threshold=27, pts_c
     info = []
     k = min(pts_center_threshold + 1, P)
     for g in range(G):
-        ins = [face_distances(p, boxes[g]).min(-1)[0] > 0 for p in pts]
+        ins = [fd(p, g).min(-1)[0] > 0 for p in pts]
         n = [int(m.sum()) for m in ins]
         best = L - 1
         for l in range(L):
@@ -52,7 +56,7 @@ def assign(sizes, origin, boxes, volumes, labels, pts_assign_threshold=27, pts_c
                 best = max(l - 1, 0)
                 break
         cand = torch.nonzero(ins[best]).squeeze(1)
-        c = R.centerness_of(face_distances(pts[best][cand], boxes[g]))
+        c = R.centerness_of(fd(pts[best][cand], g))
         t = torch.topk(c, k).values[-1] if len(c) >= k else torch.tensor(-1.0)
         keep = c > t
         idx = cand[keep] + int(offs[best])

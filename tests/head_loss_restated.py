@@ -59,10 +59,11 @@ def centerness_of(d):
 
 
 # ------------------------------------------------------------------------------------------------------------------ assignment
-def assign(sizes, origin, boxes, volumes, labels, pts_assign_threshold=27, pts_center_threshold=18, details=False):
+def assign(sizes, origin, boxes, volumes, labels, pts_assign_threshold=27, pts_center_threshold=18, details=False, points=None):
     """Targets of one scene: labels (P,) int64 (-1: none), box_index (P,) int64 (-1), center_targets (P,), bbox_targets (P, 6) (zero
-    where no box).  boxes (G, 6) = cat(gravity_center, size), volumes (G,), labels (G,).  Equal volumes: the lowest box index."""
-    pts = [level_points(s, l, origin) for l, s in enumerate(sizes)]
+    where no box).  boxes (G, 6) = cat(gravity_center, size), volumes (G,), labels (G,).  Equal volumes: the lowest box index.
+    points: the levels' (N, 3) points handed in (a hand-built geometry) instead of level_points(size, level, origin)."""
+    pts = [level_points(s, l, origin) for l, s in enumerate(sizes)] if points is None else list(points)
     offs = np.cumsum([0] + [len(p) for p in pts])
     P, L, G = int(offs[-1]), len(sizes), int(boxes.shape[0])
     vmin = torch.full((P,), FLOAT_MAX)
@@ -112,6 +113,17 @@ def focal_terms(x, target, gamma=2.0, alpha=0.25):
     term_p = -alpha * (1 - p).pow(gamma) * torch.log(p.clamp(min=tiny))
     term_n = -(1 - alpha) * p.pow(gamma) * torch.log((1 - p).clamp(min=tiny))
     return torch.where(pos, term_p, term_n)
+
+
+def focal_grads(x, target, gamma=2.0, alpha=0.25):
+    """d focal_terms / d x as mmcv's sigmoid focal loss hands it back (its backward is the closed form by p = sigmoid(x), with the
+    same floor under the logarithm, not autograd through the clamp): the same shape and dtype as x."""
+    tiny = torch.finfo(torch.float32).tiny
+    p = torch.sigmoid(x)
+    pos = target.view(-1, 1) == torch.arange(x.shape[1], device=x.device).view(1, -1)
+    grad_p = -alpha * (1 - p).pow(gamma) * (1 - p - gamma * p * torch.log(p.clamp(min=tiny)))
+    grad_n = -(1 - alpha) * p.pow(gamma) * (gamma * (1 - p) * torch.log((1 - p).clamp(min=tiny)) - p)
+    return torch.where(pos, grad_p, grad_n)
 
 
 def aligned_iou(a, b):

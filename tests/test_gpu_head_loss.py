@@ -4,7 +4,9 @@ hold, without a host synchronisation, with the same bits from run to run, and th
 
 Deviations seen on an MI355X against G18 (bars: 1e-4 relative per loss, 1e-4 of a map's largest absolute reference gradient): losses
 at most 3.1e-7 relative (the reference's own float32 result is up to 1.0e-7 from its float64 evaluation), gradients at most 4.3e-7 of
-a map's maximum; targets bit for bit.  test_loss_by_feat_equals_g18 prints them per case (run with -s); the table is in DESIGN.md 4.8."""
+a map's maximum; targets bit for bit.  These are the figures of the kernels as they are now, measured again after iou_loss took
+ATen's tie routing and bce_logits ATen's log_sigmoid form: both maxima are unchanged, one entry moved (case one's centre loss, from
+0 to 7.0e-8).  test_loss_by_feat_equals_g18 prints them per case (run with -s); the table is in DESIGN.md 4.8."""
 import ctypes
 
 import numpy as np

@@ -8,7 +8,9 @@ these tests establish is "the true rotated IoU and its gradient, to the project'
 
 Bars (the project's, from G18): labels, chosen boxes and box targets bit for bit; centerness targets at positive points and each loss
 within 1e-4 relative; gradients within 1e-4 of a map's largest absolute reference gradient.  test_loss_by_feat_equals_g19 prints
-ours against the fixture's float32 and float64 results per case (run with -s); the table is in DESIGN.md 4.9."""
+ours against the fixture's float32 and float64 results per case (run with -s); the table is in DESIGN.md 4.9 (measured again after
+the z faces took ATen's tie routing and bce_logits ATen's log_sigmoid form: losses at most 2.1e-7 relative, gradients at most 7.7e-6
+of a map's maximum, as before)."""
 import math
 
 import numpy as np
@@ -19,6 +21,7 @@ from conftest import load_golden
 
 import head_loss_arkit_restated as A
 import head_loss_restated as R
+from head_loss_planted import plant
 from test_head_loss_arkit_host import CASES, NAMES, check_gradients, check_targets
 
 pytestmark = pytest.mark.gpu
@@ -157,23 +160,9 @@ def _planted(gpu, pred, target, weight=0.7):
     w, l, h = (float(x) for x in pred[3:6])
     d = torch.tensor([w / 2 - sx, w / 2 + sx, l / 2 - sy, l / 2 + sy, h / 2 - sz, h / 2 + sz, float(pred[6])])
     assert bool((d[:6] > 0).all())                              # the head's distances are exponentials
-    bbox = torch.ones(1, 7, 2, 2, 2)
-    bbox.view(7, 8)[:, i] = d
-    bbox = bbox.to(gpu).requires_grad_(True)
-    center = torch.zeros(1, 1, 2, 2, 2, device=gpu, requires_grad=True)
-    cls = torch.zeros(1, 1, 2, 2, 2, device=gpu, requires_grad=True)
-    labels = torch.full((1, 8), -1, dtype=torch.int64)
-    labels[0, i] = 0
-    center_t = torch.full((1, 8), -1.0)
-    center_t[0, i] = weight
-    bbox_t = torch.zeros(1, 8, 7)
-    bbox_t[0, i] = target.float()
-    targets = ops.HeadTargets(labels.to(gpu), labels.to(gpu).int(), center_t.to(gpu), bbox_t.to(gpu), geom)
-    sums = ops.head_loss_rotated([center], [bbox], [cls], torch.ones(1, 1, 2, 2, 2, device=gpu), targets)
-    assert int(sums.n_pos[0]) == 1 and int(sums.n_valid[0]) == 8 and abs(float(sums.weight_sum[0]) - weight) < 1e-6
-    sums.bbox.sum().backward()
-    g = bbox.grad.view(7, 8).cpu()
-    assert bool(torch.isfinite(bbox.grad).all()) and not bool(g[:, [j for j in range(8) if j != i]].any())
+    sums, g = plant(gpu, geom, i, d, target, weight)
+    assert abs(float(sums.weight_sum[0]) - weight) < 1e-6
+    assert bool(torch.isfinite(g).all())
     loss = float(sums.bbox[0].detach())
     assert math.isfinite(loss)
     return 1.0 - loss / weight, loss, g[:, i], pts[i], d
