@@ -10,7 +10,7 @@ csrc/costreg_head.hip (25 ms per scene instead of 59.3 ms at the reference-true 
 (`conv0.conv.weight`, `conv0.bn.*`, ..., `conv9.0.weight`, `conv9.1.*`, `conv11.0.weight`, `conv11.1.*`,
 `prob.weight/bias`), so a reference checkpoint's `cost_regularization.*` entries load with `load_state_dict`
 (tests/test_integration.py compares the outputs with the reference module itself).  D, H, W must be divisible by 4
-(two stride-2 levels), as in the reference.
+(two stride-2 levels), as in the reference.  `layers.route_stats` counts which layer calls leave our kernels.
 
 At the reference-true shape the network is ~2.8 TFLOP per scene against ~1 ms for the whole hot path around it:
 on the GPU it, not the plane sweep, is what a scene costs.
@@ -33,8 +33,8 @@ sys.modules[__name__].__class__ = layers.ForwardedToggles   # costreg.RELU_MASKS
 _ConvK3S1, _ConvK3S2, _ConvT3S2 = ConvK3S1, ConvK3S2, ConvT3S2
 
 
-def _bn_hip_ok(bn: nn.BatchNorm3d, x: torch.Tensor) -> bool:
-    return bn.training and x.is_cuda and x.dtype == torch.float32 and bn.affine
+def _bn_hip_ok(bn: nn.BatchNorm3d, call: layers.Call) -> bool:
+    return bn.training and call.tensor and bn.affine
 
 
 # module -> {device: the stream the second half of its views runs on} (CostRegNet3DGS.view_streams); outside the modules because a
@@ -121,10 +121,9 @@ class CostRegNet3DGS(DerivedTensorsMixin, nn.Module):
         # next waits for that event (mvsdet_amd/scratch.py) -- no dependence on which stream ran the module before
         self._scl = EventPool(64)
 
-    def _chain_ok(self, x) -> bool:
+    def _chain_ok(self, call) -> bool:
         """The eval route on which every layer hands the next one its output already cut into bf16 pieces."""
-        return (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and not self.training
-                and self.matrix_precision == "bf16x3" and self.layer_forms == "scl"
+        return (layers.decide(call) == "eval" and self.matrix_precision == "bf16x3" and self.layer_forms == "scl"
                 and all(c.out_channels % 64 == 0 for c in (self.conv0.conv, self.conv1.conv, self.conv2.conv, self.conv3.conv,
                                                            self.conv4.conv, self.conv9[0], self.conv11[0])))
 
@@ -195,7 +194,9 @@ class CostRegNet3DGS(DerivedTensorsMixin, nn.Module):
     def forward(self, x):
         if any(s % 4 for s in x.shape[2:]):
             raise ValueError(f"CostRegNet3DGS: D, H, W must be divisible by 4, got {tuple(x.shape[2:])}")
-        if self._chain_ok(x):
+        call = layers.call_facts(x, self)   # the same for every layer of this pass
+        if self._chain_ok(call):
+            layers.count_hip(8)   # the layers of `_forward_chain`, once however many pieces of the views run it
             n = x.shape[0]
             k = min(int(self.view_streams), n // 4)
             if k < 2:
@@ -221,25 +222,32 @@ class CostRegNet3DGS(DerivedTensorsMixin, nn.Module):
                 cur.wait_stream(sides[i - 1])
                 parts[i].record_stream(cur)            # allocated under a side stream, read by the concatenation on this one
             return torch.cat(parts, 0)
-        full = self._cbr(self.conv0, x)                           # (N, 64, D, H, W)
+        full = self._cbr(call, self.conv0, x)                     # (N, 64, D, H, W)
         # the stride-2 layers hand their input back as the skip tensor (`ConvK3S2`: its gradient joins the input gradient in
         # that layer's own kernel)
-        h1, full = self._cbr(self.conv1, full, split_skip=True)
-        half = self._cbr(self.conv2, h1)                          # (N, 128, D/2, H/2, W/2)
-        q1, half = self._cbr(self.conv3, half, split_skip=True)
-        quarter = self._cbr(self.conv4, q1)                       # (N, 256, D/4, H/4, W/4)
-        half = self._up(self.conv9, quarter, half)        # half + relu(bn(deconv(quarter)))
-        full = self._up(self.conv11, half, full)
-        return self._head(full)                       # (N, 2, D, H, W)
+        h1, full = self._cbr(call, self.conv1, full, split_skip=True)
+        half = self._cbr(call, self.conv2, h1)                    # (N, 128, D/2, H/2, W/2)
+        q1, half = self._cbr(call, self.conv3, half, split_skip=True)
+        quarter = self._cbr(call, self.conv4, q1)                 # (N, 256, D/4, H/4, W/4)
+        half = self._up(call, self.conv9, quarter, half)          # half + relu(bn(deconv(quarter)))
+        full = self._up(call, self.conv11, half, full)
+        return self._head(call, full)                             # (N, 2, D, H, W)
 
-    def _cbr(self, layer, x, split_skip: bool = False):
+    def _route(self, call, conv) -> str:
+        """`layers.decide` with a layer's own rule; the autograd kernels (`hip_backward`) also need input channels in 64s."""
+        if conv is self.prob:   # no BatchNorm behind it: any mode, any channel count
+            return layers.decide(call, other=self.hip_backward, any_mode=True)
+        fits = conv.out_channels % 64 == 0 and conv.stride in ((1, 1, 1), (2, 2, 2))   # (the transposed layers: stride 2)
+        return layers.decide(call, fits, self.hip_backward, conv.in_channels % 64 == 0)
+
+    def _cbr(self, call, layer, x, split_skip: bool = False):
         """A ConvBnReLU3D layer (mvsnet.py:76-82: conv0..conv4, stride 1 or 2).  Without autograd and in eval mode
         (BatchNorm = per-channel affine) the fp32-MFMA kernel of csrc/costreg_conv0.hip runs conv + BN + ReLU in one
         pass -- conv0 at the reference-true shape: 15.7 ms (130 TFLOP/s) instead of 33.6 + 0.5 ms for MIOpen, the same
         fp32 FMA sums."""
         conv, bn = layer.conv, layer.bn
-        if (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and not self.training
-                and conv.out_channels % 64 == 0 and conv.stride in ((1, 1, 1), (2, 2, 2))):
+        route = layers.record(self, self._route(call, conv), layer)
+        if route == "eval":
             scale, shift = bn_affine(bn)
             if self.matrix_precision == "bf16x3":
                 # the bf16 matrix cores with three-term split operands (csrc/costreg_bf16.hip): conv0 4.8 ms instead of 15.2
@@ -255,15 +263,14 @@ class CostRegNet3DGS(DerivedTensorsMixin, nn.Module):
             wperm = ops.permute_conv_weight(conv.weight)   # a few MB at most, negligible next to the convolution
             y = ops.conv3d_k3_mfma(x, wperm, scale, shift, True, conv.stride[0])
             return (y, x) if split_skip else y
-        if (self.hip_backward and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled()
-                and conv.stride in ((1, 1, 1), (2, 2, 2)) and conv.out_channels % 64 == 0 and conv.in_channels % 64 == 0):
+        if route == "grad":
             # autograd: convolution forward / backward on our kernels; BatchNorm + ReLU too when it uses batch statistics
             skip = x
             parts = pivot = None
             if conv.stride == (1, 1, 1):
                 # the BatchNorm's statistics from the convolution's epilogue (16x16x32 form of the kernel: the default), also on
                 # grids split over the input channels (the neck refuses those)
-                if self.matrix_precision == "bf16x3" and _bn_hip_ok(bn, x) and layers.fused_stats_ok(x):
+                if self.matrix_precision == "bf16x3" and _bn_hip_ok(bn, call) and layers.fused_stats_ok(x):
                     # sums around the running mean (read by the convolution and by the BatchNorm's finishing kernel before the
                     # in-place update of the buffer that follows them on the same stream)
                     pivot = bn.running_mean.detach() if bn.running_mean is not None else None
@@ -274,16 +281,16 @@ class CostRegNet3DGS(DerivedTensorsMixin, nn.Module):
                 y, skip = ConvK3S2.apply(x, conv.weight, self.matrix_precision == "bf16x3", True)
             else:
                 y = ConvK3S2.apply(x, conv.weight, self.matrix_precision == "bf16x3")
-            y = bn_train(bn, y, bn, parts, pivot) if _bn_hip_ok(bn, y) else torch.relu_(bn(y))
+            y = bn_train(bn, y, bn, parts, pivot) if _bn_hip_ok(bn, call) else layers.bn_relu_framework(self, layer, bn, y)
             return (y, skip) if split_skip else y
         return (layer(x), x) if split_skip else layer(x)
 
-    def _up(self, seq, x, skip):
+    def _up(self, call, seq, x, skip):
         """mvsnet.py:110-111: skip + Sequential(ConvTranspose3d, BatchNorm3d, ReLU)(x); one fp32-MFMA kernel per output
         parity in (d, h) (csrc/costreg_conv0.hip) without autograd in eval mode."""
         deconv, bn = seq[0], seq[1]
-        if (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and not self.training
-                and deconv.out_channels % 64 == 0):
+        route = layers.record(self, self._route(call, deconv), seq)
+        if route == "eval":
             scale, shift = bn_affine(bn)
             if self.matrix_precision == "bf16x3":
                 # 8 output parity classes = 8 small stride-1 convolutions over the coarse input (csrc/costreg_bf16.hip)
@@ -292,9 +299,8 @@ class CostRegNet3DGS(DerivedTensorsMixin, nn.Module):
                 return ops.convT3d_k3_s2_bf16x3(xs, ops.split_conv_weight(deconv.weight, 2), scale, shift, skip, True)
             wperm = ops.permute_convT_weight(deconv.weight)
             return ops.convT3d_k3_s2_mfma(x, wperm, scale, shift, skip, True)
-        if (self.hip_backward and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled()
-                and deconv.out_channels % 64 == 0 and deconv.in_channels % 64 == 0):
-            if layers.FUSED_BN_STATS and self.matrix_precision == "bf16x3" and _bn_hip_ok(bn, x):
+        if route == "grad":
+            if layers.FUSED_BN_STATS and self.matrix_precision == "bf16x3" and _bn_hip_ok(bn, call):
                 # the BatchNorm's statistics from the transposed kernel's epilogue, around the running mean
                 pivot = bn.running_mean.detach() if bn.running_mean is not None else None
                 y, parts = ConvT3S2.apply(x, deconv.weight, True, True, pivot)
@@ -302,17 +308,18 @@ class CostRegNet3DGS(DerivedTensorsMixin, nn.Module):
                     return bn_train(bn, y, bn, parts, pivot, skip=skip)
                 return bn_train(bn, y, bn, skip=skip)
             y = ConvT3S2.apply(x, deconv.weight, self.matrix_precision == "bf16x3")
-            if _bn_hip_ok(bn, y):
+            if _bn_hip_ok(bn, call):
                 return bn_train(bn, y, bn, skip=skip)   # the skip addition in the BatchNorm's second pass
-            return skip + torch.relu_(bn(y))
+            return skip + layers.bn_relu_framework(self, seq, bn, y)
         return skip + seq(x)
 
-    def _head(self, full):
+    def _head(self, call, full):
         """mvsnet.py:112.  Two output channels make a poor GEMM (MIOpen: 8.2 ms at the reference-true shape); without
         autograd the streaming HIP kernel of csrc/costreg_head.hip does it in a fraction of that."""
-        if full.is_cuda and full.dtype == torch.float32 and not torch.is_grad_enabled():
-                return ops.conv3d_k3_cout2(full, self.prob.weight.detach(), self.prob.bias.detach())
-        if self.hip_backward and full.is_cuda and full.dtype == torch.float32 and torch.is_grad_enabled():
+        route = layers.record(self, self._route(call, self.prob), self.prob)
+        if route == "eval":
+            return ops.conv3d_k3_cout2(full, self.prob.weight.detach(), self.prob.bias.detach())
+        if route == "grad":
             return _HeadConv.apply(full, self.prob.weight, self.prob.bias, self.matrix_precision == "bf16x3")
         return self.prob(full)
 

@@ -34,7 +34,7 @@ from typing import List, Sequence, Tuple
 import torch
 from torch import Tensor, nn
 
-from . import ops
+from . import layers, ops
 from .layers import ConvK3S1, DerivedTensorsMixin, autograd_route_from_env, await_made, check_route, fp32_under_autocast, mark_made
 
 
@@ -97,8 +97,8 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
         await_made(self._fused[1])   # computed on another stream a moment ago: this stream waits for it (layers._PENDING)
         return self._fused[1]
 
-    def _hip_autograd(self, x: Tensor) -> bool:
-        return check_route(self) == "hip" and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled()
+    def _route(self, x) -> str:   # the autograd kernels: keyed on autograd, whatever `training` is (`layers.decide`)
+        return layers.decide(layers.call_facts(x, self), other=check_route(self) == "hip")
 
     def _fused_weight_autograd(self) -> Tensor:
         """[center | reg | cls | zeros] as ONE (64 m, C, 3, 3, 3) weight in the autograd graph (made per call: the weights change
@@ -112,6 +112,7 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
     def _forward_single_hip(self, x: Tensor, scale: Scale, w: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
         if x.shape[1] % 64:
             raise ValueError(f"NerfDetHeadConvs (autograd_route='hip'): {x.shape[1]} input channels, a multiple of 64 needed")
+        layers.count_hip()
         y = ConvK3S1.apply(x, w, True)
         r, c = self.n_reg_outs, self.n_classes
         center = y[:, :1]
@@ -122,8 +123,9 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
             reg = torch.exp(scale(y[:, 1:1 + r]))
         return center, reg, cls
 
-    def _forward_single(self, x: Tensor, scale: Scale) -> Tuple[Tensor, Tensor, Tensor]:
-        if x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and not self.training:
+    def _forward_single(self, x: Tensor, scale: Scale, route: str) -> Tuple[Tensor, Tensor, Tensor]:
+        if route == "eval":
+            layers.count_hip()
             if HEAD_BF16X3:
                 y = ops.conv3d_k3_bf16x3(x, self._fused_weight(), None, None, False)
             else:
@@ -136,6 +138,7 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
             else:
                 reg = torch.exp(y[:, 1:1 + r] * scale.scale.detach())
             return center, reg, cls
+        layers.record(self, route, "conv_center", "conv_reg", "conv_cls")
         if self.arkit_head:
             reg_final = self.conv_reg(x)
             return self.conv_center(x), torch.cat((torch.exp(scale(reg_final[:, :6])), reg_final[:, 6:]), dim=1), self.conv_cls(x)
@@ -144,12 +147,10 @@ class NerfDetHeadConvs(DerivedTensorsMixin, nn.Module):
     @fp32_under_autocast
     def forward(self, x: Sequence[Tensor]) -> Tuple[List[Tensor], List[Tensor], List[Tensor]]:
         """mmdet's multi_apply(self._forward_single, x, self.scales): a tuple of three per-level lists."""
-        if any(self._hip_autograd(xi) for xi in x):
-            w = self._fused_weight_autograd()
-            res = [self._forward_single_hip(xi, s, w) if self._hip_autograd(xi) else self._forward_single(xi, s)
-                   for xi, s in zip(x, self.scales)]
-        else:
-            res = [self._forward_single(xi, s) for xi, s in zip(x, self.scales)]
+        routes = [self._route(xi) for xi in x]
+        w = self._fused_weight_autograd() if "grad" in routes else None
+        res = [self._forward_single_hip(xi, s, w) if r == "grad" else self._forward_single(xi, s, r)
+               for xi, s, r in zip(x, self.scales, routes)]
         return tuple(map(list, zip(*res)))
 
     def predict_by_feat(self, center_preds: List[List[Tensor]], bbox_preds: List[List[Tensor]], cls_preds: List[List[Tensor]],

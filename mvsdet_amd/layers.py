@@ -1,13 +1,15 @@
 """Layer code shared by the cost network (costreg.py), the 3-D neck (neck.py) and the detection head (head.py): the caches of
-tensors derived from parameters and their stream ordering, the `--amp` wrapper, the training route option, the 3x3x3 autograd
-functions on our convolution kernels, and training-mode BatchNorm with its ReLU-decision test hook.  None of those three modules
-imports another; each imports from here.
+tensors derived from parameters and their stream ordering, the `--amp` wrapper, the training route option, the facts that decide
+whether a layer call runs on our kernels or on the framework's with the counters of both outcomes (`route_stats`,
+`framework_calls`), the 3x3x3 autograd functions on our convolution kernels, and training-mode BatchNorm with its ReLU-decision test
+hook.  None of those three modules imports another; each imports from here.
 
 Tests toggle `RELU_MASKS` and `FUSED_BN_STATS` on this module: read them through the module object at call time.  `costreg` and
 `neck` forward their attributes of those names here (`ForwardedToggles`).
 """
 from __future__ import annotations
 
+import collections
 import functools
 import os
 import types
@@ -133,6 +135,96 @@ def check_route(module: nn.Module) -> str:
     if route not in AUTOGRAD_ROUTES:
         raise ValueError(f"{type(module).__name__}.autograd_route must be one of {AUTOGRAD_ROUTES}, got {route!r}")
     return route
+
+
+# ------------------------------------------------------------------------------------------ which route a layer call takes
+# A layer of costreg / neck / head runs on this library's eval kernels, on its second family of kernels (autograd / training), or
+# on the framework's own layers (ATen / MIOpen).  The facts of a call that decide between them are the same for every layer of one
+# forward pass: a module's forward reads them once (`call_facts`) and hands them to its layers; each layer adds only its own rule
+# (channel multiples, stride, `ops.gemm_layer_ok`, the module's options) and `decide` is the one table both the route and, for the
+# framework, the reason come from.  They read only x.is_cuda, x.dtype, module.training and torch.is_grad_enabled().
+def hip_tensor(x) -> bool:
+    """A tensor our kernels take: on a ROCm device, float32."""
+    return x.is_cuda and x.dtype == torch.float32
+
+
+Call = collections.namedtuple("Call", "tensor grad training")   # hip_tensor(x), autograd is on, the module's mode
+
+
+def call_facts(x, module: nn.Module) -> Call:
+    return Call(hip_tensor(x), torch.is_grad_enabled(), module.training)
+
+
+def decide(call: Call, fits: bool = True, other=None, other_fits: bool = True, keyed: str = "grad", any_mode: bool = False) -> str:
+    """The route of a layer call: "eval" = our eval kernels, "grad" = our other kernels, else why the framework runs it.
+    eval kernels: a `hip_tensor`, autograd off, the module not training, and `fits` (the layer's shape rule).  `any_mode`: `training`
+        is not looked at (the cost network's head convolution, which has no BatchNorm behind it).
+    other kernels: `other` is None where the site has none, else the option that enables them (`hip_backward`, `autograd_route ==
+        "hip"`).  They run when the fact named by `keyed` is set, WHATEVER THE OTHER FACT IS, and `fits and other_fits`.  The modules
+        differ here, on purpose: the cost network and the head key on "grad" (autograd on, in .train() or .eval(): a cost network in
+        .train() under no_grad has no kernel route at all, and in .eval() under autograd its convolutions run here while its
+        BatchNorms, on running statistics, go to the framework: `bn_relu_framework`); the neck keys on "training" (the neck's
+        training kernels run with autograd on or off; a block of it called in training mode is on the framework by that option).
+    reasons, the first that applies: "tensor" (not a `hip_tensor`), "option" (the kernels for this call exist and the module's option
+        chose the framework), "mode" (an autograd / training combination the site has no kernels for), "shape" (the layer's own rule:
+        a channel multiple, a stride, `ops.gemm_layer_ok`, odd extents, a BatchNorm without affine parameters)."""
+    if not call.tensor:
+        return "tensor"
+    if other is not None and (call.grad if keyed == "grad" else call.training):
+        return "option" if not other else "grad" if fits and other_fits else "shape"
+    if call.grad or (call.training and not any_mode):
+        return "mode"
+    return "eval" if fits else "shape"
+
+
+# Which way each layer call went.  The unit is one layer of the reference module -- a convolution with the BatchNorm and ReLU behind
+# it, a shortcut, the head's fused convolution of a level -- counted once per call, whichever of our kernels run it; a BatchNorm that
+# goes to the framework beside a convolution of ours is one "framework" call of its own.  Host-side dict increments: no tensor
+# operation, no synchronisation, no warning (a CPU run takes the framework everywhere, legitimately).  Under a captured graph they
+# count at capture time only, not per replay.  A choice between two kernels of ours (bf16x3 / fp32 MFMA / fp16 + MX, packed or plain
+# input) is not a route and is not counted.
+route_stats = {"hip": 0, "framework": 0}   # layer calls on a kernel of this library | on the framework's layer, GEMM or BatchNorm
+framework_calls: dict = {}                 # (site, reason) -> count; site = "<owner's class>.<layer attribute>"
+
+
+def reset_route_stats() -> None:
+    route_stats.update(hip=0, framework=0)
+    framework_calls.clear()
+
+
+def count_hip(n: int = 1) -> None:
+    route_stats["hip"] += n
+
+
+def count_framework(owner: nn.Module, reason: str, *path) -> None:
+    """One layer call handed to the framework.  path: the sub-module of `owner` that ran, or its attribute name (then, for a part of
+    a layer, the sub-module of that one): the site is the owner's class and those names, "CostRegNet3DGS.conv0", "_UpBlock.3",
+    "CostRegNet3DGS.conv9.1"."""
+    names, parent = [type(owner).__name__], owner
+    for child in path:
+        names.append(child if isinstance(child, str) else next(k for k, m in parent._modules.items() if m is child))
+        parent = child
+    key = (".".join(names), reason)
+    route_stats["framework"] += 1
+    framework_calls[key] = framework_calls.get(key, 0) + 1
+
+
+def record(owner: nn.Module, route: str, *sublayers) -> str:
+    """Count the call of each of `owner`'s layers `sublayers` (sub-modules or their attribute names) by the route their site decided
+    (`decide`) and hand the route back."""
+    if route == "eval" or route == "grad":
+        route_stats["hip"] += len(sublayers)
+    else:
+        for layer in sublayers:
+            count_framework(owner, route, layer)
+    return route
+
+
+def bn_relu_framework(owner: nn.Module, layer: nn.Module, bn: nn.BatchNorm3d, y: Tensor) -> Tensor:
+    """relu(bn(y)) on the framework's BatchNorm behind an autograd convolution of ours (`layer`'s), counted: it runs on running
+    statistics ("mode") or has no affine parameters ("shape"), and the training kernels take neither."""
+    count_framework(owner, "shape" if bn.training else "mode", layer, bn)
+    return torch.relu_(bn(y))
 
 
 # ------------------------------------------------------------------------------------------ 3x3x3 convolutions under autograd

@@ -11,7 +11,8 @@ fp32-MFMA kernels of csrc/costreg_conv0.hip) with eval-mode BatchNorm, ReLU and 
 epilogue; the small levels split their input channels until ~768 blocks run.  The 1x1x1 stride-2 shortcut and the
 kernel-2 stride-2 transposed convolutions are one GEMM each on csrc/neck_gemm.hip (a kernel-2 stride-2 transposed
 convolution is 8 independent single-tap classes; bias, ReLU and the 2x2x2 interleave in the epilogue; no rocBLAS call).
-Training, CPU tensors and other shapes take the framework's layers -- unless `autograd_route` is "hip" (below).
+Training, CPU tensors and other shapes take the framework's layers -- unless `autograd_route` is "hip" (below) --, each such
+layer call counted with its reason in `layers.framework_calls`.
 
 Training on the HIP kernels (opt-in: `IndoorImVoxelNeck.autograd_route` / `NerfDetHeadConvs.autograd_route`, initial value from the
 environment variable MVSDET_DETECTOR_AUTOGRAD, "aten" by default).  With "hip", a neck in training mode on CUDA fp32 tensors runs every
@@ -56,8 +57,8 @@ class _ConvModule(nn.Module):
         return relu_hooked(self, x) if self.with_act else x
 
 
-def _hip_ok(x: Tensor, module: nn.Module) -> bool:
-    return x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and not module.training
+def _block_route(x: Tensor, block: nn.Module, conv: nn.Module) -> str:   # by the block's own `training`: it is a module of its own
+    return layers.decide(layers.call_facts(x, block), conv.out_channels % 64 == 0, other=False, keyed="training")
 
 
 # Stride-1 3x3x3 convolutions on volumes of at least this many voxels go to the bf16 matrix cores with three-term split
@@ -149,12 +150,14 @@ class ResModule(nn.Module):
         self.stride = stride
 
     def forward(self, x):
-        if _hip_ok(x, self) and self.conv0.conv.out_channels % 64 == 0:
+        route = layers.record(self, _block_route(x, self, self.conv0.conv), "conv0", "conv1")
+        if route == "eval":
             identity = x
             if self.stride != 1:   # 1x1x1 stride-2 convolution + BN: one GEMM on the sub-sampled volume
                 ds = self.downsample
-                if (self.stride == 2 and ops.gemm_layer_ok(ds.conv.out_channels, ds.conv.in_channels)
-                        and not any(v % 2 for v in x.shape[2:])):
+                gemm = (self.stride == 2 and ops.gemm_layer_ok(ds.conv.out_channels, ds.conv.in_channels)
+                        and not any(v % 2 for v in x.shape[2:]))
+                if layers.record(self, "eval" if gemm else "shape", "downsample") == "eval":
                     wq, bias = _gemm_weight(ds.conv, ds.bn, split=True)      # the sub-sampling is the kernel's gather
                     identity = ops.conv3d_k1_s2_bf16x3(x, wq, bias, ds.conv.out_channels)
                 else:   # a shape the GEMM kernel refuses (odd extents, channel counts outside `gemm_layer_ok`): torch.baddbmm
@@ -168,6 +171,7 @@ class ResModule(nn.Module):
         identity = x
         x = self.conv1(self.conv0(x))
         if self.stride != 1:
+            layers.record(self, route, "downsample")
             identity = self.downsample(identity)
         return relu_hooked(self, x + identity)
 
@@ -180,6 +184,7 @@ class ResModule(nn.Module):
             identity = x
             y0, parts, pivot = _conv3_train(c0.conv, x, c0.bn)
         else:
+            layers.count_hip(2)   # conv0 and the shortcut
             y0, yd = _DownS2.apply(x, c0.conv.weight, self.downsample.conv.weight)
             identity = bn_train(self.downsample.bn, yd, None)
             parts = pivot = None
@@ -196,13 +201,14 @@ class _UpBlock(nn.Sequential):
                          nn.Conv3d(cout, cout, 3, 1, 1, bias=False), nn.BatchNorm3d(cout), nn.ReLU(inplace=True))
 
     def forward(self, x):
-        if _hip_ok(x, self) and self[3].out_channels % 64 == 0:
+        route = layers.record(self, _block_route(x, self, self[3]), "3")
+        if route == "eval":
             deconv, bn = self[0], self[1]
             n, cin, d, h, w = x.shape
             cout = deconv.out_channels
             # out[:, o, 2i+p, 2j+q, 2k+r] = sum_c x[:, c, i, j, k] * W[c, o, p, q, r]: one (8*Cout x Cin) GEMM with the BatchNorm's
             # shift as its bias; the ReLU writes the interleaved (N, Cout, 2D, 2H, 2W) tensor directly (one pass, no copy)
-            if ops.gemm_layer_ok(8 * cout, cin):
+            if layers.record(self, "eval" if ops.gemm_layer_ok(8 * cout, cin) else "shape", "0") == "eval":
                 wq, bias = _gemm_weight(deconv, bn, split=True)      # bias, ReLU and the 2x2x2 interleave in the GEMM's epilogue
                 return _conv_k3(ops.convT3d_k2_s2_bf16x3(x, wq, bias, cout, True), self[3], self[4], True)
             # channel counts the GEMM kernel refuses (`gemm_layer_ok` false): torch.baddbmm, then the ReLU interleaves
@@ -211,9 +217,11 @@ class _UpBlock(nn.Sequential):
             out = torch.empty((n, cout, 2 * d, 2 * h, 2 * w), dtype=x.dtype, device=x.device)
             torch.clamp_min(y.permute(0, 4, 5, 1, 6, 2, 7, 3), 0.0, out=out.view(n, cout, d, 2, h, 2, w, 2))
             return _conv_k3(out, self[3], self[4], True)
+        layers.record(self, route, "0")
         return super().forward(x) if layers.RELU_MASKS is None else _seq_hooked(self, x)
 
     def _train_hip(self, x):
+        layers.count_hip()
         y = _ConvT2S2.apply(x, self[0].weight)
         h = bn_train(self[1], y, self[2])
         y, parts, pivot = _conv3_train(self[3], h, self[4])
@@ -227,7 +235,7 @@ class _OutBlock(nn.Sequential):
         super().__init__(nn.Conv3d(cin, cout, 3, 1, 1, bias=False), nn.BatchNorm3d(cout), nn.ReLU(inplace=True))
 
     def forward(self, x):
-        if _hip_ok(x, self) and self[0].out_channels % 64 == 0:
+        if layers.record(self, _block_route(x, self, self[0]), "0") == "eval":
             return _conv_k3(x, self[0], self[1], True)
         return super().forward(x) if layers.RELU_MASKS is None else _seq_hooked(self, x)
 
@@ -262,7 +270,8 @@ class IndoorImVoxelNeck(DerivedTensorsMixin, nn.Module):
 
     @fp32_under_autocast
     def forward(self, x: Tensor) -> List[Tensor]:
-        hip = check_route(self) == "hip" and self.training and x.is_cuda and x.dtype == torch.float32
+        # the training kernels: keyed on the neck's `training`, whatever autograd is (`layers.decide`)
+        hip = layers.decide(layers.call_facts(x, self), other=check_route(self) == "hip", keyed="training") == "grad"
         if hip:
             self._check_hip_train(x)
 
@@ -333,6 +342,7 @@ def _conv3_train(conv: nn.Conv3d, x: Tensor, bn: nn.BatchNorm3d):
     BatchNorm statistics' partial sums from the epilogue (around the running mean) where the stride-1 kernel may give them
     (`layers.fused_stats_ok`) and its grid is not split over the input channels (the 20x20x8 and 10x10x4 levels are; the epilogue
     form would run them unsplit), else (y, None, None)."""
+    layers.count_hip()
     if conv.stride[0] == 2:
         return ConvK3S2.apply(x, conv.weight, True), None, None
     n, _, d, h, w = x.shape
