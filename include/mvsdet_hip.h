@@ -51,6 +51,8 @@ const char* mvsdet_last_error(void);
  *   "sweep_xcd"     0 | 1   XCD-aware block map for fewer than 8 channel slabs
  *   "sweep_inside"  1 (default) | 0   planes whose bilinear taps all lie inside the source image take the slab kernel's lean
  *                   decode (no range tests, no clamps of the tap offsets); 0 = every plane takes the general decode
+ *   "sweep_pool"    1 (default) | 0   mvsdet_plane_sweep_table_pooled_f32 builds the pooled geometry; 0 = it builds what
+ *                   mvsdet_plane_sweep_table[_pitched]_f32 build
  *   "sweep_dsplit", "sweep_groups", "bwd_groups", "conv_*"   schedules of the sweep's plane split, of the bf16x3
  *                   convolutions and of the fp16 + MX convolution ("conv_mx_th") (csrc/common.h: struct Options)
  * "sweep_tw" decides the layout of the sweep geometry: consume one (mvsdet_plane_sweep_variance_tabled_f32) under the
@@ -145,6 +147,10 @@ int mvsdet_plane_sweep_table_f32(const float* proj, const float* depth, void* sc
 int mvsdet_plane_sweep_variance_tabled_f32(const float* packed, const int64_t* nbr, const void* table,
                                            size_t table_bytes, float* var, int N, int K, int C, int D, int H,
                                            int W, mvsdet_stream_t stream);
+/* fp16 storage of the tabled sweep: the values mvsdet_plane_sweep_variance_shard_f16 stores, var_f16 (N,C,D,H,W) contiguous. */
+int mvsdet_plane_sweep_variance_tabled_f16(const float* packed, const int64_t* nbr, const void* table,
+                                           size_t table_bytes, void* var_f16, int N, int K, int C, int D, int H,
+                                           int W, mvsdet_stream_t stream);
 /* The same two calls for a PITCHED cost volume: `var` is (N,C,D,H,out_w_pitch) in memory and columns [0, W) of every row are
  * written (the caller hands out that view; mvsdet.py:467 materialises a contiguous volume -- same values, other strides).
  * With out_w_pitch a multiple of 32 every row starts on a 128-byte line and the sweep writes whole lines from 32x4 pixel
@@ -152,6 +158,14 @@ int mvsdet_plane_sweep_variance_tabled_f32(const float* packed, const int64_t* n
  * must be built with the pitch it is consumed with. */
 int mvsdet_plane_sweep_table_pitched_f32(const float* proj, const float* depth, void* scratch, size_t scratch_bytes, int N,
                                          int K, int D, int H, int W, int out_w_pitch, mvsdet_stream_t stream);
+/* The geometry under the POOLED run policy, for the forward sweep: with K == 2 and 32x4 pixel tiles the two LDS slots of a
+ * block are one pool, and over planes on which one neighbour has no footprint the other's union box may take up to
+ * 2 * (capacity + 8) - 8 texels at the pool's base -- fewer box refills on the near planes, the same results bit for bit.
+ * Every other (K, tile shape) gets the slot geometry.  The table carries its own mark: mvsdet_plane_sweep_variance_tabled_f32
+ * and _tabled_pitched_f32 take it (build it with the out_w_pitch it is consumed with; 0 or W = contiguous), the backward
+ * (mvsdet_plane_sweep_variance_bwd_packed_f32) refuses it like any mismatched geometry: NaN output, nothing touched. */
+int mvsdet_plane_sweep_table_pooled_f32(const float* proj, const float* depth, void* scratch, size_t scratch_bytes, int N,
+                                        int K, int D, int H, int W, int out_w_pitch, mvsdet_stream_t stream);
 int mvsdet_plane_sweep_variance_tabled_pitched_f32(const float* packed, const int64_t* nbr, const void* table,
                                                    size_t table_bytes, float* var, int N, int K, int C, int D, int H, int W,
                                                    int out_w_pitch, mvsdet_stream_t stream);

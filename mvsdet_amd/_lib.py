@@ -103,6 +103,8 @@ SIGNATURES = {
     "mvsdet_split_conv_weights_batched": [_vp, _vp, _vp, _vp, _vp, _i, _vp],
     "mvsdet_scl_pack_f32": [_vp, _i64p, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_plane_sweep_table_pitched_f32": [_vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_plane_sweep_variance_tabled_f16": [_vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_plane_sweep_table_pooled_f32": [_vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_plane_sweep_variance_tabled_pitched_f32": [_vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_conv3d_k3_bf16x3_workspace_bytes": [_i, _i, _i, _i, _i, _i],
     "mvsdet_conv3d_k3_s2_bf16x3_workspace_bytes": [_i, _i, _i, _i, _i, _i],

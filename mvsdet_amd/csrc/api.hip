@@ -25,7 +25,8 @@ Options& options() {
     static Options o = {env_int("MVSDET_SWEEP_TW", 0), env_int("MVSDET_SWEEP_BOXCAP", 512), env_int("MVSDET_SWEEP_XCD", 1),
                         env_int("MVSDET_SWEEP_DSPLIT", 0), env_int("MVSDET_SWEEP_GROUPS", -1),
                         env_int("MVSDET_CONV_NSPLIT", 0), env_int("MVSDET_CONV_XCD", 1), env_int("MVSDET_CONV_SPLIT_BLOCKS", 768),
-                        env_int("MVSDET_CONV_SPLIT_MIN_GROUPS", 2), env_int("MVSDET_BWD_GROUPS", 0), env_int("MVSDET_SWEEP_INSIDE", 1), env_int("MVSDET_CONV_MX_TH", 0)};
+                        env_int("MVSDET_CONV_SPLIT_MIN_GROUPS", 2), env_int("MVSDET_BWD_GROUPS", 0), env_int("MVSDET_SWEEP_INSIDE", 1), env_int("MVSDET_CONV_MX_TH", 0),
+                        env_int("MVSDET_SWEEP_POOL", 1)};
     return o;
 }
 
@@ -38,6 +39,7 @@ static int* option_slot(const char* name) {
     if (!strcmp(name, "sweep_dsplit")) return &o.sweep_dsplit;
     if (!strcmp(name, "sweep_groups")) return &o.sweep_groups;
     if (!strcmp(name, "sweep_inside")) return &o.sweep_inside;
+    if (!strcmp(name, "sweep_pool")) return &o.sweep_pool;
     if (!strcmp(name, "conv_nsplit")) return &o.conv_nsplit;
     if (!strcmp(name, "conv_xcd")) return &o.conv_xcd;
     if (!strcmp(name, "bwd_groups")) return &o.bwd_groups;

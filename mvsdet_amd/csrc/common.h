@@ -33,6 +33,8 @@ struct Options {
                        // lean decode; 0 = every plane takes the general decode (A/B runs, tests)
     int conv_mx_th;    // fp16 + MX convolution (costreg_mx.h): 0 (default) = wave-specialised kernel (8 multiplying + 4 staging waves, 4 x 8 x 16 tiles);
                        // 8 / 12 = every wave does everything on 4 x 8 x 16 (8 waves) / 4 x 12 x 16 (12 waves) tiles
+    int sweep_pool;    // 1 (default) = mvsdet_plane_sweep_table_pooled_f32 builds the pooled geometry (K == 2, 32x4 tiles: a footprint box may
+                       // take the other neighbour's idle LDS slot); 0 = it builds the geometry of mvsdet_plane_sweep_table_f32 (A/B runs, tests)
 };
 Options& options();
 
@@ -48,6 +50,8 @@ struct SweepGeometry {
     unsigned short* groups;   // [N*tiles][kSweepGroups + 1] plane-group boundaries of every tile (sweep_kernel.h)
 };
 constexpr int kGeoMagic = 0x4d565347;   // "MVSG"
+constexpr int kGeoMagicPooled = 0x4d565350;   // "MVSP": a geometry of the pooled run policy (mvsdet_plane_sweep_table_pooled_f32): boxes of more
+                                              // texels than the capacity in the header live at the pool's base.  Only the forward slab kernel knows it.
 constexpr int kSweepGroups = 6;   // at most this many plane groups (blocks) per (tile, slab)
 SweepGeometry sweep_geometry(void* scratch, int N, int K, int D, int tiles);
 

@@ -210,7 +210,7 @@ int launch_slab(dim3 grid, hipStream_t stream, size_t lds, const float* packed, 
 template <int TW>
 int launch_sweep(const float* packed, const int64_t* nbr, const float* proj, const float* depth, void* var_any,
                  void* scratch, int N, int K, int C, int D, int H, int W, hipStream_t stream, int phases, int n_src,
-                 int ref_first, bool half_out, int Wo) {
+                 int ref_first, bool half_out, int Wo, bool pooled) {
     float* var = static_cast<float*>(var_any);
     __half* var16 = static_cast<__half*>(var_any);  // half_out: same kernel, variance rounded to fp16 at the store
     // phases: bit 0 = build the sweep geometry (coords kernel), bit 1 = run the slab kernel.  N reference views starting at view ref_first of the n_src packed source views (a view shard;
@@ -229,6 +229,10 @@ int launch_sweep(const float* packed, const int64_t* nbr, const float* proj, con
     // refill flags and the union boxes carry it implicitly -- so its LDS slots are sized for the largest capacity any
     // geometry of this (K, tile shape) can have: "sweep_boxcap" may change between the two calls without harm.
     const int box_cap = (phases == 2) ? max_box_cap(K, TW) : effective_box_cap(K, TW);
+    // the pooled run policy (sweep_kernel.h): K == 2 and 32x4 tiles; every other pooled table holds the slot policy's geometry
+    // under the pooled mark
+    const int pool_cap = (pooled && K == 2 && TW == 32 && box_cap > 0) ? K * (box_cap + kBoxPad) - kBoxPad : box_cap;
+    const int magic = pooled ? kGeoMagicPooled : kGeoMagic;
     // every block sweeps all its planes (reference features stay in registers, a resident footprint box serves a run
     // of planes) unless the grid would be too small to fill 256 CUs x 2 blocks
     int dsplit = 1;
@@ -273,7 +277,8 @@ int launch_sweep(const float* packed, const int64_t* nbr, const float* proj, con
         if (phases & 1)                                                                                               \
             hipLaunchKernelGGL((plane_sweep_coords_kernel<KV, TW>), cgrid, dim3(kThreads),                            \
                                (size_t)D * (KV * sizeof(int4) + sizeof(unsigned) + sizeof(float)), stream, proj, depth,               \
-                               geo.header, geo.boxes, geo.flags, geo.proj, geo.depth, geo.groups, gmax, D, H, W, tiles_x, tiles, box_cap); \
+                               geo.header, geo.boxes, geo.flags, geo.proj, geo.depth, geo.groups, gmax, D, H, W, tiles_x, tiles, box_cap, \
+                               pool_cap, magic);                                                                      \
         if (phases & 2) rc = fast ? MVS_SLAB(KV, true) : MVS_SLAB(KV, false);                                         \
         break;
     switch (K) {
@@ -323,7 +328,7 @@ extern "C" size_t mvsdet_plane_sweep_scratch_bytes(int N, int K, int D, int H, i
 static int sweep_entry(const char* name, const float* packed, const int64_t* nbr, const float* proj, const float* depth,
                        void* var, void* scratch, size_t scratch_bytes, int N, int K, int C, int D, int H, int W,
                        mvsdet_stream_t stream, int phases, int n_src = -1, int ref_first = 0, bool half_out = false,
-                       int out_pitch = 0) {
+                       int out_pitch = 0, bool pooled = false) {
     if (n_src < 0) n_src = N;
     const int Wo = out_pitch > 0 ? out_pitch : W;
     MVS_REQUIRE(Wo >= W, "%s: output row pitch %d < W=%d", name, Wo, W);
@@ -345,8 +350,8 @@ static int sweep_entry(const char* name, const float* packed, const int64_t* nbr
     MVS_REQUIRE(K == 0 || ((uintptr_t)scratch % 16 == 0), "%s: scratch must be 16-byte aligned", name);
     const int tw = pick_tile_width(W, D, Wo);
     hipStream_t st = (hipStream_t)stream;
-    if (tw == 16) return launch_sweep<16>(packed, nbr, proj, depth, var, scratch, N, K, C, D, H, W, st, phases, n_src, ref_first, half_out, Wo);
-    return launch_sweep<32>(packed, nbr, proj, depth, var, scratch, N, K, C, D, H, W, st, phases, n_src, ref_first, half_out, Wo);
+    if (tw == 16) return launch_sweep<16>(packed, nbr, proj, depth, var, scratch, N, K, C, D, H, W, st, phases, n_src, ref_first, half_out, Wo, pooled);
+    return launch_sweep<32>(packed, nbr, proj, depth, var, scratch, N, K, C, D, H, W, st, phases, n_src, ref_first, half_out, Wo, pooled);
 }
 
 extern "C" int mvsdet_plane_sweep_variance_packed_f32(const float* packed, const int64_t* nbr, const float* proj,
@@ -386,6 +391,15 @@ extern "C" int mvsdet_plane_sweep_variance_tabled_f32(const float* packed, const
                        table_bytes, N, K, C, D, H, W, stream, 2);
 }
 
+// fp16 storage of the tabled sweep (contiguous volume): what mvsdet_plane_sweep_variance_shard_f16 stores, on a geometry built
+// beforehand -- either form of it.
+extern "C" int mvsdet_plane_sweep_variance_tabled_f16(const float* packed, const int64_t* nbr, const void* table,
+                                                      size_t table_bytes, void* var_f16, int N, int K, int C, int D, int H,
+                                                      int W, mvsdet_stream_t stream) {
+    return sweep_entry("plane_sweep_variance_tabled_f16", packed, nbr, nullptr, nullptr, var_f16, const_cast<void*>(table),
+                       table_bytes, N, K, C, D, H, W, stream, 2, -1, 0, true);
+}
+
 // The two halves again for a PITCHED output: var is (N,C,D,H,out_w_pitch) in memory, of which columns [0, W) are written
 // (the caller hands out the view).  A pitch that is a multiple of 32 puts every row on a 128-byte line and selects the
 // 32x4 tiles (pick_tile_width); the geometry must be built with the same pitch (the tile shape decides its layout).
@@ -393,6 +407,15 @@ extern "C" int mvsdet_plane_sweep_table_pitched_f32(const float* proj, const flo
                                                     int N, int K, int D, int H, int W, int out_w_pitch, mvsdet_stream_t stream) {
     return sweep_entry("plane_sweep_table_pitched", nullptr, nullptr, proj, depth, nullptr, scratch, scratch_bytes, N, K, 1, D, H,
                        W, stream, 1, -1, 0, false, out_w_pitch);
+}
+
+// The geometry under the POOLED run policy (sweep_kernel.h: a footprint box may take the other neighbour's idle LDS slot), for the
+// forward sweep only: mvsdet_plane_sweep_variance_tabled[_pitched]_f32 take it, the backward refuses it.  out_w_pitch: 0 or W for
+// a contiguous volume.  Option "sweep_pool" 0: the geometry of mvsdet_plane_sweep_table[_pitched]_f32, mark included.
+extern "C" int mvsdet_plane_sweep_table_pooled_f32(const float* proj, const float* depth, void* scratch, size_t scratch_bytes,
+                                                   int N, int K, int D, int H, int W, int out_w_pitch, mvsdet_stream_t stream) {
+    return sweep_entry("plane_sweep_table_pooled", nullptr, nullptr, proj, depth, nullptr, scratch, scratch_bytes, N, K, 1, D, H,
+                       W, stream, 1, -1, 0, false, out_w_pitch, options().sweep_pool != 0);
 }
 
 extern "C" int mvsdet_plane_sweep_variance_tabled_pitched_f32(const float* packed, const int64_t* nbr, const void* table,

@@ -23,6 +23,14 @@
 //                 fetch the tap offsets and weights with DPP (a bank-masked row shift for the neighbour's quad, once per
 //                 pass, then one quad_perm broadcast per value and step) -- no LDS tables, no barrier.
 //       FAST    = C % 32 == 0 and W % 4 == 0: four unconditional 16-byte stores under one lane predicate.
+//       POOL    = (K == 2, 32x4 tiles, a geometry of mvsdet_plane_sweep_table_pooled_f32) the two slots are ONE pool of
+//                 2 * (box_cap + kBoxPad) - kBoxPad = 632 texels: over planes on which the other neighbour has no footprint a
+//                 run's union box may take up to the whole pool, at the pool's base.  A neighbour's LDS base is set when its box
+//                 is loaded (slot or pool base), beside the box itself; nothing changes per plane and nothing in the refill
+//                 sequence.  The geometry kernel guarantees that a box which is read was not overwritten since it was loaded
+//                 (INVARIANT at its run pass; tests/test_gpu_sweep_pool.py replays it for every first plane of a block).
+//                 Fewer refills on the near planes, where one neighbour is out of view and the other's footprint moves
+//                 fastest: docs/KERNEL_NOTES.md 4.1.
 //
 // Design history and what bounds the kernel: DESIGN.md 4.1.
 //
@@ -149,7 +157,10 @@ __global__ __launch_bounds__(kThreads) void plane_sweep_coords_kernel(const floa
                                                                        int4* __restrict__ header, int4* __restrict__ boxes,
                                                                        unsigned* __restrict__ flags, float* __restrict__ proj_copy,
                                                                        float* __restrict__ depth_copy, unsigned short* __restrict__ groups,
-                                                                       int gmax, int D, int H, int W, int tiles_x, int tiles, int box_cap) {
+                                                                       int gmax, int D, int H, int W, int tiles_x, int tiles, int box_cap,
+                                                                       int pool_cap, int magic) {
+    // pool_cap: texels a union box may take while the other neighbour has no footprint (K == 2; the pooled run policy below);
+    // pool_cap == box_cap is the slot policy.  magic: kGeoMagic, or kGeoMagicPooled for a table whose boxes may exceed box_cap.
     constexpr int TH = kTilePix / TW;
     extern __shared__ int4 s_geo[];    // [K][D] the tile's boxes of all planes, then [D] flags words, then [D] plane depths
     int4* s_pb = s_geo;
@@ -165,7 +176,7 @@ __global__ __launch_bounds__(kThreads) void plane_sweep_coords_kernel(const floa
         s_dv[d] = depth[(size_t)n * D + d];   // one global round trip for all planes instead of one per plane
     }
     __syncthreads();
-    if (bt == 0 && tid == 0) *header = make_int4(kGeoMagic, TW | (box_cap << 8), W, (D << 8) | K);   // what this layout was built for
+    if (bt == 0 && tid == 0) *header = make_int4(magic, TW | (box_cap << 8), W, (D << 8) | K);   // what this layout was built for
     if (tile == 0) {  // the slab kernel reads the camera data from the scratch buffer (the tabled entry point has no other)
         for (int i = tid; i < K * 16; i += kThreads) proj_copy[(size_t)n * K * 16 + i] = proj[(size_t)n * K * 16 + i];
         for (int d = tid; d < D; d += kThreads) depth_copy[(size_t)n * D + d] = depth[(size_t)n * D + d];
@@ -291,14 +302,34 @@ __global__ __launch_bounds__(kThreads) void plane_sweep_coords_kernel(const floa
                 const int e = e0 + lane;
                 if (e < last) {
                     const int4 o = bj[e];
-                    if (box_nonempty(o) && box_area(o) <= box_cap) {
+                    if (box_nonempty(o) && box_area(o) <= pool_cap) {   // every footprint inside a run is one of its members
                         bj[e] = u;
                         atomicOr(s_fl + e, (kFlagStaged | ((e == first && differs) ? kFlagRefill : 0u)) << sh);
                     }
                 }
             }
         };
+        // POOLED policy (K == 2, pool_cap > box_cap).  The K slots are one pool of K*(box_cap + kBoxPad) - kBoxPad texels.  A union
+        // box of at most box_cap texels lives in its neighbour's own slot; a WIDE one (box_cap < texels <= pool_cap) lives at the
+        // pool's base and overlaps the other neighbour's slot.  A run may be wide only if the other neighbour has no footprint
+        // (an empty box) on any plane from the run's first to its last member: greedy growth cuts a run that would become wide
+        // where that dead stretch begins and ends, a run that stays within box_cap crosses those borders as before.
+        //   * a wide run always refills on its first plane (its place in the pool may have been written since);
+        //   * the other neighbour's next staged plane after a wide run carries kFlagRefill (second pass below), whether
+        //     or not its box changed.
+        // INVARIANT: on every plane, for a block that starts its sweep at any plane, the boxes it holds resident (per neighbour
+        // the box of its latest staged plane so far) and then READS do not overlap in the pool, load_box's extra piece of
+        // kBoxPad texels past the box included: two narrow boxes sit in disjoint slots of box_cap + kBoxPad; while a wide box is
+        // being read the other neighbour has staged nothing since it was loaded, and that neighbour's next read is a reload.
+        // Whether a footprint is empty never changes during this pass (close_run rewrites non-empty boxes with their supersets,
+        // component by component), so wave j may read the other neighbour's boxes while wave j^1 rewrites them.
+        const bool pooled = K == 2 && pool_cap > box_cap;
+        const int4* bo = s_pb + (size_t)(wave ^ 1) * D;   // the other neighbour's boxes (pooled only)
+        auto differs_from = [&](const int4& a, const int4& r) {
+            return box_area(a) > box_cap || a.x != r.x || a.y != r.y || a.z != r.z || a.w != r.w;
+        };
         int run_first = -1;
+        int last_other = -1;   // pooled: the last plane of the chunks walked so far on which the other neighbour has a footprint
         int4 u = make_int4(0, 0, 0, 0), res = make_int4(0, -1, 0, -1);   // res: what the sweep holds resident in this slot
         for (int base = 0; base < D; base += 64) {
             const int4 mine = base + lane < D ? bj[base + lane] : make_int4(0, -1, 0, -1);
@@ -306,28 +337,58 @@ __global__ __launch_bounds__(kThreads) void plane_sweep_coords_kernel(const floa
             // live: the taps run; an empty footprint with a non-finite position too (from global memory, giving NaN)
             if (base + lane < D && (live || mine.w != kBoxSkip)) atomicOr(s_fl + base + lane, kFlagLive << sh);
             unsigned long long todo = box_cap > 0 ? __ballot(live) : 0ull;   // the walk only visits non-empty footprints
+            unsigned long long other = 0ull;   // planes of this chunk on which the other neighbour has a footprint
+            if (pooled) other = __ballot(base + lane < D && box_nonempty(bo[base + lane]));
             while (todo) {
                 const int i = __builtin_ctzll(todo);
                 todo &= todo - 1;
                 const int d = base + i;
                 const int4 b = lane_box(mine, i);
+                const unsigned long long upto = other & ((2ull << i) - 1ull);   // ... up to and including this plane
+                const int lo = upto ? base + 63 - __builtin_clzll(upto) : last_other;
+                const int cap_b = lo < d ? pool_cap : box_cap;   // the other neighbour is dead here: a wide box may stand alone
                 bool close = false;
-                if (box_area(b) > box_cap) {
+                if (box_area(b) > cap_b) {
                     close = true;
                 } else if (run_first >= 0) {
                     const int4 c = make_int4(min(u.x, b.x), max(u.y, b.y), min(u.z, b.z), max(u.w, b.w));
-                    if (box_area(c) <= box_cap) { u = c; continue; }
+                    const int ac = box_area(c);
+                    if (ac <= box_cap || (ac <= pool_cap && lo < run_first)) { u = c; continue; }
                     close = true;
                 }
                 if (close && run_first >= 0) {
-                    close_run(run_first, d, u, u.x != res.x || u.y != res.y || u.z != res.z || u.w != res.w);
+                    close_run(run_first, d, u, differs_from(u, res));
                     res = u;
                     run_first = -1;
                 }
-                if (box_area(b) <= box_cap) { run_first = d; u = b; }
+                if (box_area(b) <= cap_b) { run_first = d; u = b; }
+            }
+            if (other) last_other = base + 63 - __builtin_clzll(other);
+        }
+        if (run_first >= 0) close_run(run_first, D, u, differs_from(u, res));
+    }
+    if (K == 2 && pool_cap > box_cap) {   // block-uniform
+        // second pass of the pooled policy: neighbour j's first staged plane after a wide staged plane of the other neighbour
+        // refills -- the wide box has overwritten (part of) slot j.  64 planes per step, all lanes at once.
+        __syncthreads();
+        if (wave < 2) {
+            const int4* bo = s_pb + (size_t)(wave ^ 1) * D;
+            const unsigned sh = 4 * wave, sho = 4 * (wave ^ 1);
+            bool carry = false;   // a wide plane of the other neighbour since this neighbour's last staged plane
+            for (int base = 0; base < D; base += 64) {
+                const int e = base + lane;
+                const unsigned f = e < D ? s_fl[e] : 0u;
+                const bool staged = (f >> sh) & kFlagStaged;
+                const bool wide_o = e < D && ((f >> sho) & kFlagStaged) && box_area(bo[e]) > box_cap;
+                const unsigned long long Wm = __ballot(wide_o), Sm = __ballot(staged);
+                const unsigned long long below = (1ull << lane) - 1ull;
+                const unsigned long long sb = Sm & below;                 // this neighbour's staged planes before mine
+                const unsigned long long since = sb ? ~((2ull << (63 - __builtin_clzll(sb))) - 1ull) : ~0ull;
+                if (staged && ((Wm & below & since) || (!sb && carry))) atomicOr(s_fl + e, kFlagRefill << sh);
+                if (Sm) carry = ((Wm >> (63 - __builtin_clzll(Sm))) >> 1) != 0ull;
+                else carry = carry || Wm != 0ull;
             }
         }
-        if (run_first >= 0) close_run(run_first, D, u, u.x != res.x || u.y != res.y || u.z != res.z || u.w != res.w);
     }
     __syncthreads();
     for (int i = tid; i < D * K; i += kThreads) boxes[(size_t)bt * D * K + i] = s_pb[(size_t)(i % K) * D + i / K];
@@ -443,7 +504,11 @@ __global__ __launch_bounds__(kThreads, (TW == 16 && K <= 2) ? 3 : 2) void plane_
     constexpr int NP = (K + 1) / 2;             // decode passes: a lane decodes ONE (pixel-step, neighbour) pair per pass
     constexpr int NPP = NP > 0 ? NP : 1;
     constexpr int TH = kTilePix / TW;
-    extern __shared__ float4 s_box[];  // K slots of (box_cap + kBoxPad) texels (8 float4 each)
+    extern __shared__ float4 s_box[];  // K slots of (box_cap + kBoxPad) texels (8 float4 each); one pool for a pooled geometry
+    // A pooled geometry (kGeoMagicPooled; K == 2, 32x4 tiles) may carry WIDE boxes, of more texels than the capacity it was built
+    // with: those live at the pool's base instead of their neighbour's slot (plane_sweep_coords_kernel states the invariant).
+    constexpr bool kPool = K == 2 && TW == 32;
+    int wide_above = INT32_MAX;   // scalar: a box of more texels than this is a wide one
 
     if constexpr (K > 0) {
         // The geometry's layout hangs on the tile shape it was built for: one that was built for another (a pitched table handed
@@ -452,13 +517,15 @@ __global__ __launch_bounds__(kThreads, (TW == 16 && K <= 2) ? 3 : 2) void plane_
         // where this kernel would look.  Nothing of it is touched: the whole output becomes NaN instead (block-uniform exit
         // before any barrier).
         const int4 hd = *header;
-        if (hd.x != kGeoMagic || (hd.y & 0xff) != TW || (hd.y >> 8) > box_cap || hd.z != W || hd.w != ((D << 8) | K)) {
+        if ((hd.x != kGeoMagic && hd.x != kGeoMagicPooled) || (hd.y & 0xff) != TW || (hd.y >> 8) > box_cap || hd.z != W || hd.w != ((D << 8) | K)) {
             const size_t total = (size_t)(n_bt / tiles) * C * D * H * Wo;
             const size_t step = (size_t)gridDim.x * gridDim.y * kThreads;
             for (size_t i = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kThreads + threadIdx.x; i < total; i += step)
                 var[i] = (OutT)__builtin_nanf("");
             return;
         }
+        if constexpr (kPool)
+            if (hd.x == kGeoMagicPooled) wide_above = __builtin_amdgcn_readfirstlane(hd.y >> 8);
     }
     const int HW = H * W;
     const int HWo = H * Wo;   // Wo = row pitch of the OUTPUT in elements (W for a contiguous volume; a multiple of 32 puts every
@@ -553,11 +620,15 @@ __global__ __launch_bounds__(kThreads, (TW == 16 && K <= 2) ? 3 : 2) void plane_
     for (int p = 0; p < NPP; ++p) { lx0[p] = 0; lx1[p] = 0; ly0[p] = 0; ly1[p] = 0; }
 #pragma unroll
     for (int j = 0; j < KK; ++j) { rx0[j] = 0; ry0[j] = 0; rx1[j] = -1; ry1[j] = -1; have[j] = false; }
+    // where that box starts in LDS, in bytes: its neighbour's slot, or the pool's base for a wide box; set at refill time
+    int lbase[NPP];
+#pragma unroll
+    for (int p = 0; p < NPP; ++p) lbase[p] = min(2 * p + qd, KK - 1) * slot_f4 * 16;
 
     // LDS-DMA of one footprint box into its slot: each wave-instruction fills 8 texel slots = 1 KiB without touching
     // VGPRs (LDS address = wave-uniform base + 16*lane, global address per lane: the texel that belongs in the lane's
     // slot).  Pieces are dealt round-robin to the block's waves.
-    auto load_box = [&](int j, int bx0, int by0, int nc, int nr) {
+    auto load_box = [&](int j, int base_f4, int bx0, int by0, int nc, int nr) {
         const int ntex = nc * nr;
         const float inv_nc = 1.0f / (float)nc;
         for (int q = wave; q * 8 <= ntex; q += 4) {
@@ -565,7 +636,7 @@ __global__ __launch_bounds__(kThreads, (TW == 16 && K <= 2) ? 3 : 2) void plane_
             const int row = (int)(((float)t + 0.5f) * inv_nc);  // t / nc for t < 2^11 (never within rounding of an integer)
             const int col = t - row * nc;
             const float4* src = nb_img[j] + ((size_t)(by0 + row) * W + (bx0 + col)) * 8 + g;
-            float4* dst = s_box + (size_t)j * slot_f4 + q * 64;  // wave-uniform
+            float4* dst = s_box + base_f4 + q * 64;  // wave-uniform
             if (t < ntex)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                                  (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
@@ -662,8 +733,15 @@ __global__ __launch_bounds__(kThreads, (TW == 16 && K <= 2) ? 3 : 2) void plane_
                     ry0[j] = __builtin_amdgcn_readfirstlane(b.z);
                     ry1[j] = __builtin_amdgcn_readfirstlane(b.w);
                     have[j] = true;
-                    if (min(2 * (j / 2) + qd, K - 1) == j) { lx0[j / 2] = rx0[j]; lx1[j / 2] = rx1[j]; ly0[j / 2] = ry0[j]; ly1[j / 2] = ry1[j]; }
-                    load_box(j, rx0[j], ry0[j], rx1[j] - rx0[j] + 1, ry1[j] - ry0[j] + 1);
+                    const int nc = rx1[j] - rx0[j] + 1, nr = ry1[j] - ry0[j] + 1;
+                    int base_f4 = j * slot_f4;   // scalar
+                    if constexpr (kPool)
+                        if (nc * nr > wide_above) base_f4 = 0;
+                    if (min(2 * (j / 2) + qd, K - 1) == j) {
+                        lx0[j / 2] = rx0[j]; lx1[j / 2] = rx1[j]; ly0[j / 2] = ry0[j]; ly1[j / 2] = ry1[j];
+                        if constexpr (kPool) lbase[j / 2] = base_f4 * 16;
+                    }
+                    load_box(j, base_f4, rx0[j], ry0[j], nc, nr);
                 }
             }
             // The LDS-DMA pieces of this wave count on vmcnt, and for a workgroup barrier hipcc only waits for lgkmcnt:
@@ -760,7 +838,7 @@ __global__ __launch_bounds__(kThreads, (TW == 16 && K <= 2) ? 3 : 2) void plane_
             const unsigned fp = fl >> (8 * p);
             constexpr unsigned kLive2 = kFlagLive | (kFlagLive << 4);
             if (!(fp & kLive2)) return;  // nothing of these neighbours is visible: warped values all zero
-            const int sbase = min(2 * p + qd, K - 1) * slot_f4 * 16;
+            const int sbase = kPool ? lbase[p] : min(2 * p + qd, K - 1) * slot_f4 * 16;
             // the position of every lane's pixel, inside the map or not (no memory is touched on its account)
             const float2 e_any = sample_at(ray[p], tr0[p], tr1[p], tr2[p], dval, H, W);
             int do0, do1, do2, do3;   // byte offsets of the four taps of the lane's decoded pixel

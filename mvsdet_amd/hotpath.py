@@ -372,10 +372,8 @@ class MVSDetHotPath:
                 t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 t0.record(side)
             pitch = self.variance_row_pitch(W)
-            if pitch != W:
-                table = ops.plane_sweep_table_pitched(geo.proj_rel, geo.depth_values, H, W, pitch)
-            else:
-                table = ops.plane_sweep_table(geo.proj_rel, geo.depth_values, H, W)
+            # forward only: the pooled geometry (a footprint box may take the other neighbour's idle LDS slot)
+            table = ops.plane_sweep_table_pooled(geo.proj_rel, geo.depth_values, H, W, pitch if pitch != W else 0)
             if events:
                 t1.record(side)
             done = torch.cuda.Event()

@@ -276,13 +276,29 @@ def _(packed, nbr, table, C, D, H, W):
     return packed.new_empty((nbr.shape[0], C, D, H, W))
 
 
+def plane_sweep_variance_tabled_f16(packed: Tensor, nbr: Tensor, table: Tensor, C: int, D: int, H: int, W: int) -> Tensor:
+    """plane_sweep_variance_tabled with fp16 storage: the fp32 result rounded to nearest-even at the store -> (N,C,D,H,W) float16.
+    Forward only."""
+    _req(packed, "packed", dim=1)
+    _req(nbr, "nbr", dtype=torch.int64, dim=2)
+    _req(table, "table", dim=1)
+    N, K = nbr.shape
+    nbr = nbr.contiguous()
+    out = torch.empty((N, C, D, H, W), dtype=torch.float16, device=packed.device)
+    with torch.cuda.device(packed.device):
+        _lib.check(_lib.load().mvsdet_plane_sweep_variance_tabled_f16(_lib.ptr(packed), _lib.ptr(nbr), _lib.ptr(table),
+                                                                      table.numel() * 4, _lib.ptr(out), N, K, C, D, H, W,
+                                                                      _stream(packed)), "plane_sweep_variance_tabled_f16")
+    return out
+
+
 def sweep_flags(table: Tensor, N: int, K: int, D: int, H: int, W: int) -> Tensor:
-    """The flags words of a geometry table (plane_sweep_table / plane_sweep_table_pitched) as an (N, tiles, D) int64 tensor:
+    """The flags words of a geometry table (plane_sweep_table / plane_sweep_table_pitched / plane_sweep_table_pooled) as an (N, tiles, D) int64 tensor:
     one nibble per neighbour -- 1 live, 2 staged, 4 refill, 8 inside (csrc/sweep_kernel.h).  Layout of the table: header int4
     {magic, tile width | box capacity << 8, W, D << 8 | K}, boxes [N*tiles*D*K] int4, then the flags."""
     words = table.view(torch.int32)
     hd = [int(v) for v in words[:4].cpu()]
-    if hd[0] != 0x4d565347 or hd[2] != W or hd[3] != ((D << 8) | K):
+    if hd[0] not in (0x4d565347, 0x4d565350) or hd[2] != W or hd[3] != ((D << 8) | K):
         raise ValueError("sweep_flags: not a geometry table of this (K, D, W)")
     tw = hd[1] & 0xff
     tiles = ((W + tw - 1) // tw) * ((H + 128 // tw - 1) // (128 // tw))
@@ -304,6 +320,17 @@ def sweep_inside_count(table: Tensor, N: int, K: int, D: int, H: int, W: int) ->
     return live, lean
 
 
+def sweep_stall_events(table: Tensor, N: int, K: int, D: int, H: int, W: int) -> Tuple[int, int]:
+    """(events, blocks) of a geometry table: the planes of a (view, tile) block on which at least one neighbour refills its
+    footprint box (one block-wide stall of the slab kernel each, for a block that sweeps all planes), and the number of blocks."""
+    fl = sweep_flags(table, N, K, D, H, W)
+    refill = 0
+    for j in range(K):
+        nib = fl >> (4 * j)
+        refill = refill | (((nib & 2) != 0) & ((nib & 4) != 0))
+    return int(refill.sum()), int(fl.shape[0] * fl.shape[1])
+
+
 def sweep_row_pitch(W: int) -> int:
     """Row pitch (elements) of a cost volume whose rows start on 128-byte lines: W rounded up to a multiple of 32."""
     return (int(W) + 31) // 32 * 32
@@ -323,6 +350,32 @@ def plane_sweep_table_pitched(proj: Tensor, depth: Tensor, H: int, W: int, w_pit
         _lib.check(lib.mvsdet_plane_sweep_table_pitched_f32(_lib.ptr(proj), _lib.ptr(depth), _lib.ptr(table), sbytes, N, K, D, H,
                                                             W, int(w_pitch), _stream(proj)), "plane_sweep_table_pitched")
     return table
+
+
+@torch.library.custom_op(f"{_NS}::plane_sweep_table_pooled", mutates_args=(), device_types="cuda")
+def plane_sweep_table_pooled(proj: Tensor, depth: Tensor, H: int, W: int, w_pitch: int = 0) -> Tensor:
+    """plane_sweep_table / plane_sweep_table_pitched (w_pitch: 0 or W = contiguous) under the pooled run policy: with two
+    neighbours and 32x4 tiles a footprint box may take the other neighbour's idle LDS slot (csrc/sweep_kernel.h).  For the
+    FORWARD sweep only (plane_sweep_variance_tabled / _pitched); the backward refuses such a table (all-NaN gradient).
+    Library option "sweep_pool" 0: the unpooled table."""
+    _req(proj, "proj", dim=4)
+    _req(depth, "depth", dim=2)
+    N, K = proj.shape[:2]
+    D = depth.shape[1]
+    lib = _lib.load()
+    sbytes = lib.mvsdet_plane_sweep_scratch_bytes(N, K, D, H, W)
+    table = torch.empty(max(sbytes // 4, 4), dtype=torch.float32, device=proj.device)
+    proj, depth = proj.contiguous(), depth.contiguous()
+    with torch.cuda.device(proj.device):
+        _lib.check(lib.mvsdet_plane_sweep_table_pooled_f32(_lib.ptr(proj), _lib.ptr(depth), _lib.ptr(table), sbytes, N, K, D, H,
+                                                           W, int(w_pitch), _stream(proj)), "plane_sweep_table_pooled")
+    return table
+
+
+@plane_sweep_table_pooled.register_fake
+def _(proj, depth, H, W, w_pitch=0):
+    sbytes = _lib.load().mvsdet_plane_sweep_scratch_bytes(proj.shape[0], proj.shape[1], depth.shape[1], H, W)
+    return proj.new_empty(max(sbytes // 4, 4))
 
 
 def plane_sweep_variance_tabled_pitched(packed: Tensor, nbr: Tensor, table: Tensor, C: int, D: int, H: int, W: int,

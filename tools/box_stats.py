@@ -2,7 +2,8 @@
 """Footprint-box statistics of a workload's sampling table: how many (tile, plane, neighbour) boxes are empty, fit
 the LDS box (staged) or fall back to global gathers, and how large they are; and over the cameras of the benchmark's first
 timed steps (seeds 1000 ..) the share of live (tile, plane, pass) triples that take the slab kernel's lean form
-(ops.sweep_inside_count).  Usage: python tools/box_stats.py [workload ...]"""
+(ops.sweep_inside_count), and the stall events per (view, tile) block -- planes on which at least one neighbour refills its box
+-- of the unpooled and of the pooled table (ops.sweep_stall_events).  Usage: python tools/box_stats.py [workload ...]"""
 import os
 import sys
 
@@ -48,14 +49,25 @@ for name in sys.argv[1:] or ["scannet_40v_64d_120x160"]:
         print(f"    planes: both skipped {both_skip:.3f}, one live {one_live:.3f}, both live {1 - both_skip - one_live:.3f}; "
               f"both staged with area0+area1 <= {CAP}: {(both_staged & (ar.sum(1) <= CAP)).mean():.3f} (of both staged {both_staged.mean():.3f})")
     # the lean form's share, over the cameras the benchmark's timed steps use (bench.step_metas: seeds 1000 + i)
-    live = lean = 0
+    live = lean = ev_slot = ev_pool = blocks = 0
+    pitch = hp.variance_row_pitch(W)
     for seed in range(1000, 1010):
         m = synthetic.make_img_meta(N, (H, W), seed=seed, per_view_intrinsics=w["per_view_K"])
         gs = hp.prepare_scene(m, dev)
         a, b = ops.sweep_inside_count(ops.plane_sweep_table(gs.proj_rel, gs.depth_values, H, W), N, K, D, H, W)
         live, lean = live + a, lean + b
+        if pitch != W:
+            tu = ops.plane_sweep_table_pitched(gs.proj_rel, gs.depth_values, H, W, pitch)
+        else:
+            tu = ops.plane_sweep_table(gs.proj_rel, gs.depth_values, H, W)
+        tp = ops.plane_sweep_table_pooled(gs.proj_rel, gs.depth_values, H, W, pitch if pitch != W else 0)
+        e0, nb = ops.sweep_stall_events(tu, N, K, D, H, W)
+        e1, _ = ops.sweep_stall_events(tp, N, K, D, H, W)
+        ev_slot, ev_pool, blocks = ev_slot + e0, ev_pool + e1, blocks + nb
     a0, b0 = ops.sweep_inside_count(table, N, K, D, H, W)
     th_ = 128 // tw
     full = (W // tw) * (H // th_)
     print(f"    lean form (kFlagInside): {lean} of {live} live (tile, plane, pass) triples = {lean / max(live, 1):.3f} over 10 timed-step "
           f"scenes (seed 0 scene: {b0 / max(a0, 1):.3f}); whole tiles {full} of {tiles} ({W}x{H} in {tw}x{th_})")
+    print(f"    stall events per (view, tile) block over the same scenes (the route's own tile shape): unpooled table "
+          f"{ev_slot / max(blocks, 1):.2f}, pooled table {ev_pool / max(blocks, 1):.2f}")

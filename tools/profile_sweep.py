@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Runs pack + plane-sweep variance a few times on one synthetic scene: the target of rocprofv3 runs
-(kernel trace, then one --pmc set per run).  Usage: python tools/profile_sweep.py [workload] [reps]"""
+(kernel trace, then one --pmc set per run).  Usage: python tools/profile_sweep.py [workload] [reps] [tabled]
+`tabled`: the forward-only route of hotpath.forward_scene -- sweep_geometry_async (the pooled geometry) + cost_volume_tabled --
+instead of the fused call, which builds the unpooled geometry."""
 import os
 import sys
 
@@ -13,6 +15,7 @@ from mvsdet_amd.hotpath import MVSDetHotPath  # noqa: E402
 
 name = sys.argv[1] if len(sys.argv) > 1 else "scannet_40v_64d_120x160"
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+tabled = len(sys.argv) > 3 and sys.argv[3] == "tabled"
 w = bench.WORKLOADS[name]
 dev = torch.device("cuda:0")
 hp = MVSDetHotPath(bench.N_VOXELS, bench.VOXEL_SIZE, list(w["near_far"]), w["D"])
@@ -38,7 +41,10 @@ for i in range(reps):
     packed = ops.pack_features(s.features)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    var = ops.plane_sweep_variance_packed(packed, geo.neighbor_ids, geo.proj_rel, geo.depth_values, w["C"], w["H"], w["W"])
+    if tabled:
+        var = hp.cost_volume_tabled(packed, geo, hp.sweep_geometry_async(geo, w["H"], w["W"]), w["C"], w["H"], w["W"])
+    else:
+        var = ops.plane_sweep_variance_packed(packed, geo.neighbor_ids, geo.proj_rel, geo.depth_values, w["C"], w["H"], w["W"])
     e1.record()
     torch.cuda.synchronize()
     ts.append(e0.elapsed_time(e1))
