@@ -395,6 +395,31 @@ int mvsdet_backproject_weigh_mean_bwd_f32(const float* feat, const int64_t* feat
                                           const int32_t* count, const float* g, float* gfeat, float* gdens,
                                           int N, int C, int h, int w, int V, int J, float vz,
                                           mvsdet_stream_t stream);
+/* a9 with ground-truth depth: the two scalars the gt_depth branch of backproject_Weigh returns (mvsdet.py:1435-1484)
+ * and what they are made of.  The volume of a9 does not depend on gt_depth; call the functions above for it.
+ *   points, projection, depth, dens + dd_strides, vz: as for a9
+ *   depth_mean + dm_strides: (N,h,w) depth expectation, element strides of a 3-D view (a crop of the padded map)
+ *   gt_depth + gt_strides:   (N,Hg,Wg) ground truth, any Hg, Wg >= 1, element strides of a 3-D view
+ *   gt_depth is resized to (h,w) as ATen's upsample_bilinear2d(align_corners=False) does it in fp32 (:1437);
+ *   mask = resized > 0 (NaN stays outside); gt_valid = original_valid & (z > g - vz) & (z < g + vz) (:1470)
+ *   scalars  (2)   fp32  {gap_all, rmse}: gap_all = mean of gap_i over the views with a valid' voxel (:1464, :1484),
+ *                        NaN when there is none (the reference divides by zero and raises); rmse = mean over the mask
+ *                        of (depth_mean - g)^2 (no square root, :1445), NaN for an empty mask
+ *   per_view (N,4) fp32  {gap_i (NaN for a skipped view), orig_gap, new_gap, n_reduce} (:1473-1479)
+ *   sums     (N,6) fp64  {sum (gt_valid - weight)^2 over original_valid, n original_valid, n valid',
+ *                        sum (depth_mean - g)^2 over the mask, n mask, n (gt_valid != valid')}: what a caller that
+ *                        splits the views needs to add up
+ *   gt_resized (N,h,w) fp32 or NULL
+ * Every term is formed in fp32 as the reference forms it and added in float64, per wave, per block and over the blocks
+ * in a fixed order without atomics: results are bit-identical from call to call.
+ * workspace (16-byte aligned) >= the query below: the resized map and one partial per block. */
+size_t mvsdet_depth_diagnostics_workspace_bytes(int N, int h, int w, int V);
+int mvsdet_depth_diagnostics_f32(const float* points, const float* projection, const float* depth, const float* dens,
+                                 const int64_t* dd_strides /*HOST[4]*/, const float* depth_mean,
+                                 const int64_t* dm_strides /*HOST[3]*/, const float* gt_depth,
+                                 const int64_t* gt_strides /*HOST[3]*/, float* scalars, float* per_view, double* sums,
+                                 float* gt_resized, void* workspace, size_t workspace_bytes, int N, int h, int w, int V,
+                                 int J, int Hg, int Wg, float vz, mvsdet_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The cost network's 3x3x3 convolutions on the bf16 matrix cores, fp32 operands cut into bf16 pieces ("bf16x3":

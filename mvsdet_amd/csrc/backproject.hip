@@ -228,6 +228,208 @@ __global__ __launch_bounds__(kThreads) void backproject_weigh_bwd_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Depth diagnostics of a9 against ground-truth depth (the gt_depth branch of backproject_Weigh, mvsdet.py:1435-1484).
+// Three launches on one stream, no atomics: every block leaves ONE partial at its own index, the last launch adds the
+// partials of a view in ascending block order, so the results do not depend on launch timing.
+//   pixel  one thread per (view, y, x) of the crop: ATen's bilinear resize (align_corners=False) of gt_depth to (h,w) ->
+//          g, staged in the workspace for the voxel pass; (depth_mean - g)^2 where g > 0        (:1437-1445)
+//   voxel  one thread per (view, voxel): project_voxel / depth_window as backproject_weigh_kernel calls them, gt_valid
+//          from g at the voxel's pixel, (gt_valid - weight)^2 and the counts                   (:1468-1479)
+//   finish sums, means and the mean over the views that kept a voxel                           (:1464-1465, :1484)
+// Terms are formed in fp32 as the reference forms them and added in float64; counts are integers.
+// ---------------------------------------------------------------------------------------------
+struct DiagPixelPartial {
+    double sq;
+    long long n;
+};
+struct DiagVoxelPartial {
+    double gap;
+    int n_orig, n_valid, n_neq, n_gt;
+};
+
+// at::native::compute_source_index_and_lambda (UpSample.h) in fp32.  The source index is ONE fused multiply-add, as the
+// CPU build of ATen contracts `scale * (dst + 0.5f) - 0.5f`.
+__device__ __forceinline__ void resize_taps(int dst, float scale, int in, int out, int& i0, int& i1, float& l0, float& l1) {
+    if (in == out) {
+        i0 = i1 = dst;
+        l0 = 1.0f;
+        l1 = 0.0f;
+        return;
+    }
+    float src = fmaf(scale, (float)dst + 0.5f, -0.5f);
+    if (src < 0.0f) src = 0.0f;
+    i0 = min((int)floorf(src), in - 1);
+    l1 = fminf(fmaxf(src - (float)i0, 0.0f), 1.0f);
+    i1 = i0 + (i0 < in - 1 ? 1 : 0);
+    l0 = 1.0f - l1;
+}
+
+// Sum over the block in a fixed order: lanes by halving shuffles, then waves 0..3 by thread 0 (its return value counts).
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) v = v + __shfl_down(v, o, kWave);
+    return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) v = v + __shfl_down(v, o, kWave);
+    return v;
+}
+
+__global__ __launch_bounds__(kThreads) void depth_diag_pixel_kernel(
+    const float* __restrict__ gt, int64_t gs0, int64_t gs1, int64_t gs2, const float* __restrict__ dmean, int64_t ms0,
+    int64_t ms1, int64_t ms2, float* __restrict__ g_stage, float* __restrict__ gt_resized,
+    DiagPixelPartial* __restrict__ part, int h, int w, int Hg, int Wg, float scale_y, float scale_x) {
+    __shared__ double s_sq[kThreads / kWave];
+    __shared__ int s_n[kThreads / kWave];
+    const int p = blockIdx.x * kThreads + threadIdx.x;
+    const int i = blockIdx.y;
+    float term = 0.0f;
+    int in_mask = 0;
+    if (p < h * w) {
+        const int y = p / w, x = p - y * w;
+        int y0, y1, x0, x1;
+        float ly0, ly1, lx0, lx1;
+        resize_taps(y, scale_y, Hg, h, y0, y1, ly0, ly1);
+        resize_taps(x, scale_x, Wg, w, x0, x1, lx0, lx1);
+        const float* src = gt + (int64_t)i * gs0;
+        const float a = src[(int64_t)y0 * gs1 + (int64_t)x0 * gs2], b = src[(int64_t)y0 * gs1 + (int64_t)x1 * gs2];
+        const float c = src[(int64_t)y1 * gs1 + (int64_t)x0 * gs2], d = src[(int64_t)y1 * gs1 + (int64_t)x1 * gs2];
+        const float g = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d);
+        const size_t o = (size_t)i * h * w + p;
+        g_stage[o] = g;
+        if (gt_resized) gt_resized[o] = g;
+        if (g > 0.0f) {  // NaN fails the test and stays outside the mask (:1444)
+            const float e = dmean[(int64_t)i * ms0 + (int64_t)y * ms1 + (int64_t)x * ms2] - g;
+            term = e * e;
+            in_mask = 1;
+        }
+    }
+    const double sq = wave_sum((double)term);
+    const int n = wave_sum(in_mask);
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    if (lane == 0) {
+        s_sq[wave] = sq;
+        s_n[wave] = n;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        DiagPixelPartial r = {0.0, 0};
+        for (int k = 0; k < kThreads / kWave; ++k) {
+            r.sq = r.sq + s_sq[k];
+            r.n += s_n[k];
+        }
+        part[(size_t)i * gridDim.x + blockIdx.x] = r;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void depth_diag_voxel_kernel(
+    const float* __restrict__ points, const float* __restrict__ projection, const float* __restrict__ depth,
+    const float* __restrict__ dens, int64_t ds0, int64_t ds1, int64_t ds2, int64_t ds3, const float* __restrict__ g_stage,
+    DiagVoxelPartial* __restrict__ part, int h, int w, int V, int J, float vz) {
+    __shared__ double s_gap[kThreads / kWave];
+    __shared__ int s_cnt[kThreads / kWave][4];
+    const int v = blockIdx.x * kThreads + threadIdx.x;
+    const int i = blockIdx.y;
+    float term = 0.0f;
+    int n_orig = 0, n_valid = 0, n_neq = 0, n_gt = 0;
+    if (v < V) {
+        float xr, yr, z, wgt = 0.0f, psum;
+        int arg;
+        const bool orig = project_voxel(projection + (size_t)i * 12, points[v], points[(size_t)V + v],
+                                        points[2 * (size_t)V + v], h, w, xr, yr, z);
+        if (orig) {
+            const int xi = (int)xr, yi = (int)yr;
+            const bool ok = depth_window(depth + (int64_t)i * ds0, dens + (int64_t)i * ds0, ds1, ds2, ds3, J, yi, xi, z, vz,
+                                         wgt, psum, arg);
+            const float g = g_stage[((size_t)i * h + yi) * w + xi];
+            const bool gt_valid = (z > g - vz) && (z < g + vz);   // :1470-1471
+            const float e = (gt_valid ? 1.0f : 0.0f) - wgt;       // :1473
+            term = e * e;
+            n_orig = 1;
+            n_valid = ok ? 1 : 0;
+            n_gt = gt_valid ? 1 : 0;
+            n_neq = (gt_valid != ok) ? 1 : 0;
+        }
+    }
+    const double gap = wave_sum((double)term);
+    const int c0 = wave_sum(n_orig), c1 = wave_sum(n_valid), c2 = wave_sum(n_neq), c3 = wave_sum(n_gt);
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    if (lane == 0) {
+        s_gap[wave] = gap;
+        s_cnt[wave][0] = c0;
+        s_cnt[wave][1] = c1;
+        s_cnt[wave][2] = c2;
+        s_cnt[wave][3] = c3;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        DiagVoxelPartial r = {0.0, 0, 0, 0, 0};
+        for (int k = 0; k < kThreads / kWave; ++k) {
+            r.gap = r.gap + s_gap[k];
+            r.n_orig += s_cnt[k][0];
+            r.n_valid += s_cnt[k][1];
+            r.n_neq += s_cnt[k][2];
+            r.n_gt += s_cnt[k][3];
+        }
+        part[(size_t)i * gridDim.x + blockIdx.x] = r;
+    }
+}
+
+// One block.  Thread t adds the partials of views t, t + 256, ... in ascending block order; thread 0 then walks the views in
+// ascending order for the two scalars: gap_all the way the reference adds its list (fp32, :1484), rmse from the float64 sums.
+__global__ __launch_bounds__(kThreads) void depth_diag_finish_kernel(
+    const DiagPixelPartial* __restrict__ ppart, const DiagVoxelPartial* __restrict__ vpart, float* __restrict__ scalars,
+    float* __restrict__ per_view, double* __restrict__ sums, int N, int V, int pblocks, int vblocks) {
+    const float nan = __int_as_float(0x7fc00000);
+    for (int i = threadIdx.x; i < N; i += kThreads) {
+        double gap = 0.0, sq = 0.0;
+        long long n_orig = 0, n_valid = 0, n_neq = 0, n_gt = 0, n_mask = 0;
+        for (int b = 0; b < vblocks; ++b) {
+            const DiagVoxelPartial r = vpart[(size_t)i * vblocks + b];
+            gap = gap + r.gap;
+            n_orig += r.n_orig;
+            n_valid += r.n_valid;
+            n_neq += r.n_neq;
+            n_gt += r.n_gt;
+        }
+        for (int b = 0; b < pblocks; ++b) {
+            const DiagPixelPartial r = ppart[(size_t)i * pblocks + b];
+            sq = sq + r.sq;
+            n_mask += r.n;
+        }
+        double* s = sums + (size_t)i * 6;
+        s[0] = gap;
+        s[1] = (double)n_orig;
+        s[2] = (double)n_valid;
+        s[3] = sq;
+        s[4] = (double)n_mask;
+        s[5] = (double)n_neq;
+        float* pv = per_view + (size_t)i * 4;
+        pv[0] = n_valid > 0 ? (float)(gap / (double)n_orig) : nan;   // a view without a valid' voxel is skipped (:1464)
+        pv[1] = (float)((double)(n_orig - n_gt) / (double)V);        // gt_valid is a subset of original_valid (:1477)
+        pv[2] = (float)((double)n_neq / (double)V);                  // :1478
+        pv[3] = (float)(n_orig - n_valid);                           // :1479
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float acc = 0.0f;
+        int kept = 0;
+        double sq = 0.0, n_mask = 0.0;
+        for (int i = 0; i < N; ++i) {
+            if (sums[(size_t)i * 6 + 2] > 0.0) {
+                acc = acc + per_view[(size_t)i * 4];
+                ++kept;
+            }
+            sq = sq + sums[(size_t)i * 6 + 3];
+            n_mask = n_mask + sums[(size_t)i * 6 + 4];
+        }
+        scalars[0] = kept > 0 ? acc / (float)kept : nan;   // the reference divides by len([]) and raises; NaN here
+        scalars[1] = (float)(sq / n_mask);                 // an empty mask: 0 / 0 = NaN, as torch.mean of nothing
+    }
+}
+
 }  // namespace mvsdet
 
 using namespace mvsdet;
@@ -324,4 +526,50 @@ extern "C" int mvsdet_backproject_weigh_mean_bwd_f32(const float* feat, const in
     MVS_REQUIRE(count, "backproject_weigh_mean_bwd: NULL count");
     return launch_stage3_bwd("backproject_weigh_mean_bwd", feat, fs, points, projection, depth, dens, ds, count, g, gfeat,
                              gdens, N, C, h, w, V, J, vz, (hipStream_t)stream);
+}
+
+// workspace of the depth diagnostics: the resized map, then one partial per (view, pixel block) and (view, voxel block)
+static size_t diag_stage_bytes(int N, int h, int w) { return ((size_t)N * h * w * sizeof(float) + 15) / 16 * 16; }
+static int diag_blocks(size_t n) { return (int)((n + kThreads - 1) / kThreads); }
+
+extern "C" size_t mvsdet_depth_diagnostics_workspace_bytes(int N, int h, int w, int V) {
+    if (N <= 0 || h <= 0 || w <= 0 || V <= 0) return 0;
+    return diag_stage_bytes(N, h, w) + (size_t)N * diag_blocks((size_t)h * w) * sizeof(DiagPixelPartial) +
+           (size_t)N * diag_blocks((size_t)V) * sizeof(DiagVoxelPartial);
+}
+
+extern "C" int mvsdet_depth_diagnostics_f32(const float* points, const float* projection, const float* depth,
+                                            const float* dens, const int64_t* ds, const float* depth_mean,
+                                            const int64_t* ms, const float* gt_depth, const int64_t* gs, float* scalars,
+                                            float* per_view, double* sums, float* gt_resized, void* workspace,
+                                            size_t workspace_bytes, int N, int h, int w, int V, int J, int Hg, int Wg,
+                                            float vz, mvsdet_stream_t stream) {
+    MVS_REQUIRE(points && projection && depth && dens && ds && depth_mean && ms && gt_depth && gs && scalars && per_view &&
+                    sums && workspace, "depth_diagnostics: NULL pointer");
+    if (int rc = check_stage3("depth_diagnostics", N, 1, h, w, V, J)) return rc;
+    MVS_REQUIRE(Hg >= 1 && Wg >= 1, "depth_diagnostics: bad gt_depth shape %dx%d", Hg, Wg);
+    MVS_REQUIRE((size_t)h * w < (size_t)INT32_MAX, "depth_diagnostics: crop %dx%d exceeds 2^31 pixels", h, w);
+    MVS_REQUIRE(((uintptr_t)workspace & 15) == 0, "depth_diagnostics: workspace must be 16-byte aligned");
+    const size_t need = mvsdet_depth_diagnostics_workspace_bytes(N, h, w, V);
+    if (workspace_bytes < need) {
+        set_error("depth_diagnostics: workspace %zu < %zu bytes", workspace_bytes, need);
+        return MVSDET_ERR_WORKSPACE;
+    }
+    const int pblocks = diag_blocks((size_t)h * w), vblocks = diag_blocks((size_t)V);
+    float* g_stage = (float*)workspace;
+    DiagPixelPartial* ppart = (DiagPixelPartial*)((char*)workspace + diag_stage_bytes(N, h, w));
+    DiagVoxelPartial* vpart = (DiagVoxelPartial*)(ppart + (size_t)N * pblocks);
+    hipStream_t st = (hipStream_t)stream;
+    // at::native::area_pixel_compute_scale: (float)input_size / output_size
+    const float scale_y = (float)Hg / (float)h, scale_x = (float)Wg / (float)w;
+    hipLaunchKernelGGL(depth_diag_pixel_kernel, dim3(pblocks, N), dim3(kThreads), 0, st, gt_depth, gs[0], gs[1], gs[2],
+                       depth_mean, ms[0], ms[1], ms[2], g_stage, gt_resized, ppart, h, w, Hg, Wg, scale_y, scale_x);
+    MVS_LAUNCH_CHECK("depth_diagnostics (pixels)");
+    hipLaunchKernelGGL(depth_diag_voxel_kernel, dim3(vblocks, N), dim3(kThreads), 0, st, points, projection, depth, dens,
+                       ds[0], ds[1], ds[2], ds[3], g_stage, vpart, h, w, V, J, vz);
+    MVS_LAUNCH_CHECK("depth_diagnostics (voxels)");
+    hipLaunchKernelGGL(depth_diag_finish_kernel, dim3(1), dim3(kThreads), 0, st, ppart, vpart, scalars, per_view, sums, N, V,
+                       pblocks, vblocks);
+    MVS_LAUNCH_CHECK("depth_diagnostics (finish)");
+    return MVSDET_OK;
 }

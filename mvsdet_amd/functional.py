@@ -152,12 +152,34 @@ def homo_warping(src_fea: Tensor, src_proj: Tensor, ref_proj: Tensor, depth_valu
 
 
 # ------------------------------------------------------------------------------------------- a9
+def depth_diagnostics(points: Tensor, projection: Tensor, est_depth: Tensor, est_dens: Tensor, depth_mean: Tensor,
+                      gt_depth: Tensor, vz: float):
+    """The gt_depth branch of backproject_Weigh (mvsdet.py:1435-1484) -> (gap_all, rmse, per_view (N,4), gt_resized (N,h,w)):
+    0-dim fp32 tensors on the features' device and the per-view table {gap_i, orig_gap, new_gap, n_reduce}, one operator call,
+    no host synchronisation.  gap_all is NaN where the reference raises (no view keeps a voxel: it divides by len([]))."""
+    depth_mean, gt_depth = amp_fp32(depth_mean, gt_depth)
+    dev = est_depth.device
+    if gt_depth.device != dev:
+        gt_depth = gt_depth.to(dev, non_blocking=True)
+    if depth_mean.device != dev:
+        depth_mean = depth_mean.to(dev, non_blocking=True)
+    scalars, per_view, _, gt_resized = ops.depth_diagnostics(points, projection, est_depth, est_dens, depth_mean, gt_depth, vz)
+    return scalars[0], scalars[1], per_view, gt_resized
+
+
 def backproject_Weigh(features: Tensor, points: Tensor, projection: Tensor, depth: Tensor, voxel_size: Sequence[float],
                       prob: Tensor, gt_depth=None, save_dir=None, img_meta=None, depth_mean=None):
     """mvsdet.py:1372-1492.  features (N,C,h,w); points (3,X,Y,Z); projection (N,3,4);
-    depth, prob (N, h*w, 1, J) -> (volume (N,C,X,Y,Z), valid (N,1,X,Y,Z) bool, gap_all, rmse)."""
+    depth, prob (N, h*w, 1, J) -> (volume (N,C,X,Y,Z), valid (N,1,X,Y,Z) bool, gap_all, rmse).
+    With gt_depth (N,Hg,Wg) and depth_mean (N,h,w) the last two are the reference's "weight_gap" and "src_rmse" as 0-dim tensors
+    on the features' device (ops.depth_diagnostics); volume and valid do not depend on gt_depth.  Without it they are the
+    reference's placeholders torch.tensor(1.)."""
     if gt_depth is not None:
-        raise NotImplementedError("the gt_depth debug branch (mvsdet.py:1435-1481) is outside the hot path")
+        if save_dir is not None:
+            raise NotImplementedError("backproject_Weigh: save_dir needs the reference's depth-image dumper (save_src_depth, "
+                                      "mvsdet.py:1448-1453), which is outside the hot path; pass save_dir=None")
+        if depth_mean is None:
+            raise ValueError("backproject_Weigh: gt_depth needs depth_mean, the (N,h,w) depth expectation (mvsdet.py:1443)")
     features, points, projection, depth, prob = amp_fp32(features, points, projection, depth, prob)
     n, c, h, w = features.shape
     nx, ny, nz = points.shape[-3:]
@@ -165,13 +187,23 @@ def backproject_Weigh(features: Tensor, points: Tensor, projection: Tensor, dept
     # (N, h*w, 1, J) is a view of (N,J,h,w): hand the kernel that view, no copy (mvsdet.py:1393-1395)
     est_depth = depth.reshape(n, h, w, j).permute(0, 3, 1, 2)
     est_dens = prob.reshape(n, h, w, j).permute(0, 3, 1, 2)
-    if LAZY_WARP and (features.is_cuda or LAZY_ANY_DEVICE) and features.dtype == torch.float32:
+    vz = float(voxel_size[-1])
+    lazy = LAZY_WARP and (features.is_cuda or LAZY_ANY_DEVICE) and features.dtype == torch.float32
+    if gt_depth is not None:
+        # launched now on both routes: two scalars, nothing to defer (the lifting below stays deferred on the lazy route)
+        if lazy:
+            from . import lazywarp
+            lazywarp.stats["diagnostics"] += 1
+        gap_all, rmse = depth_diagnostics(points, projection, est_depth, est_dens, depth_mean, gt_depth, vz)[:2]
+    else:
+        gap_all, rmse = torch.tensor(1.), torch.tensor(1.)
+    if lazy:
         # inside the patched reference: `volume.sum(dim=0)` / `valid.sum(dim=0)` (mvsdet.py:509-511) then cost one launch
         # of the fused lifting kernel instead of a (N,C,X,Y,Z) volume and a reduction over it (lazywarp.py)
         from . import lazywarp
-        volume, valid = lazywarp.lazy_backproject(features, points, projection, est_depth, est_dens, float(voxel_size[-1]))
-        return volume, valid, torch.tensor(1.), torch.tensor(1.)
-    volume, valid = ops.backproject_weigh(features, points, projection, est_depth, est_dens, float(voxel_size[-1]))
+        volume, valid = lazywarp.lazy_backproject(features, points, projection, est_depth, est_dens, vz)
+        return volume, valid, gap_all, rmse
+    volume, valid = ops.backproject_weigh(features, points, projection, est_depth, est_dens, vz)
     volume = volume.view(n, c, nx, ny, nz)
     valid = valid.view(n, 1, nx, ny, nz)
-    return volume, valid, torch.tensor(1.), torch.tensor(1.)
+    return volume, valid, gap_all, rmse

@@ -499,17 +499,27 @@ class MVSDetHotPath:
             raise ValueError("forward_scene needs `cost_logits` when no cost_regularization module is set")
         return geo, packed, variance, cost_logits
 
-    def _lift_tail(self, feature, geo, packed, variance, cost_logits) -> "SceneOutputs":
-        """a5..a10 of one scene (mvsdet.py:470-515) on the current stream."""
+    def _lift_tail(self, feature, geo, packed, variance, cost_logits, gt_depth: Optional[Tensor] = None) -> "SceneOutputs":
+        """a5..a10 of one scene (mvsdet.py:470-515) on the current stream; with `gt_depth` the depth diagnostics of the lifting
+        block (the gt_depth branch of backproject_Weigh, :1435-1484) behind them, on the same stream."""
         prob, off, est_depth, est_dens, est_idx, avg_depth = self.depth_distribution(cost_logits)
         volume_mean, valid = self.lift(feature, packed, geo, est_depth, est_dens)
         h, w = geo.height, geo.width
-        return SceneOutputs(volume=volume_mean, valid=valid, variance=variance, prob_volume=prob, off_pred=off,
-                            est_depth=est_depth[:, :, :h, :w], est_densities=est_dens[:, :, :h, :w],
-                            depth_coding=avg_depth[:, :h, :w].unsqueeze(1), geometry=geo,
-                            # mvsdet.py:582 `opacity = torch.max(prob_volume, dim=1)[0]`: the first of the sorted top-k values IS
-                            # that maximum (the depth-distribution kernel has it in registers); uncropped like prob_volume
-                            opacity=est_dens[:, 0])
+        out = SceneOutputs(volume=volume_mean, valid=valid, variance=variance, prob_volume=prob, off_pred=off,
+                         est_depth=est_depth[:, :, :h, :w], est_densities=est_dens[:, :, :h, :w],
+                         depth_coding=avg_depth[:, :h, :w].unsqueeze(1), geometry=geo,
+                         # mvsdet.py:582 `opacity = torch.max(prob_volume, dim=1)[0]`: the first of the sorted top-k values IS
+                         # that maximum (the depth-distribution kernel has it in registers); uncropped like prob_volume
+                         opacity=est_dens[:, 0])
+        if gt_depth is not None:
+            gap, rmse, per_view, gt_resized = F_.depth_diagnostics(geo.points, geo.projection, est_depth[:, :, :h, :w],
+                                                                   est_dens[:, :, :h, :w], avg_depth[:, :h, :w], gt_depth,
+                                                                   float(self.voxel_size[-1]))
+            out._put("weight_gap", gap)                 # predictions[i].weight_gap / .src_rmse of MVSDet.predict (:1054-1058)
+            out._put("src_rmse", rmse)
+            out._put("depth_diagnostics", per_view)     # (N,4) {gap_i, orig_gap, new_gap, n_reduce} (:1473-1479)
+            out._put("gt_depth_resized", gt_resized)
+        return out
 
     # name -> (detector tail on the side stream, view streams of the cost network beside it; None = the module's own setting)
     OVERLAP_ROUTES = {"one": (False, None), "side1": (True, 1), "side2": (True, 2)}
@@ -612,14 +622,17 @@ class MVSDetHotPath:
         return predict_head_maps(*head_out, valid, img_metas, self.test_cfg, rotated=bool(getattr(self.bbox_head, "arkit_head", False)))
 
     def forward_scene(self, feature: Tensor, img_meta: dict, cost_logits: Optional[Tensor] = None,
-                      geo: Optional[SceneGeometry] = None) -> dict:
+                      geo: Optional[SceneGeometry] = None, gt_depth: Optional[Tensor] = None) -> dict:
         """One scene through a1..a10.  `cost_logits` (N,2,D,Hf,Wf) stands in for the cost regularisation
         network's output when `self.cost_regularization` is None (benchmarks / parity tests).
         With `pitched_variance = "auto"` (default) `out["variance"]` may be a NON-CONTIGUOUS (N,C,D,H,W) view of a buffer whose
         rows are `variance_row_pitch(W)` elements apart (same values; only for widths 16 mod 32 with 48+ planes, and only when
         the consumer is None or `CostRegNet3DGS`): `.view()` on it raises; set `pitched_variance = False` for a contiguous one.
         The result is a `SceneOutputs`: with `overlap_detector` a value read from it makes the reading stream wait for the side
-        stream's event first."""
+        stream's event first.
+        `gt_depth` (N,Hg,Wg), any size: the result gains `weight_gap` and `src_rmse` (0-dim device tensors: what the reference's
+        backproject_Weigh returns with gt_depth), `depth_diagnostics` (N,4) {gap_i, orig_gap, new_gap, n_reduce} per view and
+        `gt_depth_resized` (N,h,w); they are made in the tail, on the stream the lifting runs on.  None: no such key."""
         route, on_side, net_streams, tuning = self._route(feature, cost_logits)
         watching = tuning is not None and tuning["choice"] is not None   # a kept side route: `_watch`
         geo, packed, variance, cost_logits = self._front(feature, img_meta, cost_logits, geo, net_streams)
@@ -629,7 +642,7 @@ class MVSDetHotPath:
             self._tune_mark(tuning, route, variance.device)
 
         def tail():
-            out = self._lift_tail(feature, geo, packed, variance, cost_logits)
+            out = self._lift_tail(feature, geo, packed, variance, cost_logits, gt_depth)
             if self.neck_3d is not None:   # the reference stacks the scenes of a batch first (batch_size = 1 per GPU): forward_scenes
                 out._put("neck", self.neck_3d(out.raw("volume").unsqueeze(0)))
                 if self.bbox_head is not None:
@@ -660,13 +673,14 @@ class MVSDetHotPath:
             self._tune_mark(tuning, route, dev, side_done=done)
         # (`lift` reads geo.projection -- a view of the ONE uploaded staging buffer, which neighbor_ids, proj_rel and depth_values
         # share: recording any view records the whole block -- and geo.points, a block of its own)
-        self._keep_for(side, cost_logits, packed, feature, geo.projection, geo.points)
+        self._keep_for(side, cost_logits, packed, feature, geo.projection, geo.points, gt_depth)
         out._put("ready", done)
         out._put("detector_ready", done)
         return out
 
     def forward_scenes(self, features: Sequence[Tensor], img_metas: Sequence[dict],
-                       cost_logits: Optional[Sequence[Tensor]] = None, keep_variance: bool = False) -> dict:
+                       cost_logits: Optional[Sequence[Tensor]] = None, keep_variance: bool = False,
+                       gt_depths: Optional[Sequence[Tensor]] = None) -> dict:
         """A BATCH of scenes the way mvsdet.py:681-698 runs it: every scene through a1..a10 on its own, then `neck_3d` (and
         `bbox_head`) ONCE on the stacked (B,C,X,Y,Z) volume -- one 40 x 40 x 16 volume is 200 blocks for 256 CUs at the neck's
         largest level and a few dozen at the others; a batch fills the chip (throughput runs, `samples_per_gpu` > 1).
@@ -677,10 +691,13 @@ class MVSDetHotPath:
         scene has to keep its tail on the caller's stream (autograd), every tail and the detector stay there -- a detector on
         the side stream would stack volumes the caller's stream is still writing.
         A scene's `variance` (2.4 GB at the reference-true shape) is dropped as soon as its cost network has read it unless
-        `keep_variance`: B of them alive until the batch returns is what would bound B."""
+        `keep_variance`: B of them alive until the batch returns is what would bound B.
+        `gt_depths`: one (N,Hg,Wg) ground-truth depth per scene; every scene's holder then carries the keys `forward_scene`
+        adds with `gt_depth`."""
         B = len(features)
-        if B == 0 or len(img_metas) != B or (cost_logits is not None and len(cost_logits) != B):
-            raise ValueError("forward_scenes: one img_meta (and one cost_logits, if given) per feature tensor")
+        if B == 0 or len(img_metas) != B or (cost_logits is not None and len(cost_logits) != B) \
+                or (gt_depths is not None and len(gt_depths) != B):
+            raise ValueError("forward_scenes: one img_meta (and one cost_logits / gt_depth, if given) per feature tensor")
         dev = features[0].device
         for i in range(B):                      # the camera algebra of every scene of the batch starts now, on the worker thread
             self.prefetch_scene(img_metas[i], dev)
@@ -693,11 +710,12 @@ class MVSDetHotPath:
         outs, side, cur = [], None, None
         for i in range(B):
             logits_i = None if cost_logits is None else cost_logits[i]
+            gt_i = None if gt_depths is None else gt_depths[i]
             geo, packed, variance, logits_i = self._front(features[i], img_metas[i], logits_i, None, net_streams)
             if not keep_variance and not (grad and variance.requires_grad):
                 variance = variance.new_empty(0)   # the holder's slot; the volume itself goes back to the allocator
             if one_stream:
-                outs.append(self._lift_tail(features[i], geo, packed, variance, logits_i))
+                outs.append(self._lift_tail(features[i], geo, packed, variance, logits_i, gt_i))
                 continue
             cur = torch.cuda.current_stream(dev)
             side = self._side_stream(dev)
@@ -705,8 +723,8 @@ class MVSDetHotPath:
             ready.record(cur)
             with torch.cuda.stream(side):
                 side.wait_event(ready)
-                outs.append(self._lift_tail(features[i], geo, packed, variance, logits_i))
-            self._keep_for(side, logits_i, packed, features[i], geo.projection, geo.points)
+                outs.append(self._lift_tail(features[i], geo, packed, variance, logits_i, gt_i))
+            self._keep_for(side, logits_i, packed, features[i], geo.projection, geo.points, gt_i)
 
         def detector():
             res = SceneOutputs(scenes=outs)

@@ -6,7 +6,8 @@ HIP-backed mirrors of this package -- same names, same signatures, same return a
 projects/NeRF-Det/configs/mvsdet_res50_2x_low_res.py:
 
     homo_warping           (imported at mvsdet.py:31 from mvs_models/module.py:105)
-    backproject_Weigh      (mvsdet.py:1372)
+    backproject_Weigh      (mvsdet.py:1372)      -- with gt_depth (extract_feat(depth=[...]), the configs' `use_depth`) it also
+                                                  returns "weight_gap" and "src_rmse" as device scalars (ops.depth_diagnostics)
     get_nearest_pose_ids   (mvsdet.py:67)      -- same ATen ops, kept for completeness
     get_points             (mvsdet.py:1316)
     MVSDet.sample_depth_prob / MVSDet.compute_avg_depth / MVSDet.collect_proj  (mvsdet.py:266, 298, 249)

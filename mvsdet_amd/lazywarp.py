@@ -19,7 +19,9 @@ import torch
 from torch import Tensor
 
 _tls = threading.local()
-stats = {"fused": 0, "materialized": 0}
+# "diagnostics": calls of the gt_depth branch of backproject_Weigh on the deferred route (functional.depth_diagnostics: launched
+# at once -- it returns two scalars -- while the lifting of the same call stays deferred)
+stats = {"fused": 0, "materialized": 0, "diagnostics": 0}
 
 
 def note_neighbor_ids(ids: Tensor) -> None:

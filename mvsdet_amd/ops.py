@@ -745,6 +745,64 @@ def _bp_bwd(ctx, g_volume, g_valid):
 backproject_weigh.register_autograd(_bp_bwd, setup_context=_bp_setup)
 
 
+# ------------------------------------------------------------------------------------------- a9 against ground-truth depth
+def _strides3(t: Tensor) -> ctypes.Array:
+    """HOST int64[3] with the element strides of a 3-D tensor."""
+    return (ctypes.c_int64 * 3)(*[int(v) for v in t.stride()])
+
+
+@torch.library.custom_op(f"{_NS}::depth_diagnostics", mutates_args=(), device_types="cuda")
+def depth_diagnostics(points: Tensor, projection: Tensor, est_depth: Tensor, est_dens: Tensor, depth_mean: Tensor,
+                      gt_depth: Tensor, vz: float) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The gt_depth branch of backproject_Weigh (mvsdet.py:1435-1484): points (3,X,Y,Z); projection (N,3,4); est_depth / est_dens
+    (N,J,h,w) any strides; depth_mean (N,h,w) any strides (the cropped depth expectation); gt_depth (N,Hg,Wg) any strides, any size
+    -> scalars (2) {gap_all ("weight_gap"), rmse ("src_rmse")}, per_view (N,4) {gap_i, orig_gap, new_gap, n_reduce}, sums (N,6)
+    float64 (include/mvsdet_hip.h), gt_resized (N,h,w).  Three launches on the current stream, no host synchronisation; no autograd
+    (the reference runs the branch under no_grad).  gap_all is NaN when no view keeps a voxel (the reference raises there)."""
+    _req(points, "points")
+    _req(projection, "projection", dim=3)
+    _req(est_depth, "est_depth", dim=4)
+    _req(est_dens, "est_dens", dim=4)
+    _req(depth_mean, "depth_mean", dim=3)
+    _req(gt_depth, "gt_depth", dim=3)
+    N, J, h, w = est_depth.shape
+    if points.shape[0] != 3:
+        raise ValueError("depth_diagnostics: points must be (3, ...)")
+    V = points.numel() // 3
+    if projection.shape != (N, 3, 4) or est_dens.shape != (N, J, h, w):
+        raise ValueError(f"depth_diagnostics: projection {tuple(projection.shape)} / est_dens {tuple(est_dens.shape)} do not match "
+                         f"est_depth {tuple(est_depth.shape)}")
+    if depth_mean.shape != (N, h, w) or gt_depth.shape[0] != N:
+        raise ValueError(f"depth_diagnostics: depth_mean {tuple(depth_mean.shape)} must be ({N},{h},{w}) and gt_depth "
+                         f"{tuple(gt_depth.shape)} ({N},Hg,Wg)")
+    if est_depth.stride() != est_dens.stride():
+        est_depth, est_dens = est_depth.contiguous(), est_dens.contiguous()
+    points, projection = points.contiguous(), projection.contiguous()
+    Hg, Wg = int(gt_depth.shape[1]), int(gt_depth.shape[2])
+    dev = est_depth.device
+    lib = _lib.load()
+    scalars = torch.empty((2,), dtype=torch.float32, device=dev)
+    per_view = torch.empty((N, 4), dtype=torch.float32, device=dev)
+    sums = torch.empty((N, 6), dtype=torch.float64, device=dev)
+    gt_resized = torch.empty((N, h, w), dtype=torch.float32, device=dev)
+    ws_bytes = int(lib.mvsdet_depth_diagnostics_workspace_bytes(N, h, w, V))
+    workspace = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mvsdet_depth_diagnostics_f32(
+            _lib.ptr(points), _lib.ptr(projection), _lib.ptr(est_depth), _lib.ptr(est_dens), _lib.strides4(est_depth),
+            _lib.ptr(depth_mean), _strides3(depth_mean), _lib.ptr(gt_depth), _strides3(gt_depth), _lib.ptr(scalars),
+            _lib.ptr(per_view), _lib.ptr(sums), _lib.ptr(gt_resized), _lib.ptr(workspace), ws_bytes, N, h, w, V, J, Hg, Wg, vz,
+            _stream(est_depth)), "depth_diagnostics")
+    return scalars, per_view, sums, gt_resized
+
+
+@depth_diagnostics.register_fake
+def _(points, projection, est_depth, est_dens, depth_mean, gt_depth, vz):
+    N, _, h, w = est_depth.shape
+    return (est_depth.new_empty((2,)), est_depth.new_empty((N, 4)), est_depth.new_empty((N, 6), dtype=torch.float64),
+            est_depth.new_empty((N, h, w)))
+
+
 # ------------------------------------------------------------------------------------------- a9+a10
 @torch.library.custom_op(f"{_NS}::backproject_weigh_mean", mutates_args=(), device_types="cuda")
 def backproject_weigh_mean(features: Tensor, packed: Tensor, points: Tensor, projection: Tensor, est_depth: Tensor,
@@ -1955,7 +2013,9 @@ bn3d_res_relu_train.register_autograd(_bn_res_bwd, setup_context=_bn_res_setup)
 # opt-in and keeps its dtypes: it has no autocast rule.
 AUTOCAST_FP32_OPS = (homo_warp, plane_sweep_variance, plane_sweep_variance_keep, depth_prob_topk, sample_depth_prob,
                      backproject_weigh, backproject_weigh_mean)
-for _op in AUTOCAST_FP32_OPS:
+# the evaluation-only diagnostics of the lifting block run under the same rule (no gradient, so not a forward operator of the path)
+AUTOCAST_FP32_DIAGNOSTICS = (depth_diagnostics,)
+for _op in AUTOCAST_FP32_OPS + AUTOCAST_FP32_DIAGNOSTICS:
     _op.register_autocast("cuda", torch.float32)
 del _op
 
