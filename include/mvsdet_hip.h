@@ -706,6 +706,55 @@ int mvsdet_head_loss_rotated_backward_f32(const float* const* center, const floa
                                           const float* bbox_targets, float gamma, float alpha, const float* coef,
                                           float* const* d_center, float* const* d_bbox, float* const* d_cls, mvsdet_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Indoor detection metrics (mmdet3d's indoor_eval: per-class AP and recall at IoU thresholds; csrc/evalmap.hip) on the caller's
+ * stream, no host synchronisation, no device allocation.  Boxes are the box classes' own rows (x, y, BOTTOM z, dx, dy, dz, yaw),
+ * fp32; labels int64 in [0, n_labels).  The IoU is BaseInstance3DBoxes.overlaps as a mathematical function in float32 (height
+ * overlap x exact area of the intersection of the two footprints, extents clamped to >= 1e-4, over clamp(v1 + v2 - overlap,
+ * 1e-8)); mmcv's box_iou_rotated rounding is not reproduced.  This is NOT iou_bev of mvsdet_bev_iou_rotated_f32.
+ *
+ * State: one DEVICE buffer of mvsdet_eval_state_bytes(n_labels, capacity, gt_capacity) bytes (0: bad sizes), 8-byte aligned,
+ *   cleared by mvsdet_eval_reset; capacity = detections, gt_capacity = ground-truth boxes the evaluator can take in all.  The same
+ *   three sizes go to every call on a state.
+ * mvsdet_eval_match_f32: a batch of B scenes: pred (B,Nmax,7), scores (B,Nmax), labels (B,Nmax), counts (B) int32; gt (B,G,7),
+ *   gt_labels (B,G), gt_counts (B) int32; scene0 = serial number of the batch's first scene, not below the serials already fed.
+ *   Appends one record per detection (score, label, scene, row, global slot of the best-overlapping ground-truth box of its label in
+ *   its scene -- the FIRST of equal IoUs -- and that IoU, -inf without such a box) and adds the ground-truth counts per label.  A
+ *   batch that would run over a capacity, a count that is negative or above Nmax / G, and a serial below the state's set a flag of
+ *   MVSDET_EVAL_FLAG_* in the state and write nothing else; a label outside [0, n_labels) sets MVSDET_EVAL_FLAG_BAD_LABEL.
+ * mvsdet_eval_compute: n_bound = a HOST upper bound of the records fed (<= capacity; fewer records than fed sets
+ *   MVSDET_EVAL_FLAG_BOUND); thresholds: HOST float[n_thr], compared in float32 (iou_max > t).  Visiting order: label, score
+ *   descending (NaN last, -0 = +0), scene serial, row.  Outputs: out_ap (n_thr,n_labels) float32 = the area AP of
+ *   average_precision; out_recall (n_thr,n_labels) float64 = the final recall; out_npos, out_ndet (n_labels) int32; out_first
+ *   (n_labels) int64 = scene << 32 | ground truth << 31 | row where the label was first seen (-1: never), the order of the
+ *   reference's dicts; out_tp (n_thr,n_bound) uint8 = true-positive flag of every record in visiting order; out_order (n_bound)
+ *   int32 = the records' feeding index in visiting order; out_info (4) int32 = records, ground-truth slots, flags, next serial.  A
+ *   label that is predicted and has no ground truth gives NaN AP and recall, as the reference does; a label without predictions 0.
+ *   The state is left as it is: more batches may follow.  Workspace: mvsdet_eval_workspace_bytes(n_labels, n_bound, gt_capacity,
+ *   n_thr) (0: bad sizes), 8-byte aligned.
+ * mvsdet_eval_iou_f32: out (n,m) = the evaluator's IoU of boxes a (n,7) and b (m,7).
+ * ------------------------------------------------------------------------------------------- */
+#define MVSDET_EVAL_MAX_RECORDS (1 << 20) /* 20 bits of a sort key */
+#define MVSDET_EVAL_MAX_LABELS 4095       /* 12 bits of a sort key, all ones kept for padding */
+#define MVSDET_EVAL_MAX_THRESHOLDS 8
+#define MVSDET_EVAL_FLAG_RECORDS_FULL 1
+#define MVSDET_EVAL_FLAG_SLOTS_FULL 2
+#define MVSDET_EVAL_FLAG_BAD_COUNT 4
+#define MVSDET_EVAL_FLAG_SERIAL 8
+#define MVSDET_EVAL_FLAG_BAD_LABEL 16
+#define MVSDET_EVAL_FLAG_BOUND 32
+size_t mvsdet_eval_state_bytes(int n_labels, int capacity, int gt_capacity);
+size_t mvsdet_eval_workspace_bytes(int n_labels, int n_bound, int gt_capacity, int n_thr);
+int mvsdet_eval_reset(void* state, size_t state_bytes, int n_labels, int capacity, int gt_capacity, mvsdet_stream_t stream);
+int mvsdet_eval_match_f32(void* state, int n_labels, int capacity, int gt_capacity, const float* pred, const float* scores,
+                          const int64_t* labels, const int* counts, int B, int Nmax, const float* gt, const int64_t* gt_labels,
+                          const int* gt_counts, int G, int scene0, mvsdet_stream_t stream);
+int mvsdet_eval_compute(const void* state, int n_labels, int capacity, int gt_capacity, int n_bound, const float* thresholds,
+                        int n_thr, float* out_ap, double* out_recall, int* out_npos, int* out_ndet, int64_t* out_first,
+                        unsigned char* out_tp, int* out_order, int* out_info, void* workspace, size_t workspace_bytes,
+                        mvsdet_stream_t stream);
+int mvsdet_eval_iou_f32(const float* a, int n, const float* b, int m, float* out, mvsdet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -134,6 +134,13 @@ SIGNATURES = {
                                      _vp],
     "mvsdet_head_loss_rotated_backward_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp,
                                               _vp, _vp, _vp],
+    "mvsdet_eval_state_bytes": [_i, _i, _i],
+    "mvsdet_eval_workspace_bytes": [_i, _i, _i, _i],
+    "mvsdet_eval_reset": [_vp, _sz, _i, _i, _i, _vp],
+    "mvsdet_eval_match_f32": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
+    "mvsdet_eval_compute": [_vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_float), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                            _vp],
+    "mvsdet_eval_iou_f32": [_vp, _i, _vp, _i, _vp, _vp],
 }
 _RESTYPE = {"mvsdet_last_error": ctypes.c_char_p, "mvsdet_conv3d_k3_bf16x3_stats_parts": ctypes.c_size_t, "mvsdet_convT3d_k3_s2_bf16x3_stats_parts": ctypes.c_size_t, "mvsdet_gemm_split_weight_bytes": ctypes.c_size_t, "mvsdet_neck_gemm_dw_partial_bytes": ctypes.c_size_t, "mvsdet_scl_bytes": ctypes.c_size_t, "mvsdet_pscl_bytes": ctypes.c_size_t,
             "mvsdet_split_conv_weight_bytes": ctypes.c_size_t, "mvsdet_packed_bytes": ctypes.c_size_t,
@@ -146,6 +153,7 @@ _RESTYPE = {"mvsdet_last_error": ctypes.c_char_p, "mvsdet_conv3d_k3_bf16x3_stats
             "mvsdet_conv3d_k3_bf16x3_workspace_bytes": ctypes.c_size_t,
             "mvsdet_conv3d_k3_s2_bf16x3_workspace_bytes": ctypes.c_size_t,
             "mvsdet_depth_diagnostics_workspace_bytes": ctypes.c_size_t,
+            "mvsdet_eval_state_bytes": ctypes.c_size_t, "mvsdet_eval_workspace_bytes": ctypes.c_size_t,
             "mvsdet_conv3d_k3_mfma_workspace_bytes": ctypes.c_size_t, "mvsdet_bn3d_workspace_bytes": ctypes.c_size_t}
 
 

@@ -49,6 +49,7 @@
 // where the floor's side is taken (no gradient through the union; ATen would halve it).  The BEV conventions above are unchanged.
 #include "common.h"
 #include "head_points.h"
+#include "rect_clip.h"
 
 #include <algorithm>
 
@@ -466,36 +467,6 @@ __device__ __forceinline__ float iou_loss(float px, float py, float pz, const fl
 
 __device__ __forceinline__ float box_loss(const AlignedBox&, float px, float py, float pz, const float* d, const float* t, float* gd) {
     return iou_loss(px, py, pz, d, t, gd);
-}
-
-// The part [t0, t1] of the segment m + tau * t, |tau| <= half, inside one axis of an axis-aligned rectangle (|coordinate| <= w).
-// m, t, n: that coordinate of the segment's midpoint, direction and outward normal.  A segment along the axis' boundary (t == 0,
-// |m| == w) counts where on_edge and the two outward normals agree (file header).
-__device__ __forceinline__ void clip_axis(float m, float t, float n, float w, bool on_edge, float& t0, float& t1) {
-    if (t == 0.f) {
-        const bool in = fabsf(m) < w || (on_edge && fabsf(m) == w && m * n > 0.f);
-        if (!in) t1 = t0;
-    } else {
-        const float a = (-w - m) / t, b = (w - m) / t;
-        t0 = fmaxf(t0, fminf(a, b));
-        t1 = fminf(t1, fmaxf(a, b));
-    }
-}
-
-// Edge k (0..3, counter-clockwise: normals +x, +y, -x, -y of its own frame) of a rectangle with half sizes (hw, hl), centre
-// (rx, ry) and axes rotated by (c, s) in the frame of an axis-aligned rectangle with half sizes (ow, ol): its inside part
-// [t0, t1] along the edge from its midpoint (t1 <= t0: none), and tx, ty its direction there
-template <int k>
-__device__ __forceinline__ void clip_edge(float rx, float ry, float c, float s, float hw, float hl, float ow, float ol, bool on_edge,
-                                          float& t0, float& t1, float& tx, float& ty) {
-    constexpr float nxl = k == 0 ? 1.f : k == 2 ? -1.f : 0.f, nyl = k == 1 ? 1.f : k == 3 ? -1.f : 0.f;
-    const float nx = nxl * c - nyl * s, ny = nxl * s + nyl * c;
-    const float h = (k & 1) ? hl : hw, half = (k & 1) ? hw : hl;
-    tx = -ny, ty = nx;
-    t0 = -half, t1 = half;
-    clip_axis(rx + h * nx, tx, nx, ow, on_edge, t0, t1);
-    clip_axis(ry + h * ny, ty, ny, ol, on_edge, t0, t1);
-    t1 = fmaxf(t1, t0);
 }
 
 // RotatedIoU3DLoss of one point: ImVoxelHead_ARKit._bbox_pred_to_bbox (:1045-1055) of the point and its seven channels d (six

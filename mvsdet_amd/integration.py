@@ -164,3 +164,25 @@ def patch_reference_nms3d(head_module) -> dict:
 def unpatch_reference_nms3d(head_module, originals: dict) -> None:
     for name, fn in originals.items():
         setattr(head_module, name, fn)
+
+
+def patch_reference_indoor_eval(metric_module, device="cuda") -> dict:
+    """Opt-in (the import hook does not apply it): rebind the module-global `indoor_eval` of an imported reference module that
+    calls it (mmdet3d.evaluation.metrics.indoor_metric, whose IndoorMetric.compute_metrics does; or
+    mmdet3d.evaluation.functional.indoor_eval itself) to evaluation.indoor_eval, which scores the detections on `device`
+    (csrc/evalmap.hip): the mathematical function of the reference's IoU, not mmcv's box_iou_rotated rounding.  Returns
+    {name: original} for `unpatch_reference_indoor_eval`."""
+    from . import evaluation
+    original = metric_module.indoor_eval
+
+    def indoor_eval(gt_annos, dt_annos, metric, label2cat, logger=None, box_mode_3d=None):
+        return evaluation.indoor_eval(gt_annos, dt_annos, metric, label2cat, logger=logger, box_mode_3d=box_mode_3d, device=device)
+
+    indoor_eval.__doc__ = getattr(original, "__doc__", None)
+    metric_module.indoor_eval = indoor_eval
+    return {"indoor_eval": original}
+
+
+def unpatch_reference_indoor_eval(metric_module, originals: dict) -> None:
+    for name, fn in originals.items():
+        setattr(metric_module, name, fn)
