@@ -53,6 +53,8 @@ const char* mvsdet_last_error(void);
  *                   decode (no range tests, no clamps of the tap offsets); 0 = every plane takes the general decode
  *   "sweep_pool"    1 (default) | 0   mvsdet_plane_sweep_table_pooled_f32 builds the pooled geometry; 0 = it builds what
  *                   mvsdet_plane_sweep_table[_pitched]_f32 build
+ *   "depthprob_ahead"  1 (default) | 0   mvsdet_depth_prob_topk[_strided]_f32 requests every input of a pixel before its first
+ *                   store (D <= 64), or runs its last pass eight planes ahead (D > 64); 0 = plane by plane, behind the stores
  *   "sweep_dsplit", "sweep_groups", "bwd_groups", "conv_*"   schedules of the sweep's plane split, of the bf16x3
  *                   convolutions and of the fp16 + MX convolution ("conv_mx_th") (csrc/common.h: struct Options)
  * "sweep_tw" decides the layout of the sweep geometry: consume one (mvsdet_plane_sweep_variance_tabled_f32) under the

@@ -26,7 +26,7 @@ Options& options() {
                         env_int("MVSDET_SWEEP_DSPLIT", 0), env_int("MVSDET_SWEEP_GROUPS", -1),
                         env_int("MVSDET_CONV_NSPLIT", 0), env_int("MVSDET_CONV_XCD", 1), env_int("MVSDET_CONV_SPLIT_BLOCKS", 768),
                         env_int("MVSDET_CONV_SPLIT_MIN_GROUPS", 2), env_int("MVSDET_BWD_GROUPS", 0), env_int("MVSDET_SWEEP_INSIDE", 1), env_int("MVSDET_CONV_MX_TH", 0),
-                        env_int("MVSDET_SWEEP_POOL", 1)};
+                        env_int("MVSDET_SWEEP_POOL", 1), env_int("MVSDET_DEPTHPROB_AHEAD", 1)};
     return o;
 }
 
@@ -40,6 +40,7 @@ static int* option_slot(const char* name) {
     if (!strcmp(name, "sweep_groups")) return &o.sweep_groups;
     if (!strcmp(name, "sweep_inside")) return &o.sweep_inside;
     if (!strcmp(name, "sweep_pool")) return &o.sweep_pool;
+    if (!strcmp(name, "depthprob_ahead")) return &o.depthprob_ahead;
     if (!strcmp(name, "conv_nsplit")) return &o.conv_nsplit;
     if (!strcmp(name, "conv_xcd")) return &o.conv_xcd;
     if (!strcmp(name, "bwd_groups")) return &o.bwd_groups;

@@ -35,6 +35,8 @@ struct Options {
                        // 8 / 12 = every wave does everything on 4 x 8 x 16 (8 waves) / 4 x 12 x 16 (12 waves) tiles
     int sweep_pool;    // 1 (default) = mvsdet_plane_sweep_table_pooled_f32 builds the pooled geometry (K == 2, 32x4 tiles: a footprint box may
                        // take the other neighbour's idle LDS slot); 0 = it builds the geometry of mvsdet_plane_sweep_table_f32 (A/B runs, tests)
+    int depthprob_ahead; // 1 (default) = depth_prob_topk requests a pixel's inputs before its first store (depth_prob_topk_ahead_kernel);
+                       // 0 = the form that requests them plane by plane, behind the stores (A/B runs, tests).  Same bits.
 };
 Options& options();
 

@@ -2,17 +2,68 @@
 // top-k plane selection and depth expectation, fused.  Reference: mvsdet.py:470-475, :266-283
 // (sample_depth_prob), :298-317 (compute_avg_depth) of Pixie8888/MVSDet.
 //
-// Roofline: HBM.  Algorithmic bytes per scene: read 2*N*D*H*W*4, write N*(2D+2*topk+1)*H*W*4.
+// Roofline: HBM.  Algorithmic bytes per scene: read 2*N*D*H*W*4, write N*(2D+3*topk+1)*H*W*4 (0.82 GB at the headline shape).
 // One thread per pixel, lanes along W so every plane access is a coalesced 256-byte run.  DREG > 0 (D <= DREG, DREG =
 // 16 / 64): the D cost logits, then their exponentials, stay in registers -- every input is read once, one expf per
 // plane instead of two, and all loads of a pass are in flight together.  DREG = 0 (D up to 512): the logits are re-read
 // from L2 in the second / third pass.  Same operations in the same order either way.
+//
+// gfx950 retires loads and stores through ONE in-order vmcnt, so a load requested behind a store cannot be waited for without
+// waiting for that store, and under a write stream a store is acknowledged thousands of cycles after it was issued.
+// depth_prob_topk_ahead_kernel therefore requests what a pixel reads before it stores anything.  What bounds it then is its
+// bytes: 0.165 ms at the headline shape against 0.138 ms for the same bytes at the packing kernel's rate, and about 0.12 ms of
+// vector issue (docs/KERNEL_NOTES.md 4.2, profiles/r09_depth_prob_ab.txt).
 #include "common.h"
 
 namespace mvsdet {
 
+// One plane's share of the depth expectation and its place in the sorted (descending) candidate list of a pixel; strict '>'
+// keeps the lower plane on ties.  kNanAware: single planes can be NaN (ready-made probabilities) and rank above every number.
+template <int KT, bool kNanAware>
+__device__ __forceinline__ void take_plane(int d, float pd, float od, float near, float interval, float& avg, float (&bv)[KT],
+                                           float (&bo)[KT], int (&bi)[KT]) {
+    // mvsdet.py:278-282  depth = idx*interval + near + off*interval (each op rounded)
+    const float dep = ((float)d * interval + near) + od * interval;
+    avg = avg + dep * pd;
+    float cv = pd, co = od;
+    int cidx = d;
+    // once the new plane is in, every entry below moves down one slot: a displaced entry is compared with nothing, or
+    // an equal value further down (a lower plane) would overtake it
+    bool moved = false;
+#pragma unroll
+    for (int k = 0; k < KT; ++k) {
+        const bool gt = kNanAware ? (moved || cv > bv[k] || (cv != cv && bv[k] == bv[k])) : (moved || cv > bv[k]);
+        moved = gt;
+        const float tv = bv[k], to = bo[k];
+        const int ti = bi[k];
+        bv[k] = gt ? cv : tv;
+        bo[k] = gt ? co : to;
+        bi[k] = gt ? cidx : ti;
+        cv = gt ? tv : cv;
+        co = gt ? to : co;
+        cidx = gt ? ti : cidx;
+    }
+}
+
+template <int KT>
+__device__ __forceinline__ void write_candidates(const float (&bv)[KT], const float (&bo)[KT], const int (&bi)[KT],
+                                                 float* __restrict__ est_depth, float* __restrict__ est_dens,
+                                                 int32_t* __restrict__ est_idx, int n, int pix, int HW, int topk, float near,
+                                                 float interval) {
+#pragma unroll
+    for (int k = 0; k < KT; ++k) {
+        if (k < topk) {
+            const size_t oi = ((size_t)n * topk + k) * HW + pix;
+            est_depth[oi] = ((float)bi[k] * interval + near) + bo[k] * interval;
+            est_dens[oi] = bv[k];
+            if (est_idx) est_idx[oi] = bi[k];
+        }
+    }
+}
+
 // KT = length of the candidate list kept per pixel (3 for the reference's topk = 3, MVSDET_MAX_TOPK otherwise): the
-// insertion is 7 VALU instructions per entry and plane, and the kernel is VALU-bound (r02_stage_kernels_pmc.txt).
+// insertion is 7 VALU instructions per entry and plane.  This kernel (option "depthprob_ahead" 0, and sample_depth_prob) requests the
+// offset logit of plane d + 1 behind the two stores of plane d and so pays one store round trip per plane.
 //
 // Non-finite inputs follow torch.topk, which ranks NaN above every number: descending value, NaN
 // first, the lower plane first among equals and among NaNs.  From logits, one NaN / +Inf logit (or all -Inf) makes the
@@ -86,27 +137,7 @@ __global__ __launch_bounds__(kThreads) void depth_prob_topk_kernel(
             pd = c[(size_t)d * HW];
             od = o[(size_t)d * HW];
         }
-        // mvsdet.py:278-282  depth = idx*interval + near + off*interval (each op rounded)
-        const float dep = ((float)d * interval + near) + od * interval;
-        avg = avg + dep * pd;
-        float cv = pd, co = od;
-        int cidx = d;
-        // once the new plane is in, every entry below moves down one slot: a displaced entry is compared with nothing, or
-        // an equal value further down (a lower plane) would overtake it
-        bool moved = false;
-#pragma unroll
-        for (int k = 0; k < KT; ++k) {
-            const bool gt = kFromLogits ? (moved || cv > bv[k]) : (moved || cv > bv[k] || (cv != cv && bv[k] == bv[k]));
-            moved = gt;
-            const float tv = bv[k], to = bo[k];
-            const int ti = bi[k];
-            bv[k] = gt ? cv : tv;
-            bo[k] = gt ? co : to;
-            bi[k] = gt ? cidx : ti;
-            cv = gt ? tv : cv;
-            co = gt ? to : co;
-            cidx = gt ? ti : cidx;
-        }
+        take_plane<KT, !kFromLogits>(d, pd, od, near, interval, avg, bv, bo, bi);
     };
     if (kFromLogits && DREG > 0) {
 #pragma unroll
@@ -127,15 +158,155 @@ __global__ __launch_bounds__(kThreads) void depth_prob_topk_kernel(
                 bi[k] = k;
             }
     }
+    write_candidates<KT>(bv, bo, bi, est_depth, est_dens, est_idx, n, pix, HW, topk, near, interval);
+}
+
+// The same pixel in the same operations (option "depthprob_ahead" 1, the default): every output has the bits of the kernel above.
+// What differs is when memory is asked.  DREG > 0: all 2 * D inputs of a pixel are requested, and the D sigmoids formed, before
+// the first store; from there to the end of the kernel a thread only computes and stores -- no load, no wait on vmcnt.  The
+// offsets stay in registers (logits, then sigmoids), and the NaN tail takes its offsets from there instead of reading off[]
+// back.  DREG = 0 (D > 64): the third pass runs kChunk planes ahead -- both inputs of chunk k + 1 are requested before the
+// stores of chunk k, so the wait for them covers no store younger than chunk k - 1's.  kFull: D == DREG, no plane is tested
+// for being there (at D = 64 the 64 tests' masks alone overflow the scalar registers).
+constexpr int kChunk = 8;
+// A block-uniform pointer the optimiser cannot look into: left alone it folds the thread's index into the base and then adds every
+// plane's offset in 64-bit vector arithmetic, one register pair per address.
+template <typename T>
+__device__ __forceinline__ __attribute__((address_space(1))) T* plane_ptr(T* p) {
+    asm("" : "+s"(p));
+    return (__attribute__((address_space(1))) T*)p;   // global memory: what the optimiser knew of p before
+}
+template <int DREG, int KT, bool kFull>
+__global__ __launch_bounds__(kThreads) void depth_prob_topk_ahead_kernel(
+    const float* __restrict__ cost_reg, const float* __restrict__ off_logit, float* __restrict__ prob,
+    float* __restrict__ off, float* __restrict__ est_depth, float* __restrict__ est_dens,
+    int32_t* __restrict__ est_idx, float* __restrict__ avg_depth, int D, int HW, int topk, float near, float interval,
+    size_t in_view_stride) {
+    const int pix = blockIdx.x * kThreads + threadIdx.x;
+    const int n = blockIdx.y;
+    if (pix >= HW) return;
+    // every address is a block-uniform pointer (scalar registers, scalar arithmetic) plus the thread's index in the block
+    const int t = threadIdx.x;
+    const size_t blk = (size_t)blockIdx.x * kThreads;
+    const float* c = cost_reg + (size_t)n * in_view_stride + blk;
+    const float* o = off_logit + (size_t)n * in_view_stride + blk;
+    float* p_out = prob + (size_t)n * D * HW + blk;
+    float* o_out = off + (size_t)n * D * HW + blk;
+
+    float bv[KT], bo[KT], fo[KT];   // fo: the offsets of planes 0 .. KT-1, for the NaN tail
+    int bi[KT];
 #pragma unroll
     for (int k = 0; k < KT; ++k) {
-        if (k < topk) {
-            const size_t oi = ((size_t)n * topk + k) * HW + pix;
-            est_depth[oi] = ((float)bi[k] * interval + near) + bo[k] * interval;
-            est_dens[oi] = bv[k];
-            if (est_idx) est_idx[oi] = bi[k];
-        }
+        bv[k] = -1.0f;
+        bo[k] = 0.0f;
+        fo[k] = 0.0f;
+        bi[k] = 0;
     }
+    float avg = 0.0f, m, s = 0.0f;
+    if constexpr (DREG > 0) {
+        float e[DREG];   // cost logits, then exp(logit - max)
+        float q[DREG];   // offset logits, then their sigmoids
+#pragma unroll
+        for (int d = 0; d < DREG; ++d) e[d] = kFull || d < D ? plane_ptr(c + (size_t)d * HW)[t] : 0.0f;
+#pragma unroll
+        for (int d = 0; d < DREG; ++d) q[d] = kFull || d < D ? plane_ptr(o + (size_t)d * HW)[t] : 0.0f;
+        __builtin_amdgcn_sched_barrier(0);   // the scheduler sinks the requests back to their uses otherwise
+        m = e[0];
+#pragma unroll
+        for (int d = 1; d < DREG; ++d)
+            if (kFull || d < D) m = e[d] > m ? e[d] : m;
+#pragma unroll
+        for (int d = 0; d < DREG; ++d)
+            if (kFull || d < D) {
+                e[d] = expf(e[d] - m);
+                s += e[d];
+                if (d % 4 == 3) __builtin_amdgcn_sched_barrier(0);   // four planes at a time: 64 at once cost more registers than there are
+            }
+#pragma unroll
+        for (int d = 0; d < DREG; ++d)
+            if (kFull || d < D) {
+                q[d] = 1.0f / (1.0f + expf(-q[d]));
+                asm volatile("" : "+v"(q[d]));   // formed here, not next to the stores of its plane
+                if (d % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+            }
+        __builtin_amdgcn_sched_barrier(0);   // every input has been used: nothing below waits for memory
+#pragma unroll
+        for (int d = 0; d < DREG; ++d)
+            if (kFull || d < D) {
+                const float pd = e[d] / s;
+                plane_ptr(p_out + (size_t)d * HW)[t] = pd;
+                plane_ptr(o_out + (size_t)d * HW)[t] = q[d];
+                take_plane<KT, false>(d, pd, q[d], near, interval, avg, bv, bo, bi);
+                // a plane is finished before the next begins: with no test between the planes the optimiser otherwise puts off the
+                // expectation and the last candidate of every plane to the end, and keeps what they need until then
+                asm volatile("" : "+v"(avg));
+#pragma unroll
+                for (int k = 0; k < KT; ++k) asm volatile("" : "+v"(bv[k]), "+v"(bo[k]), "+v"(bi[k]));
+            }
+#pragma unroll
+        for (int k = 0; k < KT; ++k) fo[k] = q[k < DREG ? k : 0];
+    } else {
+        const float* ct = c + t;
+        m = ct[0];
+#pragma unroll 4
+        for (int d = 1; d < D; ++d) {
+            const float v = ct[(size_t)d * HW];
+            m = v > m ? v : m;
+        }
+#pragma unroll 4
+        for (int d = 0; d < D; ++d) s += expf(ct[(size_t)d * HW] - m);
+
+        float cc[kChunk], oc[kChunk], cn[kChunk], on[kChunk];   // the chunk at hand, the chunk requested
+        // a chunk that reaches past D repeats plane D - 1: every request stays inside the view, none is tested plane by plane
+        auto request = [&](int d0) {
+#pragma unroll
+            for (int j = 0; j < kChunk; ++j) {
+                const size_t at = (size_t)min(d0 + j, D - 1) * HW;
+                cn[j] = plane_ptr(c + at)[t];
+                on[j] = plane_ptr(o + at)[t];
+            }
+        };
+        auto finish = [&](int d, int j) {
+            const float pd = expf(cc[j] - m) / s;
+            const float od = 1.0f / (1.0f + expf(-oc[j]));
+            plane_ptr(p_out + (size_t)d * HW)[t] = pd;
+            plane_ptr(o_out + (size_t)d * HW)[t] = od;
+            if (j < KT) fo[j < KT ? j : 0] = d == j ? od : fo[j < KT ? j : 0];   // planes 0 .. KT-1 are in the first chunk
+            take_plane<KT, false>(d, pd, od, near, interval, avg, bv, bo, bi);
+        };
+        request(0);
+        int d0 = 0;
+        for (; d0 + kChunk <= D; d0 += kChunk) {
+#pragma unroll
+            for (int j = 0; j < kChunk; ++j) {
+                cc[j] = cn[j];
+                oc[j] = on[j];
+            }
+            if (d0 + kChunk < D) request(d0 + kChunk);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < kChunk; ++j) finish(d0 + j, j);
+        }
+#pragma unroll
+        for (int j = 0; j < kChunk; ++j)
+            if (d0 + j < D) {
+                cc[j] = cn[j];
+                oc[j] = on[j];
+                finish(d0 + j, j);
+            }
+    }
+    avg_depth[(size_t)n * HW + pix] = avg;
+    if (s != s) {
+        // every probability is NaN and none was inserted (NaN > x is false): all planes tie as NaN, the lowest come first
+#pragma unroll
+        for (int k = 0; k < KT; ++k)
+            if (k < topk) {   // topk <= D: plane k exists
+                bv[k] = s;
+                bo[k] = fo[k];
+                bi[k] = k;
+            }
+    }
+    write_candidates<KT>(bv, bo, bi, est_depth, est_dens, est_idx, n, pix, HW, topk, near, interval);
 }
 
 // backward: dL/dcost = p * (gp - sum_d gp_d p_d), dL/doff_logit = go * off * (1 - off), where gp / go
@@ -215,15 +386,22 @@ extern "C" int mvsdet_depth_prob_topk_strided_f32(const float* cost_reg, const f
     MVS_REQUIRE(view_stride >= (long long)D * H * W, "depth_prob_topk: view stride %lld < D*H*W", view_stride);
     const int HW = H * W;
     dim3 grid((HW + kThreads - 1) / kThreads, N);
-#define MVS_DP_LAUNCH(DR, KTV)                                                                                             \
-    hipLaunchKernelGGL((depth_prob_topk_kernel<true, DR, KTV>), grid, dim3(kThreads), 0, (hipStream_t)stream, cost_reg, off_logit, \
-                       prob, off, est_depth, est_dens, est_idx, avg_depth, D, HW, topk, near, interval, (size_t)view_stride)
-#define MVS_DP_BY_D(KTV)                  \
-    if (D <= 16) MVS_DP_LAUNCH(16, KTV);  \
-    else if (D <= 64) MVS_DP_LAUNCH(64, KTV); \
-    else MVS_DP_LAUNCH(0, KTV);
+#define MVS_DP_LAUNCH(KERNEL)                                                                                          \
+    hipLaunchKernelGGL(KERNEL, grid, dim3(kThreads), 0, (hipStream_t)stream, cost_reg, off_logit, prob, off, est_depth, est_dens, \
+                       est_idx, avg_depth, D, HW, topk, near, interval, (size_t)view_stride)
+#define MVS_DP_FORM(DR, KTV)                                                              \
+    if (ahead && D == DR) MVS_DP_LAUNCH((depth_prob_topk_ahead_kernel<DR, KTV, true>));   \
+    else if (ahead) MVS_DP_LAUNCH((depth_prob_topk_ahead_kernel<DR, KTV, false>));        \
+    else MVS_DP_LAUNCH((depth_prob_topk_kernel<true, DR, KTV>))
+#define MVS_DP_BY_D(KTV)                                                                  \
+    if (D <= 16) { MVS_DP_FORM(16, KTV); }                                                \
+    else if (D <= 64) { MVS_DP_FORM(64, KTV); }                                           \
+    else if (ahead) MVS_DP_LAUNCH((depth_prob_topk_ahead_kernel<0, KTV, false>));         \
+    else MVS_DP_LAUNCH((depth_prob_topk_kernel<true, 0, KTV>));
+    const bool ahead = options().depthprob_ahead != 0;
     if (topk <= 3) { MVS_DP_BY_D(3) } else { MVS_DP_BY_D(MVSDET_MAX_TOPK) }
 #undef MVS_DP_BY_D
+#undef MVS_DP_FORM
 #undef MVS_DP_LAUNCH
     MVS_LAUNCH_CHECK("depth_prob_topk");
     return MVSDET_OK;

@@ -57,6 +57,7 @@ __global__ __launch_bounds__(256) void store_kernel(float* __restrict__ var, int
     const int g = lane & 7, ps = lane >> 3;
     const int p0 = 32 * wave + 4 * ps;
     const int px0 = tx0 + p0 % TW, py = ty0 + p0 / TW;
+    if (py >= H || px0 + 4 > W) return;   // the last tile of a row / column may reach past the map (W = 160: TW = 64, 128)
     const size_t st_off = (size_t)py * W + px0;
     const v4f vv = {1.0f * id, 2.0f, 3.0f, (float)lane};
     for (int d = 0; d < D; ++d) {
@@ -108,7 +109,7 @@ int main() {
     const double gb = elems * 4 / 1e9;
 #define RUN(TWV, NTV, ORD)                                                                                     \
     {                                                                                                          \
-        const int tiles_x = W / TWV, tiles = tiles_x * (H / (128 / TWV));                                      \
+        const int tiles_x = (W + TWV - 1) / TWV, tiles = tiles_x * ((H + 128 / TWV - 1) / (128 / TWV));        \
         const int blocks = N * tiles * (C / 32);                                                               \
         float ms = time_ms([&] { hipLaunchKernelGGL((store_kernel<TWV, NTV, ORD>), dim3(blocks), dim3(256), 0, 0, var, N, C, D, H, W, tiles_x, tiles); }); \
         printf("tile %3dx%d  nt=%d order=%d : %.3f ms  %.0f GB/s\n", TWV, 128 / TWV, (int)NTV, ORD, ms, gb / ms * 1e3); \
