@@ -192,6 +192,29 @@ int mvsdet_plane_sweep_variance_bwd_packed_f32(const float* packed, const int64_
                                                int C, int D, int H, int W, mvsdet_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * a3 / a3+a4 at PER-PIXEL depth hypotheses -- homo_warping's depth_values (B,D,H,W) form (mvs_models/module.py:130-133):
+ * every reference pixel carries its own D hypotheses (what a coarse-to-fine cost volume sweeps).  Same sampling and the
+ * same rounding points as the plane forms above: a depth map that is constant per plane gives their results bit for bit.
+ * No geometry scratch.  The depths carry no gradient (the grid is built under no_grad, module.py:115).
+ *   depth (B,D,H,W) / (N,D,H,W) contiguous;  out (B,C,D,H,W);  var (N,C,D,H,W) contiguous fp32;  K in [0, MVSDET_MAX_NEIGHBORS].
+ * Backward passes: g = dL/dout resp. dL/dvar, contiguous; gsrc (B,C,H,W) / gfeat (N,C,H,W) are OVERWRITTEN.  The tap
+ * gradients are summed with float atomics into a packed gradient map in `workspace` (>=
+ * mvsdet_plane_sweep_pixel_bwd_workspace_bytes, 16-byte aligned, overwritten), so the last bits depend on arrival order.
+ * Not offered in this form: fp16 storage, pitched output, view shards, tabled / pooled geometry.
+ * ------------------------------------------------------------------------------------------- */
+int mvsdet_homo_warp_pixel_f32(const float* src, const float* proj, const float* depth, float* out,
+                               int B, int C, int D, int H, int W, mvsdet_stream_t stream);
+int mvsdet_homo_warp_pixel_bwd_f32(const float* proj, const float* depth, const float* g, float* gsrc, void* workspace,
+                                   size_t workspace_bytes, int B, int C, int D, int H, int W, mvsdet_stream_t stream);
+int mvsdet_plane_sweep_variance_pixel_packed_f32(const float* packed, const int64_t* nbr, const float* proj, const float* depth,
+                                                 float* var, int N, int K, int C, int D, int H, int W, mvsdet_stream_t stream);
+size_t mvsdet_plane_sweep_pixel_bwd_workspace_bytes(int N, int C, int H, int W);
+int mvsdet_plane_sweep_variance_pixel_bwd_packed_f32(const float* packed, const int64_t* nbr, const float* proj,
+                                                     const float* depth, const float* g, float* gfeat, void* workspace,
+                                                     size_t workspace_bytes, int N, int K, int C, int D, int H, int W,
+                                                     mvsdet_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a5-a7  depth probability, top-k plane selection, depth expectation --
  * mvsdet.py:470-475 (softmax / sigmoid), :266-283 (sample_depth_prob), :298-317 (compute_avg_depth).
  *   cost_reg, off_logit (N,D,H,W)  the two output channels of CostRegNet_3DGS

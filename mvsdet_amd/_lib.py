@@ -141,6 +141,11 @@ SIGNATURES = {
     "mvsdet_eval_compute": [_vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_float), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                             _vp],
     "mvsdet_eval_iou_f32": [_vp, _i, _vp, _i, _vp, _vp],
+    "mvsdet_homo_warp_pixel_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_homo_warp_pixel_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_plane_sweep_variance_pixel_packed_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_plane_sweep_pixel_bwd_workspace_bytes": [_i, _i, _i, _i],
+    "mvsdet_plane_sweep_variance_pixel_bwd_packed_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp],
 }
 _RESTYPE = {"mvsdet_last_error": ctypes.c_char_p, "mvsdet_conv3d_k3_bf16x3_stats_parts": ctypes.c_size_t, "mvsdet_convT3d_k3_s2_bf16x3_stats_parts": ctypes.c_size_t, "mvsdet_gemm_split_weight_bytes": ctypes.c_size_t, "mvsdet_neck_gemm_dw_partial_bytes": ctypes.c_size_t, "mvsdet_scl_bytes": ctypes.c_size_t, "mvsdet_pscl_bytes": ctypes.c_size_t,
             "mvsdet_split_conv_weight_bytes": ctypes.c_size_t, "mvsdet_packed_bytes": ctypes.c_size_t,
@@ -149,6 +154,7 @@ _RESTYPE = {"mvsdet_last_error": ctypes.c_char_p, "mvsdet_conv3d_k3_bf16x3_stats
             "mvsdet_head_targets_workspace_bytes": ctypes.c_size_t, "mvsdet_head_loss_workspace_bytes": ctypes.c_size_t,
             "mvsdet_plane_sweep_scratch_bytes": ctypes.c_size_t, "mvsdet_plane_sweep_workspace_bytes": ctypes.c_size_t,
             "mvsdet_plane_sweep_bwd_workspace_bytes": ctypes.c_size_t,
+            "mvsdet_plane_sweep_pixel_bwd_workspace_bytes": ctypes.c_size_t,
             "mvsdet_conv3d_k3_dw_partial_bytes": ctypes.c_size_t,
             "mvsdet_conv3d_k3_bf16x3_workspace_bytes": ctypes.c_size_t,
             "mvsdet_conv3d_k3_s2_bf16x3_workspace_bytes": ctypes.c_size_t,

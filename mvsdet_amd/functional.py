@@ -137,18 +137,25 @@ def compute_projection(img_meta: dict, stride: int, angles=None) -> Tensor:
 
 # ------------------------------------------------------------------------------------------- a3
 def homo_warping(src_fea: Tensor, src_proj: Tensor, ref_proj: Tensor, depth_values: Tensor) -> Tensor:
-    """mvs_models/module.py:105-146.  src_fea (B,C,H,W), src_proj/ref_proj (B,4,4), depth_values (B,D)
-    -> warped (B,C,D,H,W)."""
-    if depth_values.dim() != 2:
-        raise NotImplementedError("per-pixel depth_values (B,D,H,W) (module.py:130-133) is unused by MVSDet")
+    """mvs_models/module.py:105-146.  src_fea (B,C,H,W), src_proj/ref_proj (B,4,4), depth_values (B,D) -- one plane per
+    hypothesis -- or (B,D,H,W) -- every reference pixel its own D hypotheses (module.py:130-133) -> warped (B,C,D,H,W)."""
+    if depth_values.dim() not in (2, 4):
+        raise ValueError(f"homo_warping: depth_values must be (B,D) or (B,D,H,W) (got shape {tuple(depth_values.shape)})")
+    pixel = depth_values.dim() == 4
+    if pixel and (src_fea.dim() != 4 or depth_values.shape[0] != src_fea.shape[0]
+                  or tuple(depth_values.shape[2:]) != tuple(src_fea.shape[2:])):
+        raise ValueError(f"homo_warping: per-pixel depth_values {tuple(depth_values.shape)} do not match src_fea "
+                         f"{tuple(src_fea.shape)}: expected (B,D,H,W)")
     src_fea, depth_values = amp_fp32(src_fea, depth_values)
     proj = relative_projection(src_proj, ref_proj).to(src_fea.device)
     depth_values = depth_values.to(src_fea.device)
+    if pixel:
+        depth_values = depth_values.contiguous()
     if LAZY_WARP and (src_fea.is_cuda or LAZY_ANY_DEVICE) and src_fea.dtype == torch.float32:
         # inside the patched reference: defer, so that its variance loop collapses into the fused kernel (lazywarp.py)
         from . import lazywarp
         return lazywarp.lazy_homo_warp(src_fea, proj, depth_values)
-    return ops.homo_warp(src_fea, proj, depth_values)
+    return ops.homo_warp_pixel(src_fea, proj, depth_values) if pixel else ops.homo_warp(src_fea, proj, depth_values)
 
 
 # ------------------------------------------------------------------------------------------- a9

@@ -404,8 +404,14 @@ class MVSDetHotPath:
             return ops.plane_sweep_variance_tabled_pitched(packed, geo.neighbor_ids, table, C, self.num_depth, H, W, pitch)
         return ops.plane_sweep_variance_tabled(packed, geo.neighbor_ids, table, C, self.num_depth, H, W)
 
-    def cost_volume(self, feature: Tensor, geo: SceneGeometry, packed: Optional[Tensor] = None) -> Tensor:
-        """a3+a4, mvsdet.py:439-467 -> variance (N,C,D,Hf,Wf)."""
+    def cost_volume(self, feature: Tensor, geo: SceneGeometry, packed: Optional[Tensor] = None,
+                    depth: Optional[Tensor] = None) -> Tensor:
+        """a3+a4, mvsdet.py:439-467 -> variance (N,C,D,Hf,Wf).  `depth` (N,D,Hf,Wf): per-pixel depth hypotheses instead of the
+        scene's planes (homo_warping's 4-D depth_values, module.py:130-133: the sweep of a refinement stage)."""
+        if depth is not None:
+            if packed is not None and not (feature.requires_grad and torch.is_grad_enabled()):
+                return ops.plane_sweep_variance_pixel_packed(packed, geo.neighbor_ids, geo.proj_rel, depth, feature.shape[1])
+            return ops.plane_sweep_variance_pixel(feature, geo.neighbor_ids, geo.proj_rel, depth)
         if packed is not None and not (feature.requires_grad and torch.is_grad_enabled()):
             n, c, h, w = feature.shape
             return ops.plane_sweep_variance_packed(packed, geo.neighbor_ids, geo.proj_rel, geo.depth_values, c, h, w)

@@ -55,7 +55,8 @@ class LazyVolume(Tensor):
                           "lazywarp.stats counts both routes.", RuntimeWarning, stacklevel=3)
         k, p = self.kind, self.payload
         if k == "warp":
-            return ops.homo_warp(p["src"], p["proj"], p["depth"])
+            # a 4-D depth is the per-pixel form (B,D,H,W)
+            return (ops.homo_warp_pixel if p["depth"].dim() == 4 else ops.homo_warp)(p["src"], p["proj"], p["depth"])
         if k == "sq":
             return p["warp"].materialize() ** 2
         if k == "sum":
@@ -187,7 +188,7 @@ def _try_fused(sq_scaled: LazyVolume, sum_scaled_sq: LazyVolume):
             return None
         proj = torch.stack([w.payload["proj"] for w in warps], dim=1)
         stats["fused"] += 1
-        return ops.plane_sweep_variance(feat, ids, proj, depth)
+        return (ops.plane_sweep_variance_pixel if depth.dim() == 4 else ops.plane_sweep_variance)(feat, ids, proj, depth)
 
 
 def lazy_homo_warp(src_fea: Tensor, proj_rel: Tensor, depth_values: Tensor) -> LazyVolume:

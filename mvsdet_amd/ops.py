@@ -516,6 +516,164 @@ def _sweep_keep_bwd(ctx, grad, g_packed, g_table):
 plane_sweep_variance_keep.register_autograd(_sweep_keep_bwd, setup_context=_sweep_keep_setup)
 
 
+# ------------------------------------------------------------------------------------------- a3 / a3+a4, per-pixel depths
+# homo_warping's depth_values (B,D,H,W) form (mvs_models/module.py:130-133): every reference pixel carries its own D
+# hypotheses.  Kernels of their own (csrc/planesweep_pixel.hip); the plane operators above still refuse a 4-D depth.
+def _check_depth_pixel(name, depth, B, H, W):
+    _req(depth, "depth", dim=4)
+    if depth.shape[0] != B or tuple(depth.shape[2:]) != (H, W):
+        raise ValueError(f"{name}: depth {tuple(depth.shape)} is not (B={B}, D, H={H}, W={W})")
+    return depth.shape[1]
+
+
+@torch.library.custom_op(f"{_NS}::homo_warp_pixel", mutates_args=(), device_types="cuda")
+def homo_warp_pixel(src: Tensor, proj: Tensor, depth: Tensor) -> Tensor:
+    """a3 at per-pixel depths: src (B,C,H,W), proj (B,4,4) = src_proj @ inv(ref_proj), depth (B,D,H,W) -> (B,C,D,H,W).
+    Differentiable in src."""
+    _req(src, "src", dim=4)
+    _req(proj, "proj", dim=3)
+    B, C, H, W = src.shape
+    D = _check_depth_pixel("homo_warp_pixel", depth, B, H, W)
+    if proj.shape != (B, 4, 4):
+        raise ValueError(f"homo_warp_pixel: proj {tuple(proj.shape)} does not match B={B}")
+    src, proj, depth = src.contiguous(), proj.contiguous(), depth.contiguous()
+    out = torch.empty((B, C, D, H, W), dtype=torch.float32, device=src.device)
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.load().mvsdet_homo_warp_pixel_f32(_lib.ptr(src), _lib.ptr(proj), _lib.ptr(depth), _lib.ptr(out),
+                                                          B, C, D, H, W, _stream(src)), "homo_warp_pixel")
+    return out
+
+
+@homo_warp_pixel.register_fake
+def _(src, proj, depth):
+    B, C, H, W = src.shape
+    return src.new_empty((B, C, depth.shape[1], H, W))
+
+
+@torch.library.custom_op(f"{_NS}::homo_warp_pixel_backward", mutates_args=(), device_types="cuda")
+def homo_warp_pixel_backward(proj: Tensor, depth: Tensor, grad: Tensor) -> Tensor:
+    """dL/dsrc (B,C,H,W) from dL/dwarped (B,C,D,H,W): bilinear scatter with float atomics (last bits depend on arrival order)."""
+    _req(grad, "grad", dim=5)
+    _req(proj, "proj", dim=3)
+    B, C, D, H, W = grad.shape
+    if _check_depth_pixel("homo_warp_pixel_backward", depth, B, H, W) != D or proj.shape != (B, 4, 4):
+        raise ValueError("homo_warp_pixel_backward: proj / depth do not match the gradient")
+    proj, depth, grad = proj.contiguous(), depth.contiguous(), grad.contiguous()
+    lib = _lib.load()
+    wbytes = int(lib.mvsdet_plane_sweep_pixel_bwd_workspace_bytes(B, C, H, W))
+    ws = torch.empty(wbytes // 4, dtype=torch.float32, device=grad.device)
+    gsrc = torch.empty((B, C, H, W), dtype=torch.float32, device=grad.device)
+    with torch.cuda.device(grad.device):
+        _lib.check(lib.mvsdet_homo_warp_pixel_bwd_f32(_lib.ptr(proj), _lib.ptr(depth), _lib.ptr(grad), _lib.ptr(gsrc), _lib.ptr(ws),
+                                                      wbytes, B, C, D, H, W, _stream(grad)), "homo_warp_pixel_backward")
+    return gsrc
+
+
+@homo_warp_pixel_backward.register_fake
+def _(proj, depth, grad):
+    B, C, D, H, W = grad.shape
+    return grad.new_empty((B, C, H, W))
+
+
+def _warp_pixel_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[1], inputs[2])
+
+
+def _warp_pixel_bwd(ctx, grad):
+    proj, depth = ctx.saved_tensors
+    return homo_warp_pixel_backward(proj, depth, grad), None, None
+
+
+homo_warp_pixel.register_autograd(_warp_pixel_bwd, setup_context=_warp_pixel_setup)
+
+
+def _check_sweep_pixel(feat, nbr, proj, depth):
+    _req(feat, "feat", dim=4)
+    _req(nbr, "nbr", dtype=torch.int64, dim=2)
+    _req(proj, "proj", dim=4)
+    N, C, H, W = feat.shape
+    D = _check_depth_pixel("plane_sweep_variance_pixel", depth, N, H, W)
+    K = nbr.shape[1]
+    if nbr.shape[0] != N or proj.shape != (N, K, 4, 4):
+        raise ValueError(f"plane_sweep_variance_pixel: nbr {tuple(nbr.shape)}, proj {tuple(proj.shape)} do not match N={N}")
+    return N, K, C, D, H, W
+
+
+@torch.library.custom_op(f"{_NS}::plane_sweep_variance_pixel_packed", mutates_args=(), device_types="cuda")
+def plane_sweep_variance_pixel_packed(packed: Tensor, nbr: Tensor, proj: Tensor, depth: Tensor, C: int) -> Tensor:
+    """a3+a4 at per-pixel depths on already packed maps: depth (N,D,H,W) -> variance (N,C,D,H,W)."""
+    _req(packed, "packed", dim=1)
+    _req(nbr, "nbr", dtype=torch.int64, dim=2)
+    _req(proj, "proj", dim=4)
+    _req(depth, "depth", dim=4)
+    N, K = nbr.shape
+    D, H, W = depth.shape[1:]
+    lib = _lib.load()
+    if packed.numel() * 4 != lib.mvsdet_packed_bytes(N, C, H, W):
+        raise ValueError("plane_sweep_variance_pixel_packed: packed buffer does not match (N,C,H,W)")
+    if proj.shape != (N, K, 4, 4) or depth.shape[0] != N:
+        raise ValueError("plane_sweep_variance_pixel_packed: proj/depth shape mismatch")
+    nbr, proj, depth = nbr.contiguous(), proj.contiguous(), depth.contiguous()
+    out = torch.empty((N, C, D, H, W), dtype=torch.float32, device=packed.device)
+    with torch.cuda.device(packed.device):
+        _lib.check(lib.mvsdet_plane_sweep_variance_pixel_packed_f32(_lib.ptr(packed), _lib.ptr(nbr), _lib.ptr(proj), _lib.ptr(depth),
+                                                                    _lib.ptr(out), N, K, C, D, H, W, _stream(packed)),
+                   "plane_sweep_variance_pixel_packed")
+    return out
+
+
+@plane_sweep_variance_pixel_packed.register_fake
+def _(packed, nbr, proj, depth, C):
+    N, D, H, W = depth.shape
+    return packed.new_empty((N, C, D, H, W))
+
+
+@torch.library.custom_op(f"{_NS}::plane_sweep_variance_pixel", mutates_args=(), device_types="cuda")
+def plane_sweep_variance_pixel(feat: Tensor, nbr: Tensor, proj: Tensor, depth: Tensor) -> Tensor:
+    """a3+a4 at per-pixel depths: feat (N,C,H,W), nbr (N,K) int64, proj (N,K,4,4), depth (N,D,H,W) -> (N,C,D,H,W).
+    Differentiable in feat (the backward packs the features again)."""
+    N, K, C, D, H, W = _check_sweep_pixel(feat, nbr, proj, depth)
+    return plane_sweep_variance_pixel_packed(pack_features(feat), nbr, proj, depth, C)
+
+
+@plane_sweep_variance_pixel.register_fake
+def _(feat, nbr, proj, depth):
+    N, C, H, W = feat.shape
+    return feat.new_empty((N, C, depth.shape[1], H, W))
+
+
+@torch.library.custom_op(f"{_NS}::plane_sweep_variance_pixel_backward", mutates_args=(), device_types="cuda")
+def plane_sweep_variance_pixel_backward(feat: Tensor, nbr: Tensor, proj: Tensor, depth: Tensor, grad: Tensor) -> Tensor:
+    N, K, C, D, H, W = _check_sweep_pixel(feat, nbr, proj, depth)
+    _req(grad, "grad", dim=5)
+    if grad.shape != (N, C, D, H, W):
+        raise ValueError("plane_sweep_variance_pixel_backward: grad shape mismatch")
+    packed = pack_features(feat)
+    nbr, proj, depth, grad = nbr.contiguous(), proj.contiguous(), depth.contiguous(), grad.contiguous()
+    lib = _lib.load()
+    wbytes = int(lib.mvsdet_plane_sweep_pixel_bwd_workspace_bytes(N, C, H, W))
+    ws = torch.empty(wbytes // 4, dtype=torch.float32, device=feat.device)
+    gfeat = torch.empty((N, C, H, W), dtype=torch.float32, device=feat.device)
+    with torch.cuda.device(feat.device):
+        _lib.check(lib.mvsdet_plane_sweep_variance_pixel_bwd_packed_f32(_lib.ptr(packed), _lib.ptr(nbr), _lib.ptr(proj), _lib.ptr(depth),
+                                                                        _lib.ptr(grad), _lib.ptr(gfeat), _lib.ptr(ws), wbytes, N, K, C,
+                                                                        D, H, W, _stream(feat)), "plane_sweep_variance_pixel_backward")
+    return gfeat
+
+
+@plane_sweep_variance_pixel_backward.register_fake
+def _(feat, nbr, proj, depth, grad):
+    return torch.empty_like(feat)
+
+
+def _sweep_pixel_bwd(ctx, grad):
+    feat, nbr, proj, depth = ctx.saved_tensors
+    return plane_sweep_variance_pixel_backward(feat, nbr, proj, depth, grad), None, None, None
+
+
+plane_sweep_variance_pixel.register_autograd(_sweep_pixel_bwd, setup_context=_sweep_setup)
+
+
 # ------------------------------------------------------------------------------------------- a5-a7
 @torch.library.custom_op(f"{_NS}::depth_prob_topk", mutates_args=(), device_types="cuda")
 def depth_prob_topk(cost_reg: Tensor, off_logit: Tensor, near: float, interval: float,
@@ -2015,7 +2173,9 @@ AUTOCAST_FP32_OPS = (homo_warp, plane_sweep_variance, plane_sweep_variance_keep,
                      backproject_weigh, backproject_weigh_mean)
 # the evaluation-only diagnostics of the lifting block run under the same rule (no gradient, so not a forward operator of the path)
 AUTOCAST_FP32_DIAGNOSTICS = (depth_diagnostics,)
-for _op in AUTOCAST_FP32_OPS + AUTOCAST_FP32_DIAGNOSTICS:
+# the per-pixel forms of a3 / a3+a4 (kept apart: AUTOCAST_FP32_OPS lists the operators of the shipped path)
+AUTOCAST_FP32_PIXEL_OPS = (homo_warp_pixel, plane_sweep_variance_pixel)
+for _op in AUTOCAST_FP32_OPS + AUTOCAST_FP32_PIXEL_OPS + AUTOCAST_FP32_DIAGNOSTICS:
     _op.register_autocast("cuda", torch.float32)
 del _op
 
