@@ -212,6 +212,11 @@ def strides4(t) -> ctypes.Array:
     return (ctypes.c_int64 * 4)(*[int(s) for s in t.stride()])
 
 
+def strides3(t) -> ctypes.Array:
+    """HOST int64[3] with the element strides of a 3-D tensor."""
+    return (ctypes.c_int64 * 3)(*[int(v) for v in t.stride()])
+
+
 def strides4_of5(t) -> ctypes.Array:
     """HOST int64[4] with the element strides of n, c, d, h of a 5-D tensor (the kernels want w stride 1)."""
     assert t.dim() == 5

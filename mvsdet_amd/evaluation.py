@@ -21,6 +21,7 @@ import torch
 from torch import Tensor
 
 from . import ops
+from .ops._common import req, to_device
 
 
 def _get(obj, *names):
@@ -54,7 +55,7 @@ def _bottom_centred(boxes: Tensor) -> Tensor:
 def _pad(rows, width, dtype, dev) -> Tensor:
     n = max([int(r.shape[0]) for r in rows], default=0)
     out = [torch.cat([r.reshape((r.shape[0],) + width).to(dtype), r.new_zeros((n - r.shape[0],) + width, dtype=dtype)]) for r in rows]
-    return ops._to_device(torch.stack(out), dev)
+    return to_device(torch.stack(out), dev)
 
 
 class IndoorEvaluator:
@@ -91,8 +92,8 @@ class IndoorEvaluator:
             if not isinstance(gt, (tuple, list)) or len(gt) not in (4, 5):
                 raise TypeError("IndoorEvaluator.update: a HeadPrediction goes with the tuple of head.pad_ground_truth[_rotated]")
             gt_boxes, gt_labels, gt_counts = gt[0], gt[-2], gt[-1]
-            ops._req(pred.boxes, "pred.boxes", dim=3)
-            ops._req(gt_boxes, "gt_boxes", dim=3)
+            req(pred.boxes, "pred.boxes", dim=3)
+            req(gt_boxes, "gt_boxes", dim=3)
             boxes, scores, labels, counts = _bottom_centred(pred.boxes), pred.scores, pred.labels, pred.counts
             gt_boxes = _bottom_centred(gt_boxes)
         else:
@@ -107,8 +108,8 @@ class IndoorEvaluator:
             scores = _pad([torch.as_tensor(_get(d, "scores_3d")).reshape(-1) for d in dets], (), torch.float32, dev)
             labels = _pad([torch.as_tensor(_get(d, "labels_3d")).reshape(-1) for d in dets], (), torch.int64, dev)
             gt_labels = _pad([torch.as_tensor(_get(g, "gt_labels_3d", "labels_3d")).reshape(-1) for g in gts], (), torch.int64, dev)
-            counts = ops._to_device(torch.tensor([int(b.shape[0]) for b in db], dtype=torch.int32), dev)
-            gt_counts = ops._to_device(torch.tensor([int(b.shape[0]) for b in gb], dtype=torch.int32), dev)
+            counts = to_device(torch.tensor([int(b.shape[0]) for b in db], dtype=torch.int32), dev)
+            gt_counts = to_device(torch.tensor([int(b.shape[0]) for b in gb], dtype=torch.int32), dev)
         ops.eval_match(self._st, boxes, scores, labels, counts, gt_boxes, gt_labels, gt_counts, self._scenes)
         self._scenes += int(boxes.shape[0])
         self._bound = min(self._bound + int(boxes.shape[0]) * int(boxes.shape[1]), self._st.capacity)

@@ -2,7 +2,7 @@
 
 Same names, argument order, shapes and return arity as projects/NeRF-Det/nerfdet/ of Pixie8888/MVSDet
 (mvs_models/module.py and mvsdet.py; file:line cited per function), so the reference's call sites -- and
-tests written against them -- read the same.  Heavy tensors go to the HIP operators in ops.py.
+tests written against them -- read the same.  Heavy tensors go to the HIP operators of the ops package.
 
 Geometry stays on the host.  The camera matrices of a scene are a few hundred floats that arrive as numpy
 arrays in img_meta (mvsdet.py:419-420).  The sampling positions are sensitive to the rounding of the 4x4

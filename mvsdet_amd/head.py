@@ -35,6 +35,7 @@ import torch
 from torch import Tensor, nn
 
 from . import layers, ops
+from .ops._common import to_device
 from .layers import ConvK3S1, DerivedTensorsMixin, autograd_route_from_env, await_made, check_route, fp32_under_autocast, mark_made
 
 
@@ -292,10 +293,10 @@ def _pad_ground_truth(batch_gt_instances_3d, device, nbox: int):
 
     def pad(ts, width, dtype):
         out = [torch.cat([t.reshape((t.shape[0],) + width), t.new_zeros((G - t.shape[0],) + width)]) for t in ts]
-        return ops._to_device(torch.stack(out).to(dtype), device)
+        return to_device(torch.stack(out).to(dtype), device)
 
     return (pad([r[0] for r in rows], (nbox,), torch.float32), pad([r[3] for r in rows], (2,), torch.float32) if nbox == 7 else None,
-            pad([r[1] for r in rows], (), torch.float32), pad([r[2] for r in rows], (), torch.int64), ops._to_device(counts, device))
+            pad([r[1] for r in rows], (), torch.float32), pad([r[2] for r in rows], (), torch.int64), to_device(counts, device))
 
 
 class SceneDetections:

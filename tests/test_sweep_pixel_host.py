@@ -138,7 +138,7 @@ def test_fake_kernels_autocast_rule_and_refusals():
     with pytest.raises(RuntimeError):
         ops.homo_warp_pixel(torch.zeros(1, 1, 2, 2), torch.zeros(1, 4, 4), torch.zeros(1, 1, 2, 2))
     import inspect
-    assert 'depth, "depth", dim=2' in inspect.getsource(ops._check_sweep)
+    assert 'depth, "depth", dim=2' in inspect.getsource(ops.sweep._check_sweep)
 
 
 @pytest.fixture(scope="module")

@@ -35,8 +35,10 @@ def wrap(name):
     return f
 
 
-for n in NAMES:
-    setattr(ops, n, wrap(n))
+for n in NAMES:   # on the package for the callers, on the stage module for its own calls (autograd formulas, composite ops)
+    for mod in (ops, ops.costnet):
+        if hasattr(mod, n):
+            setattr(mod, n, wrap(n))
 
 
 def run(prec):
