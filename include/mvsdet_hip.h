@@ -215,6 +215,32 @@ int mvsdet_plane_sweep_variance_pixel_bwd_packed_f32(const float* packed, const 
                                                      mvsdet_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Group-wise correlation cost volume (the reference's mvs_models/lss_fpn.py:499-506), fused with the warp:
+ *   out[n,j,g,d,y,x] = (1/Cg) * sum over the Cg = C/G channels c of group g of  f[n,c,y,x] * warped_j[n,c,d,y,x]
+ * out (N,K,G,D,H,W) contiguous fp32, one volume per neighbour j; warped_j is what mvsdet_homo_warp[_pixel]_f32 returns for
+ * the view nbr[n,j] (same sampling, zero padding, NaN for a non-finite position); group g = channels [g*Cg, (g+1)*Cg).
+ *   packed: the packed maps of all N views;  nbr (N,K) int64, K in [1, MVSDET_MAX_NEIGHBORS] (a view may be its own
+ *   neighbour, a neighbour may repeat);  proj (N,K,4,4).
+ *   depth + depth_strides[3] = {view, hypothesis, pixel} in elements, all >= 0: hypothesis d of pixel p of view n is
+ *   depth[n*s0 + d*s1 + p*s2], p = y*W + x.  (N,D,H,W) contiguous: {D*H*W, H*W, 1};  plane depths (N,D): {D, 1, 0}.
+ *   Group widths: C % G == 0 and Cg in {4, 8, 16} or Cg % 32 == 0; anything else is MVSDET_ERR_INVALID_ARG.  With Cg in
+ *   {4, 8, 16} C need not be a multiple of 32.  One slab image < 2^31 bytes; N and the slab count <= 65535.
+ * The forward uses no atomics: the same inputs give the same bits on every run.
+ * Backward: grad = dL/dout (N,K,G,D,H,W) contiguous; gfeat (N,C,H,W) is OVERWRITTEN with dL/dfeat (the reference view's own
+ * term and the neighbours' tap gradients; depth and proj get none).  The tap gradients are summed with float atomics into a
+ * packed gradient map in `workspace` (>= mvsdet_plane_sweep_pixel_bwd_workspace_bytes(N, C, H, W), 16-byte aligned,
+ * overwritten): the last bits depend on arrival order.  MVSDET_ERR_WORKSPACE for a workspace that is too small.
+ * Not offered: fp16 storage, pitched output, view shards.
+ * ------------------------------------------------------------------------------------------- */
+int mvsdet_plane_sweep_groupcorr_packed_f32(const float* packed, const int64_t* nbr, const float* proj, const float* depth,
+                                            const int64_t* depth_strides, float* out, int N, int K, int C, int G, int D, int H,
+                                            int W, mvsdet_stream_t stream);
+int mvsdet_plane_sweep_groupcorr_bwd_packed_f32(const float* packed, const int64_t* nbr, const float* proj, const float* depth,
+                                                const int64_t* depth_strides, const float* grad, float* gfeat, void* workspace,
+                                                size_t workspace_bytes, int N, int K, int C, int G, int D, int H, int W,
+                                                mvsdet_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * a5-a7  depth probability, top-k plane selection, depth expectation --
  * mvsdet.py:470-475 (softmax / sigmoid), :266-283 (sample_depth_prob), :298-317 (compute_avg_depth).
  *   cost_reg, off_logit (N,D,H,W)  the two output channels of CostRegNet_3DGS

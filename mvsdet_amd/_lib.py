@@ -146,6 +146,8 @@ SIGNATURES = {
     "mvsdet_plane_sweep_variance_pixel_packed_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_plane_sweep_pixel_bwd_workspace_bytes": [_i, _i, _i, _i],
     "mvsdet_plane_sweep_variance_pixel_bwd_packed_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_plane_sweep_groupcorr_packed_f32": [_vp, _vp, _vp, _vp, _i64p, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_plane_sweep_groupcorr_bwd_packed_f32": [_vp, _vp, _vp, _vp, _i64p, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp],
 }
 _RESTYPE = {"mvsdet_last_error": ctypes.c_char_p, "mvsdet_conv3d_k3_bf16x3_stats_parts": ctypes.c_size_t, "mvsdet_convT3d_k3_s2_bf16x3_stats_parts": ctypes.c_size_t, "mvsdet_gemm_split_weight_bytes": ctypes.c_size_t, "mvsdet_neck_gemm_dw_partial_bytes": ctypes.c_size_t, "mvsdet_scl_bytes": ctypes.c_size_t, "mvsdet_pscl_bytes": ctypes.c_size_t,
             "mvsdet_split_conv_weight_bytes": ctypes.c_size_t, "mvsdet_packed_bytes": ctypes.c_size_t,

@@ -158,6 +158,31 @@ def homo_warping(src_fea: Tensor, src_proj: Tensor, ref_proj: Tensor, depth_valu
     return ops.homo_warp_pixel(src_fea, proj, depth_values) if pixel else ops.homo_warp(src_fea, proj, depth_values)
 
 
+def groupwise_correlation(feature: Tensor, neighbor_ids: Tensor, ref_proj: Tensor, nei_projs: Sequence[Tensor], depth_values: Tensor,
+                          num_groups: int, reduce: str = "none") -> Tensor:
+    """The group-wise correlation cost of mvs_models/lss_fpn.py:499-506 on this project's cameras: feature (N,C,H,W),
+    neighbor_ids (N,K), ref_proj (N,4,4), nei_projs K x (N,4,4) (what `collect_proj` returns), depth_values (N,D) or (N,D,H,W)
+    -> (N,K,G,D,H,W): per neighbour j and group g the mean over the group's C/G channels of feature x homo_warping(neighbour j).
+    reduce="mean": the mean over the K neighbours, (N,G,D,H,W) -- what a group-wise-correlation network feeds its regulariser.
+    One fused launch; differentiable in `feature`."""
+    if reduce not in ("none", "mean"):
+        raise ValueError(f"groupwise_correlation: reduce must be 'none' or 'mean' (got {reduce!r})")
+    if depth_values.dim() not in (2, 4):
+        raise ValueError(f"groupwise_correlation: depth_values must be (N,D) or (N,D,H,W) (got shape {tuple(depth_values.shape)})")
+    if feature.dim() != 4 or depth_values.shape[0] != feature.shape[0] or (
+            depth_values.dim() == 4 and tuple(depth_values.shape[2:]) != tuple(feature.shape[2:])):
+        raise ValueError(f"groupwise_correlation: depth_values {tuple(depth_values.shape)} do not match feature {tuple(feature.shape)}")
+    nei_projs = tuple(nei_projs)
+    if neighbor_ids.dim() != 2 or len(nei_projs) != neighbor_ids.shape[1] or len(nei_projs) < 1:
+        raise ValueError(f"groupwise_correlation: {len(nei_projs)} neighbour projections for neighbor_ids {tuple(neighbor_ids.shape)}")
+    ops.sweep._check_groups("groupwise_correlation", feature.shape[1], int(num_groups))
+    feature, depth_values = amp_fp32(feature, depth_values)
+    dev = feature.device
+    proj = torch.stack([relative_projection(p, ref_proj) for p in nei_projs], dim=1).to(dev)     # module.py:116 per neighbour
+    corr = ops.sweep.plane_sweep_groupcorr(feature, neighbor_ids.to(dev), proj, depth_values.to(dev).contiguous(), int(num_groups))
+    return corr.mean(dim=1) if reduce == "mean" else corr
+
+
 # ------------------------------------------------------------------------------------------- a9
 def depth_diagnostics(points: Tensor, projection: Tensor, est_depth: Tensor, est_dens: Tensor, depth_mean: Tensor,
                       gt_depth: Tensor, vz: float):

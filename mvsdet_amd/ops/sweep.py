@@ -536,6 +536,145 @@ def _sweep_pixel_bwd(ctx, grad):
 plane_sweep_variance_pixel.register_autograd(_sweep_pixel_bwd, setup_context=_sweep_setup)
 
 
+# ------------------------------------------------------------------------------------------- group-wise correlation
+# The second reduction of stage 1 (the reference's mvs_models/lss_fpn.py:499-506): per neighbour the mean over a group's C/G
+# channels of reference feature x warped feature, fused with the warp (csrc/groupcorr.hip).  Plane depths (N,D) and per-pixel
+# depths (N,D,H,W) run the same kernel: the depth is read through strides, a plane depth with pixel stride 0.
+# These operators are names of THIS module (ops.sweep.plane_sweep_groupcorr ...), not re-exported by the package: its recorded
+# surface (tests/golden/ops_surface.json) is closed.  functional.groupwise_correlation is the interface callers use.
+GROUPCORR_RULE = "C % groups == 0 and C / groups in {4, 8, 16} or a multiple of 32"
+
+
+def _check_groups(name, C, groups):
+    if groups < 1 or C % groups != 0 or not (C // groups in (4, 8, 16) or (C // groups) % 32 == 0):
+        raise ValueError(f"{name}: C={C}, groups={groups}: the supported group widths are {GROUPCORR_RULE}")
+
+
+def _check_groupcorr_depth(name, nbr, proj, depth, N, H, W):
+    """nbr (N,K) with K >= 1, proj (N,K,4,4), depth (N,D) or (N,D,H,W) -> K, D."""
+    req(nbr, "nbr", dtype=torch.int64, dim=2)
+    req(proj, "proj", dim=4)
+    if depth.dim() == 4:
+        D = _check_depth_pixel(name, depth, N, H, W)
+    elif depth.dim() == 2:
+        req(depth, "depth", dim=2)
+        D = depth.shape[1]
+        if depth.shape[0] != N:
+            raise ValueError(f"{name}: depth {tuple(depth.shape)} is not (N={N}, D)")
+    else:
+        raise ValueError(f"{name}: depth must be (N,D) or (N,D,H,W) (got shape {tuple(depth.shape)})")
+    K = nbr.shape[1]
+    if K < 1:
+        raise ValueError(f"{name}: at least one neighbour per view (K={K})")
+    if nbr.shape[0] != N or proj.shape != (N, K, 4, 4):
+        raise ValueError(f"{name}: nbr {tuple(nbr.shape)}, proj {tuple(proj.shape)} do not match N={N}")
+    return K, D
+
+
+def _depth_strides(depth):
+    """depth_strides of the C entries for a contiguous depth: {view, hypothesis, pixel}; pixel stride 0 for plane depths."""
+    D = depth.shape[1]
+    if depth.dim() == 2:
+        return (ctypes.c_int64 * 3)(D, 1, 0)
+    HW = depth.shape[2] * depth.shape[3]
+    return (ctypes.c_int64 * 3)(D * HW, HW, 1)
+
+
+@torch.library.custom_op(f"{_NS}::plane_sweep_groupcorr_packed", mutates_args=(), device_types="cuda")
+def plane_sweep_groupcorr_packed(packed: Tensor, nbr: Tensor, proj: Tensor, depth: Tensor, C: int, groups: int, H: int = 0,
+                                 W: int = 0) -> Tensor:
+    """Group-wise correlation on already packed maps of (N,C,H,W) features: nbr (N,K), proj (N,K,4,4), depth (N,D) or (N,D,H,W)
+    -> (N,K,groups,D,H,W) float32.  H, W: needed with plane depths only, which do not carry the map's shape."""
+    name = "plane_sweep_groupcorr_packed"
+    req(packed, "packed", dim=1)
+    _check_groups(name, C, groups)
+    if depth.dim() == 4 and (H, W) == (0, 0):
+        H, W = depth.shape[-2:]
+    if H < 1 or W < 1:
+        raise ValueError(f"{name}: plane depths need the map's H and W")
+    N = nbr.shape[0] if nbr.dim() == 2 else -1
+    K, D = _check_groupcorr_depth(name, nbr, proj, depth, N, H, W)
+    if packed.numel() * 4 != _lib.load().mvsdet_packed_bytes(N, C, H, W):
+        raise ValueError(f"{name}: packed buffer does not match (N,C,H,W)")
+    nbr, proj, depth = nbr.contiguous(), proj.contiguous(), depth.contiguous()
+    out = torch.empty((N, K, groups, D, H, W), dtype=torch.float32, device=packed.device)
+    with torch.cuda.device(packed.device):
+        _lib.check(_lib.load().mvsdet_plane_sweep_groupcorr_packed_f32(_lib.ptr(packed), _lib.ptr(nbr), _lib.ptr(proj), _lib.ptr(depth),
+                                                                       _depth_strides(depth), _lib.ptr(out), N, K, C, groups, D, H, W,
+                                                                       stream(packed)), name)
+    return out
+
+
+@plane_sweep_groupcorr_packed.register_fake
+def _(packed, nbr, proj, depth, C, groups, H=0, W=0):
+    if depth.dim() == 4 and (H, W) == (0, 0):
+        H, W = depth.shape[-2:]
+    return packed.new_empty((nbr.shape[0], nbr.shape[1], groups, depth.shape[1], H, W))
+
+
+@torch.library.custom_op(f"{_NS}::plane_sweep_groupcorr", mutates_args=(), device_types="cuda")
+def plane_sweep_groupcorr(feat: Tensor, nbr: Tensor, proj: Tensor, depth: Tensor, groups: int) -> Tensor:
+    """Group-wise correlation cost volume: feat (N,C,H,W), nbr (N,K) int64, proj (N,K,4,4), depth (N,D) or (N,D,H,W) ->
+    (N,K,groups,D,H,W): out[n,j,g] = mean over the C/groups channels of group g of feat[n] * warp_j(feat[nbr[n,j]]).
+    Differentiable in feat (the backward packs the features again)."""
+    req(feat, "feat", dim=4)
+    N, C, H, W = feat.shape
+    _check_groups("plane_sweep_groupcorr", C, groups)
+    _check_groupcorr_depth("plane_sweep_groupcorr", nbr, proj, depth, N, H, W)
+    return plane_sweep_groupcorr_packed(pack_features(feat), nbr, proj, depth, C, groups, H, W)
+
+
+@plane_sweep_groupcorr.register_fake
+def _(feat, nbr, proj, depth, groups):
+    N, C, H, W = feat.shape
+    return feat.new_empty((N, nbr.shape[1], groups, depth.shape[1], H, W))
+
+
+@torch.library.custom_op(f"{_NS}::plane_sweep_groupcorr_backward", mutates_args=(), device_types="cuda")
+def plane_sweep_groupcorr_backward(feat: Tensor, nbr: Tensor, proj: Tensor, depth: Tensor, grad: Tensor, groups: int) -> Tensor:
+    """dL/dfeat (N,C,H,W) from dL/dcorr (N,K,groups,D,H,W): float atomics, the last bits depend on arrival order."""
+    name = "plane_sweep_groupcorr_backward"
+    req(feat, "feat", dim=4)
+    N, C, H, W = feat.shape
+    _check_groups(name, C, groups)
+    K, D = _check_groupcorr_depth(name, nbr, proj, depth, N, H, W)
+    req(grad, "grad", dim=6)
+    if grad.shape != (N, K, groups, D, H, W):
+        raise ValueError(f"{name}: grad {tuple(grad.shape)} is not (N,K,groups,D,H,W) = {(N, K, groups, D, H, W)}")
+    packed = pack_features(feat)
+    nbr, proj, depth, grad = nbr.contiguous(), proj.contiguous(), depth.contiguous(), grad.contiguous()
+    lib = _lib.load()
+    wbytes = int(lib.mvsdet_plane_sweep_pixel_bwd_workspace_bytes(N, C, H, W))
+    ws = torch.empty(wbytes // 4, dtype=torch.float32, device=feat.device)
+    gfeat = torch.empty((N, C, H, W), dtype=torch.float32, device=feat.device)
+    with torch.cuda.device(feat.device):
+        _lib.check(lib.mvsdet_plane_sweep_groupcorr_bwd_packed_f32(_lib.ptr(packed), _lib.ptr(nbr), _lib.ptr(proj), _lib.ptr(depth),
+                                                                   _depth_strides(depth), _lib.ptr(grad), _lib.ptr(gfeat), _lib.ptr(ws),
+                                                                   wbytes, N, K, C, groups, D, H, W, stream(feat)), name)
+    return gfeat
+
+
+@plane_sweep_groupcorr_backward.register_fake
+def _(feat, nbr, proj, depth, grad, groups):
+    return torch.empty_like(feat)
+
+
+def _groupcorr_setup(ctx, inputs, output):
+    feat, nbr, proj, depth, groups = inputs
+    ctx.save_for_backward(feat, nbr, proj, depth)
+    ctx.groups = groups
+
+
+def _groupcorr_bwd(ctx, grad):
+    feat, nbr, proj, depth = ctx.saved_tensors
+    return plane_sweep_groupcorr_backward(feat, nbr, proj, depth, grad, ctx.groups), None, None, None, None
+
+
+plane_sweep_groupcorr.register_autograd(_groupcorr_bwd, setup_context=_groupcorr_setup)
+# under torch.autocast low-precision floating inputs are cast to float32, the rule of the package's other forward operators
+plane_sweep_groupcorr.register_autocast("cuda", torch.float32)
+
+
 # ------------------------------------------------------------------------------------------- the benchmark's two yardsticks
 def device_copy(src: Tensor, dst: Tensor):
     """float4 device-to-device copy kernel (bench.py's achievable-HBM yardstick)."""
