@@ -473,6 +473,34 @@ int mvsdet_depth_diagnostics_f32(const float* points, const float* projection, c
                                  int J, int Hg, int Wg, float vz, mvsdet_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Depth supervision (csrc/depthloss.hip): the reference's two masked depth objectives, one scene per call.
+ *   kind MVSDET_DEPTH_LOSS_L1         MVSDet.depth_loss_func_new (mvsdet.py:893-915): gt (N,Hg,Wg), any Hg, Wg >= 1, is resized to
+ *                                     (h,w) as ATen's upsample_bilinear2d(align_corners=False) does it in fp32; the mask is
+ *                                     resized > 0 (NaN stays outside); the term |est - resized|; mask / mask_strides are ignored
+ *   kind MVSDET_DEPTH_LOSS_SMOOTH_L1  mvsnet_loss (mvs_models/mvsnet.py:292-294): gt and mask are (N,h,w) (Hg = h, Wg = w); inside
+ *                                     where mask > 0.5; the term 0.5 d^2 for |d| < 1, else |d| - 0.5, d = est - gt (beta = 1)
+ *   est + est_strides: (N,h,w), element strides of a 3-D view (the crop of a padded map is read in place, and only inside
+ *   the mask); gt, mask + strides likewise.
+ *   loss (1) fp32 = sum of the terms / count, NaN for an empty mask (0 / 0, torch.mean of nothing); count (1) int32.
+ * Terms are formed in fp32 and added in float64 per wave, per block and over the blocks in a fixed order without atomics:
+ * results are bit-identical from call to call.  Two launches, no host synchronisation.
+ * workspace (16-byte aligned) >= the query below: one 16-byte partial per block of 256 pixels.
+ * Backward: grad (N,h,w) contiguous, written densely: 0 outside the mask; inside (g_loss / count) * sign(d) (l1; sign(0) = 0) or
+ * (g_loss / count) * clamp(d, -1, 1) (smooth_l1), the quotient one IEEE fp32 division.  g_loss (1) fp32 and count (1) int32 are
+ * DEVICE pointers (count as the forward wrote it).  The resized ground truth is formed again from gt.  One launch. */
+#define MVSDET_DEPTH_LOSS_L1 0
+#define MVSDET_DEPTH_LOSS_SMOOTH_L1 1
+size_t mvsdet_depth_loss_workspace_bytes(int N, int h, int w);
+int mvsdet_depth_loss_f32(const float* est, const int64_t* est_strides /*HOST[3]*/, const float* gt,
+                          const int64_t* gt_strides /*HOST[3]*/, const float* mask, const int64_t* mask_strides /*HOST[3]*/,
+                          float* loss, int32_t* count, void* workspace, size_t workspace_bytes, int N, int h, int w, int Hg,
+                          int Wg, int kind, mvsdet_stream_t stream);
+int mvsdet_depth_loss_bwd_f32(const float* est, const int64_t* est_strides /*HOST[3]*/, const float* gt,
+                              const int64_t* gt_strides /*HOST[3]*/, const float* mask,
+                              const int64_t* mask_strides /*HOST[3]*/, const float* g_loss, const int32_t* count, float* grad,
+                              int N, int h, int w, int Hg, int Wg, int kind, mvsdet_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The cost network's 3x3x3 convolutions on the bf16 matrix cores, fp32 operands cut into bf16 pieces ("bf16x3":
  * x*w ~ x_hi*w_hi + x_hi*w_mid + x_mid*w_hi, fp32 accumulation; csrc/costreg_bf16.hip).  Replaces the same layers of
  * mvs_models/mvsnet.py:76-82,104-108 as mvsdet_conv3d_k3_mfma_ws_f32 does, at 3/16 of the fp32 matrix-core time; results

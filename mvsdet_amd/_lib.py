@@ -89,6 +89,9 @@ SIGNATURES = {
     "mvsdet_depth_diagnostics_workspace_bytes": [_i, _i, _i, _i],
     "mvsdet_depth_diagnostics_f32": [_vp, _vp, _vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _vp, _vp, _vp, _vp, _sz,
                                      _i, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "mvsdet_depth_loss_workspace_bytes": [_i, _i, _i],
+    "mvsdet_depth_loss_f32": [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_depth_loss_bwd_f32": [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_copy_f32": [_vp, _vp, _sz, _vp],
     "mvsdet_store_pattern_probe_f32": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_store_pattern_probe_f16": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
@@ -161,6 +164,7 @@ _RESTYPE = {"mvsdet_last_error": ctypes.c_char_p, "mvsdet_conv3d_k3_bf16x3_stats
             "mvsdet_conv3d_k3_bf16x3_workspace_bytes": ctypes.c_size_t,
             "mvsdet_conv3d_k3_s2_bf16x3_workspace_bytes": ctypes.c_size_t,
             "mvsdet_depth_diagnostics_workspace_bytes": ctypes.c_size_t,
+            "mvsdet_depth_loss_workspace_bytes": ctypes.c_size_t,
             "mvsdet_eval_state_bytes": ctypes.c_size_t, "mvsdet_eval_workspace_bytes": ctypes.c_size_t,
             "mvsdet_conv3d_k3_mfma_workspace_bytes": ctypes.c_size_t, "mvsdet_bn3d_workspace_bytes": ctypes.c_size_t}
 

@@ -6,6 +6,7 @@
 // Roofline: HBM.  Per-view form writes N*C*V*4 B (mostly zeros); the fused mean writes C*V*4 B and reads
 // one packed feature column (C*4 B, contiguous) per valid (view, voxel) pair.
 #include "common.h"
+#include "depth_resize.h"
 #include "pack.h"
 
 namespace mvsdet {
@@ -248,35 +249,6 @@ struct DiagVoxelPartial {
     int n_orig, n_valid, n_neq, n_gt;
 };
 
-// at::native::compute_source_index_and_lambda (UpSample.h) in fp32.  The source index is ONE fused multiply-add, as the
-// CPU build of ATen contracts `scale * (dst + 0.5f) - 0.5f`.
-__device__ __forceinline__ void resize_taps(int dst, float scale, int in, int out, int& i0, int& i1, float& l0, float& l1) {
-    if (in == out) {
-        i0 = i1 = dst;
-        l0 = 1.0f;
-        l1 = 0.0f;
-        return;
-    }
-    float src = fmaf(scale, (float)dst + 0.5f, -0.5f);
-    if (src < 0.0f) src = 0.0f;
-    i0 = min((int)floorf(src), in - 1);
-    l1 = fminf(fmaxf(src - (float)i0, 0.0f), 1.0f);
-    i1 = i0 + (i0 < in - 1 ? 1 : 0);
-    l0 = 1.0f - l1;
-}
-
-// Sum over the block in a fixed order: lanes by halving shuffles, then waves 0..3 by thread 0 (its return value counts).
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v = v + __shfl_down(v, o, kWave);
-    return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v = v + __shfl_down(v, o, kWave);
-    return v;
-}
-
 __global__ __launch_bounds__(kThreads) void depth_diag_pixel_kernel(
     const float* __restrict__ gt, int64_t gs0, int64_t gs1, int64_t gs2, const float* __restrict__ dmean, int64_t ms0,
     int64_t ms1, int64_t ms2, float* __restrict__ g_stage, float* __restrict__ gt_resized,
@@ -289,14 +261,7 @@ __global__ __launch_bounds__(kThreads) void depth_diag_pixel_kernel(
     int in_mask = 0;
     if (p < h * w) {
         const int y = p / w, x = p - y * w;
-        int y0, y1, x0, x1;
-        float ly0, ly1, lx0, lx1;
-        resize_taps(y, scale_y, Hg, h, y0, y1, ly0, ly1);
-        resize_taps(x, scale_x, Wg, w, x0, x1, lx0, lx1);
-        const float* src = gt + (int64_t)i * gs0;
-        const float a = src[(int64_t)y0 * gs1 + (int64_t)x0 * gs2], b = src[(int64_t)y0 * gs1 + (int64_t)x1 * gs2];
-        const float c = src[(int64_t)y1 * gs1 + (int64_t)x0 * gs2], d = src[(int64_t)y1 * gs1 + (int64_t)x1 * gs2];
-        const float g = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d);
+        const float g = resized_at(gt + (int64_t)i * gs0, gs1, gs2, y, x, h, w, Hg, Wg, scale_y, scale_x);   // depth_resize.h
         const size_t o = (size_t)i * h * w + p;
         g_stage[o] = g;
         if (gt_resized) gt_resized[o] = g;

@@ -239,3 +239,69 @@ def backproject_Weigh(features: Tensor, points: Tensor, projection: Tensor, dept
     volume = volume.view(n, c, nx, ny, nz)
     valid = valid.view(n, 1, nx, ny, nz)
     return volume, valid, gap_all, rmse
+
+
+# ------------------------------------------------------------------------------------------- depth supervision
+def _refuse_gt_grad(name: str, *tensors):
+    for t in tensors:
+        if isinstance(t, Tensor) and t.requires_grad:
+            raise RuntimeError(f"{name}: the ground truth and the mask carry no gradient (the reference gives them none); detach them")
+
+
+def _scene_depth_loss(est: Tensor, gt: Tensor) -> Tensor:
+    """One scene of depth_loss_func_new (mvsdet.py:902-913): est (N,h,w), gt (N,Hg,Wg) -> 0-dim loss."""
+    if est.is_cuda:
+        est, gt = amp_fp32(est, gt)
+        if gt.device != est.device:
+            gt = gt.to(est.device, non_blocking=True)
+        return ops.depth.depth_loss(est, gt, None, ops.depth.DEPTH_LOSS_L1)[0]
+    import torch.nn.functional as F
+    height, width = est.shape[1], est.shape[2]
+    cur_gt = F.interpolate(gt.unsqueeze(1), size=(height, width), mode="bilinear").squeeze(1)
+    tmp_mask = cur_gt > 0
+    return torch.mean(torch.abs(est[tmp_mask] - cur_gt[tmp_mask]))
+
+
+def depth_loss_func_new(est_depth: Sequence[Tensor], gt_depth: Sequence[Tensor]) -> dict:
+    """MVSDet.depth_loss_func_new (mvsdet.py:893-915) without `self`: lists over the batch of est (N,1,h,w) and gt (N,Hg,Wg) ->
+    dict(loss_depth=sum over the scenes, in list order from 0., of the mean of |est - resized gt| where resized gt > 0).
+    Device tensors: one `ops.depth.depth_loss` per scene (two launches, no host synchronisation, no boolean-mask gather; est --
+    a crop of the padded depth expectation -- and gt are read in place); the first scene's mean is the sum so far (0. + x = x),
+    every further scene costs one 0-dim addition.  CPU tensors: the reference's own ops in its order.  Differentiable in est.
+    An unmodified reference never reaches this function with data: extract_feat leaves `est_depth_crop` empty (mvsdet.py:400,698),
+    so its loss_depth is the 0. of an empty loop; `MVSDetHotPath.depth_loss` hands over what it meant to, depth_coding."""
+    if len(est_depth) != len(gt_depth):
+        raise ValueError(f"depth_loss_func_new: {len(est_depth)} estimates for {len(gt_depth)} ground-truth maps")
+    loss = 0.
+    for i, (est, gt) in enumerate(zip(est_depth, gt_depth)):
+        _refuse_gt_grad("depth_loss_func_new", gt)
+        if est.dim() != 4 or est.shape[1] != 1 or gt.dim() != 3 or gt.shape[0] != est.shape[0]:
+            raise ValueError(f"depth_loss_func_new: scene {i}: est {tuple(est.shape)} must be (N,1,h,w) and gt {tuple(gt.shape)} (N,Hg,Wg)")
+        term = _scene_depth_loss(est.squeeze(1), gt)
+        loss = term if (i == 0 and term.is_cuda) else loss + term
+    return dict(loss_depth=loss)
+
+
+def mvsnet_loss(depth_est: Tensor, depth_gt: Tensor, mask: Tensor) -> Tensor:
+    """mvs_models/mvsnet.py:292-294: the mean over mask > 0.5 of smooth_l1(depth_est - depth_gt) (beta 1), three tensors of one
+    shape (B,H,W).  Device tensors: one `ops.depth.depth_loss` (two launches, no host synchronisation), all three read in place; a
+    mask that is not float32 (bool, as some loaders hand it over) is converted first.  CPU tensors: the reference's ops.
+    Differentiable in depth_est."""
+    _refuse_gt_grad("mvsnet_loss", depth_gt, mask)
+    if not (depth_est.shape == depth_gt.shape == mask.shape):
+        raise ValueError(f"mvsnet_loss: shapes differ: {tuple(depth_est.shape)} / {tuple(depth_gt.shape)} / {tuple(mask.shape)}")
+    if not depth_est.is_cuda:
+        import torch.nn.functional as F
+        m = mask > 0.5
+        return F.smooth_l1_loss(depth_est[m], depth_gt[m], reduction="mean")
+    if depth_est.dim() < 2:
+        raise ValueError(f"mvsnet_loss: depth maps must be at least 2-D (got shape {tuple(depth_est.shape)})")
+    depth_est, depth_gt, mask = amp_fp32(depth_est, depth_gt, mask)
+    dev = depth_est.device
+    depth_gt, mask = (t if t.device == dev else t.to(dev, non_blocking=True) for t in (depth_gt, mask))
+    if mask.dtype != torch.float32:
+        mask = mask.float()
+    if depth_est.dim() != 3:
+        H, W = depth_est.shape[-2:]
+        depth_est, depth_gt, mask = (t.reshape(-1, H, W) for t in (depth_est, depth_gt, mask))
+    return ops.depth.depth_loss(depth_est, depth_gt, mask, ops.depth.DEPTH_LOSS_SMOOTH_L1)[0]

@@ -527,6 +527,15 @@ class MVSDetHotPath:
             out._put("gt_depth_resized", gt_resized)
         return out
 
+    def depth_loss(self, outputs, gt_depth) -> dict:
+        """`loss_depth` of MVSDet.loss (mvsdet.py:771-843, depth_loss_func_new :893-915) for one `SceneOutputs` and its ground
+        truth (N,Hg,Wg), or a sequence of them and the matching depths -> dict(loss_depth=...).  The estimate is
+        outputs["depth_coding"] (N,1,h,w) -- what the reference meant to collect in `est_depth_crop` -- so the gradient reaches
+        the cost network through depth_prob_topk's backward (its g_avg)."""
+        if isinstance(outputs, Mapping):
+            outputs, gt_depth = [outputs], [gt_depth]
+        return F_.depth_loss_func_new([o["depth_coding"] for o in outputs], list(gt_depth))
+
     # name -> (detector tail on the side stream, view streams of the cost network beside it; None = the module's own setting)
     OVERLAP_ROUTES = {"one": (False, None), "side1": (True, 1), "side2": (True, 2)}
     _TUNE_WARM, _TUNE_SPAN = 2, 4    # scenes of a route left out (the previous route drains), scenes measured

@@ -143,6 +143,30 @@ def unpatch_reference_head(head_module, originals: dict) -> None:
         setattr(head_module.NerfDetHead, name.split(".", 1)[1], fn)
 
 
+def patch_reference_depth_loss(mvsdet_module) -> dict:
+    """Opt-in (the import hook does not apply it): rebind `MVSDet.depth_loss_func_new` (mvsdet.py:893-915) of an imported reference
+    `mvsdet` module so that lists of device tensors go to the HIP kernel (functional.depth_loss_func_new: no `nonzero`, no host
+    synchronisation) and anything else to the original.  An unmodified `extract_feat` leaves `est_depth_crop` empty
+    (mvsdet.py:400,698), so this matters once the caller fills that list.  Returns {name: original} for
+    `unpatch_reference_depth_loss`."""
+    cls = mvsdet_module.MVSDet
+    original = cls.__dict__["depth_loss_func_new"]
+
+    def depth_loss_func_new(self, est_depth, gt_depth):
+        if len(est_depth) > 0 and all(getattr(t, "is_cuda", False) for t in est_depth):
+            return F_.depth_loss_func_new(est_depth, gt_depth)
+        return original(self, est_depth, gt_depth)
+
+    depth_loss_func_new.__doc__ = original.__doc__
+    cls.depth_loss_func_new = depth_loss_func_new
+    return {"MVSDet.depth_loss_func_new": original}
+
+
+def unpatch_reference_depth_loss(mvsdet_module, originals: dict) -> None:
+    for name, fn in originals.items():
+        setattr(mvsdet_module.MVSDet, name.split(".", 1)[1], fn)
+
+
 def patch_reference_nms3d(head_module) -> dict:
     """Opt-in (the import hook does not apply it): rebind the module-global `nms3d` of an imported reference `nerfdet_head` module
     (mmcv.ops.nms3d, which ImVoxelHead_ARKit._single_scene_multiclass_nms calls) so that its unmodified predict runs the rotated

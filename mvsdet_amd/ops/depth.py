@@ -207,3 +207,95 @@ def _dp_bwd(ctx, g_prob, g_off, g_depth, g_dens, g_idx, g_avg):
 
 
 depth_prob_topk.register_autograd(_dp_bwd, setup_context=_dp_setup)
+
+
+# ------------------------------------------------------------------------------------------- depth supervision (csrc/depthloss.hip)
+DEPTH_LOSS_L1, DEPTH_LOSS_SMOOTH_L1 = 0, 1   # include/mvsdet_hip.h: MVSDET_DEPTH_LOSS_*
+
+
+def _check_depth_loss(name: str, est: Tensor, gt: Tensor, mask: Optional[Tensor], kind: int):
+    req(est, "est", dim=3)
+    req(gt, "gt", dim=3)
+    if kind not in (DEPTH_LOSS_L1, DEPTH_LOSS_SMOOTH_L1):
+        raise ValueError(f"{name}: kind must be {DEPTH_LOSS_L1} (l1) or {DEPTH_LOSS_SMOOTH_L1} (smooth_l1), got {kind}")
+    if gt.shape[0] != est.shape[0]:
+        raise ValueError(f"{name}: est {tuple(est.shape)} and gt {tuple(gt.shape)} disagree on the number of views")
+    if kind == DEPTH_LOSS_SMOOTH_L1:
+        if mask is None:
+            raise ValueError(f"{name}: smooth_l1 needs a mask")
+        req(mask, "mask", dim=3)
+        if gt.shape != est.shape or mask.shape != est.shape:
+            raise ValueError(f"{name}: smooth_l1 takes gt and mask at the shape of est {tuple(est.shape)}, got {tuple(gt.shape)} / "
+                             f"{tuple(mask.shape)}")
+    elif mask is not None:
+        raise ValueError(f"{name}: l1 takes its mask from the resized gt (> 0); pass mask=None")
+    N, h, w = est.shape
+    return N, h, w, int(gt.shape[1]), int(gt.shape[2])
+
+
+@torch.library.custom_op(f"{_NS}::depth_loss", mutates_args=(), device_types="cuda")
+def depth_loss(est: Tensor, gt: Tensor, mask: Optional[Tensor], kind: int) -> Tuple[Tensor, Tensor]:
+    """One scene of the reference's depth objectives -> (loss () fp32, count () int32).  est (N,h,w) any strides (the crop of a
+    padded map is read in place).  kind 0 (l1, MVSDet.depth_loss_func_new, mvsdet.py:893-915): gt (N,Hg,Wg) any strides and size is
+    resized to (h,w) as F.interpolate(mode='bilinear') does; mask = resized > 0; mean of |est - resized|; `mask` must be None.
+    kind 1 (smooth_l1, mvsnet_loss, mvs_models/mvsnet.py:292-294): gt, mask (N,h,w); mean over mask > 0.5 of smooth-L1 (beta 1).
+    Two launches on the current stream, no atomics, no host synchronisation; an empty mask gives NaN and count 0.
+    Differentiable in est only."""
+    N, h, w, Hg, Wg = _check_depth_loss("depth_loss", est, gt, mask, kind)
+    dev = est.device
+    lib = _lib.load()
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    count = torch.empty((), dtype=torch.int32, device=dev)
+    ws_bytes = int(lib.mvsdet_depth_loss_workspace_bytes(N, h, w))
+    workspace = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.mvsdet_depth_loss_f32(
+            _lib.ptr(est), _lib.strides3(est), _lib.ptr(gt), _lib.strides3(gt), _lib.ptr(mask),
+            None if mask is None else _lib.strides3(mask), _lib.ptr(loss), _lib.ptr(count), _lib.ptr(workspace), ws_bytes,
+            N, h, w, Hg, Wg, kind, stream(est)), "depth_loss")
+    return loss, count
+
+
+@depth_loss.register_fake
+def _(est, gt, mask, kind):
+    return est.new_empty(()), est.new_empty((), dtype=torch.int32)
+
+
+@torch.library.custom_op(f"{_NS}::depth_loss_backward", mutates_args=(), device_types="cuda")
+def depth_loss_backward(est: Tensor, gt: Tensor, mask: Optional[Tensor], count: Tensor, g_loss: Tensor, kind: int) -> Tensor:
+    """d loss / d est of `depth_loss` -> (N,h,w) fp32, dense: 0 outside the mask, (g_loss / count) * sign(est - g) (l1) or
+    * clamp(est - gt, -1, 1) (smooth_l1) inside.  count () int32 as the forward returned it and g_loss () fp32 are read on the
+    device.  One launch."""
+    N, h, w, Hg, Wg = _check_depth_loss("depth_loss_backward", est, gt, mask, kind)
+    req(g_loss, "g_loss")
+    if count.dtype != torch.int32 or count.numel() != 1 or g_loss.numel() != 1 or count.device != est.device:
+        raise ValueError("depth_loss_backward: count must be one int32 and g_loss one float32 on the device of est")
+    grad = torch.empty((N, h, w), dtype=torch.float32, device=est.device)
+    with torch.cuda.device(est.device):
+        _lib.check(_lib.load().mvsdet_depth_loss_bwd_f32(
+            _lib.ptr(est), _lib.strides3(est), _lib.ptr(gt), _lib.strides3(gt), _lib.ptr(mask),
+            None if mask is None else _lib.strides3(mask), _lib.ptr(g_loss), _lib.ptr(count), _lib.ptr(grad), N, h, w, Hg, Wg, kind,
+            stream(est)), "depth_loss_backward")
+    return grad
+
+
+@depth_loss_backward.register_fake
+def _(est, gt, mask, count, g_loss, kind):
+    return est.new_empty(tuple(est.shape))
+
+
+def _dl_setup(ctx, inputs, output):
+    est, gt, mask, kind = inputs
+    if gt.requires_grad or (mask is not None and mask.requires_grad):
+        raise RuntimeError("depth_loss: the ground truth and the mask carry no gradient (the reference gives them none); "
+                           "detach them")
+    ctx.save_for_backward(est, gt, mask, output[1])
+    ctx.kind = kind
+
+
+def _dl_bwd(ctx, g_loss, g_count):
+    est, gt, mask, count = ctx.saved_tensors
+    return depth_loss_backward(est, gt, mask, count, g_loss.contiguous(), ctx.kind), None, None, None
+
+
+depth_loss.register_autograd(_dl_bwd, setup_context=_dl_setup)
