@@ -501,6 +501,59 @@ int mvsdet_depth_loss_bwd_f32(const float* est, const int64_t* est_strides /*HOS
                               int N, int h, int w, int Hg, int Wg, int kind, mvsdet_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Photometric consistency (csrc/photoloss.hip): the reference's self-supervised depth objective, mvs_models/homography.py
+ * (inverse_warping, _bilinear_sample, compute_reconstr_loss) and MVSDet.photometric_loss (mvsdet.py:845-874).  fp32, no atomics, no
+ * host synchronisation; every result is bit-identical from call to call.
+ *
+ * mvsdet_photo_geometry_f32 (one launch): for pair b, the left view left_idx[b] and the right view right_idx[b] (DEVICE int64; NULL =
+ *   view b), geo[b] (24 floats) = K_left^-1 (9, row-major), K_left [R_right R_left^T | t_right - R_rel t_left] (12, row-major 3x4),
+ *   3 unused -- the LEFT intrinsics project into the right view, as the reference has it.  Formed in float64 from the fp32 cameras
+ *   (the inverse by the adjugate) and rounded once.  ext_*: rows [R|t] of 4 floats, *_view_stride elements between views ((N,4,4): 16,
+ *   the packed (B,2,3,4) cameras: 24); k_left: 3 rows k_row_stride apart, k_view_stride between views (0: one matrix for all).
+ *   An index outside [0, n_left) / [0, n_right) gives a NaN geometry and reads nothing.
+ * mvsdet_photo_warp_f32 (one launch, one thread per (b, y, x)): img (n_img,h,w,C) through img_strides {view, y, x, channel} and
+ *   src_idx[b], depth (n_depth,h,w) through depth_strides and depth_idx[b] (DEVICE int64; NULL = b, then the count must be B);
+ *   xg (w), yg (h): the pixel grid (linspace(-1,1,W) + 1) * 0.5 * (W-1) of the reference, fp32.  Per pixel, in the reference's fp32
+ *   order: cam = (K^-1 [xg,yg,1]) depth, p = P [cam;1], x = p0 / (p2 + 1e-10), the round trip / (W-1) * 2 - 1, (. + 1) * (W-1) / 2,
+ *   x0 = floor(x), x1 = x0 + 1; mask = x0 >= 0 && x1 <= W-1 && y0 >= 0 && y0 <= H-1 (on y0; NaN is outside); the four indices
+ *   clamped, weights from the CLAMPED x1, y1: wa = (x1-x)(y1-y) on (y0,x0), wb = (x1-x)(1-(y1-y)) on (y1,x0), wc on (y0,x1), wd on
+ *   (y1,x1).  warped (B,h,w,C) and mask (B,h,w) float 0/1, contiguous; outside the mask warped is that same (extrapolating) formula.
+ *   An index outside its range gives NaN, mask 0, and reads nothing.
+ * mvsdet_photo_warp_bwd_f32 (one launch): grad (n_depth,h,w) contiguous, dense = sum over the pairs b with depth_idx[b] = view, in
+ *   ascending b, of sum_c g_warped * d warped / d depth (floor and clamp carry no gradient).  A pixel whose g_warped is 0 in every
+ *   channel contributes exactly 0.
+ * mvsdet_photo_loss_f32 (two launches): wm = warped * mask, rm = ref * mask (ref (B,h,w,C) through ref_strides);
+ *   terms[0] = mean smooth_l1(wm - rm) (beta 1), terms[1] / terms[2] = the same of the forward differences along w / h (each over its
+ *   own B h (w-1) C / B (h-1) w C elements); loss (1) = simple ? terms[0] : 0.5 terms[0] + 0.5 (terms[1] + terms[2]); count (1) int32 = pixels
+ *   with mask != 0.  Terms fp32, sums float64 per wave, per block, over the blocks in ascending order.
+ *   workspace (16-byte aligned) >= the query: one 32-byte partial per block of 256 pixels.
+ * mvsdet_photo_loss_bwd_f32 (one launch): grad (B,h,w,C) = g_loss (DEVICE) * d L / d warped, exactly 0 where mask = 0.
+ * mvsdet_photo_select_f32 (two launches): masks (n, total) contiguous, L (n), n <= 32: per pixel v_i = L_i + 1e4 (1 - mask_i); the
+ *   scene of the smallest v wins it (the lower index on a tie) if that v < 1e4.  wins (n) int32, loss (1) = sum_i wins_i L_i / total
+ *   (float64, rounded once).  workspace >= the query.  mvsdet_photo_select_bwd_f32: grad (n) = g_loss (DEVICE) * wins_i / total. */
+int mvsdet_photo_geometry_f32(const float* ext_left, int64_t ext_left_view_stride, const float* k_left, int64_t k_view_stride,
+                              int64_t k_row_stride, const float* ext_right, int64_t ext_right_view_stride, const int64_t* left_idx,
+                              const int64_t* right_idx, int n_left, int n_right, float* geo, int B, mvsdet_stream_t stream);
+int mvsdet_photo_warp_f32(const float* img, const int64_t* img_strides /*HOST[4]*/, const int64_t* src_idx, int n_img,
+                          const float* depth, const int64_t* depth_strides /*HOST[3]*/, const int64_t* depth_idx, int n_depth,
+                          const float* geo, const float* xg, const float* yg, float* warped, float* mask, int B, int h, int w, int C,
+                          mvsdet_stream_t stream);
+int mvsdet_photo_warp_bwd_f32(const float* img, const int64_t* img_strides /*HOST[4]*/, const int64_t* src_idx, int n_img,
+                              const float* depth, const int64_t* depth_strides /*HOST[3]*/, const int64_t* depth_idx, int n_depth,
+                              const float* geo, const float* xg, const float* yg, const float* g_warped, float* grad, int B, int h,
+                              int w, int C, mvsdet_stream_t stream);
+size_t mvsdet_photo_loss_workspace_bytes(int B, int h, int w);
+int mvsdet_photo_loss_f32(const float* warped, const float* mask, const float* ref, const int64_t* ref_strides /*HOST[4]*/, float* loss,
+                          float* terms, int32_t* count, void* workspace, size_t workspace_bytes, int B, int h, int w, int C, int simple,
+                          mvsdet_stream_t stream);
+int mvsdet_photo_loss_bwd_f32(const float* warped, const float* mask, const float* ref, const int64_t* ref_strides /*HOST[4]*/,
+                              const float* g_loss, float* grad, int B, int h, int w, int C, int simple, mvsdet_stream_t stream);
+size_t mvsdet_photo_select_workspace_bytes(int n, int total);
+int mvsdet_photo_select_f32(const float* masks, const float* L, int32_t* wins, float* loss, void* workspace, size_t workspace_bytes,
+                            int n, int total, mvsdet_stream_t stream);
+int mvsdet_photo_select_bwd_f32(const int32_t* wins, const float* g_loss, float* grad, int n, int total, mvsdet_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The cost network's 3x3x3 convolutions on the bf16 matrix cores, fp32 operands cut into bf16 pieces ("bf16x3":
  * x*w ~ x_hi*w_hi + x_hi*w_mid + x_mid*w_hi, fp32 accumulation; csrc/costreg_bf16.hip).  Replaces the same layers of
  * mvs_models/mvsnet.py:76-82,104-108 as mvsdet_conv3d_k3_mfma_ws_f32 does, at 3/16 of the fp32 matrix-core time; results

@@ -19,6 +19,7 @@ _i = ctypes.c_int
 _f = ctypes.c_float
 _sz = ctypes.c_size_t
 _i64p = ctypes.POINTER(ctypes.c_int64)
+_i64 = ctypes.c_int64
 
 # name -> argtypes (all return int unless listed in _RESTYPE); mirrors include/mvsdet_hip.h one to one
 SIGNATURES = {
@@ -92,6 +93,15 @@ SIGNATURES = {
     "mvsdet_depth_loss_workspace_bytes": [_i, _i, _i],
     "mvsdet_depth_loss_f32": [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_depth_loss_bwd_f32": [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_photo_geometry_f32": [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _i, _i, _vp, _i, _vp],
+    "mvsdet_photo_warp_f32": [_vp, _i64p, _vp, _i, _vp, _i64p, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "mvsdet_photo_warp_bwd_f32": [_vp, _i64p, _vp, _i, _vp, _i64p, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "mvsdet_photo_loss_workspace_bytes": [_i, _i, _i],
+    "mvsdet_photo_loss_f32": [_vp, _vp, _vp, _i64p, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_photo_loss_bwd_f32": [_vp, _vp, _vp, _i64p, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_photo_select_workspace_bytes": [_i, _i],
+    "mvsdet_photo_select_f32": [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp],
+    "mvsdet_photo_select_bwd_f32": [_vp, _vp, _vp, _i, _i, _vp],
     "mvsdet_copy_f32": [_vp, _vp, _sz, _vp],
     "mvsdet_store_pattern_probe_f32": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_store_pattern_probe_f16": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
@@ -165,6 +175,7 @@ _RESTYPE = {"mvsdet_last_error": ctypes.c_char_p, "mvsdet_conv3d_k3_bf16x3_stats
             "mvsdet_conv3d_k3_s2_bf16x3_workspace_bytes": ctypes.c_size_t,
             "mvsdet_depth_diagnostics_workspace_bytes": ctypes.c_size_t,
             "mvsdet_depth_loss_workspace_bytes": ctypes.c_size_t,
+            "mvsdet_photo_loss_workspace_bytes": ctypes.c_size_t, "mvsdet_photo_select_workspace_bytes": ctypes.c_size_t,
             "mvsdet_eval_state_bytes": ctypes.c_size_t, "mvsdet_eval_workspace_bytes": ctypes.c_size_t,
             "mvsdet_conv3d_k3_mfma_workspace_bytes": ctypes.c_size_t, "mvsdet_bn3d_workspace_bytes": ctypes.c_size_t}
 

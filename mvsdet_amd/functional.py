@@ -305,3 +305,181 @@ def mvsnet_loss(depth_est: Tensor, depth_gt: Tensor, mask: Tensor) -> Tensor:
         H, W = depth_est.shape[-2:]
         depth_est, depth_gt, mask = (t.reshape(-1, H, W) for t in (depth_est, depth_gt, mask))
     return ops.depth.depth_loss(depth_est, depth_gt, mask, ops.depth.DEPTH_LOSS_SMOOTH_L1)[0]
+
+
+# ------------------------------------------------------------------------------------------- photometric consistency
+def _refuse_photo_grad(name: str, **tensors):
+    for what, t in tensors.items():
+        if isinstance(t, Tensor) and t.requires_grad:
+            raise RuntimeError(f"{name}: `{what}` carries no gradient here (the depth, through the sample position, and the warped "
+                               "image do); detach it")
+
+
+def _check_packed_cams(name: str, img: Tensor, left_cam: Tensor, right_cam: Tensor, depth: Tensor):
+    if img.dim() != 4:
+        raise ValueError(f"{name}: img must be (B,h,w,C), got {tuple(img.shape)}")
+    B, h, w, _ = img.shape
+    for what, cam in (("left_cam", left_cam), ("right_cam", right_cam)):
+        if tuple(cam.shape) != (B, 2, 3, 4):
+            raise ValueError(f"{name}: {what} must be ({B},2,3,4): [R|t] and K of every view, got {tuple(cam.shape)}")
+    if depth.numel() != B * h * w or depth.dim() not in (3, 4) or tuple(depth.shape[-2:]) != (h, w):
+        raise ValueError(f"{name}: depth must be ({B},1,{h},{w}), got {tuple(depth.shape)}")
+    return B, h, w
+
+
+def _inverse_warping_host(img: Tensor, left_cam: Tensor, right_cam: Tensor, depth: Tensor) -> Tuple[Tensor, Tensor]:
+    """The reference's operation sequence (homography.py:6-201) on whatever device the tensors live on."""
+    B, h, w, C = img.shape
+    K_left = left_cam[:, 1, :3, :3]
+    R_rel = torch.matmul(right_cam[:, 0, :3, :3], left_cam[:, 0, :3, :3].permute(0, 2, 1))
+    t_rel = right_cam[:, 0, :3, 3:4] - torch.matmul(R_rel, left_cam[:, 0, :3, 3:4])
+    bottom = torch.tensor([0.0, 0.0, 0.0, 1.0], device=img.device).reshape(1, 1, 4).repeat(B, 1, 1)
+    transform = torch.cat([torch.cat([R_rel, t_rel], dim=2).float(), bottom], dim=1)
+    xg, yg = (v.to(img.device) for v in ops.photo.pixel_grid(h, w))
+    grid = torch.stack([xg.repeat(h), yg.repeat_interleave(w), torch.ones(h * w, device=img.device)], dim=0)
+    cam = torch.matmul(torch.inverse(K_left).float(), grid.unsqueeze(0).repeat(B, 1, 1)) * depth.reshape(B, 1, h * w).float()
+    cam_hom = torch.cat([cam, torch.ones((B, 1, h * w), device=img.device)], dim=1)
+    k_hom = torch.cat([torch.cat([K_left.float(), torch.zeros((B, 3, 1), device=img.device)], dim=2), bottom], dim=1)
+    p = torch.matmul(torch.matmul(k_hom, transform), cam_hom)
+    z = p[:, 2:3] + 1e-10
+    x = (p[:, 0:1] / z).reshape(-1) / (w - 1) * 2.0 - 1.0
+    y = (p[:, 1:2] / z).reshape(-1) / (h - 1) * 2.0 - 1.0
+    x = (x + 1.0) * (w - 1.0) / 2.0
+    y = (y + 1.0) * (h - 1.0) / 2.0
+    x0 = torch.floor(x).int()
+    y0 = torch.floor(y).int()
+    x1, y1 = x0 + 1, y0 + 1
+    mask = ((x0 >= 0) & (x1 <= w - 1) & (y0 >= 0) & (y0 <= h - 1)).float()
+    x0, x1, y0, y1 = x0.clamp(0, w - 1), x1.clamp(0, w - 1), y0.clamp(0, h - 1), y1.clamp(0, h - 1)
+    base = (torch.arange(B, device=img.device) * (h * w)).repeat_interleave(h * w)
+    flat = img.reshape(-1, C).float()
+    row0, row1 = base + y0.long() * w, base + y1.long() * w
+    ax, ay = x1.float() - x, y1.float() - y
+    wa, wb, wc, wd = ax * ay, ax * (1.0 - ay), (1.0 - ax) * ay, (1.0 - ax) * (1.0 - ay)
+    out = (wa.unsqueeze(1) * flat[row0 + x0.long()] + wb.unsqueeze(1) * flat[row1 + x0.long()]
+           + wc.unsqueeze(1) * flat[row0 + x1.long()] + wd.unsqueeze(1) * flat[row1 + x1.long()])
+    return out.reshape(B, h, w, C), mask.reshape(B, h, w, 1)
+
+
+def inverse_warping(img: Tensor, left_cam: Tensor, right_cam: Tensor, depth: Tensor) -> Tuple[Tensor, Tensor]:
+    """mvs_models/homography.py:6-63: img (B,h,w,C) of the right views, left_cam / right_cam (B,2,3,4) ([:,0] the world-to-camera
+    [R|t], [:,1,:3,:3] K), depth (B,1,h,w) of the left views -> warped (B,h,w,C), mask (B,h,w,1) float 0/1.  The reference's quirks
+    are kept: the LEFT intrinsics project into the right view, the pixel grid is the fp32 linspace, the mask's last test is on y0 and
+    the weights use the clamped x1, y1 (outside the mask warped is an extrapolation).  Device tensors: `ops.photo.photo_geometry` +
+    `ops.photo.inverse_warp` (two launches, no torch.inverse, no host synchronisation; img and depth read in place).  CPU tensors: the
+    reference's own operation sequence.  Differentiable in depth (through the sample position)."""
+    B, h, w = _check_packed_cams("inverse_warping", img, left_cam, right_cam, depth)
+    _refuse_photo_grad("inverse_warping", img=img, left_cam=left_cam, right_cam=right_cam)
+    if not img.is_cuda:
+        return _inverse_warping_host(img, left_cam, right_cam, depth)
+    img, left_cam, right_cam, depth = amp_fp32(img, left_cam, right_cam, depth)
+    dev = img.device
+    left_cam, right_cam, depth = (t if t.device == dev else t.to(dev, non_blocking=True) for t in (left_cam, right_cam, depth))
+    geo = ops.photo.photo_geometry(left_cam[:, 0], left_cam[:, 1], right_cam[:, 0], None, None)
+    return ops.photo.inverse_warp(img, depth[:, 0] if depth.dim() == 4 else depth, geo, None, None)
+
+
+def _reconstr_loss_host(warped: Tensor, ref: Tensor, mask: Tensor, simple: bool) -> Tensor:
+    """The reference's operation sequence (homography.py:204-225) on whatever device the tensors live on."""
+    import torch.nn.functional as F
+    wm, rm = warped * mask, ref * mask
+    photo = F.smooth_l1_loss(wm, rm, reduction="mean")
+    if simple:
+        return photo
+    grad = (F.smooth_l1_loss(wm[:, :, 1:] - wm[:, :, :-1], rm[:, :, 1:] - rm[:, :, :-1], reduction="mean")
+            + F.smooth_l1_loss(wm[:, 1:] - wm[:, :-1], rm[:, 1:] - rm[:, :-1], reduction="mean"))
+    return (1 - 0.5) * photo + 0.5 * grad
+
+
+def _photometric_loss_host(warped_list, mask_list, ref_list) -> dict:
+    """The reference's operation sequence (mvsdet.py:845-874) on whatever device the tensors live on."""
+    vols = [_reconstr_loss_host(w, r, m, False) + 1e4 * (1 - m) for w, m, r in zip(warped_list, mask_list, ref_list)]
+    vol = torch.stack(vols).permute(1, 2, 3, 4, 0)
+    top = torch.neg(torch.topk(torch.neg(vol), k=1, sorted=False)[0])
+    top = top * (top < 1e4 * torch.ones_like(top)).float()
+    return dict(loss_pc=torch.mean(torch.sum(top, dim=-1)))
+
+
+def compute_reconstr_loss(warped: Tensor, ref: Tensor, mask: Tensor, simple: bool = True) -> Tensor:
+    """mvs_models/homography.py:204-225 -> 0-dim L.  wm = warped * mask, rm = ref * mask; simple: smooth_l1(wm, rm) (beta 1, mean);
+    else 0.5 of it + 0.5 (smooth_l1 of the forward differences along w + along h, each its own mean): a masked pixel next to a valid
+    one contributes its step.  Device tensors: `ops.photo.reconstr_loss` (two launches, float64 sums in a fixed order).  CPU tensors:
+    the reference's ops.  Differentiable in warped."""
+    if not (warped.dim() == 4 and ref.shape == warped.shape and tuple(mask.shape) == tuple(warped.shape[:3]) + (1,)):
+        raise ValueError(f"compute_reconstr_loss: warped {tuple(warped.shape)} and ref {tuple(ref.shape)} must be one (B,h,w,C) and mask "
+                         f"{tuple(mask.shape)} (B,h,w,1)")
+    _refuse_photo_grad("compute_reconstr_loss", ref=ref)
+    if not warped.is_cuda:
+        return _reconstr_loss_host(warped, ref, mask, simple)
+    warped, ref, mask = amp_fp32(warped, ref, mask)
+    return ops.photo.reconstr_loss(warped, ref, mask.detach(), bool(simple))[0]
+
+
+def photometric_loss(warped_list: Sequence[Tensor], mask_list: Sequence[Tensor], ref_list: Sequence[Tensor]) -> dict:
+    """MVSDet.photometric_loss (mvsdet.py:845-874) without `self`: one entry per scene, all of one shape -> dict(loss_pc=...).
+    L_i = compute_reconstr_loss(..., simple=False); per pixel the smallest L_i + 1e4 (1 - mask_i) over the scenes, dropped where it is
+    not < 1e4; the mean over (B,h,w).  For one scene that is L * mean(mask).  Device tensors: `ops.photo.reconstr_loss` per scene and
+    one `ops.photo.photometric_select` (integer win counts, ties to the lower scene; d loss_pc / d L_i = the share of pixels scene i
+    wins).  CPU tensors: the reference's ops."""
+    n = len(warped_list)
+    if n == 0 or len(mask_list) != n or len(ref_list) != n:
+        raise ValueError(f"photometric_loss: {n} warped images, {len(mask_list)} masks and {len(ref_list)} reference images")
+    if any(w.shape != warped_list[0].shape for w in warped_list) or any(m.shape != mask_list[0].shape for m in mask_list):
+        raise ValueError("photometric_loss: the scenes must share one shape (the reference stacks them)")
+    if not warped_list[0].is_cuda:
+        for r in ref_list:
+            _refuse_photo_grad("photometric_loss", ref=r)
+        return _photometric_loss_host(warped_list, mask_list, ref_list)
+    L = [compute_reconstr_loss(w, r, m, simple=False) for w, m, r in zip(warped_list, mask_list, ref_list)]
+    masks = [amp_fp32(m).detach().reshape(1, -1) for m in mask_list]
+    loss, _ = ops.photo.photometric_select(masks[0] if n == 1 else torch.cat(masks, dim=0), L[0].reshape(1) if n == 1 else torch.stack(L))
+    return dict(loss_pc=loss)
+
+
+def _warp_img_host(small: Tensor, neighbor_ids: Tensor, ref_w2c: Tensor, ref_feat_intrinsic: Tensor, ref_depth: Tensor, ref_id: Tensor):
+    """The reference's gathers (mvsdet.py:723-742) behind the resize, on whatever device the tensors live on: small (N,h,w,C)."""
+    N = small.shape[0]
+    full_cam = torch.stack([ref_w2c.float(), ref_feat_intrinsic.float().expand(N, -1, -1)], dim=1)[:, :, :3, :]
+    src_id = neighbor_ids.long()[ref_id, 0]
+    warped, mask = _inverse_warping_host(small[src_id], full_cam[ref_id], full_cam[src_id], ref_depth[ref_id])
+    return warped, mask, small[ref_id]
+
+
+def warp_img(ref_imgs: Tensor, neighbor_ids: Tensor, ref_w2c: Tensor, ref_feat_intrinsic: Tensor, ref_depth: Tensor, ref_id=None):
+    """MVSDet.warp_img (mvsdet.py:701-768) without `self`: ref_imgs (N,3,Hi,Wi) in [0,1], neighbor_ids (N,k), ref_w2c (N,4,4),
+    ref_feat_intrinsic (4,4) (or (N,4,4): per-view), ref_depth (N,1,h,w) -> (warped (B,h,w,3), mask (B,h,w,1), chose_ref_imgs
+    (B,h,w,3)), B = min(10, N): the images are resized by 0.25 (one F.interpolate) and cropped to (h,w); `ref_id` (B) picks the views
+    (None: torch.randperm(N)[:B] drawn on the CPU, as the reference); each is compared with its FIRST neighbour warped into it by its
+    own depth.  Device tensors: the operators read the resized planar images, the cameras and ref_depth (any strides: the crop of
+    the padded depth expectation) in place through ref_id and neighbor_ids[ref_id, 0]; CPU tensors: the reference's own sequence."""
+    import torch.nn.functional as F
+    if ref_imgs.dim() != 4 or ref_depth.dim() != 4 or ref_depth.shape[1] != 1 or ref_depth.shape[0] != ref_imgs.shape[0]:
+        raise ValueError(f"warp_img: ref_imgs {tuple(ref_imgs.shape)} must be (N,C,Hi,Wi) and ref_depth {tuple(ref_depth.shape)} (N,1,h,w)")
+    N = ref_imgs.shape[0]
+    if neighbor_ids.dim() != 2 or neighbor_ids.shape[0] != N or neighbor_ids.shape[1] < 1:
+        raise ValueError(f"warp_img: neighbor_ids must be ({N},k>=1), got {tuple(neighbor_ids.shape)}")
+    if tuple(ref_w2c.shape) != (N, 4, 4) or tuple(ref_feat_intrinsic.shape) not in ((4, 4), (N, 4, 4)):
+        raise ValueError(f"warp_img: ref_w2c must be ({N},4,4) and ref_feat_intrinsic (4,4) or ({N},4,4), got {tuple(ref_w2c.shape)} / "
+                         f"{tuple(ref_feat_intrinsic.shape)}")
+    _refuse_photo_grad("warp_img", ref_imgs=ref_imgs, ref_w2c=ref_w2c, ref_feat_intrinsic=ref_feat_intrinsic)
+    h, w = ref_depth.shape[2], ref_depth.shape[3]
+    dev = ref_imgs.device
+    ref_imgs, ref_w2c, ref_feat_intrinsic, ref_depth = amp_fp32(ref_imgs, ref_w2c, ref_feat_intrinsic, ref_depth)
+    small = F.interpolate(ref_imgs, scale_factor=0.25, mode="bilinear")[:, :, :h, :w]
+    if tuple(small.shape[2:]) != (h, w):
+        raise ValueError(f"warp_img: a quarter of the {tuple(ref_imgs.shape[2:])} images is smaller than the depth map {(h, w)}")
+    small = small.permute(0, 2, 3, 1)                                   # (N,h,w,C): a view of the planar resize
+    if ref_id is None:
+        ref_id = torch.randperm(N)[:min(10, N)]
+    ref_id = torch.as_tensor(ref_id, dtype=torch.int64)
+    if not ref_imgs.is_cuda:
+        return _warp_img_host(small, neighbor_ids, ref_w2c, ref_feat_intrinsic, ref_depth, ref_id)
+    from .ops._common import to_device
+    ref_id = to_device(ref_id, dev)
+    nbr = neighbor_ids.to(dev, non_blocking=True).long()
+    src_id = nbr[ref_id, 0]
+    ref_w2c, ref_feat_intrinsic, ref_depth = (t if t.device == dev else t.to(dev, non_blocking=True)
+                                              for t in (ref_w2c, ref_feat_intrinsic, ref_depth))
+    geo = ops.photo.photo_geometry(ref_w2c.float(), ref_feat_intrinsic.float(), ref_w2c.float(), ref_id, src_id)
+    warped, mask = ops.photo.inverse_warp(small, ref_depth[:, 0], geo, src_id, ref_id)
+    return warped, mask, small[ref_id]

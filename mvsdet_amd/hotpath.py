@@ -312,12 +312,10 @@ class MVSDetHotPath:
         intr = torch.stack([K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2], K[:, 0, 1]], dim=1).float()
         return ops.ray_depth(intr.to(est_depth.device), est_depth, int(h), int(w))
 
-    def _host_geometry(self, img_meta: dict):
-        """The reference's ATen-CPU operator sequence (mvsdet.py:407-450) -> host tensors."""
+    def _feature_cameras(self, img_meta: dict):
+        """World-to-camera matrices (N,4,4) and the intrinsics at feature level, (4,4) or per view (N,4,4) (mvsdet.py:419-431), on
+        the host."""
         stride = self.stride
-        projection = F_.compute_projection(img_meta, stride)
-        height = img_meta["img_shape"][0] // stride
-        width = img_meta["img_shape"][1] // stride
         w2c = torch.tensor(np.array(img_meta["lidar2img"]["extrinsic"]))
         K = torch.tensor(np.array(img_meta["lidar2img"]["intrinsic"]))
         ratio = img_meta["ori_shape"][0] / (img_meta["img_shape"][0] / stride)
@@ -326,6 +324,15 @@ class MVSDetHotPath:
             K_feat[:2] /= ratio
         else:
             K_feat[:, :2] /= ratio
+        return w2c, K_feat
+
+    def _host_geometry(self, img_meta: dict):
+        """The reference's ATen-CPU operator sequence (mvsdet.py:407-450) -> host tensors."""
+        stride = self.stride
+        projection = F_.compute_projection(img_meta, stride)
+        height = img_meta["img_shape"][0] // stride
+        width = img_meta["img_shape"][1] // stride
+        w2c, K_feat = self._feature_cameras(img_meta)
         n = w2c.shape[0]
         k = min(2, n - 1)  # mvsdet.py:432
         c2w = w2c.inverse()
@@ -535,6 +542,32 @@ class MVSDetHotPath:
         if isinstance(outputs, Mapping):
             outputs, gt_depth = [outputs], [gt_depth]
         return F_.depth_loss_func_new([o["depth_coding"] for o in outputs], list(gt_depth))
+
+    def photometric_loss(self, outputs, images, img_meta, ref_id=None) -> dict:
+        """`loss_pc`, the self-supervised photometric consistency term the reference ships commented out (mvsdet.py:687-692, 838-839;
+        warp_img :701-768, photometric_loss :845-874), for one `SceneOutputs` with its images (N,3,Hi,Wi) in [0,1] and its img_meta,
+        or sequences of them -> dict(loss_pc=...).  The depth is outputs["depth_coding"] (N,1,h,w), so the gradient reaches the cost
+        network through depth_prob_topk's backward (its g_avg) -- through the sample position, no ground-truth depth involved.
+        Neighbours come from the scene's geometry, world-to-camera matrices and feature-level intrinsics from img_meta as
+        `forward_scene` derives them.  `ref_id` fixes the chosen views (None: torch.randperm on the CPU, at most 10, as the reference)."""
+        if isinstance(outputs, Mapping):
+            outputs, images, img_meta, ref_id = [outputs], [images], [img_meta], [ref_id]
+        elif ref_id is None:
+            ref_id = [None] * len(outputs)
+        if not (len(outputs) == len(images) == len(img_meta) == len(ref_id)):
+            raise ValueError(f"photometric_loss: {len(outputs)} scenes, {len(images)} image stacks, {len(img_meta)} metas, {len(ref_id)} selections")
+        warped, masks, refs = [], [], []
+        for out, img, meta, rid in zip(outputs, images, img_meta, ref_id):
+            depth = out["depth_coding"]
+            w2c, K_feat = self._feature_cameras(meta)
+            w2c, K_feat = w2c.float(), K_feat.float()
+            if depth.is_cuda:
+                w2c, K_feat = (ops._common.to_device(t, depth.device) for t in (w2c, K_feat))
+            wv, mv, rv = F_.warp_img(img, out["geometry"].neighbor_ids, w2c, K_feat, depth, ref_id=rid)
+            warped.append(wv)
+            masks.append(mv)
+            refs.append(rv)
+        return F_.photometric_loss(warped, masks, refs)
 
     # name -> (detector tail on the side stream, view streams of the cost network beside it; None = the module's own setting)
     OVERLAP_ROUTES = {"one": (False, None), "side1": (True, 1), "side2": (True, 2)}

@@ -167,6 +167,36 @@ def unpatch_reference_depth_loss(mvsdet_module, originals: dict) -> None:
         setattr(mvsdet_module.MVSDet, name.split(".", 1)[1], fn)
 
 
+def patch_reference_photometric(mvsdet_module) -> dict:
+    """Opt-in (the import hook does not apply it): rebind `MVSDet.warp_img` (mvsdet.py:701-768) and `MVSDet.photometric_loss`
+    (:845-874) of an imported reference `mvsdet` module so that device tensors go to the HIP kernels (functional.warp_img /
+    functional.photometric_loss: no torch.inverse, no host synchronisation, no gathers) and anything else to the originals.  The
+    reference ships both call sites commented out (mvsdet.py:687-692, 838-839): this matters once the caller re-enables them.
+    Returns {name: original} for `unpatch_reference_photometric`."""
+    cls = mvsdet_module.MVSDet
+    originals = {"MVSDet.warp_img": cls.__dict__["warp_img"], "MVSDet.photometric_loss": cls.__dict__["photometric_loss"]}
+    warp_original, loss_original = originals["MVSDet.warp_img"], originals["MVSDet.photometric_loss"]
+
+    def warp_img(self, ref_imgs, neighbor_ids, ref_w2c, ref_feat_intrinsic, ref_depth):
+        if getattr(ref_imgs, "is_cuda", False) and getattr(ref_depth, "is_cuda", False):
+            return F_.warp_img(ref_imgs, neighbor_ids, ref_w2c, ref_feat_intrinsic, ref_depth)
+        return warp_original(self, ref_imgs, neighbor_ids, ref_w2c, ref_feat_intrinsic, ref_depth)
+
+    def photometric_loss(self, warped_img_list, mask_list, chose_ref_img_list):
+        if len(warped_img_list) > 0 and all(getattr(t, "is_cuda", False) for t in warped_img_list):
+            return F_.photometric_loss(warped_img_list, mask_list, chose_ref_img_list)
+        return loss_original(self, warped_img_list, mask_list, chose_ref_img_list)
+
+    warp_img.__doc__, photometric_loss.__doc__ = warp_original.__doc__, loss_original.__doc__
+    cls.warp_img, cls.photometric_loss = warp_img, photometric_loss
+    return originals
+
+
+def unpatch_reference_photometric(mvsdet_module, originals: dict) -> None:
+    for name, fn in originals.items():
+        setattr(mvsdet_module.MVSDet, name.split(".", 1)[1], fn)
+
+
 def patch_reference_nms3d(head_module) -> dict:
     """Opt-in (the import hook does not apply it): rebind the module-global `nms3d` of an imported reference `nerfdet_head` module
     (mmcv.ops.nms3d, which ImVoxelHead_ARKit._single_scene_multiclass_nms calls) so that its unmodified predict runs the rotated

@@ -34,6 +34,7 @@ from .head_train import (  # noqa: F401
 from .evalmap import (  # noqa: F401
     EVAL_MAX_RECORDS, EVAL_MAX_LABELS, EVAL_MAX_THRESHOLDS, EVAL_FLAGS, EvalState, EvalResult, eval_state, eval_reset, eval_match,
     eval_compute, eval_iou)
+from . import photo  # noqa: F401  (ops.photo.<name>: not re-exported)
 
 # ------------------------------------------------------------------------------------------- --amp (tools/train.py:24-28)
 # Under torch.autocast the 2-D backbone hands out float16 / bfloat16 maps.  The hot path computes in float32 -- the rule torch's own
