@@ -3,7 +3,7 @@
   1. decomposition      -- corr against the float64 mean_c(f * w_j) of the GPU's own homo_warp[_pixel] output w_j;
   2. broadcast identity -- the (N,D) call and its (N,D,H,W) broadcast give the same bits, and so do two runs;
   3. fixture G23        -- the reference's own output, at the project's forward bar, through ops and through functional;
-  4. gradients          -- against the float64 gradient of tests/groupcorr_restated.py (G23 and shapes A, C);
+  4. gradients          -- against the float64 gradient of tests/groupcorr_restated.py (G23 and shapes A, C, F);
   5. contention         -- every tap gradient of a (view, neighbour) pair into four texels;
   6. guarded memory     -- the two C entries inside tests/canvas.py frames;
   7. refusals           -- an unsupported group width and a gradient of the wrong shape raise.
@@ -11,12 +11,13 @@
 Shapes (N, K, C, D, H, W; G): A (3, 2, 40, 5, 9, 21; 10 and 5) Cg 4 and 8, a partial second slab, partial tiles, W % 4 != 0;
 B (2, 1, 48, 2, 8, 32; 3) Cg 16, half a slab of padding, the whole-vector stores; C (3, 2, 96, 3, 9, 21; 1 and 3) Cg 96 and 32: a
 group over three slabs and one slab per group; D (4, 3, 64, 2, 6, 10; 1) Cg 64, K = 3: the second decode pass; E (4, 2, 64, 12,
-16, 80; 8) the 80-wide map.  Neighbour ids include a view that is its own neighbour and a repeated neighbour.
+16, 80; 8) the 80-wide map; F (5, 4, 32, 2, 6, 10; 8, 4, 2 and 1) Cg 4, 8, 16 and 32: every forward mode at K = 4, half a tile,
+test_gpu_sweep_pixel.py's S-k4 neighbours.  Neighbour ids include a view that is its own neighbour and a repeated neighbour.
 
 Bound of rule 1 (derived, not measured): |corr - mean64| <= (Cg + 2) 2^-24 mean_c|f w_j| -- the worst case of Cg fp32 roundings of a
 running sum plus the product's and the final scale's.  Gradient bound (rule 4), test_gpu_sweep_pixel.py's:
 |g - g64| <= max(1e-4 |g64| + 1.25e-6 max|g64|, 4 x grad_err_fp32), grad_err_fp32 being the reference's own fp32 summation error
-(from the fixture; for A and C that of the fp32 restatement, computed here).
+(from the fixture; for A, C and F that of the fp32 restatement, computed here).
 
 Measured on an MI355X (DESIGN.md 4.12): rule 1 at most 0.35 of its bound; G23 forward 2.4e-7 through ops, 5.5e-5 through functional;
 gradients at most 0.25 of their bound; contention 3.7e-6 relative."""
@@ -29,6 +30,7 @@ import torch
 
 from conftest import load_golden
 import groupcorr_restated as GR
+from pixel_scenes import check_grad as _check_grad, scene
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
 from lcg import lcg_uniform  # noqa: E402
@@ -37,39 +39,16 @@ pytestmark = pytest.mark.gpu
 
 TOL = 1e-4   # the project's forward bar (test_gpu_parity.py)
 SHAPES = {"A": (3, 2, 40, 5, 9, 21), "B": (2, 1, 48, 2, 8, 32), "C": (3, 2, 96, 3, 9, 21), "D": (4, 3, 64, 2, 6, 10),
-          "E": (4, 2, 64, 12, 16, 80)}
-GROUPS = {"A": (10, 5), "B": (3,), "C": (1, 3), "D": (1,), "E": (8,)}
+          "E": (4, 2, 64, 12, 16, 80), "F": (5, 4, 32, 2, 6, 10)}
+GROUPS = {"A": (10, 5), "B": (3,), "C": (1, 3), "D": (1,), "E": (8,), "F": (8, 4, 2, 1)}
 NBR = {"A": [[0, 1], [2, 2], [1, 0]], "B": [[1], [1]], "C": [[0, 1], [2, 2], [1, 0]], "D": [[1, 2, 3], [0, 0, 2], [2, 3, 1], [0, 1, 2]],
-       "E": [[1, 2], [1, 1], [3, 3], [0, 2]]}
+       "E": [[1, 2], [1, 1], [3, 3], [0, 2]], "F": [[1, 2, 3, 4], [0, 0, 2, 2], [2, 3, 4, 0], [4, 1, 1, 0], [3, 2, 1, 0]]}
 CASES = [(name, G) for name in SHAPES for G in GROUPS[name]]
 G23 = [(tag, kind, G) for tag, gs in (("n3_d8", (1, 2, 4, 8)), ("n6_d12_arkit", (1, 2))) for kind in ("plane", "pixel") for G in gs]
 
 
-def _rot(rx, ry, rz):
-    cx, sx, cy, sy, cz, sz = np.cos(rx), np.sin(rx), np.cos(ry), np.sin(ry), np.cos(rz), np.sin(rz)
-    return (np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]]) @ np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
-            @ np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]]))
-
-
-def _scene(name, seed=5):
-    """feat (N,C,H,W), nbr (N,K), proj (N,K,4,4) = src_proj @ inverse(ref_proj) of mildly rotated and shifted cameras, plane
-    depths (N,D) in [0.6, 4]: CPU tensors."""
-    N, K, C, D, H, W = SHAPES[name]
-    u = lcg_uniform(N * 6 + 1, seed).astype(np.float64)
-    Kmat = np.eye(4)
-    Kmat[0, 0] = Kmat[1, 1] = 0.9 * W
-    Kmat[0, 2], Kmat[1, 2] = (W - 1) / 2, (H - 1) / 2
-    E = []
-    for n in range(N):
-        e = np.eye(4)
-        e[:3, :3] = _rot(*(0.08 * u[6 * n:6 * n + 3]))
-        e[:3, 3] = 0.25 * u[6 * n + 3:6 * n + 6]
-        E.append(Kmat @ e)
-    nbr = np.array(NBR[name], np.int64)
-    proj = np.stack([np.stack([E[nbr[n, j]] @ np.linalg.inv(E[n]) for j in range(K)]) for n in range(N)]).astype(np.float32)
-    feat = torch.from_numpy(lcg_uniform(N * C * H * W, seed + 1)).reshape(N, C, H, W)
-    depth = torch.from_numpy(np.tile(np.linspace(0.6, 4.0, D, dtype=np.float32), (N, 1)))
-    return feat, torch.from_numpy(nbr), torch.from_numpy(proj), depth
+def _scene(name):
+    return scene(SHAPES[name], NBR[name])
 
 
 def _palette_depth(name):
@@ -84,18 +63,6 @@ def _palette_depth(name):
 def _rough_depth(name, seed):
     N, K, C, D, H, W = SHAPES[name]
     return (2.3 + 1.7 * torch.from_numpy(lcg_uniform(N * D * H * W, seed)).reshape(N, D, H, W)).contiguous()
-
-
-def _grad_bound(g64, grad_err_fp32):
-    return torch.maximum(1e-4 * g64.abs() + 1.25e-6 * g64.abs().max(), torch.full_like(g64, 4.0 * grad_err_fp32))
-
-
-def _check_grad(got, g64, grad_err_fp32, what):
-    got = got.detach().double().cpu()
-    excess = (got - g64).abs() / _grad_bound(g64, grad_err_fp32)
-    print(f"{what}: max |g - g64| = {float((got - g64).abs().max()):.3e} (max |g64| {float(g64.abs().max()):.3f}, "
-          f"grad_err_fp32 {grad_err_fp32:.2e}), worst ratio to the bound {float(excess.max()):.3f}")
-    assert torch.isfinite(got).all() and float(excess.max()) <= 1.0, what
 
 
 def _g23_inputs(tag, kind, G):
@@ -195,8 +162,8 @@ def test_g23_gradients(gpu, tag, kind, G):
 
 
 @pytest.mark.parametrize("pixel", [False, True], ids=["plane", "pixel"])
-@pytest.mark.parametrize("name,G", [c for c in CASES if c[0] in "AC"])
-def test_gradients_of_shapes_a_and_c(gpu, name, G, pixel):
+@pytest.mark.parametrize("name,G", [c for c in CASES if c[0] in "ACF"])
+def test_gradients_of_shapes_a_c_and_f(gpu, name, G, pixel):
     from mvsdet_amd import ops
     N, K, C, D, H, W = SHAPES[name]
     feat, nbr, proj, d2 = _scene(name)

@@ -120,7 +120,7 @@ def main() -> int:
     ap.add_argument("--asm-dir", default=None, help="keep the assembly here (before_*.s, after_*.s) and reuse what is already there")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmpdir:
-        tmp = a.asm_dir or tmpdir
+        tmp = os.path.abspath(a.asm_dir) if a.asm_dir else tmpdir   # assemble() runs the compiler inside the source directory
         os.makedirs(tmp, exist_ok=True)
         before = tree(os.path.abspath(a.before), tmp, "before", a.jobs)
         after = tree(os.path.abspath(a.after), tmp, "after", a.jobs)
