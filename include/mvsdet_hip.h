@@ -554,6 +554,43 @@ int mvsdet_photo_select_f32(const float* masks, const float* L, int32_t* wins, f
 int mvsdet_photo_select_bwd_f32(const int32_t* wins, const float* g_loss, float* grad, int n, int total, mvsdet_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Gaussian rasteriser (csrc/splat.hip): what gs_src/model/decoder/cuda_splatting.py::render_cuda asks of its external extension
+ * (Kerbl et al. 2023 with spherical harmonics up to degree 4), for V views that share one set of G Gaussians.  fp32, 16x16 tiles, no
+ * float atomics, no host synchronisation; forward and backward are bit-identical from call to call.  DESIGN.md 4.15 has every
+ * constant.  Limits: d_sh in {1, 4, 9, 16, 25}; V <= 65535; V G, V tiles, 9 V max_keys and 3 V H W below 2^31.
+ *
+ * mvsdet_splat_cameras_f32 (one launch, one thread per view): cams (V,40) = view matrix (16) and full projection (16), both in the
+ *   row-vector (transposed) form render_cuda hands over, tan(fov_x / 2), tan(fov_y / 2), camera position (3), scale, 2 unused -- from
+ *   extrinsics (camera-to-world rows of 4 floats, ext_view_stride elements between views, last row taken as 0 0 0 1), normalised
+ *   intrinsics (3 rows k_row_stride apart, k_view_stride between views) and near / far (V).  scale_invariant: scale = 1 / near
+ *   multiplies the translation, near and far in fp32 as the reference does, and the rasteriser multiplies means by scale and
+ *   covariances by scale^2 itself; otherwise scale = 1.  Inverses, field of view and the matrix product in float64, rounded once.
+ * mvsdet_splat_forward_f32: means (G,3) through means_strides {g, c}, covariances (G,3,3) through cov_strides {g, row, col} (the upper
+ *   triangle is read), harmonics (G,3,d_sh) through sh_strides {g, channel, k}, opacities (G) opacity_stride apart, background (V,3),
+ *   -> image (V,3,H,W) contiguous.  use_sh 0: harmonics (G,3,1) are the colours themselves (no basis, no + 0.5, no clamp).
+ *   max_keys: (Gaussian, tile) pairs a view may have; the count a view needs goes to its status word, the first int4 block of the
+ *   workspace {needed, capacity, overflow, 0} per view.  A view that needs more writes nothing past its share: its image is NaN and
+ *   the backward gives NaN for every gradient.  workspace (256-byte aligned) >= the query; the backward reads it.
+ * mvsdet_splat_backward_f32 (two launches): g_image (V,3,H,W) contiguous -> g_means (G,3), g_covariances (G,3,3: upper triangle, the
+ *   off-diagonals with both symmetric terms; lower triangle 0), g_harmonics (G,3,d_sh), g_opacities (G), summed over the views in
+ *   ascending order.  slots: 9 V max_keys floats of scratch.  Same inputs and workspace as the forward that filled it. */
+size_t mvsdet_splat_workspace_bytes(int V, int G, int H, int W, int max_keys);
+int mvsdet_splat_cameras_f32(const float* extrinsics, int64_t ext_view_stride, const float* intrinsics, int64_t k_view_stride,
+                             int64_t k_row_stride, const float* near, const float* far, int scale_invariant, float* cams, int V,
+                             mvsdet_stream_t stream);
+int mvsdet_splat_forward_f32(const float* means, const int64_t* means_strides /*HOST[2]*/, const float* covariances,
+                             const int64_t* cov_strides /*HOST[3]*/, const float* harmonics, const int64_t* sh_strides /*HOST[3]*/,
+                             const float* opacities, int64_t opacity_stride, const float* cams, const float* background, float* image,
+                             void* workspace, size_t workspace_bytes, int V, int G, int d_sh, int use_sh, int H, int W, int max_keys,
+                             mvsdet_stream_t stream);
+int mvsdet_splat_backward_f32(const float* means, const int64_t* means_strides /*HOST[2]*/, const float* covariances,
+                              const int64_t* cov_strides /*HOST[3]*/, const float* harmonics, const int64_t* sh_strides /*HOST[3]*/,
+                              const float* opacities, int64_t opacity_stride, const float* cams, const float* background,
+                              const float* g_image, void* workspace, size_t workspace_bytes, float* slots, float* g_means,
+                              float* g_covariances, float* g_harmonics, float* g_opacities, int V, int G, int d_sh, int use_sh, int H,
+                              int W, int max_keys, mvsdet_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The cost network's 3x3x3 convolutions on the bf16 matrix cores, fp32 operands cut into bf16 pieces ("bf16x3":
  * x*w ~ x_hi*w_hi + x_hi*w_mid + x_mid*w_hi, fp32 accumulation; csrc/costreg_bf16.hip).  Replaces the same layers of
  * mvs_models/mvsnet.py:76-82,104-108 as mvsdet_conv3d_k3_mfma_ws_f32 does, at 3/16 of the fp32 matrix-core time; results

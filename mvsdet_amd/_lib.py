@@ -102,6 +102,11 @@ SIGNATURES = {
     "mvsdet_photo_select_workspace_bytes": [_i, _i],
     "mvsdet_photo_select_f32": [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp],
     "mvsdet_photo_select_bwd_f32": [_vp, _vp, _vp, _i, _i, _vp],
+    "mvsdet_splat_workspace_bytes": [_i, _i, _i, _i, _i],
+    "mvsdet_splat_cameras_f32": [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _i, _vp, _i, _vp],
+    "mvsdet_splat_forward_f32": [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_splat_backward_f32": [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i, _i,
+                                  _i, _i, _i, _i, _i, _vp],
     "mvsdet_copy_f32": [_vp, _vp, _sz, _vp],
     "mvsdet_store_pattern_probe_f32": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_store_pattern_probe_f16": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
@@ -176,6 +181,7 @@ _RESTYPE = {"mvsdet_last_error": ctypes.c_char_p, "mvsdet_conv3d_k3_bf16x3_stats
             "mvsdet_depth_diagnostics_workspace_bytes": ctypes.c_size_t,
             "mvsdet_depth_loss_workspace_bytes": ctypes.c_size_t,
             "mvsdet_photo_loss_workspace_bytes": ctypes.c_size_t, "mvsdet_photo_select_workspace_bytes": ctypes.c_size_t,
+            "mvsdet_splat_workspace_bytes": ctypes.c_size_t,
             "mvsdet_eval_state_bytes": ctypes.c_size_t, "mvsdet_eval_workspace_bytes": ctypes.c_size_t,
             "mvsdet_conv3d_k3_mfma_workspace_bytes": ctypes.c_size_t, "mvsdet_bn3d_workspace_bytes": ctypes.c_size_t}
 

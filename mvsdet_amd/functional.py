@@ -483,3 +483,51 @@ def warp_img(ref_imgs: Tensor, neighbor_ids: Tensor, ref_w2c: Tensor, ref_feat_i
     geo = ops.photo.photo_geometry(ref_w2c.float(), ref_feat_intrinsic.float(), ref_w2c.float(), ref_id, src_id)
     warped, mask = ops.photo.inverse_warp(small, ref_depth[:, 0], geo, src_id, ref_id)
     return warped, mask, small[ref_id]
+
+
+# ------------------------------------------------------------------------------------------- Gaussian splatting (the NVS branch)
+def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, image_shape: Tuple[int, int], background_color: Tensor,
+                gaussian_means: Tensor, gaussian_covariances: Tensor, gaussian_sh_coefficients: Tensor, gaussian_opacities: Tensor,
+                scale_invariant: bool = True, use_sh: bool = True, scene=None, *, max_keys=None) -> Tensor:
+    """gs_src/model/decoder/cuda_splatting.py:49-138: extrinsics (B,4,4) camera-to-world, intrinsics (B,3,3) normalised, near / far
+    (B), background_color (B,3), gaussian_means (B,G,3), gaussian_covariances (B,G,3,3), gaussian_sh_coefficients (B,G,3,d_sh),
+    gaussian_opacities (B,G) -> images (B,3,h,w).  The camera matrices come from one launch (`ops.splat.splat_cameras`: no
+    torch.inverse, no .item()); the scale_invariant multiplications happen inside the rasteriser, so no scaled copies are made.
+    Batch rows that are expanded views of one Gaussian set (stride 0, what DecoderSplattingCUDA hands over before it copies them) or
+    B == 1 go out as one call over B views; distinct rows one call per row.  max_keys: (Gaussian, tile) pairs a view may have
+    (default 8 G); a view that needs more comes out NaN.  There is no CPU path.  `scene` is accepted and unused, as in the reference."""
+    if not (use_sh or gaussian_sh_coefficients.shape[-1] == 1):
+        raise ValueError("render_cuda: without use_sh the coefficients are the colours, (B,G,3,1)")
+    tensors = amp_fp32(extrinsics, intrinsics, near, far, background_color, gaussian_means, gaussian_covariances,
+                       gaussian_sh_coefficients, gaussian_opacities)
+    extrinsics, intrinsics, near, far, background_color, means, covs, shs, opacs = tensors
+    if means.dim() != 3 or covs.dim() != 4 or shs.dim() != 4 or opacs.dim() != 2:
+        raise ValueError(f"render_cuda: means {tuple(means.shape)}, covariances {tuple(covs.shape)}, coefficients {tuple(shs.shape)} and "
+                         f"opacities {tuple(opacs.shape)} must be (B,G,3), (B,G,3,3), (B,G,3,d_sh) and (B,G)")
+    b, G = means.shape[:2]
+    h, w = (int(v) for v in image_shape)
+    if extrinsics.shape[0] != b or background_color.shape[0] != b:
+        raise ValueError(f"render_cuda: {extrinsics.shape[0]} cameras and {background_color.shape[0]} backgrounds for {b} batch rows")
+    keys = ops.splat.default_max_keys(G) if max_keys is None else int(max_keys)
+    cams = ops.splat.splat_cameras(extrinsics, intrinsics, near, far, bool(scale_invariant))
+    if b == 1 or all(t.stride(0) == 0 for t in (means, covs, shs, opacs)):
+        return ops.splat.rasterize(means[0], covs[0], shs[0], opacs[0], cams, background_color, h, w, keys, bool(use_sh))[0]
+    return torch.cat([ops.splat.rasterize(means[i], covs[i], shs[i], opacs[i], cams[i:i + 1], background_color[i:i + 1], h, w, keys,
+                                          bool(use_sh))[0] for i in range(b)])
+
+
+def decode_splatting(gaussians, extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, image_shape: Tuple[int, int],
+                     background_color=None, *, max_keys=None) -> Tensor:
+    """The colour output of DecoderSplattingCUDA.forward (gs_src/model/decoder/decoder_splatting_cuda.py:37-62): gaussians with
+    `.means` (b,G,3), `.covariances` (b,G,3,3), `.harmonics` (b,G,3,d_sh) and `.opacities` (b,G); extrinsics (b,v,4,4), intrinsics
+    (b,v,3,3), near / far (b,v) -> colour (b,v,3,h,w).  One rasteriser call per batch element over its v views: the Gaussians are not
+    repeated per view.  background_color (3), default black (the decoder's registered buffer comes from the dataset config)."""
+    b, v = extrinsics.shape[:2]
+    dev = extrinsics.device
+    bg = torch.zeros(3, dtype=torch.float32, device=dev) if background_color is None else background_color.to(dev)
+    rows = []
+    for i in range(b):
+        rows.append(render_cuda(extrinsics[i], intrinsics[i], near[i], far[i], image_shape, bg.expand(v, 3),
+                                gaussians.means[i].expand(v, -1, -1), gaussians.covariances[i].expand(v, -1, -1, -1),
+                                gaussians.harmonics[i].expand(v, -1, -1, -1), gaussians.opacities[i].expand(v, -1), max_keys=max_keys))
+    return torch.stack(rows)

@@ -197,6 +197,43 @@ def unpatch_reference_photometric(mvsdet_module, originals: dict) -> None:
         setattr(mvsdet_module.MVSDet, name.split(".", 1)[1], fn)
 
 
+SPLATTING_EXTENSION = "diff_gaussian_rasterization"
+
+
+def patch_reference_splatting(splatting_module=None) -> dict:
+    """Opt-in (the import hook does not apply it): make `import diff_gaussian_rasterization` resolve to
+    mvsdet_amd.diff_gaussian_rasterization when the real extension cannot be imported (it has no ROCm build), so that the reference's
+    unmodified gs_src/model/decoder/cuda_splatting.py::render_cuda imports and runs on the HIP rasteriser.  A real, importable
+    extension is left alone.  splatting_module: an already imported module that took the two classes by `from ... import` (a
+    stand-in, or cuda_splatting itself imported against a stub) -- its `GaussianRasterizationSettings` / `GaussianRasterizer` are
+    rebound too.  Returns what `unpatch_reference_splatting` needs."""
+    import importlib
+
+    from . import diff_gaussian_rasterization as shim
+    state = {"registered": False, "module": splatting_module, "originals": {}}
+    try:
+        importlib.import_module(SPLATTING_EXTENSION)
+    except ImportError:
+        sys.modules[SPLATTING_EXTENSION] = shim
+        state["registered"] = True
+    if splatting_module is not None and sys.modules.get(SPLATTING_EXTENSION) is shim:
+        for name in ("GaussianRasterizationSettings", "GaussianRasterizer"):
+            state["originals"][name] = getattr(splatting_module, name, None)
+            setattr(splatting_module, name, getattr(shim, name))
+    return state
+
+
+def unpatch_reference_splatting(state: dict) -> None:
+    from . import diff_gaussian_rasterization as shim
+    if state.get("registered") and sys.modules.get(SPLATTING_EXTENSION) is shim:
+        del sys.modules[SPLATTING_EXTENSION]
+    for name, original in state.get("originals", {}).items():
+        if original is None:
+            delattr(state["module"], name)
+        else:
+            setattr(state["module"], name, original)
+
+
 def patch_reference_nms3d(head_module) -> dict:
     """Opt-in (the import hook does not apply it): rebind the module-global `nms3d` of an imported reference `nerfdet_head` module
     (mmcv.ops.nms3d, which ImVoxelHead_ARKit._single_scene_multiclass_nms calls) so that its unmodified predict runs the rotated

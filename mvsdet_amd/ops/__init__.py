@@ -35,6 +35,7 @@ from .evalmap import (  # noqa: F401
     EVAL_MAX_RECORDS, EVAL_MAX_LABELS, EVAL_MAX_THRESHOLDS, EVAL_FLAGS, EvalState, EvalResult, eval_state, eval_reset, eval_match,
     eval_compute, eval_iou)
 from . import photo  # noqa: F401  (ops.photo.<name>: not re-exported)
+from . import splat  # noqa: F401  (ops.splat.<name>: not re-exported)
 
 # ------------------------------------------------------------------------------------------- --amp (tools/train.py:24-28)
 # Under torch.autocast the 2-D backbone hands out float16 / bfloat16 maps.  The hot path computes in float32 -- the rule torch's own
