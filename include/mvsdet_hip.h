@@ -591,6 +591,37 @@ int mvsdet_splat_backward_f32(const float* means, const int64_t* means_strides /
                               int W, int max_keys, mvsdet_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Gaussian adapter (csrc/adapter.hip): the pixel Gaussians the rasteriser above renders -- GaussianAdapter.forward
+ * (gs_src/model/encoder/common/gaussian_adapter.py:50-98) with the offset lines of mvsdet.py:576-578, for V source views of R = h w
+ * feature pixels and S surfaces each.  Gaussian g = (v R + r) S + s, the reference's flattened order.  fp32, no atomics, no host
+ * synchronisation; the same bits on every run.  DESIGN.md 4.16 has the formulas.
+ * Limits: d_sh in {1, 4, 9, 16, 25}; V <= 65535; R = h w; R S (10 + 3 d_sh) < 2^31 (a view's rows); V R S 3 d_sh < 2^31.
+ *
+ * One row of `raw` has 9 + 3 d_sh floats: offset (2), scales (3), quaternion x y z w (4), harmonics (3, d_sh).  Row (v, r, s) starts
+ *   at raw + v raw_view_stride + (r S + s) raw_row_stride (elements); its floats are adjacent.  g_raw is laid out by its own two strides.
+ * mvsdet_adapter_cameras_f32 (one launch, one thread per view): cams (V, MVSDET_ADAPTER_CAM) = C_v = E_v[:3,:3] (9, row-major), the
+ *   origin E_v[:3,3] (3), K_v^-1 by the adjugate (9), m_v = 0.1 sum_i (K_v[:2,:2]^-1 (1/w, 1/h))_i, 2 unused, then at float 24 the
+ *   rotation blocks D_l of the harmonics, degree after degree (l = 0 .. 4: 1 + 9 + 25 + 49 + 81 floats, row-major; blocks above the
+ *   degree of d_sh are 0), 3 unused.  sh_rot NULL: the blocks are built for the basis of csrc/sh_basis.h, sum_j (D c)_j Y_j(C d) =
+ *   sum_j c_j Y_j(d), in float64 and rounded once.  sh_rot (V, sum_{l <= L} (2l+1)^2) contiguous: copied as given.
+ * mvsdet_adapter_forward_f32 (one launch): depth (V,R) contiguous -> means (G,3), covariances (G,3,3: all nine), harmonics (G,3,d_sh),
+ *   contiguous; scales (G,3) and rotations (G,4: the normalised quaternion) unless both NULL.
+ * mvsdet_adapter_backward_f32 (one launch): g_means (G,3), g_covariances (G,3,3: any 3x3 gradient, symmetric or not), g_harmonics
+ *   (G,3,d_sh), contiguous, each may be NULL (= zeros) -> g_raw (every float of every row written) and g_depth (V,R,S). */
+#define MVSDET_ADAPTER_CAM 192
+int mvsdet_adapter_cameras_f32(const float* extrinsics, int64_t ext_view_stride, const float* intrinsics, int64_t k_view_stride,
+                               int64_t k_row_stride, const float* sh_rot /*may be NULL*/, float* cams, int V, int h, int w, int d_sh,
+                               mvsdet_stream_t stream);
+int mvsdet_adapter_forward_f32(const float* raw, int64_t raw_view_stride, int64_t raw_row_stride, const float* depth, const float* cams,
+                               float* means, float* covariances, float* harmonics, float* scales /*may be NULL*/,
+                               float* rotations /*may be NULL*/, int V, int h, int w, int S, int d_sh, float scale_min, float scale_max,
+                               mvsdet_stream_t stream);
+int mvsdet_adapter_backward_f32(const float* raw, int64_t raw_view_stride, int64_t raw_row_stride, const float* depth, const float* cams,
+                                const float* g_means, const float* g_covariances, const float* g_harmonics, float* g_raw,
+                                int64_t g_raw_view_stride, int64_t g_raw_row_stride, float* g_depth, int V, int h, int w, int S, int d_sh,
+                                float scale_min, float scale_max, mvsdet_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The cost network's 3x3x3 convolutions on the bf16 matrix cores, fp32 operands cut into bf16 pieces ("bf16x3":
  * x*w ~ x_hi*w_hi + x_hi*w_mid + x_mid*w_hi, fp32 accumulation; csrc/costreg_bf16.hip).  Replaces the same layers of
  * mvs_models/mvsnet.py:76-82,104-108 as mvsdet_conv3d_k3_mfma_ws_f32 does, at 3/16 of the fp32 matrix-core time; results

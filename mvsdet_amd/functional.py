@@ -531,3 +531,51 @@ def decode_splatting(gaussians, extrinsics: Tensor, intrinsics: Tensor, near: Te
                                 gaussians.means[i].expand(v, -1, -1), gaussians.covariances[i].expand(v, -1, -1, -1),
                                 gaussians.harmonics[i].expand(v, -1, -1, -1), gaussians.opacities[i].expand(v, -1), max_keys=max_keys))
     return torch.stack(rows)
+
+
+class PixelGaussians:
+    """What `pixel_gaussians` returns and `decode_splatting` takes: `.means` (1,G,3), `.covariances` (1,G,3,3), `.harmonics`
+    (1,G,3,d_sh), `.opacities` (1,G); `.scales` (1,G,3) and `.rotations` (1,G,4) when asked for, else None."""
+    __slots__ = ("means", "covariances", "harmonics", "opacities", "scales", "rotations")
+
+    def __init__(self, means, covariances, harmonics, opacities, scales=None, rotations=None):
+        self.means, self.covariances, self.harmonics, self.opacities = means, covariances, harmonics, opacities
+        self.scales, self.rotations = scales, rotations
+
+
+def pixel_gaussians(extrinsics: Tensor, intrinsics: Tensor, raw: Tensor, depths: Tensor, opacities: Tensor, image_shape: Tuple[int, int],
+                    gaussian_scale_min: float, gaussian_scale_max: float, sh_degree: int, *, sh_rotation=None,
+                    with_scales: bool = False) -> PixelGaussians:
+    """mvsdet.py:576-632 in one call: the offset of every pixel's ray, GaussianAdapter.forward
+    (gs_src/model/encoder/common/gaussian_adapter.py:50-98) and the flattening to (v, r, s) order.  extrinsics (V,4,4) camera-to-world
+    and intrinsics (V,3,3) normalised, of the chosen source views; raw (V,R,S,2 + 7 + 3 d_sh), the rearranged output of `to_gaussians`
+    (it may be a slice of a wider buffer: read in place); depths (V,R) along the ray; opacities (V,R), passed through and repeated
+    over S; image_shape (h, w) of the feature map, R = h w.  Two launches (cameras, Gaussians), no torch.inverse, no host read.
+    sh_rotation None: the harmonics are rotated into the world frame for the basis the rasteriser evaluates; a (V,
+    sum_l (2l+1)^2) tensor: those blocks instead (INTEGRATION.md shows how to pass e3nn's).  Gradients reach raw, depths, opacities."""
+    h, w = (int(v) for v in image_shape)
+    extrinsics, intrinsics, raw, depths, opacities, sh_rotation = amp_fp32(extrinsics, intrinsics, raw, depths, opacities, sh_rotation)
+    if raw.dim() != 4 or depths.dim() != 2 or opacities.dim() != 2 or tuple(opacities.shape) != tuple(depths.shape):
+        raise ValueError(f"pixel_gaussians: raw {tuple(raw.shape)}, depths {tuple(depths.shape)} and opacities {tuple(opacities.shape)} "
+                         "must be (V,R,S,2 + 7 + 3 d_sh), (V,R) and (V,R)")
+    V, R, S, _ = raw.shape
+    cams = ops.adapter.adapter_cameras(extrinsics.detach(), intrinsics.detach(), h, w, int(sh_degree),
+                                       None if sh_rotation is None else sh_rotation.detach())
+    out = ops.adapter.pixel_gaussians(raw, depths, cams, h, w, gaussian_scale_min, gaussian_scale_max, int(sh_degree), with_scales)
+    opac = opacities[:, :, None].expand(V, R, S).reshape(1, V * R * S)
+    return PixelGaussians(*[t[None] for t in out[:3]], opac, *[t[None] for t in out[3:]])
+
+
+def nvs_loss_func(rgb_pred: Sequence[Tensor], gt_rgb: Sequence[Tensor]) -> dict:
+    """MVSDet.nvs_loss_func (mvsdet.py:878-890) without use_nerf_mask: sum over the scenes of mean((rgb - gt)^2), rgb = the scene's
+    colour (1,n_tgt,3,H,W) with its leading 1 taken off (or already (n_tgt,3,H,W)), gt (n_tgt,3,H,W) -> dict(loss_nvs=...).  The
+    reference's assertion that gt lies in [0,1] is a host read and is left to the caller."""
+    if len(rgb_pred) != len(gt_rgb) or not rgb_pred:
+        raise ValueError(f"nvs_loss_func: {len(rgb_pred)} renders for {len(gt_rgb)} ground truths")
+    loss = 0
+    for rgb, gt in zip(rgb_pred, gt_rgb):
+        rgb = rgb[0] if rgb.dim() == 5 else rgb
+        if rgb.shape != gt.shape:
+            raise ValueError(f"nvs_loss_func: render {tuple(rgb.shape)} against ground truth {tuple(gt.shape)}")
+        loss = loss + torch.mean((rgb - gt) ** 2)
+    return dict(loss_nvs=loss)

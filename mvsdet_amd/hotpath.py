@@ -569,6 +569,87 @@ class MVSDetHotPath:
             refs.append(rv)
         return F_.photometric_loss(warped, masks, refs)
 
+    # ---- the NVS branch (mvsdet.py:518-677, 878-890) -------------------------------------------------
+    def render_source_ids(self, img_meta: dict, tgt_c2w, num_select: int = 3) -> Tensor:
+        """mvsdet.py:532-535: the `num_select` nearest source views of every target view, unique and ascending -> (n_src) int64 on
+        the host.  tgt_c2w (n_tgt,4,4) camera-to-world, array or tensor.  The poses are host data (img_meta), so the `unique` here
+        costs no device synchronisation."""
+        w2c, _ = self._feature_cameras(img_meta)
+        src_c2w = w2c.inverse()
+        tgt = torch.as_tensor(np.asarray(tgt_c2w.detach().cpu() if isinstance(tgt_c2w, Tensor) else tgt_c2w)).to(src_c2w.dtype)
+        ids = F_.get_nearest_pose_ids(tgt, src_c2w, num_select=num_select, maskself=False)
+        return torch.unique(ids.reshape(-1))
+
+    def novel_views(self, outputs, feature: Tensor, img_meta: dict, to_gaussians, tgt_c2w, tgt_intrinsic, tgt_shape, rgb_raw=None, *,
+                    num_surfaces: int = 1, gaussian_scale_min: float = 0.5, gaussian_scale_max: float = 15.0, sh_degree: int = 4,
+                    num_select: int = 3, sh_rotation=None, background_color=None, max_keys=None) -> Tensor:
+        """The novel-view branch of extract_feat for one scene (mvsdet.py:519-677) -> colour (1,n_tgt,3,H,W), what
+        `self.decoder.forward(...)` returns as `.color`.  outputs: the scene's `SceneOutputs`; feature (N,C,Hf,Wf); to_gaussians:
+        the caller's nn.Sequential(ReLU, Linear) with num_surfaces * (2 + 7 + 3 d_sh) outputs, run by torch; tgt_c2w (n_tgt,4,4),
+        tgt_intrinsic (4,4) or (n_tgt,4,4) in pixels of the target image, tgt_shape (H, W, ...); rgb_raw (n_src,R,3) or (1,n_src,R,3):
+        what process_rgb_raw returns for `use_rgb_gaussian` (the resize stays with the caller).  Source views by `render_source_ids`;
+        feature rows, depth_coding and rgb_raw are concatenated as :561-569; opacity is the largest probability (:581-582); the depth
+        along the ray is depth_coding / (depth_scale + 1e-8) (:583); then `functional.pixel_gaussians` and
+        `functional.decode_splatting` with near / far = near_far_range.  Gradients reach feature, to_gaussians' parameters, depth_coding
+        and the opacity.  The scale / degree defaults are those of the shipped configs."""
+        geo = outputs["geometry"]
+        h, w = geo.height, geo.width
+        dev = feature.device
+        src_id = self.render_source_ids(img_meta, tgt_c2w, num_select)
+        n_src, R = int(src_id.numel()), h * w
+        w2c, K_feat = self._feature_cameras(img_meta)
+        K = K_feat.clone().float()
+        if K.dim() == 2:                                   # one intrinsic matrix for all views (ScanNet), :546-548
+            K[0] /= w
+            K[1] /= h
+            K = K[None, :3, :3].repeat(n_src, 1, 1)
+        else:                                              # per view (ARKitScenes), :551-553
+            K[:, 0] /= w
+            K[:, 1] /= h
+            K = K[src_id, :3, :3]
+        c2w = w2c.inverse().float()[src_id]
+        ids, K, c2w = (ops._common.to_device(t, dev) for t in (src_id, K.contiguous(), c2w.contiguous()))
+        depth_coding = outputs["depth_coding"]
+        rows = [feature[ids][:, :, :h, :w].reshape(n_src, feature.shape[1], R).transpose(1, 2), depth_coding[ids].reshape(n_src, R, 1)]
+        if rgb_raw is not None:
+            rows.append(rgb_raw.reshape(n_src, R, 3).to(rows[0].dtype))
+        raw = to_gaussians(torch.cat(rows, dim=-1))
+        raw = raw.reshape(n_src, R, int(num_surfaces), raw.shape[-1] // int(num_surfaces))
+        opacity = outputs["opacity"][ids][:, :h, :w].reshape(n_src, R)
+        # compute_depth_scale[_MultiIntrin] (:1158-1216) through the kernel of `ray_depth`, without candidates
+        Kp = torch.tensor(np.array(img_meta["lidar2img"]["intrinsic"])).clone()
+        ratio = img_meta["ori_shape"][0] / (img_meta["img_shape"][0] / self.stride)
+        if Kp.dim() == 2:
+            Kp[:2] /= ratio
+            Kp = Kp.unsqueeze(0).repeat(feature.shape[0], 1, 1)
+        else:
+            Kp[:, :2] /= ratio
+        intr = torch.stack([Kp[:, 0, 0], Kp[:, 1, 1], Kp[:, 0, 2], Kp[:, 1, 2], Kp[:, 0, 1]], dim=1).float()
+        scale, _ = ops.ray_depth(ops._common.to_device(intr, dev), None, int(h), int(w))
+        ray = (depth_coding.reshape(feature.shape[0], R, 1) / (scale + 1e-8))[ids].reshape(n_src, R)
+        gaussians = F_.pixel_gaussians(c2w, K, raw, ray, opacity, (h, w), gaussian_scale_min, gaussian_scale_max, sh_degree,
+                                       sh_rotation=sh_rotation)
+        # the target cameras (:645-662)
+        H, W = int(tgt_shape[0]), int(tgt_shape[1])
+        tgt = torch.as_tensor(np.asarray(tgt_c2w.detach().cpu() if isinstance(tgt_c2w, Tensor) else tgt_c2w)).float()
+        Kt = torch.as_tensor(np.asarray(tgt_intrinsic.detach().cpu() if isinstance(tgt_intrinsic, Tensor) else tgt_intrinsic)).float().clone()
+        n_tgt = tgt.shape[0]
+        if Kt.dim() == 2:
+            Kt = Kt[None].repeat(n_tgt, 1, 1)
+        Kt[:, 0] /= W
+        Kt[:, 1] /= H
+        near = torch.full((1, n_tgt), self.near_far_range[0])
+        far = torch.full((1, n_tgt), self.near_far_range[1])
+        tgt, Kt, near, far = (ops._common.to_device(t, dev) for t in (tgt[None].contiguous(), Kt[None, :, :3, :3].contiguous(), near, far))
+        return F_.decode_splatting(gaussians, tgt, Kt, near, far, (H, W), background_color, max_keys=max_keys)
+
+    def nvs_loss(self, rgb_preds, gt_rgb) -> dict:
+        """`loss_nvs` of MVSDet.loss (nvs_loss_func, mvsdet.py:878-890, without use_nerf_mask): rgb_preds, one colour (1,n_tgt,3,H,W)
+        per scene as `novel_views` returns it (or one tensor), gt_rgb the matching (n_tgt,3,H,W) in [0,1] -> dict(loss_nvs=...)."""
+        if isinstance(rgb_preds, Tensor):
+            rgb_preds, gt_rgb = [rgb_preds], [gt_rgb]
+        return F_.nvs_loss_func(list(rgb_preds), list(gt_rgb))
+
     # name -> (detector tail on the side stream, view streams of the cost network beside it; None = the module's own setting)
     OVERLAP_ROUTES = {"one": (False, None), "side1": (True, 1), "side2": (True, 2)}
     _TUNE_WARM, _TUNE_SPAN = 2, 4    # scenes of a route left out (the previous route drains), scenes measured
