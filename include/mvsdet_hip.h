@@ -955,6 +955,31 @@ int mvsdet_eval_compute(const void* state, int n_labels, int capacity, int gt_ca
                         mvsdet_stream_t stream);
 int mvsdet_eval_iou_f32(const float* a, int n, const float* b, int m, float* out, mvsdet_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Scores of the rendered target views of one scene (save_rendered_img_Image / save_rendered_depth of the reference's
+ * nerf_utils/save_rendered_img.py, averaged as NVSMetric does; csrc/nvsmetric.hip) on the caller's stream, no host synchronisation,
+ * no device allocation, no atomics; all arithmetic after the load is float64, and two runs give the same bits.
+ *
+ * State: MVSDET_NVS_STATE_DOUBLES float64 on the DEVICE, 8-byte aligned = {sum of the scenes' psnr, of their ssim, of their rmse,
+ *   scenes}, cleared by mvsdet_nvs_reset.  NULL: nothing is accumulated.
+ * mvsdet_nvs_score_f32: pred, gt = n_tgt x 3 x H x W float32 images in [0,1], each with HOST int64[4] element strides (view,
+ *   channel, row, column) and read in place; pred_depth, gt_depth = n_tgt x H x W with HOST int64[3] strides, or both NULL.
+ *   out_views (n_tgt,2) float64 = per view psnr = -10 log(mse) / log(10) (mse over the view's 3 H W elements; +inf for mse 0) and
+ *   ssim = skimage's structural_similarity(channel_axis=-1, data_range=1): 7x7 box windows wholly inside the image, sample
+ *   covariance, K1 = 0.01, K2 = 0.03, mean over the (H-6)(W-6) windows of a channel, then over the channels.  out_scene (3) float64 =
+ *   the means over the views of psnr, ssim and of mean((pred_depth - gt_depth)^2) (the reference's "rmse": no root; 0 without a
+ *   depth pair); they are added to the state with a scene count of 1.  pred = gt = NULL with a depth pair: out_scene = (0, 0, rmse),
+ *   out_views is not written and state must be NULL.  Two launches.  H, W >= 7 and n_tgt * 3 * H * W < 2^31.
+ *   Workspace: mvsdet_nvs_workspace_bytes(n_tgt, H, W, with_depth) (0: bad sizes), 8-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define MVSDET_NVS_STATE_DOUBLES 4
+size_t mvsdet_nvs_workspace_bytes(int n_tgt, int H, int W, int with_depth);
+int mvsdet_nvs_reset(double* state, mvsdet_stream_t stream);
+int mvsdet_nvs_score_f32(double* state, const float* pred, const int64_t* pred_strides, const float* gt, const int64_t* gt_strides,
+                         const float* pred_depth, const int64_t* pred_depth_strides, const float* gt_depth,
+                         const int64_t* gt_depth_strides, int n_tgt, int H, int W, double* out_views, double* out_scene,
+                         void* workspace, size_t workspace_bytes, mvsdet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

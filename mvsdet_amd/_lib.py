@@ -162,6 +162,9 @@ SIGNATURES = {
     "mvsdet_eval_compute": [_vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_float), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                             _vp],
     "mvsdet_eval_iou_f32": [_vp, _i, _vp, _i, _vp, _vp],
+    "mvsdet_nvs_workspace_bytes": [_i, _i, _i, _i],
+    "mvsdet_nvs_reset": [_vp, _vp],
+    "mvsdet_nvs_score_f32": [_vp, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _i, _i, _i, _vp, _vp, _vp, _sz, _vp],
     "mvsdet_homo_warp_pixel_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "mvsdet_homo_warp_pixel_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp],
     "mvsdet_plane_sweep_variance_pixel_packed_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
@@ -186,6 +189,7 @@ _RESTYPE = {"mvsdet_last_error": ctypes.c_char_p, "mvsdet_conv3d_k3_bf16x3_stats
             "mvsdet_photo_loss_workspace_bytes": ctypes.c_size_t, "mvsdet_photo_select_workspace_bytes": ctypes.c_size_t,
             "mvsdet_splat_workspace_bytes": ctypes.c_size_t,
             "mvsdet_eval_state_bytes": ctypes.c_size_t, "mvsdet_eval_workspace_bytes": ctypes.c_size_t,
+            "mvsdet_nvs_workspace_bytes": ctypes.c_size_t,
             "mvsdet_conv3d_k3_mfma_workspace_bytes": ctypes.c_size_t, "mvsdet_bn3d_workspace_bytes": ctypes.c_size_t}
 
 

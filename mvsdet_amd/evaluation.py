@@ -10,7 +10,10 @@ What is computed is BaseInstance3DBoxes.overlaps as a mathematical function, in 
 computed directly, where the reference recovers it from mmcv's box_iou_rotated.  mmcv's own float32 rounding is not reproduced (it
 is not installed where this package is developed; the distance to it is not measured).  Equal scores inside a label are visited by
 (scene, row); the reference's np.argsort leaves that order open.  A label that is predicted and has no ground truth anywhere gives
-NaN AP and recall, and with them NaN mAP and mAR, as the reference does."""
+NaN AP and recall, and with them NaN mAP and mAR, as the reference does.
+
+The view-synthesis side (the reference's NVSMetric and MVSMetric) is at the end of the module: `NVSEvaluator`, `MVSEvaluator` and
+`nvs_eval` over csrc/nvsmetric.hip (ops.nvsmetric)."""
 from __future__ import annotations
 
 import logging
@@ -181,3 +184,108 @@ def indoor_eval(gt_annos, dt_annos, metric, label2cat, logger=None, box_mode_3d=
     log = logger if isinstance(logger, logging.Logger) else logging.getLogger(logger if isinstance(logger, str) else __name__)
     log.info("\n%s", _table(ret, tuple(metric)))
     return ret
+
+
+# ------------------------------------------------------------------------------------------- view synthesis (NVSMetric, MVSMetric)
+def _scene_list(x, name: str, dims) -> list:
+    """A tensor of one scene, or a list of scenes; None entries stay."""
+    if x is None:
+        return []
+    scenes = [x] if isinstance(x, Tensor) else list(x)
+    out = []
+    for t in scenes:
+        if t is not None:
+            t = torch.as_tensor(t)
+            t = t[0] if t.dim() == dims + 1 and t.shape[0] == 1 else t
+            if t.dim() != dims:
+                raise ValueError(f"NVS evaluation: {name} {tuple(t.shape)}: one scene is "
+                                 f"{'(n_tgt,3,H,W) or (1,n_tgt,3,H,W)' if dims == 4 else '(n_tgt,H,W) or (1,n_tgt,H,W)'}")
+        out.append(t)
+    return out
+
+
+class NVSEvaluator:
+    """The reference's NVSMetric (mmdet3d/evaluation/metrics/Indoor_NVS.py:15-106) over the triples its test loop stores per scene
+    (mvsdet.py:1017-1040: save_rendered_img_Image, and save_rendered_depth where a rendered depth exists), scored and accumulated on
+    `device` (csrc/nvsmetric.hip; a CPU device takes ops.nvsmetric.nvs_score's torch float64 route).  `update` makes no host synchronisation,
+    `compute` one read-back.  PSNR and SSIM are evaluated in float64: the reference's float32 route lies up to 1.4e-7 (SSIM) and
+    2.3e-6 dB (PSNR) from them (DESIGN 4.17).  `last_scene`: the device row (psnr, ssim, rmse) of the scene fed last;
+    `last_views`: its (n_tgt,2) psnr and ssim per view."""
+
+    def __init__(self, device="cuda"):
+        self._st = ops.nvsmetric.nvs_state(device)
+        self._scenes = 0
+        self.last_scene: Optional[Tensor] = None
+        self.last_views: Optional[Tensor] = None
+
+    @property
+    def device(self) -> torch.device:
+        return self._st.device
+
+    def reset(self) -> None:
+        ops.nvsmetric.nvs_reset(self._st)
+        self._scenes, self.last_scene, self.last_views = 0, None, None
+
+    def update(self, rgb_pred, gt_rgb, depth_pred=None, gt_depth=None) -> None:
+        """One scene -- rgb_pred (1,n_tgt,3,H,W) as `MVSDetHotPath.novel_views` returns it, or (n_tgt,3,H,W); gt_rgb the same shape
+        without the leading 1; depth_pred / gt_depth (n_tgt,H,W) or None -- or lists with one entry per scene (a depth entry may be
+        None: that scene counts rmse 0, as the reference's triple does).  Shapes may differ from scene to scene."""
+        preds, gts = _scene_list(rgb_pred, "rgb_pred", 4), _scene_list(gt_rgb, "gt_rgb", 4)
+        dps, dgs = _scene_list(depth_pred, "depth_pred", 3), _scene_list(gt_depth, "gt_depth", 3)
+        if len(preds) != len(gts) or len(dps) != len(dgs) or (dps and len(dps) != len(preds)):
+            raise ValueError(f"NVSEvaluator.update: {len(preds)} renders, {len(gts)} ground truths, {len(dps)} / {len(dgs)} depth maps")
+        for i, (p, g) in enumerate(zip(preds, gts)):
+            dp, dg = (dps[i], dgs[i]) if dps else (None, None)
+            dev = self.device
+            p, g, dp, dg = (None if t is None else (t if t.device == dev else to_device(t, dev)) for t in (p, g, dp, dg))
+            self.last_views, self.last_scene = ops.nvsmetric.nvs_score(self._st, p, g, dp, dg)
+            self._scenes += 1
+
+    def compute(self) -> Dict[str, float]:
+        """NVSMetric.compute_metrics' dict {'psnr', 'ssim', 'rmse'}: the plain means over the scenes fed, as Python floats."""
+        if self._scenes == 0:
+            raise RuntimeError("NVSEvaluator.compute: no scene was fed")
+        psnr, ssim, rmse = ops.nvsmetric.nvs_result(self._st).cpu().tolist()
+        return {"psnr": psnr, "ssim": ssim, "rmse": rmse}
+
+
+class MVSEvaluator:
+    """The reference's MVSMetric (Indoor_NVS.py:232-283) over the depth diagnostics of the lifting block, accumulated on the device.
+    The reference's quirk is kept: `src_rmse` is the mean over the scenes, but `weight_gap` is the LAST scene's value -- it computes
+    the mean (final_weight_gap, :277) and then returns the loop variable (:280).  `update` makes no host synchronisation, `compute`
+    one read-back."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self) -> None:
+        self._acc: Optional[Tensor] = None     # (2) float64 on the inputs' device: the last scene's weight_gap, the sum of src_rmse
+        self._scenes = 0
+
+    def update(self, outputs_or_pair) -> None:
+        """A scene's `SceneOutputs` (or any mapping with "weight_gap" and "src_rmse"), or the pair (weight_gap, src_rmse)."""
+        if hasattr(outputs_or_pair, "keys"):
+            gap, rmse = outputs_or_pair["weight_gap"], outputs_or_pair["src_rmse"]
+        else:
+            gap, rmse = outputs_or_pair
+        gap, rmse = (torch.as_tensor(t).detach().reshape(()).to(torch.float64) for t in (gap, rmse))
+        if self._acc is None:
+            self._acc = torch.stack((gap, rmse))
+        else:
+            self._acc = torch.stack((gap.to(self._acc.device), self._acc[1] + rmse.to(self._acc.device)))
+        self._scenes += 1
+
+    def compute(self) -> Dict[str, float]:
+        """MVSMetric.compute_metrics' dict {'weight_gap': the last scene's, 'src_rmse': the mean}, as Python floats."""
+        if self._scenes == 0:
+            raise RuntimeError("MVSEvaluator.compute: no scene was fed")
+        gap, total = self._acc.cpu().tolist()
+        return {"weight_gap": gap, "src_rmse": total / self._scenes}
+
+
+def nvs_eval(rgb_preds, gt_rgbs, depth_preds=None, gt_depths=None, device="cuda") -> Dict[str, float]:
+    """The function form beside `indoor_eval`: the scenes' renders and ground truth (lists, or one scene's tensors; depth lists may
+    hold None) -> NVSMetric's dict {'psnr', 'ssim', 'rmse'}."""
+    ev = NVSEvaluator(device)
+    ev.update(rgb_preds, gt_rgbs, depth_preds, gt_depths)
+    return ev.compute()

@@ -579,3 +579,54 @@ def nvs_loss_func(rgb_pred: Sequence[Tensor], gt_rgb: Sequence[Tensor]) -> dict:
             raise ValueError(f"nvs_loss_func: render {tuple(rgb.shape)} against ground truth {tuple(gt.shape)}")
         loss = loss + torch.mean((rgb - gt) ** 2)
     return dict(loss_nvs=loss)
+
+
+# ------------------------------------------------------------------------------------------- scores of the rendered views (test loop)
+def _no_mask(name: str, mask) -> None:
+    if mask is not None:
+        raise NotImplementedError(f"{name}: the masked form (cv2.boundingRect; save_rendered_img.py:23-24, 32-35) is never reached by the "
+                                  "reference's calls and is not provided")
+
+
+def _no_save_dir(name: str, save_dir) -> None:
+    if save_dir is not None:
+        raise NotImplementedError(f"{name}: writing pictures under save_dir is not provided; score with save_dir=None")
+
+
+def _one_view(name: str, pred: Tensor, target: Tensor):
+    if pred.dim() != 3 or pred.shape != target.shape or pred.shape[-1] != 3:
+        raise ValueError(f"{name}: pred {tuple(pred.shape)} and target {tuple(target.shape)} must be two equal (H,W,3) views")
+    return pred.permute(2, 0, 1)[None], target.permute(2, 0, 1)[None]
+
+
+def compute_psnr(pred: Tensor, target: Tensor, mask=None) -> Tensor:
+    """nerf_utils/save_rendered_img.py:17-26 for one (H,W,3) view in [0,1]: -10 log(mean((pred - target)^2)) / log(10), +inf for equal
+    images, as a 0-dim float64 tensor on the inputs' device (the reference returns a host array: `.cpu().numpy()`).  The view is
+    read in place through its strides; the sums are float64 (ops.nvsmetric.nvs_score).  No host synchronisation."""
+    _no_mask("compute_psnr", mask)
+    return ops.nvsmetric.nvs_score(None, *_one_view("compute_psnr", pred, target))[0][0, 0]
+
+
+def compute_ssim(pred: Tensor, target: Tensor, mask=None) -> Tensor:
+    """nerf_utils/save_rendered_img.py:29-44 for one (H,W,3) view: skimage's structural_similarity(channel_axis=-1, data_range=1)
+    -- 7x7 box windows inside the image, sample covariance, K1 = 0.01, K2 = 0.03 -- evaluated in float64 on the device, as a 0-dim
+    float64 tensor (the reference copies both images to the host).  A side below 7 raises ValueError, as skimage does."""
+    _no_mask("compute_ssim", mask)
+    return ops.nvsmetric.nvs_score(None, *_one_view("compute_ssim", pred, target))[0][0, 1]
+
+
+def save_rendered_img_Image(pred: Tensor, gt: Tensor, img_meta=None, save_dir=None):
+    """nerf_utils/save_rendered_img.py:178-212 without the picture writing: pred, gt (n_tgt,3,H,W) in [0,1] -> (psnr, ssim, 0), the
+    means over the target views, the first two as 0-dim float64 device tensors.  One scoring call for all views, no host
+    synchronisation.  img_meta is accepted and unused (the reference takes the scene's name from it for the pictures)."""
+    _no_save_dir("save_rendered_img_Image", save_dir)
+    scene = ops.nvsmetric.nvs_score(None, pred, gt)[1]
+    return scene[0], scene[1], 0
+
+
+def save_rendered_depth(pred: Tensor, gt: Tensor, img_meta=None, save_dir=None) -> Tensor:
+    """nerf_utils/save_rendered_img.py:215-235 without the picture writing and without its print of the extrema (a host read): pred,
+    gt (n_tgt,H,W) -> the mean over the views of mean((pred - gt)^2) as a 0-dim float64 device tensor.  The reference calls it rmse;
+    it is a mean squared error with no root, and stays that.  The views go through the scoring kernel's tiles: sides of 7 needed."""
+    _no_save_dir("save_rendered_depth", save_dir)
+    return ops.nvsmetric.nvs_score(None, None, None, pred, gt)[1][2]

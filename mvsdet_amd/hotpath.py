@@ -650,6 +650,24 @@ class MVSDetHotPath:
             rgb_preds, gt_rgb = [rgb_preds], [gt_rgb]
         return F_.nvs_loss_func(list(rgb_preds), list(gt_rgb))
 
+    def nvs_scores(self, rgb_preds, gt_rgb, evaluator=None) -> dict:
+        """What the reference's test loop stores for a scene (mvsdet.py:1017-1040: save_rendered_img_Image; no rendered depth in the
+        shipped configs, so rmse is 0): rgb_preds, the scene's colour (1,n_tgt,3,H,W) as `novel_views` returns it (or (n_tgt,3,H,W)),
+        gt_rgb the matching (n_tgt,3,H,W) in [0,1] -> dict(psnr=, ssim=, rmse=) as 0-dim float64 device tensors, the means over the
+        target views.  evaluator: an `evaluation.NVSEvaluator` that is fed the scene (it then scores it; no second launch).  No host
+        synchronisation."""
+        if not isinstance(rgb_preds, Tensor):
+            if len(rgb_preds) != 1:
+                raise ValueError(f"nvs_scores: one scene at a time (got {len(rgb_preds)}); NVSEvaluator.update takes lists")
+            rgb_preds, gt_rgb = rgb_preds[0], gt_rgb if isinstance(gt_rgb, Tensor) else gt_rgb[0]
+        rgb = rgb_preds[0] if rgb_preds.dim() == 5 else rgb_preds
+        if evaluator is not None:
+            evaluator.update(rgb, gt_rgb)
+            scene = evaluator.last_scene
+        else:
+            scene = ops.nvsmetric.nvs_score(None, rgb, gt_rgb)[1]
+        return dict(psnr=scene[0], ssim=scene[1], rmse=scene[2])
+
     # name -> (detector tail on the side stream, view streams of the cost network beside it; None = the module's own setting)
     OVERLAP_ROUTES = {"one": (False, None), "side1": (True, 1), "side2": (True, 2)}
     _TUNE_WARM, _TUNE_SPAN = 2, 4    # scenes of a route left out (the previous route drains), scenes measured

@@ -25,6 +25,8 @@ from __future__ import annotations
 
 import sys
 
+import torch
+
 from . import functional as F_
 
 
@@ -277,3 +279,37 @@ def patch_reference_indoor_eval(metric_module, device="cuda") -> dict:
 def unpatch_reference_indoor_eval(metric_module, originals: dict) -> None:
     for name, fn in originals.items():
         setattr(metric_module, name, fn)
+
+
+def patch_reference_nvs_scores(mvsdet_module) -> dict:
+    """Opt-in (the import hook does not apply it): rebind the module-globals `save_rendered_img_Image` and `save_rendered_depth` of an
+    imported reference `mvsdet` module (imported at mvsdet.py:17 from nerf_utils/save_rendered_img.py, called by MVSDet.predict at
+    :1020 and :1024).  With save_dir None the replacements score the scene on the tensors' device (functional.save_rendered_img_Image
+    / save_rendered_depth over csrc/nvsmetric.hip: no per-view copies of the images to the host, no skimage) and return host numbers,
+    because predict stores them on the data sample: one read-back per call.  With a save_dir (the pictures) they call the
+    originals.  Returns {name: original} for `unpatch_reference_nvs_scores`."""
+    originals = {"save_rendered_img_Image": mvsdet_module.save_rendered_img_Image,
+                 "save_rendered_depth": mvsdet_module.save_rendered_depth}
+    img_original, depth_original = originals["save_rendered_img_Image"], originals["save_rendered_depth"]
+
+    def save_rendered_img_Image(pred, gt, img_meta, save_dir=None):
+        if save_dir is not None:
+            return img_original(pred, gt, img_meta, save_dir=save_dir)
+        psnr, ssim, _ = F_.save_rendered_img_Image(pred, gt, img_meta)
+        psnr, ssim = torch.stack((psnr, ssim)).cpu().tolist()
+        return psnr, ssim, 0
+
+    def save_rendered_depth(pred, gt, img_meta, save_dir=None):
+        if save_dir is not None:
+            return depth_original(pred, gt, img_meta, save_dir=save_dir)
+        return float(F_.save_rendered_depth(pred, gt, img_meta).cpu())
+
+    save_rendered_img_Image.__doc__ = getattr(img_original, "__doc__", None)
+    save_rendered_depth.__doc__ = getattr(depth_original, "__doc__", None)
+    mvsdet_module.save_rendered_img_Image, mvsdet_module.save_rendered_depth = save_rendered_img_Image, save_rendered_depth
+    return originals
+
+
+def unpatch_reference_nvs_scores(mvsdet_module, originals: dict) -> None:
+    for name, fn in originals.items():
+        setattr(mvsdet_module, name, fn)

@@ -2,7 +2,7 @@
 
 Every operator enqueues hand-written gfx950 kernels of libmvsdet_hip.so on the current HIP stream through ctypes; torch supplies
 device memory, streams and autograd plumbing only.  Operators raise if their inputs are not float32 tensors on a ROCm device --
-there is no CPU implementation here.  Callers look a name up as `ops.<name>` at call time: every public name is re-exported.
+there is no CPU implementation here (one exception: ops.nvsmetric scores CPU tensors in torch float64).  Callers look a name up as `ops.<name>` at call time: every public name is re-exported.
 """
 from __future__ import annotations
 
@@ -34,6 +34,7 @@ from .head_train import (  # noqa: F401
 from .evalmap import (  # noqa: F401
     EVAL_MAX_RECORDS, EVAL_MAX_LABELS, EVAL_MAX_THRESHOLDS, EVAL_FLAGS, EvalState, EvalResult, eval_state, eval_reset, eval_match,
     eval_compute, eval_iou)
+from . import nvsmetric  # noqa: F401  (ops.nvsmetric.<name>: not re-exported)
 from . import photo  # noqa: F401  (ops.photo.<name>: not re-exported)
 from . import splat  # noqa: F401  (ops.splat.<name>: not re-exported)
 from . import adapter  # noqa: F401  (ops.adapter.<name>: not re-exported)
