@@ -386,6 +386,13 @@ __global__ __launch_bounds__(kThreads) void splat_ranges_kernel(SplatWs ws, int6
 }
 
 // ------------------------------------------------------------------------------------------------ render
+// alpha of a Gaussian at a pixel, capped at 0.99.  A comparison, not fminf: fminf returns its non-NaN argument, which would paint a
+// Gaussian of NaN opacity as an opaque 0.99 layer and show no NaN; this keeps it.  The same value for every other input.
+__device__ __forceinline__ float splat_alpha(float opacity, float gauss) {
+    const float a = opacity * gauss;
+    return a > 0.99f ? 0.99f : a;
+}
+
 __global__ __launch_bounds__(kThreads) void splat_render_kernel(SplatWs ws, const float* __restrict__ bg, float* __restrict__ image, int G,
                                                                 int H, int W, int tiles_x, int tiles) {
     __shared__ float2 s_xy[kThreads];
@@ -432,7 +439,7 @@ __global__ __launch_bounds__(kThreads) void splat_render_kernel(SplatWs ws, cons
             const float dx = xy.x - fx, dy = xy.y - fy;
             const float power = -0.5f * (co.x * dx * dx + co.z * dy * dy) - co.y * dx * dy;
             if (power > 0.0f) continue;
-            const float alpha = fminf(0.99f, co.w * expf(power));
+            const float alpha = splat_alpha(co.w, expf(power));
             if (alpha < 1.0f / 255.0f) continue;
             const float Tn = T * (1.0f - alpha);
             if (Tn < 0.0001f) {
@@ -510,7 +517,7 @@ __global__ __launch_bounds__(kThreads) void splat_render_bwd_kernel(SplatWs ws, 
                 const float power = -0.5f * (co.x * dx * dx + co.z * dy * dy) - co.y * dx * dy;
                 if (!(power > 0.0f)) {
                     const float Gs = expf(power);
-                    const float alpha = fminf(0.99f, co.w * Gs);
+                    const float alpha = splat_alpha(co.w, Gs);
                     if (!(alpha < 1.0f / 255.0f)) {
                         hit = true;
                         T = T / (1.0f - alpha);

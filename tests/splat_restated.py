@@ -198,7 +198,8 @@ def render(means, covs, sh, opac, cams, bg, H, W, dtype=torch.float64, use_sh=Tr
                 m_cap = torch.where(c2, (raw.double() / ALPHA_CAP - 1.0).abs(), one)
                 pm = torch.minimum(pm, torch.minimum(m_alpha, torch.minimum(m_T, m_cap)))
             w = torch.where(c3, alpha * T, torch.zeros_like(T))
-            C = C + p["colour"][g][:, None, None] * w
+            # a pixel that skips the Gaussian takes nothing from it: not colour * 0, which a NaN colour would turn into NaN
+            C = C + torch.where(c3, p["colour"][g][:, None, None] * w, torch.zeros_like(C))
             T = torch.where(c3, Tn, T)
             last = torch.where(c3, count, last)
             done = done | stop

@@ -1,4 +1,4 @@
-"""Seeded scenes for the Gaussian rasteriser's tests (test_splat_host.py, test_gpu_splat.py).
+"""Seeded scenes for the Gaussian rasteriser's tests (test_splat_host.py, test_gpu_splat.py, test_gpu_splat_edges.py).
 
 A scene is drawn so that every Gaussian-level decision of the algorithm is DECIDED: a Gaussian whose margin to one of them (the near
 bound, the radius' ceil, the tile rectangle's truncations, the two tan clamps, the colour clamp) is under 1e-3 -- relative, or in
@@ -172,5 +172,104 @@ def special_reference(name):
     key = "special:" + name
     if key not in _CACHE:
         sc = SPECIAL[name]()
+        _CACHE[key] = (sc,) + with_gradients(sc)
+    return _CACHE[key]
+
+
+# ------------------------------------------------------------------------------------------- edge scenes (test_gpu_splat_edges.py)
+LIST_LENGTHS = (63, 64, 65, 255, 256, 257)            # one under, at and one over the backward's and the forward's LDS batch
+SMALL_IMAGES = ((1, 1), (5, 7), (16, 17), (17, 16), (15, 33), (32, 48))
+BIT_SHAPES = ((2, 16, 16), (3, 16, 16), (4, 16, 16), (2, 32, 32), (4, 32, 32))       # V * tiles = 2, 3, 4, 8, 16
+PAD_SIZES = (257, 511, 513, 1000)
+BEHIND = (0.0, 0.0, -1.0)                             # a mean behind every camera that `scene` draws
+
+
+def visible(sc):
+    """(V,G) bool: not culled, by the float64 restatement's preprocess."""
+    t = [torch.from_numpy(sc[k]).double() for k in ("means", "covs", "sh", "opac")]
+    return np.stack([R.preprocess(*t, torch.from_numpy(sc["cams"][v]), sc["H"], sc["W"])["ok"].numpy() for v in range(sc["V"])])
+
+
+def subset(sc, idx):
+    """The scene of the Gaussians idx, in that order."""
+    idx = np.asarray(idx)
+    return dict(sc, G=int(idx.size), **{k: np.ascontiguousarray(sc[k][idx]) for k in ("means", "covs", "sh", "opac")})
+
+
+def spread_out(sc, G, at):
+    """The scene's Gaussians at the ascending indices `at` of a set of G; every other one sits behind the cameras and is culled."""
+    at = np.asarray(at)
+    assert at.size == sc["G"] and (np.diff(at) > 0).all() and at[0] >= 0 and at[-1] < G
+    means = np.tile(np.asarray(BEHIND, np.float32), (G, 1))
+    covs = np.tile(np.eye(3, dtype=np.float32) * np.float32(0.01), (G, 1, 1))
+    sh = np.full((G, 3, sc["d_sh"]), 0.25, np.float32)
+    opac = np.full(G, 0.5, np.float32)
+    for big, k in zip((means, covs, sh, opac), ("means", "covs", "sh", "opac")):
+        big[at] = sc[k]
+    return dict(sc, G=G, means=means, covs=covs, sh=sh, opac=opac)
+
+
+def padded(sc, G, where, seed=23):
+    """spread_out with the padding in front of the live Gaussians ("front": they come last), behind them ("behind": they come first) or
+    around them, at seeded indices that include 0 and G - 1 ("interleaved") -> (scene, the live indices)."""
+    n = sc["G"]
+    if where == "front":
+        at = np.arange(G - n, G)
+    elif where == "behind":
+        at = np.arange(n)
+    else:
+        inner = np.random.RandomState(seed).choice(np.arange(1, G - 1), n - 2, replace=False)
+        at = np.sort(np.concatenate([[0, G - 1], inner]))
+    return spread_out(sc, G, at), at
+
+
+def both_views(sc):
+    """The first Gaussian that no view culls."""
+    return int(np.nonzero(visible(sc).all(0))[0][0])
+
+
+def _list(n):
+    """the first n non-culled Gaussians of `one_tile` (16x16, one view): one key each, a tile list of exactly n entries"""
+    def build():
+        sc = scene(**CASES["one_tile"])
+        return subset(sc, np.nonzero(visible(sc)[0])[0][:n])
+    return build
+
+
+def _first(n):
+    """sh4 cut to its first n Gaussians; n = 1 keeps the first that no view culls"""
+    def build():
+        sc = scene(**CASES["sh4"])
+        return subset(sc, [both_views(sc)] if n == 1 else np.arange(n))
+    return build
+
+
+def small_image(h, w):
+    return scene(seed=41, G=96, V=2, d_sh=4, H=h, W=w)
+
+
+def bit_scene(V, H, W):
+    return scene(seed=43, G=96, V=V, d_sh=4, H=H, W=W)
+
+
+def _front():
+    """a small nearest Gaussian at pixel (24, 8), radius 4, well inside tile (1, 0) of 41x33; three ordinary ones behind it that
+    cover the image centre"""
+    tanx, tany = 0.5 / 0.9, 0.5 / 1.1
+    x, y = (49.0 / 41.0 - 1.0) * tanx, (17.0 / 33.0 - 1.0) * tany
+    return special([[x, y, 1.0], [0.05, 0.02, 2.0], [-0.1, 0.05, 3.0], [0.1, -0.12, 2.5]],
+                   [iso(0.02), iso(0.25), iso(0.45), iso(0.3)], [0.8, 0.7, 0.9, 0.6])
+
+
+EDGES = {f"list{n}": _list(n) for n in LIST_LENGTHS}
+EDGES.update({"first1": _first(1), "first255": _first(255), "front": _front})
+EDGES.update({f"small{h}x{w}": (lambda h=h, w=w: small_image(h, w)) for h, w in SMALL_IMAGES})
+EDGES.update({f"bits{v}x{h}x{w}": (lambda v=v, h=h, w=w: bit_scene(v, h, w)) for v, h, w in BIT_SHAPES})
+
+
+def edge_reference(name):
+    key = "edge:" + name
+    if key not in _CACHE:
+        sc = EDGES[name]()
         _CACHE[key] = (sc,) + with_gradients(sc)
     return _CACHE[key]

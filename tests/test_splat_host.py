@@ -1,7 +1,8 @@
 """The Gaussian rasteriser's restatement (tests/splat_restated.py), scenes (tests/splat_scenes.py) and fixture G26 on the CPU: what the
-GPU tests of test_gpu_splat.py stand on.  No GPU, no kernel: the restatement against closed forms and scipy, the scenes' conditions
-(every Gaussian-level decision decided by 1e-3, at most 1 % of the pixels left out, float32 and float64 restatements agreeing on
-every decision of the kept pixels), the fixture's contents, and the refusals that need no device.
+GPU tests of test_gpu_splat.py and test_gpu_splat_edges.py stand on.  No GPU, no kernel: the restatement against closed forms and
+scipy, the scenes' conditions (the edge scenes of splat_scenes.EDGES included: every Gaussian-level decision decided by 1e-3, at most
+1 % of the pixels left out, float32 and float64 restatements agreeing on every decision of the kept pixels), the fixture's contents,
+and the refusals that need no device.
 """
 import numpy as np
 import pytest
@@ -12,11 +13,11 @@ import splat_scenes as S
 from conftest import load_golden
 
 NAMES = ("means", "covs", "sh", "opac")
-ALL = [("case", n) for n in S.CASES] + [("special", n) for n in S.SPECIAL]
+ALL = [("case", n) for n in S.CASES] + [("special", n) for n in S.SPECIAL] + [("edge", n) for n in S.EDGES]
 
 
 def get(kind, name):
-    return S.reference(name) if kind == "case" else S.special_reference(name)
+    return {"case": S.reference, "special": S.special_reference, "edge": S.edge_reference}[kind](name)
 
 
 def test_a_single_isotropic_gaussian_against_its_closed_form():
@@ -168,3 +169,96 @@ def test_argument_errors_return_without_launching():
     assert lib.mvsdet_splat_backward_f32(*args[:10], None, one, 1 << 30, one, one, one, one, one, 1, 8, 4, 1, 16, 16, 64, None) == 1
     assert lib.mvsdet_splat_cameras_f32(one, 16, one, 9, 2, one, one, 1, one, 1, None) == 1 and b"intrinsics rows" in lib.mvsdet_last_error()
     assert lib.mvsdet_splat_workspace_bytes(1, 8, 16, 16, 0) == 0
+
+
+# ------------------------------------------------------------------------------------------- the edge scenes' own conditions
+@pytest.mark.parametrize("n", S.LIST_LENGTHS)
+def test_list_scenes_have_one_tile_list_of_exactly_n_entries(n):
+    """The first n non-culled Gaussians of `one_tile` in index order, one key each; some pixel walks the list to its last entry or the
+    one before it, so the last LDS batch of the forward and the first of the backward are really used."""
+    sc, o64, _, _ = S.edge_reference(f"list{n}")
+    full = S.scene(**S.CASES["one_tile"])
+    first = np.nonzero(S.visible(full)[0])[0][:n]
+    info = o64["info"]
+    print(f"list{n}: keys {info['keys']}, largest n_contrib {int(info['n_contrib'].max())}, stopped pixels {int(info['stopped'].sum())}")
+    assert (sc["H"], sc["W"], sc["V"], sc["G"]) == (16, 16, 1, n) and np.array_equal(sc["means"], full["means"][first])
+    assert bool(info["ok"].all()) and info["keys"] == [n]
+    assert int(info["n_contrib"].max()) >= n - 1
+    assert bool(info["stopped"].any())
+
+
+def test_padding_is_culled_and_leaves_the_live_gaussians_alone():
+    """What spread_out puts between the live Gaussians is culled in both views of sh4 by a decided margin; front, behind and
+    interleaved put the live ones last, first, and at seeded indices with 0 and G - 1 among them."""
+    sc, o64, _, _ = S.reference("sh4")
+    seen = S.visible(sc)
+    one = S.spread_out(S.subset(sc, [0]), 2, [1])
+    assert not S.visible(one)[:, 0].any()
+    assert float(S.gaussian_margin(one["means"], one["covs"], one["sh"], one["opac"], sc["cams"], sc["H"], sc["W"])[0]) >= S.MARGIN
+    for G in S.PAD_SIZES:
+        for where in ("front", "behind", "interleaved"):
+            big, at = S.padded(sc, G, where)
+            assert big["G"] == G and len(at) == sc["G"] and (np.diff(at) > 0).all()
+            assert {"front": at[0] == G - sc["G"], "behind": at[-1] == sc["G"] - 1, "interleaved": at[0] == 0 and at[-1] == G - 1}[where]
+            vis = S.visible(big)
+            assert np.array_equal(vis[:, at], seen) and vis.sum() == seen.sum()
+            assert all(np.array_equal(big[k][at], sc[k]) for k in NAMES)
+    big, at = S.padded(sc, 257, "interleaved")
+    again, _, _ = S.restate(big, torch.float64, grad=False)
+    assert np.array_equal(again["image"], o64["image"]) and again["info"]["keys"] == o64["info"]["keys"]
+
+
+def test_cut_scenes_and_the_gaussian_of_the_non_finite_variants():
+    sc, o64, _, _ = S.reference("sh4")
+    g = S.both_views(sc)
+    one, o1, _, _ = S.edge_reference("first1")
+    print("sh4: the first Gaussian that no view culls is", g, "-- keys of the scene cut to it", o1["info"]["keys"])
+    assert bool(o64["info"]["ok"][:, g].all()) and bool(o1["info"]["ok"].all()) and min(o1["info"]["keys"]) >= 1
+    assert one["G"] == 1 and np.array_equal(one["means"][0], sc["means"][g])
+    cut, o255, _, _ = S.edge_reference("first255")
+    assert cut["G"] == 255 and np.array_equal(cut["means"], sc["means"][:255])
+    # without it both views of sh4 need fewer keys
+    away = sc["means"].copy()
+    away[g] = S.BEHIND
+    gone, _, _ = S.restate(dict(sc, means=away), torch.float64, grad=False)
+    assert all(a < b for a, b in zip(gone["info"]["keys"], o64["info"]["keys"])) and not bool(gone["info"]["ok"][:, g].any())
+
+
+def test_small_image_and_bit_scenes_are_what_their_tests_say():
+    tiles = lambda sc: -(-sc["H"] // 16) * -(-sc["W"] // 16)  # noqa: E731
+    assert [v * -(-h // 16) * -(-w // 16) for v, h, w in S.BIT_SHAPES] == [2, 3, 4, 8, 16] and all(v > 1 for v, _, _ in S.BIT_SHAPES)
+    for v, h, w in S.BIT_SHAPES:
+        sc, o64, _, _ = S.edge_reference(f"bits{v}x{h}x{w}")
+        last = o64["info"]["ok"][v - 1]
+        assert sc["V"] == v and sc["G"] == 96 and v * tiles(sc) in (2, 3, 4, 8, 16) and bool(last.any())
+    for h, w in S.SMALL_IMAGES:
+        sc, o64, _, _ = S.edge_reference(f"small{h}x{w}")
+        print(f"small{h}x{w}: keys {o64['info']['keys']}, stopped pixels {o64['info']['stopped'].sum((1, 2)).tolist()}")
+        assert (sc["H"], sc["W"], sc["V"], sc["G"]) == (h, w, 2, 96) and min(o64["info"]["keys"]) >= 64
+    _, o64, _, _ = S.edge_reference("small1x1")
+    assert bool(o64["info"]["stopped"].all())
+
+
+def test_the_front_scene_and_its_nan_variants():
+    """`front`: the nearest Gaussian is small, has tile (1, 0) of 41x33 alone as its rectangle, lies at least 4 px from that tile's
+    edges, and has a positive definite conic.  Restated with a NaN opacity, the image is NaN on exactly that tile; with a NaN
+    coefficient in channel 1, channel 1 alone, on a proper part of the tile."""
+    sc, o64, _, _ = S.edge_reference("front")
+    p = R.preprocess(*[torch.from_numpy(sc[k]).double() for k in NAMES], torch.from_numpy(sc["cams"][0]), sc["H"], sc["W"])
+    A, B, C = p["conic"][0].tolist()
+    px, py, radius = float(p["px"][0]), float(p["py"][0]), float(p["radius"][0])
+    print(f"front: pixel ({px:.4f}, {py:.4f}), radius {radius}, rectangle {p['rect'][0].tolist()}, keys {o64['info']['keys']}")
+    assert bool(p["ok"].all()) and int(p["depth"].argmin()) == 0
+    assert p["rect"][0].tolist() == [1, 2, 0, 1] and abs(px - 24) < 1e-3 and abs(py - 8) < 1e-3 and radius == 4
+    assert A > 0 and A * C - B * B > 0
+    tile = np.zeros((1, 3, sc["H"], sc["W"]), bool)
+    tile[:, :, 0:16, 16:32] = True
+    opac, sh = sc["opac"].copy(), sc["sh"].copy()
+    opac[0], sh[0, 1, 0] = np.nan, np.nan
+    a, _, _ = S.restate(dict(sc, opac=opac), torch.float64, grad=False)
+    assert np.array_equal(np.isnan(a["image"]), tile)
+    b, _, _ = S.restate(dict(sc, sh=sh), torch.float64, grad=False)
+    nan = np.isnan(b["image"])
+    assert not nan[:, [0, 2]].any() and 20 < nan[0, 1].sum() < 256 and not (nan & ~tile).any()
+    assert np.array_equal(b["kept"], o64["kept"])            # no per-pixel margin depends on a colour
+    assert np.array_equal(b["image"][:, [0, 2]], o64["image"][:, [0, 2]])
