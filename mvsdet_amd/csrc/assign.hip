@@ -47,7 +47,7 @@
 // overlap's gradient on that axis: identical boxes do not lose half their pull and touching boxes are still drawn together.  The
 // forward values do not depend on any of this.  Left as it is: the exact tie un0 == 1e-6 of the axis-aligned union with its floor,
 // where the floor's side is taken (no gradient through the union; ATen would halve it).  The BEV conventions above are unchanged.
-#include "common.h"
+#include "block_reduce.h"
 #include "head_points.h"
 #include "rect_clip.h"
 
@@ -207,22 +207,8 @@ __device__ __forceinline__ SubBlock box_sub_block(const Box& box, const float* g
     return s;
 }
 
-// sum of v over the workgroup in a fixed tree (lanes by shuffles, then the waves in order); valid in thread 0
-template <class T>
-__device__ __forceinline__ T block_sum(T v, T* wave_part) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if (lane == 0) wave_part[wave] = v;
-    __syncthreads();
-    T s = wave_part[0];
-    for (int w = 1; w < nw; ++w) s += wave_part[w];
-    return s;
-}
-
 template <class Box>
 __global__ __launch_bounds__(kCountThreads) void assign_count_kernel(AssignParams p) {
-    __shared__ int part[kCountThreads / 64];
     const int g = blockIdx.x, l = blockIdx.y, b = blockIdx.z;
     if (g >= p.counts[b]) return;
     const GridLevel lv = p.lv[l];
@@ -231,17 +217,16 @@ __global__ __launch_bounds__(kCountThreads) void assign_count_kernel(AssignParam
     Box box;
     load_box(p, (size_t)b * p.G + g, box);
     const SubBlock sb = box_sub_block(box, geo, lv);
-    int n = 0;
+    int n[1] = {0};
     for (int j = threadIdx.x; j < sb.size(); j += kCountThreads) {
         int x, y, z;
         float px, py, pz, d[6];
         sb.at(j, x, y, z);
         grid_point(geo, x, y, z, px, py, pz);
         face_distances(px, py, pz, box, d);
-        n += inside_box(d) ? 1 : 0;
+        n[0] += inside_box(d) ? 1 : 0;
     }
-    n = block_sum(n, part);
-    if (threadIdx.x == 0) p.n_inside[((size_t)b * p.G + g) * kMaxL + l] = n;
+    if (block_sums<kCountThreads>(n)) p.n_inside[((size_t)b * p.G + g) * kMaxL + l] = n[0];
 }
 
 template <class Box>
@@ -567,8 +552,6 @@ __device__ __forceinline__ float bce_logits(float x, float t) {
 template <class Box>
 __global__ __launch_bounds__(kPointThreads) void head_loss_kernel(LossParams p, float* part_f, int* part_i) {
     constexpr int R = Box::kReg;
-    __shared__ float fpart[kPointThreads / 64];
-    __shared__ int ipart[kPointThreads / 64];
     const int b = blockIdx.y, i = blockIdx.x * kPointThreads + threadIdx.x;
     PointTerms s{0.f, 0.f, 0.f, 0.f, 0, 0};
     if (i < p.P) {
@@ -590,16 +573,12 @@ __global__ __launch_bounds__(kPointThreads) void head_loss_kernel(LossParams p, 
             }
         }
     }
-    const float f0 = block_sum(s.center, fpart), f1 = block_sum(s.bbox, fpart), f2 = block_sum(s.cls, fpart), f3 = block_sum(s.w, fpart);
-    const int i0 = block_sum(s.pos, ipart), i1 = block_sum(s.valid, ipart);
-    if (threadIdx.x == 0) {
+    float f[4] = {s.center, s.bbox, s.cls, s.w};
+    int n[2] = {s.pos, s.valid};
+    if (block_sums<kPointThreads>(f, n)) {   // block_reduce.h; the sign of a -0.f total ends at head_loss_finish_kernel's 0.f seed
         const size_t o = (size_t)b * gridDim.x + blockIdx.x;
-        part_f[o * 4 + 0] = f0;
-        part_f[o * 4 + 1] = f1;
-        part_f[o * 4 + 2] = f2;
-        part_f[o * 4 + 3] = f3;
-        part_i[o * 2 + 0] = i0;
-        part_i[o * 2 + 1] = i1;
+        for (int q = 0; q < 4; ++q) part_f[o * 4 + q] = f[q];
+        for (int q = 0; q < 2; ++q) part_i[o * 2 + q] = n[q];
     }
 }
 

@@ -5,7 +5,7 @@
 //
 // Roofline: HBM.  Per-view form writes N*C*V*4 B (mostly zeros); the fused mean writes C*V*4 B and reads
 // one packed feature column (C*4 B, contiguous) per valid (view, voxel) pair.
-#include "common.h"
+#include "block_reduce.h"
 #include "depth_resize.h"
 #include "pack.h"
 
@@ -231,8 +231,8 @@ __global__ __launch_bounds__(kThreads) void backproject_weigh_bwd_kernel(
 
 // ---------------------------------------------------------------------------------------------
 // Depth diagnostics of a9 against ground-truth depth (the gt_depth branch of backproject_Weigh, mvsdet.py:1435-1484).
-// Three launches on one stream, no atomics: every block leaves ONE partial at its own index, the last launch adds the
-// partials of a view in ascending block order, so the results do not depend on launch timing.
+// Three launches on one stream, no atomics: every block leaves ONE partial at its own index (block_reduce.h's block_sums), the
+// last launch adds the partials of a view in ascending block order, so the results do not depend on launch timing.
 //   pixel  one thread per (view, y, x) of the crop: ATen's bilinear resize (align_corners=False) of gt_depth to (h,w) ->
 //          g, staged in the workspace for the voxel pass; (depth_mean - g)^2 where g > 0        (:1437-1445)
 //   voxel  one thread per (view, voxel): project_voxel / depth_window as backproject_weigh_kernel calls them, gt_valid
@@ -253,8 +253,6 @@ __global__ __launch_bounds__(kThreads) void depth_diag_pixel_kernel(
     const float* __restrict__ gt, int64_t gs0, int64_t gs1, int64_t gs2, const float* __restrict__ dmean, int64_t ms0,
     int64_t ms1, int64_t ms2, float* __restrict__ g_stage, float* __restrict__ gt_resized,
     DiagPixelPartial* __restrict__ part, int h, int w, int Hg, int Wg, float scale_y, float scale_x) {
-    __shared__ double s_sq[kThreads / kWave];
-    __shared__ int s_n[kThreads / kWave];
     const int p = blockIdx.x * kThreads + threadIdx.x;
     const int i = blockIdx.y;
     float term = 0.0f;
@@ -271,30 +269,15 @@ __global__ __launch_bounds__(kThreads) void depth_diag_pixel_kernel(
             in_mask = 1;
         }
     }
-    const double sq = wave_sum((double)term);
-    const int n = wave_sum(in_mask);
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) {
-        s_sq[wave] = sq;
-        s_n[wave] = n;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        DiagPixelPartial r = {0.0, 0};
-        for (int k = 0; k < kThreads / kWave; ++k) {
-            r.sq = r.sq + s_sq[k];
-            r.n += s_n[k];
-        }
-        part[(size_t)i * gridDim.x + blockIdx.x] = r;
-    }
+    double sq[1] = {(double)term};
+    int n[1] = {in_mask};
+    if (block_sums(sq, n)) part[(size_t)i * gridDim.x + blockIdx.x] = {sq[0], n[0]};
 }
 
 __global__ __launch_bounds__(kThreads) void depth_diag_voxel_kernel(
     const float* __restrict__ points, const float* __restrict__ projection, const float* __restrict__ depth,
     const float* __restrict__ dens, int64_t ds0, int64_t ds1, int64_t ds2, int64_t ds3, const float* __restrict__ g_stage,
     DiagVoxelPartial* __restrict__ part, int h, int w, int V, int J, float vz) {
-    __shared__ double s_gap[kThreads / kWave];
-    __shared__ int s_cnt[kThreads / kWave][4];
     const int v = blockIdx.x * kThreads + threadIdx.x;
     const int i = blockIdx.y;
     float term = 0.0f;
@@ -318,28 +301,9 @@ __global__ __launch_bounds__(kThreads) void depth_diag_voxel_kernel(
             n_neq = (gt_valid != ok) ? 1 : 0;
         }
     }
-    const double gap = wave_sum((double)term);
-    const int c0 = wave_sum(n_orig), c1 = wave_sum(n_valid), c2 = wave_sum(n_neq), c3 = wave_sum(n_gt);
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) {
-        s_gap[wave] = gap;
-        s_cnt[wave][0] = c0;
-        s_cnt[wave][1] = c1;
-        s_cnt[wave][2] = c2;
-        s_cnt[wave][3] = c3;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        DiagVoxelPartial r = {0.0, 0, 0, 0, 0};
-        for (int k = 0; k < kThreads / kWave; ++k) {
-            r.gap = r.gap + s_gap[k];
-            r.n_orig += s_cnt[k][0];
-            r.n_valid += s_cnt[k][1];
-            r.n_neq += s_cnt[k][2];
-            r.n_gt += s_cnt[k][3];
-        }
-        part[(size_t)i * gridDim.x + blockIdx.x] = r;
-    }
+    double gap[1] = {(double)term};
+    int n[4] = {n_orig, n_valid, n_neq, n_gt};
+    if (block_sums(gap, n)) part[(size_t)i * gridDim.x + blockIdx.x] = {gap[0], n[0], n[1], n[2], n[3]};
 }
 
 // One block.  Thread t adds the partials of views t, t + 256, ... in ascending block order; thread 0 then walks the views in
@@ -515,11 +479,7 @@ extern "C" int mvsdet_depth_diagnostics_f32(const float* points, const float* pr
     MVS_REQUIRE(Hg >= 1 && Wg >= 1, "depth_diagnostics: bad gt_depth shape %dx%d", Hg, Wg);
     MVS_REQUIRE((size_t)h * w < (size_t)INT32_MAX, "depth_diagnostics: crop %dx%d exceeds 2^31 pixels", h, w);
     MVS_REQUIRE(((uintptr_t)workspace & 15) == 0, "depth_diagnostics: workspace must be 16-byte aligned");
-    const size_t need = mvsdet_depth_diagnostics_workspace_bytes(N, h, w, V);
-    if (workspace_bytes < need) {
-        set_error("depth_diagnostics: workspace %zu < %zu bytes", workspace_bytes, need);
-        return MVSDET_ERR_WORKSPACE;
-    }
+    MVS_REQUIRE_WORKSPACE("depth_diagnostics", workspace_bytes, mvsdet_depth_diagnostics_workspace_bytes(N, h, w, V));
     const int pblocks = diag_blocks((size_t)h * w), vblocks = diag_blocks((size_t)V);
     float* g_stage = (float*)workspace;
     DiagPixelPartial* ppart = (DiagPixelPartial*)((char*)workspace + diag_stage_bytes(N, h, w));

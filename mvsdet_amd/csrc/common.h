@@ -78,6 +78,18 @@ constexpr int kXcds = 8;        // MI355X: 8 XCDs, blocks are dealt round-robin 
         }                                                                             \
     } while (0)
 
+// A caller's buffer of `have` bytes where `need` are needed: the one wording of MVSDET_ERR_WORKSPACE, the operator's name first.
+#define MVS_REQUIRE_WORKSPACE(name, have, need)                                                                        \
+    do {                                                                                                               \
+        if ((size_t)(have) < (size_t)(need)) {                                                                         \
+            ::mvsdet::set_error("%s: workspace of %zu bytes, %zu needed", name, (size_t)(have), (size_t)(need));       \
+            return MVSDET_ERR_WORKSPACE;                                                                               \
+        }                                                                                                              \
+    } while (0)
+
+// blocks of kThreads threads for one thread per element
+inline long long blocks_of(long long total) { return (total + kThreads - 1) / kThreads; }
+
 // Blocks b and b+8 share an XCD (and its 4 MiB L2).  Map the hardware block id to a logical id so
 // that every XCD walks ONE contiguous range of logical ids: neighbouring tiles of a view then find
 // the source rows they share in their own L2.  Bijective for any nblocks (speed only, never

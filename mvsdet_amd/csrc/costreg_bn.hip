@@ -11,30 +11,13 @@
 // (reductions, then apply); the ReLU mask is recomputed from x with the forward's own arithmetic instead of being stored.
 // The sums are taken per thread in fp32 over a short strip, then in double across the block and the splits (a channel of
 // the full-resolution layers has 2.3 M elements).  A channel's elements are N contiguous runs of `vol` floats.
-#include "common.h"
+#include "block_reduce.h"
 
 #include <algorithm>
 
 namespace mvsdet {
 
 constexpr int kBnSplit = 32;   // blocks per channel in the reduction kernels
-
-__device__ __forceinline__ double2 block_sum2(double a, double b) {
-    __shared__ double s_a[kThreads / 64], s_b[kThreads / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        a += __shfl_down(a, o, 64);
-        b += __shfl_down(b, o, 64);
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();   // a previous use of the buffers
-    if (lane == 0) { s_a[wave] = a; s_b[wave] = b; }
-    __syncthreads();
-    double ra = 0.0, rb = 0.0;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) { ra += s_a[w]; rb += s_b[w]; }
-    return make_double2(ra, rb);
-}
 
 // the strip of channel c that block (c, split) reduces: elements [begin, end) of the channel's N*vol, in units of 4 floats
 // when vol % 4 == 0 (VEC) or single floats
@@ -71,8 +54,8 @@ __global__ __launch_bounds__(kThreads) void bn_stats_kernel(const float* __restr
             q += v * v;
         }
     });
-    const double2 r = block_sum2((double)s, (double)q);
-    if (threadIdx.x == 0) partial[(size_t)c * gridDim.y + split] = r;
+    double r[2] = {(double)s, (double)q};
+    if (block_sums(r)) partial[(size_t)c * gridDim.y + split] = make_double2(r[0], r[1]);
 }
 
 // one thread per channel: statistics from the partial sums, running statistics, the affine of the apply pass
@@ -100,7 +83,7 @@ __global__ void bn_finalize_kernel(const float* __restrict__ x, size_t vol, cons
 
 // The same, from the partial sums a convolution's epilogue left (costreg_bf16.hip: sums of the raw values and of their squares, one
 // double2 per (channel, block), of (value - pivot_c), added up in double from the block's fp32 lane sums).  One block per
-// channel: the `parts` entries are added in a fixed order (strided over the threads, then block_sum2): the same bits on every run.
+// channel: the `parts` entries are added in a fixed order (strided over the threads, then block_reduce.h's block_sums): the same bits on every run.
 __global__ __launch_bounds__(kThreads) void bn_finalize_parts_kernel(const double2* __restrict__ partial, size_t parts, const float* __restrict__ pivot,
                                                                      const float* __restrict__ gamma,
                                                                      const float* __restrict__ beta, float* __restrict__ running_mean,
@@ -114,11 +97,11 @@ __global__ __launch_bounds__(kThreads) void bn_finalize_parts_kernel(const doubl
         s += e.x;
         q += e.y;
     }
-    const double2 r = block_sum2(s, q);
-    if (threadIdx.x != 0) return;
-    const double dm = r.x / M;                    // mean of (x - pivot)
+    double r[2] = {s, q};
+    if (!block_sums(r)) return;
+    const double dm = r[0] / M;                   // mean of (x - pivot)
     const double mean = (pivot ? (double)pivot[c] : 0.0) + dm;
-    double var = r.y / M - dm * dm;
+    double var = r[1] / M - dm * dm;
     var = var < 0.0 ? 0.0 : var;
     const float invstd = (float)(1.0 / sqrt(var + (double)eps));
     save_mean[c] = (float)mean;
@@ -210,8 +193,8 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(const float* __
             one(x[off], gy[off], OUTMASK ? yout[off] : 0.0f);
         }
     });
-    const double2 r = block_sum2((double)s, (double)q);
-    if (threadIdx.x == 0) partial[(size_t)c * gridDim.y + split] = r;
+    double r[2] = {(double)s, (double)q};
+    if (block_sums(r)) partial[(size_t)c * gridDim.y + split] = make_double2(r[0], r[1]);
 }
 
 __global__ void bn_affine_kernel(const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
@@ -298,10 +281,7 @@ int bn_check(const char* name, int N, int C, long long vol, const void* workspac
     MVS_REQUIRE(N > 0 && C > 0 && vol > 0, "%s: bad shape N=%d C=%d volume=%lld", name, N, C, vol);
     MVS_REQUIRE(C <= 65535 && N <= 65535, "%s: N or C > 65535", name);
     MVS_REQUIRE(workspace && ((uintptr_t)workspace & 15u) == 0, "%s: workspace NULL or not 16-byte aligned", name);
-    if (workspace_bytes < mvsdet_bn3d_workspace_bytes(C)) {
-        set_error("%s: workspace %zu B < %zu B", name, workspace_bytes, mvsdet_bn3d_workspace_bytes(C));
-        return MVSDET_ERR_WORKSPACE;
-    }
+    MVS_REQUIRE_WORKSPACE(name, workspace_bytes, mvsdet_bn3d_workspace_bytes(C));
     return MVSDET_OK;
 }
 }  // namespace

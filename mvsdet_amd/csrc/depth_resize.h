@@ -1,5 +1,5 @@
 // What the depth diagnostics (backproject.hip) and the depth losses (depthloss.hip) share: ATen's bilinear resize of the
-// ground-truth depth in ATen's own op order, and the fixed-order sums of a block.
+// ground-truth depth in ATen's own op order.
 #pragma once
 #include "common.h"
 
@@ -32,18 +32,6 @@ __device__ __forceinline__ float resized_at(const float* __restrict__ src, int64
     const float a = src[(int64_t)y0 * s1 + (int64_t)x0 * s2], b = src[(int64_t)y0 * s1 + (int64_t)x1 * s2];
     const float c = src[(int64_t)y1 * s1 + (int64_t)x0 * s2], d = src[(int64_t)y1 * s1 + (int64_t)x1 * s2];
     return ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d);
-}
-
-// Sum over the block in a fixed order: lanes by halving shuffles, then waves 0..3 by thread 0 (its return value counts).
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v = v + __shfl_down(v, o, kWave);
-    return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v = v + __shfl_down(v, o, kWave);
-    return v;
 }
 
 }  // namespace mvsdet

@@ -3,13 +3,13 @@
 //                       (h,w) of est, mask = g > 0, loss = mean over the mask of |est - g|
 //   kind 1 (smooth_l1)  mvsnet_loss (mvs_models/mvsnet.py:292-294): mask > 0.5, gt at est's size, smooth-L1 with beta = 1, mean
 // Forward: two launches on one stream, no atomics.  One thread per (view, y, x) forms its term in fp32; a block adds terms (float64)
-// and count over its lanes by shuffles, then over its waves in order, and leaves ONE partial at its own index; the finishing launch
-// adds the partials in ascending block order and writes loss = sum / count (fp32) and count (int32).  Backward: one launch, one
+// and count in block_reduce.h's fixed order and leaves ONE partial at its own index; the finishing launch adds the partials in
+// ascending block order (the same header's walk) and writes loss = sum / count (fp32) and count (int32).  Backward: one launch, one
 // thread per pixel, a dense (N,h,w) gradient; it forms g again from gt (the same inlined code as the forward, so the same bits)
 // instead of reading a staged copy: 4 taps of a map that sits in L2 against a (N,h,w) buffer kept alive from forward to backward.
 //
 // Roofline: neither.  N*h*w = 1.9e5 pixels per scene, 1.5 MB read at the most: the launches bound it.
-#include "common.h"
+#include "block_reduce.h"
 #include "depth_resize.h"
 
 namespace mvsdet {
@@ -17,6 +17,10 @@ namespace mvsdet {
 struct DepthLossPartial {
     double sum;
     long long n;
+    __device__ void add(const DepthLossPartial& r) {
+        sum = sum + r.sum;
+        n += r.n;
+    }
 };
 
 // est - target and whether the pixel is inside the mask.  p = (i * h + y) * w + x.
@@ -47,8 +51,6 @@ __global__ __launch_bounds__(kThreads) void depth_loss_kernel(
     const float* __restrict__ est, int64_t es0, int64_t es1, int64_t es2, const float* __restrict__ gt, int64_t gs0, int64_t gs1,
     int64_t gs2, const float* __restrict__ mask, int64_t ms0, int64_t ms1, int64_t ms2, DepthLossPartial* __restrict__ part,
     long long total, int h, int w, int Hg, int Wg, float scale_y, float scale_x) {
-    __shared__ double s_sum[kThreads / kWave];
-    __shared__ int s_n[kThreads / kWave];
     const long long p = (long long)blockIdx.x * kThreads + threadIdx.x;
     float term = 0.0f;
     int in_mask = 0;
@@ -61,51 +63,18 @@ __global__ __launch_bounds__(kThreads) void depth_loss_kernel(
             in_mask = 1;
         }
     }
-    const double sum = wave_sum((double)term);
-    const int n = wave_sum(in_mask);
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) {
-        s_sum[wave] = sum;
-        s_n[wave] = n;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        DepthLossPartial r = {0.0, 0};
-        for (int k = 0; k < kThreads / kWave; ++k) {
-            r.sum = r.sum + s_sum[k];
-            r.n += s_n[k];
-        }
-        part[blockIdx.x] = r;
-    }
+    double sum[1] = {(double)term};
+    int n[1] = {in_mask};
+    if (block_sums(sum, n)) part[blockIdx.x] = {sum[0], n[0]};
 }
 
-// One block.  Thread t adds the partials of its run of consecutive blocks in ascending order; thread 0 then adds the threads' sums
-// in ascending order: every partial enters in ascending block order, the same association on every call.
+// One block: every partial enters in ascending block order (ordered_partial_sum), the same association on every call.
 __global__ __launch_bounds__(kThreads) void depth_loss_finish_kernel(const DepthLossPartial* __restrict__ part, int nblocks,
                                                                      float* __restrict__ loss, int32_t* __restrict__ count) {
-    __shared__ double s_sum[kThreads];
-    __shared__ long long s_n[kThreads];
-    const int run = (nblocks + kThreads - 1) / kThreads;
-    const int first = threadIdx.x * run, last = min(first + run, nblocks);
-    double sum = 0.0;
-    long long n = 0;
-    for (int b = first; b < last; ++b) {
-        const DepthLossPartial r = part[b];
-        sum = sum + r.sum;
-        n += r.n;
-    }
-    s_sum[threadIdx.x] = sum;
-    s_n[threadIdx.x] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        sum = 0.0;
-        n = 0;
-        for (int t = 0; t < kThreads; ++t) {
-            sum = sum + s_sum[t];
-            n += s_n[t];
-        }
-        loss[0] = (float)(sum / (double)n);   // an empty mask: 0 / 0 = NaN, as torch.mean of nothing
-        count[0] = (int32_t)n;
+    DepthLossPartial r;
+    if (ordered_partial_sum(part, nblocks, r)) {
+        loss[0] = (float)(r.sum / (double)r.n);   // an empty mask: 0 / 0 = NaN, as torch.mean of nothing
+        count[0] = (int32_t)r.n;
     }
 }
 
@@ -132,8 +101,6 @@ __global__ __launch_bounds__(kThreads) void depth_loss_bwd_kernel(
 
 using namespace mvsdet;
 
-static long long loss_blocks(long long total) { return (total + kThreads - 1) / kThreads; }
-
 static int check_depth_loss(const char* name, const float* est, const int64_t* es, const float* gt, const int64_t* gs,
                             const float* mask, const int64_t* ms, int N, int h, int w, int Hg, int Wg, int kind) {
     MVS_REQUIRE(est && es && gt && gs, "%s: NULL pointer", name);
@@ -149,9 +116,26 @@ static int check_depth_loss(const char* name, const float* est, const int64_t* e
     return MVSDET_OK;
 }
 
+// One thread per pixel of l1 (kernel<0>) or smooth_l1 (kernel<1>), picked by `kind`; `own` are the kernel's arguments between the
+// maps and the sizes.  Returns the block count.
+template <class Kernel, class... Own>
+static int launch_by_kind(Kernel l1, Kernel smooth_l1, int kind, mvsdet_stream_t stream, const float* est, const int64_t* es,
+                          const float* gt, const int64_t* gs, const float* mask, const int64_t* mask_strides, int N, int h, int w, int Hg,
+                          int Wg, Own... own) {
+    const long long total = (long long)N * h * w;
+    const int nblocks = (int)blocks_of(total);
+    const int64_t zero[3] = {0, 0, 0};
+    const int64_t* ms = mask_strides ? mask_strides : zero;
+    // at::native::area_pixel_compute_scale: (float)input_size / output_size
+    const float scale_y = (float)Hg / (float)h, scale_x = (float)Wg / (float)w;
+    hipLaunchKernelGGL(kind == MVSDET_DEPTH_LOSS_L1 ? l1 : smooth_l1, dim3(nblocks), dim3(kThreads), 0, (hipStream_t)stream, est, es[0],
+                       es[1], es[2], gt, gs[0], gs[1], gs[2], mask, ms[0], ms[1], ms[2], own..., total, h, w, Hg, Wg, scale_y, scale_x);
+    return nblocks;
+}
+
 extern "C" size_t mvsdet_depth_loss_workspace_bytes(int N, int h, int w) {
     if (N <= 0 || h <= 0 || w <= 0) return 0;
-    return (size_t)loss_blocks((long long)N * h * w) * sizeof(DepthLossPartial);
+    return (size_t)blocks_of((long long)N * h * w) * sizeof(DepthLossPartial);
 }
 
 extern "C" int mvsdet_depth_loss_f32(const float* est, const int64_t* est_strides, const float* gt, const int64_t* gt_strides,
@@ -160,27 +144,12 @@ extern "C" int mvsdet_depth_loss_f32(const float* est, const int64_t* est_stride
     if (int rc = check_depth_loss("depth_loss", est, est_strides, gt, gt_strides, mask, mask_strides, N, h, w, Hg, Wg, kind)) return rc;
     MVS_REQUIRE(loss && count && workspace, "depth_loss: NULL pointer");
     MVS_REQUIRE(((uintptr_t)workspace & 15) == 0, "depth_loss: workspace must be 16-byte aligned");
-    const size_t need = mvsdet_depth_loss_workspace_bytes(N, h, w);
-    if (workspace_bytes < need) {
-        set_error("depth_loss: workspace %zu < %zu bytes", workspace_bytes, need);
-        return MVSDET_ERR_WORKSPACE;
-    }
-    const long long total = (long long)N * h * w;
-    const int nblocks = (int)loss_blocks(total);
-    const int64_t zero[3] = {0, 0, 0};
-    const int64_t *es = est_strides, *gs = gt_strides, *ms = mask_strides ? mask_strides : zero;
+    MVS_REQUIRE_WORKSPACE("depth_loss", workspace_bytes, mvsdet_depth_loss_workspace_bytes(N, h, w));
     DepthLossPartial* part = (DepthLossPartial*)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    // at::native::area_pixel_compute_scale: (float)input_size / output_size
-    const float scale_y = (float)Hg / (float)h, scale_x = (float)Wg / (float)w;
-    if (kind == MVSDET_DEPTH_LOSS_L1)
-        hipLaunchKernelGGL(depth_loss_kernel<0>, dim3(nblocks), dim3(kThreads), 0, st, est, es[0], es[1], es[2], gt, gs[0], gs[1],
-                           gs[2], mask, ms[0], ms[1], ms[2], part, total, h, w, Hg, Wg, scale_y, scale_x);
-    else
-        hipLaunchKernelGGL(depth_loss_kernel<1>, dim3(nblocks), dim3(kThreads), 0, st, est, es[0], es[1], es[2], gt, gs[0], gs[1],
-                           gs[2], mask, ms[0], ms[1], ms[2], part, total, h, w, Hg, Wg, scale_y, scale_x);
+    const int nblocks = launch_by_kind(depth_loss_kernel<0>, depth_loss_kernel<1>, kind, stream, est, est_strides, gt, gt_strides, mask,
+                                       mask_strides, N, h, w, Hg, Wg, part);
     MVS_LAUNCH_CHECK("depth_loss (terms)");
-    hipLaunchKernelGGL(depth_loss_finish_kernel, dim3(1), dim3(kThreads), 0, st, part, nblocks, loss, count);
+    hipLaunchKernelGGL(depth_loss_finish_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, part, nblocks, loss, count);
     MVS_LAUNCH_CHECK("depth_loss (finish)");
     return MVSDET_OK;
 }
@@ -191,18 +160,8 @@ extern "C" int mvsdet_depth_loss_bwd_f32(const float* est, const int64_t* est_st
     if (int rc = check_depth_loss("depth_loss_bwd", est, est_strides, gt, gt_strides, mask, mask_strides, N, h, w, Hg, Wg, kind))
         return rc;
     MVS_REQUIRE(g_loss && count && grad, "depth_loss_bwd: NULL pointer");
-    const long long total = (long long)N * h * w;
-    const int nblocks = (int)loss_blocks(total);
-    const int64_t zero[3] = {0, 0, 0};
-    const int64_t *es = est_strides, *gs = gt_strides, *ms = mask_strides ? mask_strides : zero;
-    hipStream_t st = (hipStream_t)stream;
-    const float scale_y = (float)Hg / (float)h, scale_x = (float)Wg / (float)w;
-    if (kind == MVSDET_DEPTH_LOSS_L1)
-        hipLaunchKernelGGL(depth_loss_bwd_kernel<0>, dim3(nblocks), dim3(kThreads), 0, st, est, es[0], es[1], es[2], gt, gs[0], gs[1],
-                           gs[2], mask, ms[0], ms[1], ms[2], g_loss, count, grad, total, h, w, Hg, Wg, scale_y, scale_x);
-    else
-        hipLaunchKernelGGL(depth_loss_bwd_kernel<1>, dim3(nblocks), dim3(kThreads), 0, st, est, es[0], es[1], es[2], gt, gs[0], gs[1],
-                           gs[2], mask, ms[0], ms[1], ms[2], g_loss, count, grad, total, h, w, Hg, Wg, scale_y, scale_x);
+    launch_by_kind(depth_loss_bwd_kernel<0>, depth_loss_bwd_kernel<1>, kind, stream, est, est_strides, gt, gt_strides, mask, mask_strides, N,
+                   h, w, Hg, Wg, g_loss, count, grad);
     MVS_LAUNCH_CHECK("depth_loss_bwd");
     return MVSDET_OK;
 }

@@ -507,10 +507,7 @@ extern "C" int mvsdet_eval_compute(const void* state, int n_labels, int capacity
     MVS_REQUIRE((uintptr_t)workspace % 8 == 0 && (uintptr_t)out_recall % 8 == 0 && (uintptr_t)out_first % 8 == 0,
                 "eval_compute: workspace, out_recall and out_first must be 8-byte aligned");
     const WsLayout w = ws_layout(n_labels, n_bound, gt_capacity, n_thr);
-    if (workspace_bytes < w.total) {
-        set_error("eval_compute: workspace of %zu bytes, %zu needed", workspace_bytes, w.total);
-        return MVSDET_ERR_WORKSPACE;
-    }
+    MVS_REQUIRE_WORKSPACE("eval_compute", workspace_bytes, w.total);
     const EvalState s = state_of(const_cast<void*>(state), n_labels, capacity);
     char* ws = static_cast<char*>(workspace);
     ComputeParams p;

@@ -19,14 +19,14 @@
 //     x and y as float32 in LDS with row loads (consecutive lanes, consecutive columns; every tensor is read in place through its
 //     element strides), adds the squared error of the pixels it owns (its 32 x 16 corner of the staged box; the last tile of a row /
 //     column owns the box to the image's edge, so every pixel has one owner), forms the five 7-tap row sums in float64 into LDS and the
-//     7-tap column sums from them, evaluates S and reduces both sums inside the block (lanes by shuffles, the four waves in order).
+//     7-tap column sums from them, evaluates S and reduces both sums inside the block (block_reduce.h).
 //     Depth planes skip the windows.  No atomics: the block writes its two sums to the workspace slot of its block index.
 //     LDS: 2 x 38 x 22 x 4 + 5 x 32 x 22 x 8 + 64 = 34912 bytes -> 4 blocks (16 waves) per CU, LDS-bound.
 //   nvs_finish_kernel, one block: a thread per plane adds the plane's slots in slot order; thread 0 then adds the channels of a view,
 //     writes (psnr_v, ssim_v) to the view's row, adds the views in order, writes the scene's (psnr, ssim, rmse) and adds them and a
 //     scene count to the accumulator state (4 float64).  One fixed order everywhere: two runs give the same bits, and a view's two
 //     values do not depend on the views beside it.
-#include "common.h"
+#include "block_reduce.h"
 
 #include <climits>
 
@@ -51,16 +51,10 @@ struct NvsParams {
     double* slots;                // [planes * tiles][2] = squared error, sum of S; then [planes][2] plane sums
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    return v;
-}
-
 __global__ __launch_bounds__(kThreads) void nvs_score_kernel(NvsParams p) {
     __shared__ float sx[kSH * kSW];
     __shared__ float sy[kSH * kSW];
     __shared__ double rs[5][kSH * kTW];
-    __shared__ double red[2][kThreads / kWave];
     const int tid = threadIdx.x;
     const int plane = blockIdx.x / p.tiles, tile = blockIdx.x % p.tiles;
     const int tx = tile % p.tiles_x, ty = tile / p.tiles_x;
@@ -127,14 +121,10 @@ __global__ __launch_bounds__(kThreads) void nvs_score_kernel(NvsParams p) {
             }
         }
     }
-    se = wave_sum(se), ss = wave_sum(ss);
-    if (tid % kWave == 0) red[0][tid / kWave] = se, red[1][tid / kWave] = ss;
-    __syncthreads();
-    if (tid == 0) {
-        double a = red[0][0], b = red[1][0];
-        for (int w = 1; w < kThreads / kWave; ++w) a += red[0][w], b += red[1][w];
-        p.slots[2 * (size_t)blockIdx.x] = a;
-        p.slots[2 * (size_t)blockIdx.x + 1] = b;
+    double sums[2] = {se, ss};
+    if (block_sums(sums)) {
+        p.slots[2 * (size_t)blockIdx.x] = sums[0];
+        p.slots[2 * (size_t)blockIdx.x + 1] = sums[1];
     }
 }
 
@@ -223,11 +213,7 @@ extern "C" int mvsdet_nvs_score_f32(double* state, const float* pred, const int6
     p.tiles = (int)tiles_of(H, W, &p.tiles_x);
     p.colour_planes = pred ? 3 * n_tgt : 0, p.planes = p.colour_planes + (pred_depth ? n_tgt : 0);
     p.slots = static_cast<double*>(workspace);
-    const size_t need = ((size_t)p.planes * p.tiles + p.planes) * 2 * sizeof(double);
-    if (workspace_bytes < need) {
-        set_error("nvs_score: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-        return MVSDET_ERR_WORKSPACE;
-    }
+    MVS_REQUIRE_WORKSPACE("nvs_score", workspace_bytes, ((size_t)p.planes * p.tiles + p.planes) * 2 * sizeof(double));
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(nvs_score_kernel, dim3((unsigned)(p.planes * p.tiles)), dim3(kThreads), 0, st, p);
     hipLaunchKernelGGL(nvs_finish_kernel, dim3(1), dim3(kThreads), 0, st, p, out_views, out_scene, state);

@@ -7,14 +7,14 @@
 // short vectors from the host) through z + 1e-10, the normalise / denormalise round trip, floor, the mask (x0 >= 0, x1 <= W-1, y0 >= 0,
 // y0 <= H-1: on y0), the four clamped taps and the weights formed from the CLAMPED x1, y1.  Depth and image are read in place through
 // strides and index vectors.
-// Loss (two launches): fp32 terms of the three smooth-L1 sums added in float64 per wave, per block, over the blocks in a fixed order.
+// Loss (two launches): fp32 terms of the three smooth-L1 sums added in float64 per wave, per block, over the blocks in the one fixed
+// order of block_reduce.h.
 // Selection over scenes (two launches): per pixel the scene of the smallest L_i + 1e4 (1 - mask_i), ties to the lower index.
 // Backward: one launch each for the loss (d L / d warped, pixel-centric: photo term and the transposed difference stencils, times the
 // mask) and for the warp (through the four weights to (x, y), through the quotient to depth).  No atomics anywhere.
 //
 // Roofline: neither.  B*h*w = 47 200 pixels per scene: the launches bound it.
-#include "common.h"
-#include "depth_resize.h"
+#include "block_reduce.h"
 
 namespace mvsdet {
 
@@ -24,6 +24,12 @@ constexpr int kPhotoMaxScenes = 32;  // photometric_select: scenes per call
 struct PhotoPartial {
     double s0, s1, s2;   // photo, d/dx, d/dy smooth-L1 sums
     long long n;         // pixels inside the mask
+    __device__ void add(const PhotoPartial& r) {
+        s0 = s0 + r.s0;
+        s1 = s1 + r.s1;
+        s2 = s2 + r.s2;
+        n += r.n;
+    }
 };
 
 // ---------------------------------------------------------------------------------------------------------------- geometry
@@ -216,8 +222,6 @@ __device__ __forceinline__ float smooth_l1_grad(float d) { return d > 1.0f ? 1.0
 __global__ __launch_bounds__(kThreads) void photo_loss_kernel(const float* __restrict__ warped, const float* __restrict__ mask,
                                                               PhotoImage ref, PhotoPartial* __restrict__ part, int total, int h, int w,
                                                               int C, int simple) {
-    __shared__ double s_sum[3][kThreads / kWave];
-    __shared__ int s_n[kThreads / kWave];
     const int p = blockIdx.x * kThreads + threadIdx.x;
     float t0 = 0.0f, t1 = 0.0f, t2 = 0.0f;
     int in_mask = 0;
@@ -238,59 +242,19 @@ __global__ __launch_bounds__(kThreads) void photo_loss_kernel(const float* __res
             if (has_y) t2 = t2 + smooth_l1((wp[(int64_t)w * C + c] * my - wm) - (rp[ref.s1 + c * ref.s3] * my - rm));
         }
     }
-    const double a0 = wave_sum((double)t0), a1 = wave_sum((double)t1), a2 = wave_sum((double)t2);
-    const int n = wave_sum(in_mask);
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) {
-        s_sum[0][wave] = a0;
-        s_sum[1][wave] = a1;
-        s_sum[2][wave] = a2;
-        s_n[wave] = n;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        PhotoPartial r = {0.0, 0.0, 0.0, 0};
-        for (int k = 0; k < kThreads / kWave; ++k) {
-            r.s0 = r.s0 + s_sum[0][k];
-            r.s1 = r.s1 + s_sum[1][k];
-            r.s2 = r.s2 + s_sum[2][k];
-            r.n += s_n[k];
-        }
-        part[blockIdx.x] = r;
-    }
+    double a[3] = {(double)t0, (double)t1, (double)t2};
+    int n[1] = {in_mask};
+    if (block_sums(a, n)) part[blockIdx.x] = {a[0], a[1], a[2], n[0]};
 }
 
-// One block; every partial enters in ascending block order (depth_loss_finish_kernel's association).
+// One block; every partial enters in ascending block order (block_reduce.h's ordered_partial_sum).
 // loss = L, terms = the three means; an empty difference term (w = 1 or h = 1) is 0 / 0 = NaN as torch.mean of nothing.
 __global__ __launch_bounds__(kThreads) void photo_loss_finish_kernel(const PhotoPartial* __restrict__ part, int nblocks,
                                                                      float* __restrict__ loss, float* __restrict__ terms,
                                                                      int32_t* __restrict__ count, double n0, double n1, double n2,
                                                                      int simple) {
-    __shared__ double s_sum[3][kThreads];
-    __shared__ long long s_n[kThreads];
-    const int run = (nblocks + kThreads - 1) / kThreads;
-    const int first = threadIdx.x * run, last = min(first + run, nblocks);
-    PhotoPartial a = {0.0, 0.0, 0.0, 0};
-    for (int b = first; b < last; ++b) {
-        const PhotoPartial r = part[b];
-        a.s0 = a.s0 + r.s0;
-        a.s1 = a.s1 + r.s1;
-        a.s2 = a.s2 + r.s2;
-        a.n += r.n;
-    }
-    s_sum[0][threadIdx.x] = a.s0;
-    s_sum[1][threadIdx.x] = a.s1;
-    s_sum[2][threadIdx.x] = a.s2;
-    s_n[threadIdx.x] = a.n;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a = {0.0, 0.0, 0.0, 0};
-        for (int t = 0; t < kThreads; ++t) {
-            a.s0 = a.s0 + s_sum[0][t];
-            a.s1 = a.s1 + s_sum[1][t];
-            a.s2 = a.s2 + s_sum[2][t];
-            a.n += s_n[t];
-        }
+    PhotoPartial a;
+    if (ordered_partial_sum(part, nblocks, a)) {
         const float m0 = (float)(a.s0 / n0);
         const float m1 = simple ? 0.0f : (float)(a.s1 / n1), m2 = simple ? 0.0f : (float)(a.s2 / n2);
         loss[0] = simple ? m0 : 0.5f * m0 + 0.5f * (m1 + m2);   // (1 - alpha) photo + alpha (dx + dy), alpha = 0.5
@@ -402,8 +366,6 @@ __global__ void photo_select_bwd_kernel(const int32_t* __restrict__ wins, const 
 
 using namespace mvsdet;
 
-static int photo_blocks(long long total) { return (int)((total + kThreads - 1) / kThreads); }
-
 static int check_photo_shape(const char* name, int B, int h, int w, int C) {
     MVS_REQUIRE(B > 0 && h > 0 && w > 0 && C > 0, "%s: bad shape B=%d h=%d w=%d C=%d", name, B, h, w, C);
     MVS_REQUIRE((long long)B * h * w * C < (long long)INT32_MAX, "%s: %dx%dx%dx%d exceeds 2^31 elements", name, B, h, w, C);
@@ -443,7 +405,7 @@ extern "C" int mvsdet_photo_warp_f32(const float* img, const int64_t* img_stride
     MVS_REQUIRE(depth_idx || n_depth == B, "photo_warp: %d depth maps for %d pairs and no index", n_depth, B);
     const PhotoImage im = {img, img_strides[0], img_strides[1], img_strides[2], img_strides[3]};
     const int total = B * h * w;
-    hipLaunchKernelGGL(photo_warp_kernel, dim3(photo_blocks(total)), dim3(kThreads), 0, (hipStream_t)stream, im, src_idx, n_img, depth,
+    hipLaunchKernelGGL(photo_warp_kernel, dim3((int)blocks_of(total)), dim3(kThreads), 0, (hipStream_t)stream, im, src_idx, n_img, depth,
                        depth_strides[0], depth_strides[1], depth_strides[2], depth_idx, n_depth, geo, xg, yg, warped, mask, total, h, w, C);
     MVS_LAUNCH_CHECK("photo_warp");
     return MVSDET_OK;
@@ -460,7 +422,7 @@ extern "C" int mvsdet_photo_warp_bwd_f32(const float* img, const int64_t* img_st
     MVS_REQUIRE(depth_idx || n_depth == B, "photo_warp_bwd: %d depth maps for %d pairs and no index", n_depth, B);
     const PhotoImage im = {img, img_strides[0], img_strides[1], img_strides[2], img_strides[3]};
     const int total = n_depth * h * w;
-    hipLaunchKernelGGL(photo_warp_bwd_kernel, dim3(photo_blocks(total)), dim3(kThreads), 0, (hipStream_t)stream, im, src_idx, n_img, depth,
+    hipLaunchKernelGGL(photo_warp_bwd_kernel, dim3((int)blocks_of(total)), dim3(kThreads), 0, (hipStream_t)stream, im, src_idx, n_img, depth,
                        depth_strides[0], depth_strides[1], depth_strides[2], depth_idx, n_depth, geo, xg, yg, g_warped, grad, total, B, h,
                        w, C);
     MVS_LAUNCH_CHECK("photo_warp_bwd");
@@ -469,7 +431,7 @@ extern "C" int mvsdet_photo_warp_bwd_f32(const float* img, const int64_t* img_st
 
 extern "C" size_t mvsdet_photo_loss_workspace_bytes(int B, int h, int w) {
     if (B <= 0 || h <= 0 || w <= 0) return 0;
-    return (size_t)photo_blocks((long long)B * h * w) * sizeof(PhotoPartial);
+    return (size_t)blocks_of((long long)B * h * w) * sizeof(PhotoPartial);
 }
 
 extern "C" int mvsdet_photo_loss_f32(const float* warped, const float* mask, const float* ref, const int64_t* ref_strides, float* loss,
@@ -478,13 +440,9 @@ extern "C" int mvsdet_photo_loss_f32(const float* warped, const float* mask, con
     if (int rc = check_photo_shape("photo_loss", B, h, w, C)) return rc;
     MVS_REQUIRE(warped && mask && ref && ref_strides && loss && terms && count && workspace, "photo_loss: NULL pointer");
     MVS_REQUIRE(((uintptr_t)workspace & 15) == 0, "photo_loss: workspace must be 16-byte aligned");
-    const size_t need = mvsdet_photo_loss_workspace_bytes(B, h, w);
-    if (workspace_bytes < need) {
-        set_error("photo_loss: workspace %zu < %zu bytes", workspace_bytes, need);
-        return MVSDET_ERR_WORKSPACE;
-    }
+    MVS_REQUIRE_WORKSPACE("photo_loss", workspace_bytes, mvsdet_photo_loss_workspace_bytes(B, h, w));
     const PhotoImage rf = {ref, ref_strides[0], ref_strides[1], ref_strides[2], ref_strides[3]};
-    const int total = B * h * w, nblocks = photo_blocks(total);
+    const int total = B * h * w, nblocks = (int)blocks_of(total);
     PhotoPartial* part = (PhotoPartial*)workspace;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(photo_loss_kernel, dim3(nblocks), dim3(kThreads), 0, st, warped, mask, rf, part, total, h, w, C, simple ? 1 : 0);
@@ -506,7 +464,7 @@ extern "C" int mvsdet_photo_loss_bwd_f32(const float* warped, const float* mask,
     // the weight of one term in L: (1 - alpha) / n0, alpha / n1, alpha / n2; an empty difference term has no element to weigh
     const float k0 = (float)((simple ? 1.0 : 0.5) / n0);
     const float k1 = (simple || n1 <= 0) ? 0.0f : (float)(0.5 / n1), k2 = (simple || n2 <= 0) ? 0.0f : (float)(0.5 / n2);
-    hipLaunchKernelGGL(photo_loss_bwd_kernel, dim3(photo_blocks(total)), dim3(kThreads), 0, (hipStream_t)stream, warped, mask, rf, g_loss,
+    hipLaunchKernelGGL(photo_loss_bwd_kernel, dim3((int)blocks_of(total)), dim3(kThreads), 0, (hipStream_t)stream, warped, mask, rf, g_loss,
                        grad, total, h, w, C, k0, k1, k2);
     MVS_LAUNCH_CHECK("photo_loss_bwd");
     return MVSDET_OK;
@@ -514,7 +472,7 @@ extern "C" int mvsdet_photo_loss_bwd_f32(const float* warped, const float* mask,
 
 extern "C" size_t mvsdet_photo_select_workspace_bytes(int n, int total) {
     if (n <= 0 || total <= 0) return 0;
-    return (size_t)photo_blocks(total) * n * sizeof(int32_t);
+    return (size_t)blocks_of(total) * n * sizeof(int32_t);
 }
 
 extern "C" int mvsdet_photo_select_f32(const float* masks, const float* L, int32_t* wins, float* loss, void* workspace,
@@ -522,12 +480,8 @@ extern "C" int mvsdet_photo_select_f32(const float* masks, const float* L, int32
     MVS_REQUIRE(masks && L && wins && loss && workspace, "photo_select: NULL pointer");
     MVS_REQUIRE(n > 0 && n <= kPhotoMaxScenes, "photo_select: %d scenes (1..%d)", n, kPhotoMaxScenes);
     MVS_REQUIRE(total > 0, "photo_select: bad pixel count %d", total);
-    const size_t need = mvsdet_photo_select_workspace_bytes(n, total);
-    if (workspace_bytes < need) {
-        set_error("photo_select: workspace %zu < %zu bytes", workspace_bytes, need);
-        return MVSDET_ERR_WORKSPACE;
-    }
-    const int nblocks = photo_blocks(total);
+    MVS_REQUIRE_WORKSPACE("photo_select", workspace_bytes, mvsdet_photo_select_workspace_bytes(n, total));
+    const int nblocks = (int)blocks_of(total);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(photo_select_kernel, dim3(nblocks), dim3(kThreads), 0, st, masks, L, (int32_t*)workspace, n, total);
     MVS_LAUNCH_CHECK("photo_select (wins)");

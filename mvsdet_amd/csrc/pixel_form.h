@@ -324,10 +324,7 @@ static PixelGrid pixel_grid(int n_bt, int U) {
 // The backward's start: the workspace holds the packed gradient map, zeroed here for the atomics.
 static int pixel_bwd_prologue(const char* name, void* workspace, size_t workspace_bytes, int N, int C, int H, int W, hipStream_t stream) {
     const size_t pb = mvsdet_plane_sweep_pixel_bwd_workspace_bytes(N, C, H, W);
-    if (workspace_bytes < pb) {
-        set_error("%s: workspace %zu B < %zu B", name, workspace_bytes, pb);
-        return MVSDET_ERR_WORKSPACE;
-    }
+    MVS_REQUIRE_WORKSPACE(name, workspace_bytes, pb);
     MVS_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", name);
     MVS_REQUIRE(N <= 65535 && num_slabs(C) <= 65535, "%s: N or C too large", name);
     if (hipMemsetAsync(workspace, 0, pb, stream) != hipSuccess) {

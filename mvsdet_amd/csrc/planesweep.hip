@@ -432,10 +432,7 @@ extern "C" int mvsdet_plane_sweep_variance_f32(const float* feat, const int64_t*
     MVS_REQUIRE(N > 0 && C > 0 && D > 0 && H > 1 && W > 1, "plane_sweep_variance: bad shape");
     const size_t pb = (mvsdet_packed_bytes(N, C, H, W) + 255) / 256 * 256;
     const size_t sb = mvsdet_plane_sweep_scratch_bytes(N, K, D, H, W);
-    if (workspace_bytes < pb + sb) {
-        set_error("plane_sweep_variance: workspace %zu B < %zu B", workspace_bytes, pb + sb);
-        return MVSDET_ERR_WORKSPACE;
-    }
+    MVS_REQUIRE_WORKSPACE("plane_sweep_variance", workspace_bytes, pb + sb);
     const int64_t fs[4] = {(int64_t)C * H * W, (int64_t)H * W, W, 1};
     int rc = mvsdet_pack_features_f32(feat, fs, (float*)workspace, N, C, H, W, stream);
     if (rc) return rc;

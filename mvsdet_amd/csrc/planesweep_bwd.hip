@@ -478,10 +478,7 @@ extern "C" int mvsdet_plane_sweep_variance_bwd_f32(const float* feat, const int6
     MVS_REQUIRE((size_t)H * W * kSlab < (size_t)INT32_MAX, "plane_sweep_variance_bwd: one slab image exceeds 2^31 elements");
     const size_t pb = (mvsdet_packed_bytes(N, C, H, W) + 255) / 256 * 256;
     const size_t sb = mvsdet_plane_sweep_scratch_bytes(N, K, D, H, W);
-    if (workspace_bytes < 2 * pb + sb) {
-        set_error("plane_sweep_variance_bwd: workspace %zu B < %zu B", workspace_bytes, 2 * pb + sb);
-        return MVSDET_ERR_WORKSPACE;
-    }
+    MVS_REQUIRE_WORKSPACE("plane_sweep_variance_bwd", workspace_bytes, 2 * pb + sb);
     float* packed = (float*)workspace;
     float* gpacked = (float*)((char*)workspace + pb);
     void* scratch = (char*)workspace + 2 * pb;
@@ -507,10 +504,7 @@ extern "C" int mvsdet_plane_sweep_variance_bwd_packed_f32(const float* packed, c
     MVS_REQUIRE(D <= MVSDET_MAX_DEPTH && H < 65535 && W < 65535, "plane_sweep_variance_bwd_packed: D > %d, or H or W > 65534", MVSDET_MAX_DEPTH);
     MVS_REQUIRE((size_t)H * W * kSlab < (size_t)INT32_MAX, "plane_sweep_variance_bwd_packed: one slab image exceeds 2^31 elements");
     const size_t pb = (mvsdet_packed_bytes(N, C, H, W) + 255) / 256 * 256;
-    if (workspace_bytes < pb) {
-        set_error("plane_sweep_variance_bwd_packed: workspace %zu B < %zu B", workspace_bytes, pb);
-        return MVSDET_ERR_WORKSPACE;
-    }
+    MVS_REQUIRE_WORKSPACE("plane_sweep_variance_bwd_packed", workspace_bytes, pb);
     MVS_REQUIRE(K == 0 || table_bytes >= mvsdet_plane_sweep_scratch_bytes(N, K, D, H, W), "plane_sweep_variance_bwd_packed: geometry buffer too small");
     return bwd_launch(packed, nbr, const_cast<void*>(table), g, gfeat, (float*)workspace, pb, N, K, C, D, H, W, (hipStream_t)stream_);
 }

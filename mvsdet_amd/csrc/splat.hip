@@ -18,7 +18,7 @@
 
 #include <climits>
 
-#include "common.h"
+#include "block_reduce.h"
 #include "sh_basis.h"
 
 namespace mvsdet {
@@ -463,12 +463,6 @@ __global__ __launch_bounds__(kThreads) void splat_render_kernel(SplatWs ws, cons
     }
 }
 
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) x += __shfl_xor(x, off, kWave);
-    return x;
-}
-
 __global__ __launch_bounds__(kThreads) void splat_render_bwd_kernel(SplatWs ws, const float* __restrict__ bg, const float* __restrict__ g_image,
                                                                     float* __restrict__ slots, int G, int H, int W, int tiles_x, int tiles) {
     __shared__ float2 s_xy[kBwdBatch];
@@ -548,7 +542,7 @@ __global__ __launch_bounds__(kThreads) void splat_render_bwd_kernel(SplatWs ws, 
             if (__ballot(hit) != 0ull) {
 #pragma unroll
                 for (int k = 0; k < kSlot; ++k) {
-                    const float s = wave_sum(val[k]);
+                    const float s = wave_sum_all(val[k]);
                     if (lane == 0) s_part[wave][j][k] = s;
                 }
             } else if (lane < kSlot) {
@@ -742,10 +736,7 @@ extern "C" int mvsdet_splat_forward_f32(const float* means, const int64_t* means
                 "splat_forward: NULL pointer");
     MVS_REQUIRE(((uintptr_t)workspace & 255) == 0, "splat_forward: the workspace must be 256-byte aligned");
     const SplatWs ws = splat_layout(workspace, V, G, H, W, max_keys);
-    if (workspace_bytes < ws.total) {
-        set_error("splat_forward: workspace of %zu bytes, %zu needed", workspace_bytes, ws.total);
-        return MVSDET_ERR_WORKSPACE;
-    }
+    MVS_REQUIRE_WORKSPACE("splat_forward", workspace_bytes, ws.total);
     const SplatIn in = splat_inputs(means, means_strides, covariances, cov_strides, harmonics, sh_strides, opacities, opacity_stride);
     const hipStream_t st = (hipStream_t)stream;
     const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile, tiles = tiles_x * tiles_y;
@@ -794,10 +785,7 @@ extern "C" int mvsdet_splat_backward_f32(const float* means, const int64_t* mean
                 "splat_backward: NULL pointer");
     MVS_REQUIRE(((uintptr_t)workspace & 255) == 0, "splat_backward: the workspace must be 256-byte aligned");
     const SplatWs ws = splat_layout(workspace, V, G, H, W, max_keys);
-    if (workspace_bytes < ws.total) {
-        set_error("splat_backward: workspace of %zu bytes, %zu needed", workspace_bytes, ws.total);
-        return MVSDET_ERR_WORKSPACE;
-    }
+    MVS_REQUIRE_WORKSPACE("splat_backward", workspace_bytes, ws.total);
     const SplatIn in = splat_inputs(means, means_strides, covariances, cov_strides, harmonics, sh_strides, opacities, opacity_stride);
     const hipStream_t st = (hipStream_t)stream;
     const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile, tiles = tiles_x * tiles_y;

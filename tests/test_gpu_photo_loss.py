@@ -212,6 +212,47 @@ def test_two_runs_give_the_same_bits(gpu, g25):
     assert same_bits(a, b) and np.array_equal(bits(a["terms"]), bits(b["terms"]))
 
 
+@pytest.mark.parametrize("shape", [(1, 10, 25), (1, 16, 16), (3, 13, 21), (1, 257, 256)], ids=lambda s: "x".join(map(str, s)))
+def test_block_counts(gpu, shape):
+    """250 pixels (one partial block), 256 (exactly one), 819 (three and a partial one), 65792 (257 blocks: one thread of the finishing
+    launch adds a run of two partials, and the threads past the last run none): the loss launches alone on LCG images under a mask with
+    holes, both forms, against the float64 restatement.  Count exact; L and each term within bar(0) = 1e-6 relative, the floor this
+    file's bar states: the terms are non-negative fp32 numbers of a few roundings each (differences of magnitude 1 on values below 1.5),
+    added in float64 and rounded to fp32 once."""
+    from mvsdet_amd.ops import photo
+    B, h, w = shape
+    C, n = 3, B * h * w
+    warped, ref = (F32(1.5) * lcg_uniform(n * C, seed + h).reshape(B, h, w, C).astype(F32) for seed in (31, 57))
+    mask = (lcg_uniform(n, 83 + w) > -0.3).astype(F32).reshape(B, h, w, 1)
+    for simple in (False, True):
+        want_L, want_terms, _, _ = R.compute_reconstr_loss(warped, ref, mask, simple)
+        want_count = int((mask != 0).sum())
+        assert 0 < want_count < n
+        L, terms, count = photo.reconstr_loss(dev(warped, gpu), dev(ref, gpu), dev(mask, gpu), simple)
+        L, terms = float(L), terms.cpu().numpy()
+        rel = [abs(L - float(want_L)) / abs(float(want_L))] + [abs(float(t) - float(v)) / abs(float(v)) for t, v in zip(terms, want_terms) if v != 0]
+        print(f"{shape} simple={simple}: count {int(count)} of {n}, L and terms from the restatement {['%.2e' % r for r in rel]} (bar {R.bar(0):.0e})")
+        assert int(count) == want_count
+        assert len(rel) == (2 if simple else 4) and max(rel) <= R.bar(0)
+        assert all(float(t) == 0.0 for t, v in zip(terms, want_terms) if v == 0)
+
+
+def test_single_masked_pixel_in_the_last_partial_block(gpu):
+    """527 pixels: blocks of 256, 256 and 15, the mask on the last pixel alone.  warped 2.5 against ref 0.5: smooth_l1(2) = 1.5 in each
+    of the 3 channels of that pixel (photo), of its left neighbour (d/dx, in the last block too) and of its upper neighbour (d/dy)."""
+    from mvsdet_amd.ops import photo
+    B, h, w, C = 1, 17, 31, 3
+    mask = np.zeros((B, h, w, 1), F32)
+    mask[0, h - 1, w - 1] = 1
+    warped, ref = np.full((B, h, w, C), 2.5, F32), np.full((B, h, w, C), 0.5, F32)
+    m = [F32(4.5 / (B * h * w * C)), F32(4.5 / (B * h * (w - 1) * C)), F32(4.5 / (B * (h - 1) * w * C))]
+    for simple in (False, True):
+        L, terms, count = photo.reconstr_loss(dev(warped, gpu), dev(ref, gpu), dev(mask, gpu), simple)
+        want = [m[0], F32(0), F32(0)] if simple else m
+        assert int(count) == 1 and np.array_equal(bits(terms), bits(np.array(want, F32)))
+        assert F32(L.cpu().numpy()) == (m[0] if simple else F32(0.5) * m[0] + F32(0.5) * (m[1] + m[2]))
+
+
 def test_strided_inputs_give_the_bits_of_contiguous_ones(gpu, g25):
     c = R.g25_case(g25, "small")
     img, depth, ref = dev(c["img"], gpu), dev(c["depth"], gpu), dev(c["ref"], gpu)
