@@ -5,8 +5,10 @@
 The module is plain PyTorch; under autograd every convolution (stride 1, stride 2, transposed, head) uses our forward /
 input-gradient / weight-gradient kernels and BatchNorm + ReLU the streaming kernels of csrc/costreg_bn.hip (training step
 83 ms instead of 858 ms on MIOpen), in eval mode without autograd every layer is
-routed to the fp32-MFMA / streaming HIP kernels of csrc/costreg_conv0.hip and
-csrc/costreg_head.hip (25 ms per scene instead of 59.3 ms at the reference-true shape, same fp32 sums).  Parameter names and shapes equal the reference's
+routed to the HIP kernels: by default the bf16x3 matrix-core kernels of csrc/costreg_bf16.hip, with fp16 + MX products at
+conv0 (csrc/costreg_mx.h), and the streaming head of csrc/costreg_head.hip -- 6.4-6.6 ms per scene instead of 59.3 ms on
+MIOpen at the reference-true shape (README); `matrix_precision = "fp32"` chooses the fp32-MFMA kernels of
+csrc/costreg_conv0.hip instead (25 ms, the same fp32 sums as ATen in another order).  Parameter names and shapes equal the reference's
 (`conv0.conv.weight`, `conv0.bn.*`, ..., `conv9.0.weight`, `conv9.1.*`, `conv11.0.weight`, `conv11.1.*`,
 `prob.weight/bias`), so a reference checkpoint's `cost_regularization.*` entries load with `load_state_dict`
 (tests/test_integration.py compares the outputs with the reference module itself).  D, H, W must be divisible by 4

@@ -69,6 +69,12 @@ constexpr int kXcds = 8;        // MI355X: 8 XCDs, blocks are dealt round-robin 
         }                                   \
     } while (0)
 
+// a helper's refusal (it has set the message) is the caller's
+#define MVS_TRY(call)                           \
+    do {                                        \
+        if (const int rc_ = (call)) return rc_; \
+    } while (0)
+
 #define MVS_LAUNCH_CHECK(name)                                                        \
     do {                                                                              \
         hipError_t e_ = hipGetLastError();                                            \
@@ -77,6 +83,21 @@ constexpr int kXcds = 8;        // MI355X: 8 XCDs, blocks are dealt round-robin 
             return MVSDET_ERR_HIP;                                                    \
         }                                                                             \
     } while (0)
+
+// The one grant of dynamic LDS: a launch that needs more than 48 KiB has the kernel's limit raised to `ceiling`, a constant of the
+// kernel -- never this call's own smaller need, which a second host thread with a larger one could find in force between its own
+// grant and its launch.  On every launch, no "done" flag: the attribute is per device, and a process may drive several.  Host-side
+// state only, nothing is enqueued: safe under stream capture.
+template <class Kernel>
+inline int grant_dynamic_lds(const char* name, Kernel* kernel, size_t need, size_t ceiling) {
+    if (need <= 48 * 1024) return MVSDET_OK;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ceiling) != hipSuccess) {
+        set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed", name);
+        return MVSDET_ERR_HIP;
+    }
+    return MVSDET_OK;
+}
+#define MVS_GRANT_LDS(name, kernel, need, ceiling) MVS_TRY(::mvsdet::grant_dynamic_lds(name, kernel, need, ceiling))
 
 // A caller's buffer of `have` bytes where `need` are needed: the one wording of MVSDET_ERR_WORKSPACE, the operator's name first.
 #define MVS_REQUIRE_WORKSPACE(name, have, need)                                                                        \

@@ -1421,6 +1421,8 @@ __global__ __launch_bounds__(TD * TH * TW * 2 / CG) void convT3d_k3_s2_bf16x3_ke
 using namespace mvsdet;
 
 #include "costreg_mx.h"   // conv0 on one fp16 + two block-scaled FP6 products per fp32-equivalent product (kernels)
+#include "conv_host.h"    // the entry points' argument check, fp32 view, XCD predicate and stride-2 / transposed tile choice
+static_assert(kS2TD == 4 && kS2TH == 8 && kBfW == 16, "s2_tile() chooses between the kernels' 4 x 8 x 16 and 3 x 16 x 8 tiles");
 
 namespace {
 struct BfPlan {
@@ -1529,18 +1531,17 @@ extern "C" int mvsdet_scl_pack_f32(const float* x, const int64_t* xstr, void* xs
     }
     const size_t vol = (size_t)D * H * W;
     dim3 grid((unsigned)((vol + kThreads - 1) / kThreads), (unsigned)C8, (unsigned)N);
-    const long long sN = xstr ? xstr[0] : (long long)C * vol, sC = xstr ? xstr[1] : (long long)vol;
-    const long long sD = xstr ? xstr[2] : (long long)H * W, sH = xstr ? xstr[3] : (long long)W;
-    MVS_REQUIRE(sN >= 0 && sC >= 0 && sD >= 0 && sH >= W, "scl_pack: bad strides");
+    const F32View v = f32_view(xstr, C, D, H, W);
+    MVS_TRY(f32_view_check("scl_pack", v, D, H, W, false));   // 64-bit offsets in both kernels
     if (zero_border == 2) {   // one pass over the padded volume: border voxels get their zeros from the kernel itself
         const size_t volp = (size_t)p.Dp * p.Hp * p.Wp;
         dim3 gridp((unsigned)((volp + kThreads - 1) / kThreads), (unsigned)C8, (unsigned)N);
-        hipLaunchKernelGGL(scl_pack_padded_kernel, gridp, dim3(kThreads), 0, st, x, sN, sC, sD, sH, static_cast<uint4*>(xs), C, C8, D,
-                           H, W, p.Dp, p.Hp, p.Wp, piece);
+        hipLaunchKernelGGL(scl_pack_padded_kernel, gridp, dim3(kThreads), 0, st, x, v.sN, v.sC, v.sD, v.sH, static_cast<uint4*>(xs), C,
+                           C8, D, H, W, p.Dp, p.Hp, p.Wp, piece);
         MVS_LAUNCH_CHECK("scl_pack");
         return MVSDET_OK;
     }
-    hipLaunchKernelGGL(scl_pack_kernel, grid, dim3(kThreads), 0, st, x, sN, sC, sD, sH, static_cast<uint4*>(xs), C, C8, D, H, W,
+    hipLaunchKernelGGL(scl_pack_kernel, grid, dim3(kThreads), 0, st, x, v.sN, v.sC, v.sD, v.sH, static_cast<uint4*>(xs), C, C8, D, H, W,
                        p.Dp, p.Hp, p.Wp, piece);
     MVS_LAUNCH_CHECK("scl_pack");
     return MVSDET_OK;
@@ -1655,12 +1656,8 @@ static int launch_bf16x3(const char* name, const void* xs, const float* xf, cons
                          const float* scale, const float* shift, const float* residual, float* out, void* out_scl, void* out_pscl,
                          int N, int Cin, int Cout, int D, int H, int W, int relu, mvsdet_stream_t stream, void* workspace = nullptr,
                          size_t workspace_bytes = 0, void* stats = nullptr, size_t stats_bytes = 0, const float* stats_pivot = nullptr) {
-    MVS_REQUIRE((xs || xf) && weight_split && (out || out_scl || out_pscl), "%s: NULL pointer", name);
-    MVS_REQUIRE((scale == nullptr) == (shift == nullptr), "%s: scale and shift come together", name);
-    MVS_REQUIRE(N > 0 && Cin > 0 && D > 0 && H > 0 && W > 0, "%s: bad shape N=%d Cin=%d D=%d H=%d W=%d", name, N, Cin, D, H, W);
-    MVS_REQUIRE(Cout > 0 && Cout % 64 == 0, "%s: Cout=%d must be a multiple of 64", name, Cout);
-    MVS_REQUIRE((((uintptr_t)xs | (uintptr_t)weight_split | (uintptr_t)out_scl | (uintptr_t)out_pscl) & 15u) == 0,
-                "%s: SCL buffers and weights must be 16-byte aligned", name);
+    MVS_TRY(conv_check_args(name, (xs || xf) && weight_split && (out || out_scl || out_pscl), scale, shift, N, Cin, Cout, D, H, W,
+                            (uintptr_t)xs | (uintptr_t)weight_split | (uintptr_t)out_scl | (uintptr_t)out_pscl));
     const BfPlan p = bf_plan_tile(D, H, W, xf != nullptr);
     const int C8 = (Cin + 7) / 8;
     MVS_REQUIRE((size_t)p.Dp * p.Hp * p.Wp < ((size_t)1 << 31), "%s: one padded channel-group volume exceeds 2^31 voxels", name);
@@ -1677,31 +1674,24 @@ static int launch_bf16x3(const char* name, const void* xs, const float* xf, cons
                     "%s: the statistics buffer holds Cout x mvsdet_conv3d_k3_bf16x3_stats_parts double2", name);
     }
     MVS_REQUIRE((long long)N * (Cout / 64) * nsplit <= 65535 && p.tiles_d <= 65535, "%s: N*Cout/64 or D too large", name);
-    const long long sN = xstr ? xstr[0] : (long long)Cin * vol, sC = xstr ? xstr[1] : (long long)vol;
-    const long long sD = xstr ? xstr[2] : (long long)H * W, sH = xstr ? xstr[3] : (long long)W;
-    if (xf) {
-        MVS_REQUIRE(sN >= 0 && sC >= 0 && sD >= 0 && sH >= W, "%s: bad strides", name);
-        MVS_REQUIRE((long long)(D - 1) * sD + (long long)(H - 1) * sH + W < (1LL << 31), "%s: one channel volume spans more than 2^31 elements", name);
-    }
+    const F32View v = f32_view(xstr, Cin, D, H, W);
+    if (xf) MVS_TRY(f32_view_check(name, v, D, H, W, true));
     const size_t piece = (size_t)N * C8 * p.Dp * p.Hp * p.Wp;
     const BfOut dst = make_out(out, out_scl, out_pscl, N, Cout, D, H, W);
     dim3 grid((unsigned)(p.tiles_w * p.tiles_h), (unsigned)p.tiles_d, (unsigned)(N * (Cout / 64) * nsplit));
-    const int xcd_map = options().conv_xcd != 0 && ((long long)grid.x * grid.y * grid.z) % 8 == 0 && (long long)grid.x * grid.y * grid.z >= 64;
+    const int xcd_map = conv_xcd_map(grid);
     hipStream_t st = (hipStream_t)stream;
-#define MVS_BF_CASE(TD_, TH_, F32_, TW_, SUBP_, CGN_)                                                                       \
-    {                                                                                                                       \
-        auto* k = conv3d_k3_bf16x3_kernel<TD_, TH_, F32_, TW_, SUBP_, CGN_>;                                                \
-        const size_t lds = bf_lds_bytes(TD_, TH_, TW_, SUBP_);                                                              \
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=  \
-            hipSuccess) {                                                                                                   \
-            set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed", name);                                  \
-            return MVSDET_ERR_HIP;                                                                                          \
-        }                                                                                                                   \
-        hipLaunchKernelGGL(k, grid, dim3(TD_ * TH_ * TW_ * 4 / CGN_), lds, st, static_cast<const uint4*>(xs), xf, sN, sC, sD, sH, \
-                           Cin, static_cast<const uint4*>(weight_split), scale, shift, residual, dst, C8, Cout, D, H, W,    \
-                           p.Dp, p.Hp, p.Wp, piece, p.tiles_w, relu, nsplit, static_cast<float*>(workspace), total, xcd_map,         \
-                           static_cast<double2*>(stats), stats_pivot);                                                      \
-    }
+    // the LDS of an instantiation follows from its template parameters: need = ceiling
+    const auto launch = [&](auto* k, int threads, size_t lds) -> int {
+        MVS_GRANT_LDS(name, k, lds, lds);
+        hipLaunchKernelGGL(k, grid, dim3(threads), lds, st, static_cast<const uint4*>(xs), xf, v.sN, v.sC, v.sD, v.sH, Cin,
+                           static_cast<const uint4*>(weight_split), scale, shift, residual, dst, C8, Cout, D, H, W, p.Dp, p.Hp, p.Wp,
+                           piece, p.tiles_w, relu, nsplit, static_cast<float*>(workspace), total, xcd_map, static_cast<double2*>(stats),
+                           stats_pivot);
+        return MVSDET_OK;
+    };
+#define MVS_BF_CASE(TD_, TH_, F32_, TW_, SUBP_, CGN_) \
+    { MVS_TRY(launch(conv3d_k3_bf16x3_kernel<TD_, TH_, F32_, TW_, SUBP_, CGN_>, TD_ * TH_ * TW_ * 4 / CGN_, bf_lds_bytes(TD_, TH_, TW_, SUBP_))); }
     // One kernel per (input form, tile): weight sub-stages of 3 k-steps (SUBP 6) and waves of 64 voxels (CGN 4), except
     //   * the 3 x 16 x 8 tile on 12 waves of 32 voxels (CGN 2) instead of 6 of 64, which sit 2/2/1/1 on the four SIMDs;
     //   * the fp32-input 4 x 12 x 16 tile (the cost network's first layer) with two sub-stages of 4 + 3 k-steps (SUBP 8) instead of
@@ -1772,8 +1762,7 @@ extern "C" int mvsdet_conv3d_k3_bf16x3_stats(const void* xs, const float* x, con
 extern "C" size_t mvsdet_conv3d_k3_s2_bf16x3_workspace_bytes(int N, int Cin, int Cout, int Di, int Hi, int Wi) {
     if (N <= 0 || Cin <= 0 || Cout <= 0 || Cout % 64 || Di <= 0 || Hi <= 0 || Wi <= 0) return 0;
     const int D = (Di - 1) / 2 + 1, H = (Hi - 1) / 2 + 1, W = (Wi - 1) / 2 + 1;
-    const long long tiles = (long long)((W + kBfW - 1) / kBfW) * ((H + kS2TH - 1) / kS2TH) * ((D + kS2TD - 1) / kS2TD);
-    const int ns = bf_nsplit(tiles * N * (Cout / 64), (Cin + 7) / 8);
+    const int ns = bf_nsplit(s2_tile(D, H, W).tiles416 * N * (Cout / 64), (Cin + 7) / 8);
     return ns > 1 ? (size_t)ns * N * Cout * D * H * W * sizeof(float) : 0;
 }
 
@@ -1782,63 +1771,43 @@ static int launch_s2_bf16x3(const float* x, const int64_t* x_strides, const void
                             int Cout, int Di, int Hi, int Wi, int relu, mvsdet_stream_t stream) {
     const char* name = x_pscl ? "conv3d_k3_s2_bf16x3 (PSCL input)" : "conv3d_k3_s2_bf16x3_f32in";
     MVS_REQUIRE((x == nullptr) != (x_pscl == nullptr), "conv3d_k3_s2_bf16x3: exactly one of x (fp32) and x_pscl");
-    MVS_REQUIRE(weight_split && (out || out_scl), "%s: NULL pointer", name);
-    MVS_REQUIRE((scale == nullptr) == (shift == nullptr), "%s: scale and shift come together", name);
-    MVS_REQUIRE(N > 0 && Cin > 0 && Di > 0 && Hi > 0 && Wi > 0, "%s: bad shape N=%d Cin=%d D=%d H=%d W=%d", name, N, Cin, Di, Hi, Wi);
-    MVS_REQUIRE(Cout > 0 && Cout % 64 == 0, "%s: Cout=%d must be a multiple of 64", name, Cout);
-    MVS_REQUIRE((((uintptr_t)weight_split | (uintptr_t)x_pscl | (uintptr_t)out_scl) & 15u) == 0, "%s: SCL buffers and weights must be 16-byte aligned", name);
+    MVS_TRY(conv_check_args(name, weight_split && (out || out_scl), scale, shift, N, Cin, Cout, Di, Hi, Wi,
+                            (uintptr_t)weight_split | (uintptr_t)x_pscl | (uintptr_t)out_scl));
     const int D = (Di - 1) / 2 + 1, H = (Hi - 1) / 2 + 1, W = (Wi - 1) / 2 + 1;
-    const size_t ivol = (size_t)Di * Hi * Wi;
-    const long long sN = x_strides ? x_strides[0] : (long long)Cin * ivol, sC = x_strides ? x_strides[1] : (long long)ivol;
-    const long long sD = x_strides ? x_strides[2] : (long long)Hi * Wi, sH = x_strides ? x_strides[3] : (long long)Wi;
-    if (x) {
-        MVS_REQUIRE(sN >= 0 && sC >= 0 && sD >= 0 && sH >= Wi, "%s: bad strides", name);
-        MVS_REQUIRE((long long)(Di - 1) * sD + (long long)(Hi - 1) * sH + Wi < (1LL << 31), "%s: one channel volume spans more than 2^31 elements", name);
-    }
-    // output tile 4 x 8 x 16 or 3 x 16 x 8, whichever pads (D, H, W) less; the number of splits follows from the former
-    const long long tiles416 = (long long)((W + kBfW - 1) / kBfW) * ((H + kS2TH - 1) / kS2TH) * ((D + kS2TD - 1) / kS2TD);
-    const long long pad416 = tiles416 * (kS2TD * kS2TH * kBfW);
-    const long long tiles38 = (long long)((W + 7) / 8) * ((H + 15) / 16) * ((D + 2) / 3), pad38 = tiles38 * (3 * 16 * 8);
-    const bool t38 = pad38 < pad416;
-    const int ttd = t38 ? 3 : kS2TD, tth = t38 ? 16 : kS2TH, ttw = t38 ? 8 : kBfW;
-    const int tiles_w = (W + ttw - 1) / ttw, tiles_h = (H + tth - 1) / tth, tiles_d = (D + ttd - 1) / ttd;
+    const F32View v = f32_view(x_strides, Cin, Di, Hi, Wi);
+    if (x) MVS_TRY(f32_view_check(name, v, Di, Hi, Wi, true));
+    const S2Tile t = s2_tile(D, H, W);   // over the output
     const size_t total = (size_t)N * Cout * D * H * W;
-    int nsplit = bf_nsplit(tiles416 * N * (Cout / 64), (Cin + 7) / 8);
+    int nsplit = bf_nsplit(t.tiles416 * N * (Cout / 64), (Cin + 7) / 8);
     if (!workspace || workspace_bytes < (size_t)nsplit * total * sizeof(float) || out_scl) nsplit = 1;   // unsplit without (enough) workspace
     MVS_REQUIRE(nsplit == 1 || out, "%s: the split form needs the fp32 output", name);
-    MVS_REQUIRE((long long)N * (Cout / 64) * nsplit <= 65535 && tiles_d <= 65535, "%s: N*Cout/64 or D too large", name);
+    MVS_REQUIRE((long long)N * (Cout / 64) * nsplit <= 65535 && t.tiles_d <= 65535, "%s: N*Cout/64 or D too large", name);
     int cDp = 0, cHp = 0, cWp = 0;
     pscl_dims(Di, Hi, Wi, cDp, cHp, cWp);
-    MVS_REQUIRE(!x_pscl || (tiles_d * ttd + 2 <= cDp && tiles_h * tth + 2 <= cHp && tiles_w * ttw + 2 <= cWp),
+    MVS_REQUIRE(!x_pscl || (t.tiles_d * t.td + 2 <= cDp && t.tiles_h * t.th + 2 <= cHp && t.tiles_w * t.tw + 2 <= cWp),
                 "%s: the PSCL padding does not cover the tiles", name);
     const int C8 = (Cin + 7) / 8;
     const size_t cpiece = (size_t)8 * N * C8 * cDp * cHp * cWp;
     const BfOut dst = make_out(out, out_scl, nullptr, N, Cout, D, H, W);
-    dim3 grid((unsigned)(tiles_w * tiles_h), (unsigned)tiles_d, (unsigned)(N * (Cout / 64) * nsplit));
-#define MVS_S2_CASE(TD_, TH_, TW_, PIN_, CG_, OB_)                                                                           \
-    {                                                                                                                        \
-        auto* k = conv3d_k3_s2_bf16x3_kernel<TD_, TH_, TW_, PIN_, CG_, OB_>;                                                 \
-        const size_t lds = s2_lds_bytes(TD_, TH_, TW_, OB_);                                                                 \
-        grid.z = (unsigned)(N * (Cout / (64 * OB_)) * nsplit);                                                               \
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=   \
-            hipSuccess) {                                                                                                    \
-            set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed", name);                                   \
-            return MVSDET_ERR_HIP;                                                                                           \
-        }                                                                                                                    \
-        hipLaunchKernelGGL(k, grid, dim3(TD_ * TH_ * TW_ * 2 / CG_), lds, (hipStream_t)stream, x, sN, sC, sD, sH, Cin,       \
-                           static_cast<const uint4*>(x_pscl), cDp, cHp, cWp, cpiece, N,                                      \
-                           static_cast<const uint4*>(weight_split), scale, shift, dst, C8, Cout, Di, Hi, Wi, D, H, W,        \
-                           tiles_w, relu, nsplit, static_cast<float*>(workspace), total,                                     \
-                           (int)(options().conv_xcd != 0 && ((long long)grid.x * grid.y * grid.z) % 8 == 0 &&                \
-                                 (long long)grid.x * grid.y * grid.z >= 64));                                                \
-    }
+    // `ob`: blocks of 64 output channels that one block of the grid computes
+    const auto launch = [&](auto* k, int threads, size_t lds, int ob) -> int {
+        dim3 grid((unsigned)(t.tiles_w * t.tiles_h), (unsigned)t.tiles_d, (unsigned)(N * (Cout / (64 * ob)) * nsplit));
+        MVS_GRANT_LDS(name, k, lds, lds);
+        hipLaunchKernelGGL(k, grid, dim3(threads), lds, (hipStream_t)stream, x, v.sN, v.sC, v.sD, v.sH, Cin,
+                           static_cast<const uint4*>(x_pscl), cDp, cHp, cWp, cpiece, N, static_cast<const uint4*>(weight_split), scale,
+                           shift, dst, C8, Cout, Di, Hi, Wi, D, H, W, t.tiles_w, relu, nsplit, static_cast<float*>(workspace), total,
+                           conv_xcd_map(grid));
+        return MVSDET_OK;
+    };
+#define MVS_S2_CASE(TD_, TH_, TW_, PIN_, CG_, OB_) \
+    { MVS_TRY(launch(conv3d_k3_s2_bf16x3_kernel<TD_, TH_, TW_, PIN_, CG_, OB_>, TD_ * TH_ * TW_ * 2 / CG_, s2_lds_bytes(TD_, TH_, TW_, OB_), OB_)); }
     // The 3 x 16 x 8 tile runs on 12 waves of one column group (against 6 waves of two: conv1 0.573 -> 0.563, conv3 0.304 -> 0.291 ms;
     // two 6-wave blocks already share a CU here), with 128 output channels per block where the layer has them and is not split;
     // the 4 x 8 x 16 tile on 8 waves of two column groups.  The PSCL-fed and the fp32-fed (training, the neck) kernels alike.
 #define MVS_S2_TILE(PIN_)                                                                                                    \
     {                                                                                                                        \
-        if (t38 && Cout % 128 == 0 && nsplit == 1) MVS_S2_CASE(3, 16, 8, PIN_, 1, 2)                                         \
-        else if (t38) MVS_S2_CASE(3, 16, 8, PIN_, 1, 1)                                                                      \
+        if (t.t38 && Cout % 128 == 0 && nsplit == 1) MVS_S2_CASE(3, 16, 8, PIN_, 1, 2)                                       \
+        else if (t.t38) MVS_S2_CASE(3, 16, 8, PIN_, 1, 1)                                                                    \
         else MVS_S2_CASE(kS2TD, kS2TH, kBfW, PIN_, 2, 1)                                                                     \
     }
     if (x_pscl) MVS_S2_TILE(true) else MVS_S2_TILE(false)
@@ -1868,74 +1837,49 @@ extern "C" int mvsdet_conv3d_k3_s2_bf16x3_io(const float* x, const int64_t* x_st
 // added last] of mvsnet.py:92-100,110-111 on the bf16 matrix cores, three-term split.  xs: SCL form of the input (N,Cin,D,H,W)
 // (mvsdet_scl_pack_f32 or a producing layer's out_scl); weight_split: mvsdet_split_conv_weight_ordered(order = 2) of the
 // (Cin,Cout,3,3,3) weight; out_f32 / residual (N,Cout,2D,2H,2W) fp32, 8-byte aligned; out_scl: the SCL form of the result.
-static bool convT_tile38(int D, int H, int W) {
-    const long long pad416 = (long long)((W + kBfW - 1) / kBfW) * kBfW * ((H + kS2TH - 1) / kS2TH) * kS2TH * ((D + kS2TD - 1) / kS2TD) * kS2TD;
-    const long long pad38 = (long long)((W + 7) / 8) * 8 * ((H + 15) / 16) * 16 * ((D + 2) / 3) * 3;
-    return pad38 < pad416;
-}
-
 static int launch_convT(const void* xs, const void* weight_split, const float* scale, const float* shift, const float* residual,
                         float* out, void* out_scl, int N, int Cin, int Cout, int D, int H, int W, int relu, mvsdet_stream_t stream,
                         void* stats = nullptr, size_t stats_bytes = 0, const float* stats_pivot = nullptr) {
     const char* name = "convT3d_k3_s2_bf16x3";
-    MVS_REQUIRE(xs && weight_split && (out || out_scl), "%s: NULL pointer", name);
-    MVS_REQUIRE((scale == nullptr) == (shift == nullptr), "%s: scale and shift come together", name);
-    MVS_REQUIRE(N > 0 && Cin > 0 && D > 0 && H > 0 && W > 0, "%s: bad shape N=%d Cin=%d D=%d H=%d W=%d", name, N, Cin, D, H, W);
-    MVS_REQUIRE(Cout > 0 && Cout % 64 == 0, "%s: Cout=%d must be a multiple of 64", name, Cout);
-    MVS_REQUIRE((((uintptr_t)xs | (uintptr_t)weight_split | (uintptr_t)out_scl) & 15u) == 0, "%s: SCL buffers and weights must be 16-byte aligned", name);
-    MVS_REQUIRE(((uintptr_t)out & 7u) == 0 && (residual == nullptr || ((uintptr_t)residual & 7u) == 0),
-                "%s: out and residual must be 8-byte aligned", name);
+    MVS_TRY(conv_check_args(name, xs && weight_split && (out || out_scl), scale, shift, N, Cin, Cout, D, H, W,
+                            (uintptr_t)xs | (uintptr_t)weight_split | (uintptr_t)out_scl));
+    MVS_CONV_ALIGNED8(name, out, residual);
     const BfPlan p = bf_plan(D, H, W);   // the padded extents of the SCL input
     const int C8 = (Cin + 7) / 8;
-    // input tile 4 x 8 x 16, or 3 x 16 x 8 where that pads (D, H, W) less
-    const bool t38 = convT_tile38(D, H, W);
-    const int ttd = t38 ? 3 : kS2TD, tth = t38 ? 16 : kS2TH, ttw = t38 ? 8 : kBfW;
-    const int tiles_w = (W + ttw - 1) / ttw, tiles_h = (H + tth - 1) / tth, tiles_d = (D + ttd - 1) / ttd;
+    const S2Tile t = s2_tile(D, H, W);   // over the input
     // the halo tile reaches one voxel past the last tile: padded index tiles*T + 1 must exist
-    MVS_REQUIRE(tiles_d * ttd + 2 <= p.Dp && tiles_h * tth + 2 <= p.Hp && tiles_w * ttw + 2 <= p.Wp,
+    MVS_REQUIRE(t.tiles_d * t.td + 2 <= p.Dp && t.tiles_h * t.th + 2 <= p.Hp && t.tiles_w * t.tw + 2 <= p.Wp,
                 "%s: the SCL padding does not cover the tiles", name);
-    MVS_REQUIRE((long long)N * (Cout / 64) <= 65535 && tiles_d <= 65535, "%s: N*Cout/64 or D too large", name);
+    MVS_REQUIRE((long long)N * (Cout / 64) <= 65535 && t.tiles_d <= 65535, "%s: N*Cout/64 or D too large", name);
     const size_t piece = (size_t)N * C8 * p.Dp * p.Hp * p.Wp;
     const BfOut dst = make_out(out, out_scl, nullptr, N, Cout, 2 * D, 2 * H, 2 * W);
-    dim3 grid((unsigned)(tiles_w * tiles_h * 4), (unsigned)tiles_d, (unsigned)(N * (Cout / 64)));
     hipStream_t st = (hipStream_t)stream;
-#define MVS_CT_CASE(TD_, TH_, TW_, CG_)                                                                                      \
-    {                                                                                                                        \
-        const size_t lds = ct_lds_bytes(TD_, TH_, TW_, CG_);                                                                 \
-        auto* k = convT3d_k3_s2_bf16x3_kernel<TD_, TH_, TW_, CG_>;                                                           \
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=   \
-            hipSuccess) {                                                                                                    \
-            set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed", name);                                   \
-            return MVSDET_ERR_HIP;                                                                                           \
-        }                                                                                                                    \
-        hipLaunchKernelGGL(k, grid, dim3(TD_ * TH_ * TW_ * 2 / CG_), lds, st, static_cast<const uint4*>(xs),                 \
-                           static_cast<const uint4*>(weight_split), scale, shift, residual, dst, C8, Cout, D, H, W, p.Dp, p.Hp, \
-                           p.Wp, piece, tiles_w, relu);                                                                      \
-    }
     // the 3 x 16 x 8 tile: all eight output parity classes in one block of 32 output channels (against one block per (PD, PH):
     // conv9 0.40 -> 0.30, conv11 0.66 -> 0.48 ms, the same bits); the 4 x 8 x 16 tile: one block per (PD, PH), 8 waves of two column groups
     if (stats) {
-        MVS_REQUIRE(t38, "%s: the statistics epilogue exists in the all-classes kernel on 3 x 16 x 8 tiles only (mvsdet_convT3d_k3_s2_bf16x3_stats_parts = 0 otherwise)", name);
+        MVS_REQUIRE(t.t38, "%s: the statistics epilogue exists in the all-classes kernel on 3 x 16 x 8 tiles only (mvsdet_convT3d_k3_s2_bf16x3_stats_parts = 0 otherwise)", name);
         MVS_REQUIRE(!scale && !residual && !relu && out && !out_scl, "%s: statistics are those of the raw fp32 output", name);
-        MVS_REQUIRE(stats_bytes >= (size_t)Cout * N * tiles_w * tiles_h * tiles_d * sizeof(double2) && ((uintptr_t)stats & 15u) == 0,
+        MVS_REQUIRE(stats_bytes >= (size_t)Cout * N * t.tiles * sizeof(double2) && ((uintptr_t)stats & 15u) == 0,
                     "%s: the statistics buffer holds Cout x mvsdet_convT3d_k3_s2_bf16x3_stats_parts double2", name);
     }
-    if (t38) {
+    if (t.t38) {
         const size_t lds = ctf_lds_bytes(3, 16, 8);
         auto* k = stats ? convT3d_k3_s2_bf16x3_fused_kernel<3, 16, 8, true> : convT3d_k3_s2_bf16x3_fused_kernel<3, 16, 8, false>;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed", name);
-            return MVSDET_ERR_HIP;
-        }
+        MVS_GRANT_LDS(name, k, lds, lds);
         MVS_REQUIRE((long long)N * (Cout / 32) <= 65535, "%s: N*Cout/32 too large", name);
-        dim3 fgrid((unsigned)(tiles_w * tiles_h), (unsigned)tiles_d, (unsigned)(N * (Cout / 32)));
-        hipLaunchKernelGGL(k, fgrid, dim3(3 * 16 * 8 * 2), lds, st, static_cast<const uint4*>(xs), static_cast<const uint4*>(weight_split),
-                           scale, shift, residual, dst, C8, Cout, D, H, W, p.Dp, p.Hp, p.Wp, piece, tiles_w, relu,
-                           (int)(options().conv_xcd != 0 && ((long long)fgrid.x * fgrid.y * fgrid.z) % 8 == 0 &&
-                                 (long long)fgrid.x * fgrid.y * fgrid.z >= 64),
+        dim3 grid((unsigned)(t.tiles_w * t.tiles_h), (unsigned)t.tiles_d, (unsigned)(N * (Cout / 32)));
+        hipLaunchKernelGGL(k, grid, dim3(3 * 16 * 8 * 2), lds, st, static_cast<const uint4*>(xs), static_cast<const uint4*>(weight_split),
+                           scale, shift, residual, dst, C8, Cout, D, H, W, p.Dp, p.Hp, p.Wp, piece, t.tiles_w, relu, conv_xcd_map(grid),
                            static_cast<double2*>(stats), stats_pivot);
-    } else MVS_CT_CASE(kS2TD, kS2TH, kBfW, 2)
-#undef MVS_CT_CASE
+    } else {
+        const size_t lds = ct_lds_bytes(kS2TD, kS2TH, kBfW, 2);
+        auto* k = convT3d_k3_s2_bf16x3_kernel<kS2TD, kS2TH, kBfW, 2>;
+        MVS_GRANT_LDS(name, k, lds, lds);
+        dim3 grid((unsigned)(t.tiles_w * t.tiles_h * 4), (unsigned)t.tiles_d, (unsigned)(N * (Cout / 64)));
+        hipLaunchKernelGGL(k, grid, dim3(kS2TD * kS2TH * kBfW * 2 / 2), lds, st, static_cast<const uint4*>(xs),
+                           static_cast<const uint4*>(weight_split), scale, shift, residual, dst, C8, Cout, D, H, W, p.Dp, p.Hp, p.Wp, piece,
+                           t.tiles_w, relu);
+    }
     MVS_LAUNCH_CHECK(name);
     return MVSDET_OK;
 }
@@ -1945,8 +1889,8 @@ static int launch_convT(const void* xs, const void* weight_split, const float* s
 // block; parts = mvsdet_convT3d_k3_s2_bf16x3_stats_parts(N, D, H, W) of the COARSE input extents, 0 = this shape has no such form).
 extern "C" size_t mvsdet_convT3d_k3_s2_bf16x3_stats_parts(int N, int D, int H, int W) {
     if (N <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-    if (!convT_tile38(D, H, W)) return 0;
-    return (size_t)N * ((W + 7) / 8) * ((H + 15) / 16) * ((D + 2) / 3);
+    const S2Tile t = s2_tile(D, H, W);
+    return t.t38 ? (size_t)N * t.tiles : 0;
 }
 
 extern "C" int mvsdet_convT3d_k3_s2_bf16x3_stats(const void* xs, const void* weight_split, float* out_f32, void* stats, size_t stats_bytes,
@@ -1999,9 +1943,9 @@ extern "C" int mvsdet_split_conv_weight_mx(const float* weight, void* weight_spl
 // Larger or interleaved views: the bf16x3 kernels (64-bit channel offsets, no pad-channel loads) are the entry point to use.
 extern "C" int mvsdet_conv3d_k3_fp16mx_ok(int N, int Cin, int D, int H, int W, const int64_t* x_strides) {
     if (N <= 0 || Cin <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-    const long long sC = x_strides ? x_strides[1] : (long long)D * H * W;
-    const long long sD = x_strides ? x_strides[2] : (long long)H * W, sH = x_strides ? x_strides[3] : (long long)W;
-    if ((x_strides && x_strides[0] < 0) || sC < 0 || sD < 0 || sH < W) return 0;
+    const F32View v = f32_view(x_strides, Cin, D, H, W);
+    if (!f32_view_ok(v, W)) return 0;
+    const long long sC = v.sC, sD = v.sD, sH = v.sH;
     // strides and extents below 2^31: each product below 2^62, their sum (in elements) below 2^63 + 2^31 -- inside 64 bits; it is
     // bounded to 2^30 elements before it is scaled to bytes
     if (sC >= (1LL << 31) || sD >= (1LL << 31) || sH >= (1LL << 31)) return 0;
@@ -2018,11 +1962,8 @@ extern "C" int mvsdet_conv3d_k3_fp16mx_f32in(const float* x, const int64_t* x_st
                                              const float* shift, float* out_f32, void* out_scl, void* out_pscl, int N, int Cin, int Cout,
                                              int D, int H, int W, int relu, mvsdet_stream_t stream) {
     const char* name = "conv3d_k3_fp16mx_f32in";
-    MVS_REQUIRE(x && weight_split_mx && (out_f32 || out_scl || out_pscl), "%s: NULL pointer", name);
-    MVS_REQUIRE((scale == nullptr) == (shift == nullptr), "%s: scale and shift come together", name);
-    MVS_REQUIRE(N > 0 && Cin > 0 && D > 0 && H > 0 && W > 0, "%s: bad shape N=%d Cin=%d D=%d H=%d W=%d", name, N, Cin, D, H, W);
-    MVS_REQUIRE(Cout > 0 && Cout % 64 == 0, "%s: Cout=%d must be a multiple of 64", name, Cout);
-    MVS_REQUIRE((((uintptr_t)weight_split_mx | (uintptr_t)out_scl | (uintptr_t)out_pscl) & 15u) == 0, "%s: SCL buffers and weights must be 16-byte aligned", name);
+    MVS_TRY(conv_check_args(name, x && weight_split_mx && (out_f32 || out_scl || out_pscl), scale, shift, N, Cin, Cout, D, H, W,
+                            (uintptr_t)weight_split_mx | (uintptr_t)out_scl | (uintptr_t)out_pscl));
     // option "conv_mx_th": 0 (default) = the wave-specialised kernel (4 x 8 x 16 tiles: 8 multiplying + 4 staging waves: 3.89 ms at conv0);
     // 8 = every wave does everything on 4 x 8 x 16 tiles (8 waves: the kernel wants ~190 registers per lane, which two waves per SIMD
     // have: 4.02); 12 = the same on 4 x 12 x 16 tiles (12 waves, 168 registers: spills, 4.1-4.7).  Same values bit for bit.
@@ -2030,39 +1971,26 @@ extern "C" int mvsdet_conv3d_k3_fp16mx_f32in(const float* x, const int64_t* x_st
     const int mx_form = options().conv_mx_th;
     if (mx_form != 12) { p.th = 8; p.tiles_h = (H + 7) / 8; }
     const int C8 = (Cin + 7) / 8;
-    const size_t vol = (size_t)D * H * W;
     MVS_REQUIRE((long long)N * (Cout / 64) <= 65535 && p.tiles_d <= 65535, "%s: N*Cout/64 or D too large", name);
-    const long long sN = x_strides ? x_strides[0] : (long long)Cin * vol, sC = x_strides ? x_strides[1] : (long long)vol;
-    const long long sD = x_strides ? x_strides[2] : (long long)H * W, sH = x_strides ? x_strides[3] : (long long)W;
-    MVS_REQUIRE(sN >= 0 && sC >= 0 && sD >= 0 && sH >= W, "%s: bad strides", name);
+    const F32View v = f32_view(x_strides, Cin, D, H, W);
+    MVS_TRY(f32_view_check(name, v, D, H, W, false));   // the span: mvsdet_conv3d_k3_fp16mx_ok, below
     MVS_REQUIRE(mvsdet_conv3d_k3_fp16mx_ok(N, Cin, D, H, W, x_strides), "%s: the view (Cin=%d, strides %lld %lld %lld %lld) spans 4 GiB or "
-                "more, or interleaves its channels: beyond the kernel's 32-bit buffer offsets (mvsdet_conv3d_k3_fp16mx_ok; use the bf16x3 kernel)", name, Cin, sN, sC, sD, sH);
+                "more, or interleaves its channels: beyond the kernel's 32-bit buffer offsets (mvsdet_conv3d_k3_fp16mx_ok; use the bf16x3 kernel)", name, Cin, v.sN, v.sC, v.sD, v.sH);
     const BfOut dst = make_out(out_f32, out_scl, out_pscl, N, Cout, D, H, W);
     dim3 grid((unsigned)(p.tiles_w * p.tiles_h), (unsigned)p.tiles_d, (unsigned)(N * (Cout / 64)));
-    const int xcd_map = options().conv_xcd != 0 && ((long long)grid.x * grid.y * grid.z) % 8 == 0 && (long long)grid.x * grid.y * grid.z >= 64;
+    const int xcd_map = conv_xcd_map(grid);
     hipStream_t st = (hipStream_t)stream;
-#define MVS_MX_CASE(TH_)                                                                                                     \
-    {                                                                                                                        \
-        auto* k = conv3d_k3_fp16mx_kernel<4, TH_>;                                                                      \
-        const size_t lds = ((size_t)2 * 2 * bf_in_slots(4, TH_, kBfW) + 2 * kMxSlots * 64) * 16;                             \
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-            set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed", name);                                  \
-            return MVSDET_ERR_HIP;                                                                                           \
-        }                                                                                                                    \
-        hipLaunchKernelGGL(k, grid, dim3(4 * TH_ * 16), lds, st, x, sN, sC, sD, sH, Cin, static_cast<const uint4*>(weight_split_mx), \
-                           scale, shift, dst, C8, Cout, D, H, W, p.tiles_w, relu, xcd_map);                                  \
-    }
-    if (mx_form == 0) {
-        auto* k = conv3d_k3_fp16mx_ws_kernel<4, 8>;
-        const size_t lds = ((size_t)2 * 2 * bf_in_slots(4, 8, kBfW) + 2 * kMxSlots * 64) * 16;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed", name);
-            return MVSDET_ERR_HIP;
-        }
-        hipLaunchKernelGGL(k, grid, dim3(4 * 8 * 16 + 256), lds, st, x, sN, sC, sD, sH, Cin, static_cast<const uint4*>(weight_split_mx), scale,
-                           shift, dst, C8, Cout, D, H, W, p.tiles_w, relu, xcd_map);
-    } else if (p.th == 12) MVS_MX_CASE(12) else MVS_MX_CASE(8)
-#undef MVS_MX_CASE
+    // a kernel on 4 x `th` x 16 tiles with `threads` threads: its LDS follows from the tile (need = ceiling)
+    const auto launch = [&](auto* k, int th, int threads) -> int {
+        const size_t lds = ((size_t)2 * 2 * bf_in_slots(4, th, kBfW) + 2 * kMxSlots * 64) * 16;
+        MVS_GRANT_LDS(name, k, lds, lds);
+        hipLaunchKernelGGL(k, grid, dim3(threads), lds, st, x, v.sN, v.sC, v.sD, v.sH, Cin, static_cast<const uint4*>(weight_split_mx),
+                           scale, shift, dst, C8, Cout, D, H, W, p.tiles_w, relu, xcd_map);
+        return MVSDET_OK;
+    };
+    if (mx_form == 0) MVS_TRY(launch(conv3d_k3_fp16mx_ws_kernel<4, 8>, 8, 4 * 8 * 16 + 256));
+    else if (p.th == 12) MVS_TRY(launch(conv3d_k3_fp16mx_kernel<4, 12>, 12, 4 * 12 * 16));
+    else MVS_TRY(launch(conv3d_k3_fp16mx_kernel<4, 8>, 8, 4 * 8 * 16));
     MVS_LAUNCH_CHECK(name);
     return MVSDET_OK;
 }

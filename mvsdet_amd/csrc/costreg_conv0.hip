@@ -14,7 +14,7 @@
 //   FMA sum in (channel, tap) order -- the same products as ATen's convolution in another order.
 // Bound: fp32 MFMA, 64 FLOP/clk/SIMD = 157 TFLOP/s; 2.04 TFLOP at (40,256,12,60,80) = 13 ms at peak.
 // Measured 15.1 ms = 135 TFLOP/s (MIOpen: 33.6 ms).
-#include "common.h"
+#include "conv_host.h"
 
 #include <algorithm>
 
@@ -269,14 +269,15 @@ extern "C" size_t mvsdet_conv3d_k3_mfma_workspace_bytes(int N, int Cin, int Cout
 static int launch_conv_mfma(const char* name, const float* x, const float* weight_perm, const float* scale,
                             const float* shift, float* out, int N, int Cin, int Cout, int Di, int Hi, int Wi, int stride,
                             int relu, mvsdet_stream_t stream, const float* residual, float* workspace, size_t workspace_bytes) {
-    MVS_REQUIRE(x && weight_perm && out, "%s: NULL pointer", name);
-    MVS_REQUIRE((scale == nullptr) == (shift == nullptr), "%s: scale and shift come together", name);
-    MVS_REQUIRE(N > 0 && Cin > 0 && Di > 0 && Hi > 0 && Wi > 0, "%s: bad shape N=%d Cin=%d D=%d H=%d W=%d", name, N, Cin, Di, Hi,
-                Wi);
+    // the shared refusals (conv_host.h) in this entry point's own order: its stride and volume checks sit between them, Cout last
+    static_assert(kC0Out == 64, "conv_require_cout: 64 output channels per block");
+    MVS_CONV_POINTERS(name, x && weight_perm && out);
+    MVS_CONV_AFFINE(name, scale, shift);
+    MVS_CONV_SHAPE(name, N, Cin, Di, Hi, Wi);
     MVS_REQUIRE(stride == 1 || stride == 2, "%s: stride %d not in {1,2}", name, stride);
-    MVS_REQUIRE(((uintptr_t)weight_perm & 15u) == 0, "%s: weights must be 16-byte aligned", name);
+    MVS_CONV_ALIGNED16(name, (uintptr_t)weight_perm, false);
     MVS_REQUIRE((size_t)Di * Hi * Wi < ((size_t)1 << 30), "%s: one channel volume exceeds 2^30 elements", name);
-    MVS_REQUIRE(Cout > 0 && Cout % kC0Out == 0, "%s: Cout=%d must be a multiple of 64", name, Cout);
+    MVS_CONV_COUT(name, Cout);
     ConvPlan p = conv_plan(N, Cin, Cout, Di, Hi, Wi, stride);
     const int D = p.D, H = p.H, W = p.W, twc = p.twc, td = p.td, tiles_w = p.tiles_w, tiles_h = p.tiles_h, tiles_d = p.tiles_d;
     const size_t total = (size_t)N * Cout * D * H * W;
@@ -517,12 +518,12 @@ extern "C" int mvsdet_convT3d_k3_s2_mfma_f32(const float* x, const float* weight
                                              const float* residual, float* out, int N, int Cin, int Cout, int D, int H, int W,
                                              int relu, mvsdet_stream_t stream) {
     const char* name = "convT3d_k3_s2_mfma";
-    MVS_REQUIRE(x && weight_perm && out, "%s: NULL pointer", name);
-    MVS_REQUIRE((scale == nullptr) == (shift == nullptr), "%s: scale and shift come together", name);
-    MVS_REQUIRE(N > 0 && Cin > 0 && D > 0 && H > 0 && W > 0, "%s: bad shape N=%d Cin=%d D=%d H=%d W=%d", name, N, Cin, D, H, W);
-    MVS_REQUIRE(((uintptr_t)weight_perm & 15u) == 0, "%s: weights must be 16-byte aligned", name);
+    MVS_CONV_POINTERS(name, x && weight_perm && out);   // the order of launch_conv_mfma
+    MVS_CONV_AFFINE(name, scale, shift);
+    MVS_CONV_SHAPE(name, N, Cin, D, H, W);
+    MVS_CONV_ALIGNED16(name, (uintptr_t)weight_perm, false);
     MVS_REQUIRE((size_t)D * H * W < ((size_t)1 << 27), "%s: one input channel volume exceeds 2^27 elements", name);
-    MVS_REQUIRE(Cout > 0 && Cout % kC0Out == 0, "%s: Cout=%d must be a multiple of 64", name, Cout);
+    MVS_CONV_COUT(name, Cout);
     // tile = 2 planes x 4*(32/twc) rows x twc columns of the INPUT grid: the column-group width that pads (H, W) least
     int twc = 32;
     long long best = -1;
@@ -536,8 +537,7 @@ extern "C" int mvsdet_convT3d_k3_s2_mfma_f32(const float* x, const float* weight
     MVS_REQUIRE((long long)N * (Cout / kC0Out) <= 65535 && tiles_d <= 65535, "%s: N*Cout/64 or D too large", name);
     dim3 grid((unsigned)(tiles_w * tiles_h), (unsigned)tiles_d, (unsigned)(N * (Cout / kC0Out)));
     hipStream_t st = (hipStream_t)stream;
-    MVS_REQUIRE(((uintptr_t)out & 7u) == 0 && (residual == nullptr || ((uintptr_t)residual & 7u) == 0),
-                "%s: out and residual must be 8-byte aligned", name);
+    MVS_CONV_ALIGNED8(name, out, residual);
 #define MVS_CT_CASE(TW_, PD_, PH_)                                                                                          \
     hipLaunchKernelGGL((convT3d_k3_s2_mfma_kernel<TW_, PD_, PH_>), grid, dim3(kThreads), 0, st, x, weight_perm, scale, shift,  \
                        residual, out, Cin, Cout, D, H, W, tiles_w, tiles_h, relu)

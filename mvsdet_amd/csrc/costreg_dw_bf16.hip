@@ -342,11 +342,7 @@ extern "C" int mvsdet_conv3d_k3_dw_bf16x3(const float* x, const float* grad_out,
     const long long nblocks = (long long)nsplit * ((Cin + 31) / 32) * ((Cout + 31) / 32);
     MVS_REQUIRE(nblocks < INT32_MAX, "conv3d_k3_dw_bf16x3: too many blocks");
     dim3 grid((unsigned)nblocks);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv3d_k3_dw_bf16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            kDbLdsB) != hipSuccess) {
-        set_error("conv3d_k3_dw_bf16x3: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-        return MVSDET_ERR_HIP;
-    }
+    MVS_GRANT_LDS("conv3d_k3_dw_bf16x3", conv3d_k3_dw_bf16x3_kernel, kDbLdsB, kDbLdsB);
     hipLaunchKernelGGL(conv3d_k3_dw_bf16x3_kernel, grid, dim3(kDbThreads), kDbLdsB, (hipStream_t)stream, x, grad_out, partial, N, Cin, Cout,
                        D, H, W, tiles_w, tiles_h, (int)ncols, nsplit);
     MVS_LAUNCH_CHECK("conv3d_k3_dw_bf16x3");

@@ -393,11 +393,7 @@ extern "C" int mvsdet_conv3d_k3_s2_dw_bf16x3(const float* x, const float* grad_o
     MVS_REQUIRE(H < 65536 && W < 65536, "conv3d_k3_s2_dw_bf16x3: H=%d, W=%d too large", H, W);
     const long long nblocks = (long long)nsplit * ((Cin + kS2dCi - 1) / kS2dCi) * ((Cout + kS2dCo - 1) / kS2dCo);
     MVS_REQUIRE(nblocks < INT32_MAX, "conv3d_k3_s2_dw_bf16x3: too many blocks");
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv3d_k3_s2_dw_bf16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            kS2dLdsB) != hipSuccess) {
-        set_error("conv3d_k3_s2_dw_bf16x3: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-        return MVSDET_ERR_HIP;
-    }
+    MVS_GRANT_LDS("conv3d_k3_s2_dw_bf16x3", conv3d_k3_s2_dw_bf16x3_kernel, kS2dLdsB, kS2dLdsB);
     hipLaunchKernelGGL(conv3d_k3_s2_dw_bf16x3_kernel, dim3((unsigned)nblocks), dim3(kS2dThreads), kS2dLdsB, (hipStream_t)stream, x,
                        grad_out, partial, N, Cin, Cout, D, H, W, tiles_w, tiles_h, (int)ncols, nsplit);
     MVS_LAUNCH_CHECK("conv3d_k3_s2_dw_bf16x3");

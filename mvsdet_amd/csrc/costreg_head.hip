@@ -606,11 +606,7 @@ extern "C" int mvsdet_conv3d_k3_cout2_dw_bf16x3(const float* x, const float* gra
 #define MVS_HDW_LAUNCH(MTV)                                                                                              \
     {                                                                                                                    \
         auto* k = conv3d_k3_cout2_dw_bf16x3_kernel<MTV>;                                                                 \
-        if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                   160 * 1024) != hipSuccess) {                                          \
-            set_error("conv3d_k3_cout2_dw_bf16x3: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");              \
-            return MVSDET_ERR_HIP;                                                                                       \
-        }                                                                                                                \
+        MVS_GRANT_LDS("conv3d_k3_cout2_dw_bf16x3", k, lds, 160 * 1024);                                                  \
         hipLaunchKernelGGL(k, dim3((unsigned)nsplit), dim3(kThreads), lds, (hipStream_t)stream, x, grad_out, partial, N, D, H, W); \
     }
     if (Cin == 64) MVS_HDW_LAUNCH(4)

@@ -866,17 +866,15 @@ int check_workspace(const char* name, const void* workspace, size_t bytes, size_
     return MVSDET_ERR_WORKSPACE;
 }
 
-// LDS of a sort kernel: a power of two of keys that holds `caps`, then `extra` bytes; above 64 KiB the kernel is told so
+// LDS of a sort kernel: a power of two of keys that holds `caps`, then `extra` bytes; above 64 KiB the kernel is told so -- granted
+// the LDS of a list at the candidate limit, not this list's: another host thread's larger list may be between its grant and its launch
 template <class Kernel>
-int sort_lds(Kernel kernel, int caps, size_t extra, const char* name, int* pmax, size_t* lds) {
+int sort_lds(Kernel* kernel, int caps, size_t extra, const char* name, int* pmax, size_t* lds) {
     *pmax = 1;
     while (*pmax < std::max(caps, 1)) *pmax <<= 1;
     *lds = (size_t)*pmax * 8 + extra;
-    if (*lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds) != hipSuccess) {
-        set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed", name);
-        return MVSDET_ERR_HIP;
-    }
+    static_assert((kLimit & (kLimit - 1)) == 0, "the ceiling below: kLimit keys, a power of two");
+    if (*lds > 64 * 1024) MVS_GRANT_LDS(name, kernel, *lds, (size_t)kLimit * 8 + extra);
     return MVSDET_OK;
 }
 

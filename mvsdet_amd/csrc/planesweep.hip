@@ -154,18 +154,6 @@ int effective_box_cap(int K, int tw) {
     return cap < 0 ? 0 : (cap > fit ? fit : cap);
 }
 
-template <typename F>
-int allow_dynamic_lds(F* kernel, size_t bytes) {
-    // above 48 KiB of dynamic LDS the launch needs the function attribute; set once per kernel (host-side state,
-    // nothing is enqueued: safe under stream capture)
-    if (bytes <= 48 * 1024) return MVSDET_OK;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess) {
-        set_error("plane_sweep_variance: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-        return MVSDET_ERR_HIP;
-    }
-    return MVSDET_OK;
-}
-
 size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace
@@ -201,7 +189,7 @@ int launch_slab(dim3 grid, hipStream_t stream, size_t lds, const float* packed, 
     // option "sweep_inside": 0 hides kFlagInside from the slab kernel, whose every plane then takes the general form
     const unsigned fl_keep = options().sweep_inside != 0 ? ~0u : ~kFlagAllInside;
     auto* k = plane_sweep_variance_kernel<KV, TW, FAST, OutT>;
-    if (int rc = allow_dynamic_lds(k, lds)) return rc;
+    MVS_GRANT_LDS("plane_sweep_variance", k, lds, 80 * 1024);   // the largest LDS of max_box_cap()
     hipLaunchKernelGGL(k, grid, dim3(kThreads), lds, stream, packed, ref_packed, nbr, geo.header, geo.proj, geo.depth, geo.boxes, geo.flags,
                        groups, var, n_src, C, S, D, H, W, Wo, tiles_x, tiles, d_per_block, box_cap, n_bt, xcd_parts, fl_keep);
     return MVSDET_OK;

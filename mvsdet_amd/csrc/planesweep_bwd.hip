@@ -533,11 +533,7 @@ static int bwd_launch(const float* packed, const int64_t* nbr, void* scratch, co
 #define MVS_BWD_LAUNCH1(KV, TWV, HV, GV)                                                                                 \
     {                                                                                                                  \
         auto* k = plane_sweep_variance_bwd_kernel<KV, TWV, HV, GV>;                                                    \
-        if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                                   80 * 1024) != hipSuccess) {                                         \
-            set_error("plane_sweep_variance_bwd: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");             \
-            return MVSDET_ERR_HIP;                                                                                     \
-        }                                                                                                              \
+        MVS_GRANT_LDS("plane_sweep_variance_bwd", k, lds, 80 * 1024);                                                  \
         hipLaunchKernelGGL(k, grid, dim3(kThreads * GV), lds, stream, packed, nbr, geo.header, geo.proj, geo.depth, geo.boxes, geo.flags, g, \
                            gpacked, N, C, S, D, H, W, tiles_x, tiles, box_cap);                                        \
     }

@@ -63,7 +63,8 @@ def _cost_network():
 
 # names the reference module looks up when it builds the model (mvsdet.py:32,228: `self.cost_regularization =
 # CostRegNet_3DGS()`): the replacement has the same parameter names, so checkpoints load, and routes every layer to
-# the fp32-MFMA kernels in eval mode without autograd (28 ms instead of 59 ms per scene)
+# the HIP kernels in eval mode without autograd: by default bf16x3 with fp16 + MX at conv0 (6.4-6.6 ms instead of 59 ms
+# per scene: README); "fp32", the fp32-MFMA kernels (28 ms here), stays a route one can choose (costreg.py)
 PATCHED_CLASSES = {
     "CostRegNet_3DGS": _cost_network,
 }
