@@ -590,6 +590,28 @@ int mvsdet_splat_backward_f32(const float* means, const int64_t* means_strides /
                               float* g_covariances, float* g_harmonics, float* g_opacities, int V, int G, int d_sh, int use_sh, int H,
                               int W, int max_keys, mvsdet_stream_t stream);
 
+/* Rendered depth (render_depth_cuda, cuda_splatting.py:237-280) as a fourth blended channel of the same pass.  DESIGN.md 4.18.
+ * Every (view, Gaussian) gets one value d = f(z), z its camera-space depth before the scale_invariant scaling, near / far (V) the
+ * caller's unscaled bounds: mode 0 depth z, 1 disparity 1 / z, 2 relative_disparity (conversions.py:17-27, eps 1e-10), 3 log as the
+ * reference writes it, log(max(min(z, near), far)) = log(far) whenever near <= far.  values (V,G) receives d (0 where culled), depth
+ * (V,H,W) the blend sum d alpha T over a background of 0, with the alpha, T, skips and early stop of the colour; a view over its key
+ * capacity is NaN.  with_colour 1: image (V,3,H,W) too, the bits of mvsdet_splat_forward_f32.  with_colour 0: harmonics, sh_strides,
+ * background, image, g_image and g_harmonics are not touched and may be NULL; d_sh and use_sh are ignored.  Workspace and cams as
+ * above.  The backward takes g_depth (V,H,W) beside g_image; slots: 10 V max_keys floats, and 10 V max_keys < 2^31. */
+int mvsdet_splat_forward_depth_f32(const float* means, const int64_t* means_strides /*HOST[2]*/, const float* covariances,
+                                   const int64_t* cov_strides /*HOST[3]*/, const float* harmonics, const int64_t* sh_strides /*HOST[3]*/,
+                                   const float* opacities, int64_t opacity_stride, const float* cams, const float* near, const float* far,
+                                   const float* background, float* image, float* depth, float* values, void* workspace,
+                                   size_t workspace_bytes, int V, int G, int d_sh, int use_sh, int with_colour, int mode, int H, int W,
+                                   int max_keys, mvsdet_stream_t stream);
+int mvsdet_splat_backward_depth_f32(const float* means, const int64_t* means_strides /*HOST[2]*/, const float* covariances,
+                                    const int64_t* cov_strides /*HOST[3]*/, const float* harmonics, const int64_t* sh_strides /*HOST[3]*/,
+                                    const float* opacities, int64_t opacity_stride, const float* cams, const float* near, const float* far,
+                                    const float* background, const float* g_image, const float* g_depth, const float* values,
+                                    void* workspace, size_t workspace_bytes, float* slots, float* g_means, float* g_covariances,
+                                    float* g_harmonics, float* g_opacities, int V, int G, int d_sh, int use_sh, int with_colour, int mode,
+                                    int H, int W, int max_keys, mvsdet_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Gaussian adapter (csrc/adapter.hip): the pixel Gaussians the rasteriser above renders -- GaussianAdapter.forward
  * (gs_src/model/encoder/common/gaussian_adapter.py:50-98) with the offset lines of mvsdet.py:576-578, for V source views of R = h w

@@ -107,6 +107,10 @@ SIGNATURES = {
     "mvsdet_splat_forward_f32": [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_splat_backward_f32": [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i, _i,
                                   _i, _i, _i, _i, _i, _vp],
+    "mvsdet_splat_forward_depth_f32": [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i,
+                                       _i, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_splat_backward_depth_f32": [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
+                                        _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_adapter_cameras_f32": [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _i, _i, _i, _i, _vp],
     "mvsdet_adapter_forward_f32": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp],
     "mvsdet_adapter_backward_f32": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i, _i, _i, _i, _i, _f, _f, _vp],

@@ -12,6 +12,10 @@
 //               written to the slot of the key's pre-sort position
 //   preprocess bwd  one thread per Gaussian adds its slots in tile order, then view order, and chains to the inputs
 // fp32, no float atomics, no host synchronisation: two runs give the same bits.
+//
+// Rendered depth (render_depth_cuda) is a fourth blended channel of the same pass: preprocess writes one value d(v, g)
+// per (view, Gaussian) -- the camera-space z mapped by the mode -- and render / render bwd / preprocess bwd are templates over
+// "blends colour" and "blends depth".  Colour alone is the form above, unchanged; the depth forms run behind entry points of their own.
 #include <cstring>   // rocPRIM calls the host memset without including it
 
 #include <rocprim/rocprim.hpp>
@@ -27,6 +31,7 @@ namespace {
 constexpr int kTile = 16;
 constexpr int kCam = 40;         // floats per view: view matrix 16, full projection 16, tan fov x / y, camera position 3, scale, 2 unused
 constexpr int kSlot = 9;         // floats per (tile, Gaussian) gradient slot: mean2D 2, conic 3, opacity 1, colour 3
+constexpr int kSlotDepth = 10;   // the depth forms' slot: the same nine (colour unused without colour) and dL/dd
 constexpr int kBwdBatch = 64;    // entries of a tile list per LDS batch of the backward
 constexpr unsigned kPadTile = 0xffffffffu;
 
@@ -63,6 +68,52 @@ struct SplatWs {
     size_t sort_bytes;
     size_t total;
 };
+
+// The depth forms' extra arguments; an empty struct in the colour-only form, whose kernels keep their argument lists.
+enum { kModeDepth = 0, kModeDisparity = 1, kModeRelativeDisparity = 2, kModeLog = 3 };
+template <bool DEP>
+struct SplatDepth {};
+template <>
+struct SplatDepth<true> {
+    const float* near;     // V, unscaled
+    const float* far;      // V, unscaled
+    float* values;         // V*G: d(v, g), 0 where culled (the reference's fake_color)
+    float* image;          // V*H*W: the rendered depth (forward) or its gradient (backward, read only)
+    int mode;
+};
+
+// slots of the gradient record a form reduces and adds: the colour slots 6..8 are skipped without colour
+template <bool COL>
+__device__ __forceinline__ constexpr bool splat_slot_used(int k) {
+    return COL || k < 6 || k > 8;
+}
+
+// d(z) of render_depth_cuda (cuda_splatting.py:253-262) and its derivative, fp32 in the reference's order of operations.  z is the
+// camera-space depth before the scale_invariant scaling; near / far are the caller's, unscaled.
+// The log mode's clamp is inverted in the reference -- min with near, then max with far -- so the value is log(far) for every
+// Gaussian whenever near <= far, and its derivative in z is 0.  Reproduced as written, not corrected.
+__device__ __forceinline__ float splat_depth_value(int mode, float z, float near, float far) {
+    if (mode == kModeDisparity) return 1.0f / z;
+    if (mode == kModeRelativeDisparity) {
+        const float e = 1e-10f;
+        const float disp_near = 1.0f / (near + e), disp_far = 1.0f / (far + e), disp = 1.0f / (z + e);
+        return 1.0f - (disp - disp_far) / (disp_near - disp_far + e);
+    }
+    // the logarithm through float64, rounded once: the value is one number per view (log(far)), and a last-bit difference between two
+    // float32 log routines would show in every pixel
+    if (mode == kModeLog) return (float)log((double)fmaxf(fminf(z, near), far));
+    return z;
+}
+__device__ __forceinline__ float splat_depth_slope(int mode, float z, float near, float far) {
+    if (mode == kModeDisparity) return -1.0f / (z * z);
+    if (mode == kModeRelativeDisparity) {
+        const float e = 1e-10f;
+        const float disp_near = 1.0f / (near + e), disp_far = 1.0f / (far + e), disp = 1.0f / (z + e);
+        return disp * disp / (disp_near - disp_far + e);
+    }
+    if (mode == kModeLog) return 0.0f;
+    return 1.0f;
+}
 
 // bits of the key above the depth: real (view, tile) ids stay below the padding key's all-ones field
 unsigned tile_bits(int V, size_t tiles) {
@@ -263,8 +314,10 @@ __device__ __forceinline__ void splat_direction(const float* __restrict__ cam, c
 }
 
 // ------------------------------------------------------------------------------------------------ preprocess
+template <bool COL, bool DEP>
 __global__ __launch_bounds__(kThreads) void splat_preprocess_kernel(SplatIn in, const float* __restrict__ cams, SplatWs ws, int V, int G,
-                                                                    int d_sh, int use_sh, int H, int W, int tiles_x, int tiles_y) {
+                                                                    int d_sh, int use_sh, int H, int W, int tiles_x, int tiles_y,
+                                                                    SplatDepth<DEP> dz) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= V * G) return;
     const int v = i / G, g = i - v * G;
@@ -275,7 +328,8 @@ __global__ __launch_bounds__(kThreads) void splat_preprocess_kernel(SplatIn in, 
     ws.depth[i] = 0.0f;
     ws.xy[i] = make_float2(0.0f, 0.0f);
     ws.conop[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    ws.rgb[i * 3 + 0] = ws.rgb[i * 3 + 1] = ws.rgb[i * 3 + 2] = 0.0f;
+    if constexpr (COL) ws.rgb[i * 3 + 0] = ws.rgb[i * 3 + 1] = ws.rgb[i * 3 + 2] = 0.0f;
+    if constexpr (DEP) dz.values[i] = 0.0f;
     Geo q;
     if (!splat_project(cam, in, g, H, W, q)) return;
     const float mid = 0.5f * (q.a + q.c);
@@ -288,8 +342,10 @@ __global__ __launch_bounds__(kThreads) void splat_preprocess_kernel(SplatIn in, 
     const int x0 = (int)fminf(fmaxf((px - radius) / ft, 0.0f), gx), x1 = (int)fminf(fmaxf((px + radius + (ft - 1.0f)) / ft, 0.0f), gx);
     const int y0 = (int)fminf(fmaxf((py - radius) / ft, 0.0f), gy), y1 = (int)fminf(fmaxf((py + radius + (ft - 1.0f)) / ft, 0.0f), gy);
     if (x1 <= x0 || y1 <= y0) return;
-    float rgb[3];
-    if (use_sh) {
+    float rgb[3] = {0.0f, 0.0f, 0.0f};
+    if constexpr (!COL) {
+        // depth alone: the harmonics are not read
+    } else if (use_sh) {
         float n[3], len, basis[kShMax];
         splat_direction(cam, q.m, n, len);
         sh_basis<float>(n[0], n[1], n[2], d_sh, basis);
@@ -311,9 +367,14 @@ __global__ __launch_bounds__(kThreads) void splat_preprocess_kernel(SplatIn in, 
     ws.depth[i] = q.t[2];
     ws.xy[i] = make_float2(px, py);
     ws.conop[i] = make_float4(q.c / q.det, -q.b / q.det, q.a / q.det, in.opac[g * in.o_g]);
-    ws.rgb[i * 3 + 0] = rgb[0];
-    ws.rgb[i * 3 + 1] = rgb[1];
-    ws.rgb[i * 3 + 2] = rgb[2];
+    if constexpr (COL) {
+        ws.rgb[i * 3 + 0] = rgb[0];
+        ws.rgb[i * 3 + 1] = rgb[1];
+        ws.rgb[i * 3 + 2] = rgb[2];
+    }
+    // the unscaled camera-space z as z_s / s: the scaled form above keeps its multiplication order (sort keys and culling do not
+    // move), and with scale 1 the division is exact
+    if constexpr (DEP) dz.values[i] = splat_depth_value(dz.mode, q.t[2] / cam[37], dz.near[v], dz.far[v]);
 }
 
 // one block per view: exclusive sums of `touched` in Gaussian order
@@ -393,11 +454,15 @@ __device__ __forceinline__ float splat_alpha(float opacity, float gauss) {
     return a > 0.99f ? 0.99f : a;
 }
 
+// COL: blends the three colour channels into image (V,3,H,W) over the background.  DEP: blends d(v, g) into dz.image (V,H,W) over a
+// background of 0, with the same alpha, T, skips, early stop and n_contrib.  Without COL no colour is staged in LDS.
+template <bool COL, bool DEP>
 __global__ __launch_bounds__(kThreads) void splat_render_kernel(SplatWs ws, const float* __restrict__ bg, float* __restrict__ image, int G,
-                                                                int H, int W, int tiles_x, int tiles) {
+                                                                int H, int W, int tiles_x, int tiles, SplatDepth<DEP> dz) {
     __shared__ float2 s_xy[kThreads];
     __shared__ float4 s_con[kThreads];
-    __shared__ float s_rgb[kThreads * 3];
+    __shared__ float s_rgb[COL ? kThreads * 3 : 1];
+    __shared__ float s_d[DEP ? kThreads : 1];
     const int v = blockIdx.z, tid = threadIdx.x;
     const int px = blockIdx.x * kTile + (tid & (kTile - 1)), py = blockIdx.y * kTile + (tid >> 4);
     const bool inside = px < W && py < H;
@@ -407,7 +472,8 @@ __global__ __launch_bounds__(kThreads) void splat_render_kernel(SplatWs ws, cons
     if (ws.status[v].z) {   // more keys than the capacity: the view is NaN, nothing was sorted for it
         if (inside) {
             const float nan = __builtin_nanf("");
-            out[0] = out[plane] = out[2 * plane] = nan;
+            if constexpr (COL) out[0] = out[plane] = out[2 * plane] = nan;
+            if constexpr (DEP) dz.image[pix] = nan;
             ws.final_T[pix] = nan;
             ws.n_contrib[pix] = 0;
         }
@@ -416,7 +482,7 @@ __global__ __launch_bounds__(kThreads) void splat_render_kernel(SplatWs ws, cons
     const int2 range = ws.ranges[v * tiles + blockIdx.y * tiles_x + blockIdx.x];
     const int n = range.y - range.x;
     const float fx = (float)px, fy = (float)py;
-    float T = 1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f;
+    float T = 1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f, D = 0.0f;
     int contributor = 0, last = 0;
     bool done = !inside;
     for (int base = 0; base < n; base += kThreads) {
@@ -426,9 +492,12 @@ __global__ __launch_bounds__(kThreads) void splat_render_kernel(SplatWs ws, cons
             const size_t gi = (size_t)v * G + ws.gid[p];
             s_xy[tid] = ws.xy[gi];
             s_con[tid] = ws.conop[gi];
-            s_rgb[tid * 3 + 0] = ws.rgb[gi * 3 + 0];
-            s_rgb[tid * 3 + 1] = ws.rgb[gi * 3 + 1];
-            s_rgb[tid * 3 + 2] = ws.rgb[gi * 3 + 2];
+            if constexpr (COL) {
+                s_rgb[tid * 3 + 0] = ws.rgb[gi * 3 + 0];
+                s_rgb[tid * 3 + 1] = ws.rgb[gi * 3 + 1];
+                s_rgb[tid * 3 + 2] = ws.rgb[gi * 3 + 2];
+            }
+            if constexpr (DEP) s_d[tid] = dz.values[gi];
         }
         __syncthreads();
         const int m = min(kThreads, n - base);
@@ -447,29 +516,41 @@ __global__ __launch_bounds__(kThreads) void splat_render_kernel(SplatWs ws, cons
                 continue;
             }
             const float w = alpha * T;
-            C0 += s_rgb[j * 3 + 0] * w;
-            C1 += s_rgb[j * 3 + 1] * w;
-            C2 += s_rgb[j * 3 + 2] * w;
+            if constexpr (COL) {
+                C0 += s_rgb[j * 3 + 0] * w;
+                C1 += s_rgb[j * 3 + 1] * w;
+                C2 += s_rgb[j * 3 + 2] * w;
+            }
+            if constexpr (DEP) D += s_d[j] * w;
             T = Tn;
             last = contributor;
         }
     }
     if (inside) {
-        out[0] = C0 + T * bg[v * 3 + 0];
-        out[plane] = C1 + T * bg[v * 3 + 1];
-        out[2 * plane] = C2 + T * bg[v * 3 + 2];
+        if constexpr (COL) {
+            out[0] = C0 + T * bg[v * 3 + 0];
+            out[plane] = C1 + T * bg[v * 3 + 1];
+            out[2 * plane] = C2 + T * bg[v * 3 + 2];
+        }
+        if constexpr (DEP) dz.image[pix] = D;
         ws.final_T[pix] = T;
         ws.n_contrib[pix] = last;
     }
 }
 
+// DEP: g_depth (dz.image) enters the recurrence as one more channel with its own accum / last pair and no background term; the slot
+// has kSlotDepth floats, the last one dL/dd.  Without COL the colour slots 6..8 are neither reduced nor written.
+template <bool COL, bool DEP>
 __global__ __launch_bounds__(kThreads) void splat_render_bwd_kernel(SplatWs ws, const float* __restrict__ bg, const float* __restrict__ g_image,
-                                                                    float* __restrict__ slots, int G, int H, int W, int tiles_x, int tiles) {
+                                                                    float* __restrict__ slots, int G, int H, int W, int tiles_x, int tiles,
+                                                                    SplatDepth<DEP> dz) {
+    constexpr int NS = DEP ? kSlotDepth : kSlot;
     __shared__ float2 s_xy[kBwdBatch];
     __shared__ float4 s_con[kBwdBatch];
-    __shared__ float s_rgb[kBwdBatch * 3];
+    __shared__ float s_rgb[COL ? kBwdBatch * 3 : 1];
+    __shared__ float s_d[DEP ? kBwdBatch : 1];
     __shared__ unsigned s_pos[kBwdBatch];
-    __shared__ float s_part[kThreads / kWave][kBwdBatch][kSlot];
+    __shared__ float s_part[kThreads / kWave][kBwdBatch][NS];
     const int v = blockIdx.z, tid = threadIdx.x, wave = tid / kWave, lane = tid % kWave;
     if (ws.status[v].z) return;   // nothing was sorted for this view; preprocess backward writes its NaN
     const int px = blockIdx.x * kTile + (tid & (kTile - 1)), py = blockIdx.y * kTile + (tid >> 4);
@@ -482,9 +563,15 @@ __global__ __launch_bounds__(kThreads) void splat_render_bwd_kernel(SplatWs ws, 
     const float T_final = inside ? ws.final_T[pix] : 0.0f;
     const int last = inside ? ws.n_contrib[pix] : 0;
     float dp[3] = {0.0f, 0.0f, 0.0f};
-    if (inside)
-        for (int ch = 0; ch < 3; ++ch) dp[ch] = g_image[(int64_t)v * 3 * plane + ch * plane + (int64_t)py * W + px];
-    const float bg_dot = bg[v * 3 + 0] * dp[0] + bg[v * 3 + 1] * dp[1] + bg[v * 3 + 2] * dp[2];
+    float bg_dot = 0.0f;
+    if constexpr (COL) {
+        if (inside)
+            for (int ch = 0; ch < 3; ++ch) dp[ch] = g_image[(int64_t)v * 3 * plane + ch * plane + (int64_t)py * W + px];
+        bg_dot = bg[v * 3 + 0] * dp[0] + bg[v * 3 + 1] * dp[1] + bg[v * 3 + 2] * dp[2];
+    }
+    float dpd = 0.0f, accum_d = 0.0f, last_d = 0.0f;
+    if constexpr (DEP)
+        if (inside) dpd = dz.image[pix];
     float T = T_final, last_alpha = 0.0f;
     float accum[3] = {0.0f, 0.0f, 0.0f}, last_col[3] = {0.0f, 0.0f, 0.0f};
     for (int base = 0; base < n; base += kBwdBatch) {   // back to front: entry n-1-base-j
@@ -496,13 +583,16 @@ __global__ __launch_bounds__(kThreads) void splat_render_bwd_kernel(SplatWs ws, 
             s_pos[tid] = p;
             s_xy[tid] = ws.xy[gi];
             s_con[tid] = ws.conop[gi];
-            s_rgb[tid * 3 + 0] = ws.rgb[gi * 3 + 0];
-            s_rgb[tid * 3 + 1] = ws.rgb[gi * 3 + 1];
-            s_rgb[tid * 3 + 2] = ws.rgb[gi * 3 + 2];
+            if constexpr (COL) {
+                s_rgb[tid * 3 + 0] = ws.rgb[gi * 3 + 0];
+                s_rgb[tid * 3 + 1] = ws.rgb[gi * 3 + 1];
+                s_rgb[tid * 3 + 2] = ws.rgb[gi * 3 + 2];
+            }
+            if constexpr (DEP) s_d[tid] = dz.values[gi];
         }
         __syncthreads();
         for (int j = 0; j < m; ++j) {
-            float val[kSlot] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            float val[NS] = {};
             bool hit = false;
             if (n - 1 - base - j < last) {
                 const float2 xy = s_xy[j];
@@ -517,16 +607,24 @@ __global__ __launch_bounds__(kThreads) void splat_render_bwd_kernel(SplatWs ws, 
                         T = T / (1.0f - alpha);
                         const float dchannel = alpha * T;
                         float dL_dalpha = 0.0f;
-                        for (int ch = 0; ch < 3; ++ch) {
-                            const float c = s_rgb[j * 3 + ch];
-                            accum[ch] = last_alpha * last_col[ch] + (1.0f - last_alpha) * accum[ch];
-                            last_col[ch] = c;
-                            dL_dalpha += (c - accum[ch]) * dp[ch];
-                            val[6 + ch] = dchannel * dp[ch];
+                        if constexpr (COL)
+                            for (int ch = 0; ch < 3; ++ch) {
+                                const float c = s_rgb[j * 3 + ch];
+                                accum[ch] = last_alpha * last_col[ch] + (1.0f - last_alpha) * accum[ch];
+                                last_col[ch] = c;
+                                dL_dalpha += (c - accum[ch]) * dp[ch];
+                                val[6 + ch] = dchannel * dp[ch];
+                            }
+                        if constexpr (DEP) {   // the fourth channel; its background is 0
+                            const float d = s_d[j];
+                            accum_d = last_alpha * last_d + (1.0f - last_alpha) * accum_d;
+                            last_d = d;
+                            dL_dalpha += (d - accum_d) * dpd;
+                            val[NS - 1] = dchannel * dpd;
                         }
                         dL_dalpha *= T;
                         last_alpha = alpha;
-                        dL_dalpha += (-T_final / (1.0f - alpha)) * bg_dot;
+                        if constexpr (COL) dL_dalpha += (-T_final / (1.0f - alpha)) * bg_dot;
                         // the 0.99 cap passes the gradient through
                         const float dL_dG = co.w * dL_dalpha;
                         const float gdx = Gs * dx, gdy = Gs * dy;
@@ -541,35 +639,43 @@ __global__ __launch_bounds__(kThreads) void splat_render_bwd_kernel(SplatWs ws, 
             }
             if (__ballot(hit) != 0ull) {
 #pragma unroll
-                for (int k = 0; k < kSlot; ++k) {
+                for (int k = 0; k < NS; ++k) {
+                    if (!splat_slot_used<COL>(k)) continue;
                     const float s = wave_sum_all(val[k]);
                     if (lane == 0) s_part[wave][j][k] = s;
                 }
-            } else if (lane < kSlot) {
+            } else if (lane < NS) {
                 s_part[wave][j][lane] = 0.0f;
             }
         }
         __syncthreads();
-        for (int e = tid; e < m * kSlot; e += kThreads) {
-            const int j = e / kSlot, k = e - j * kSlot;
+        for (int e = tid; e < m * NS; e += kThreads) {
+            const int j = e / NS, k = e - j * NS;
+            if (!splat_slot_used<COL>(k)) continue;
             float s = s_part[0][j][k];
             for (int w = 1; w < kThreads / kWave; ++w) s += s_part[w][j][k];
-            slots[(size_t)s_pos[j] * kSlot + k] = s;
+            slots[(size_t)s_pos[j] * NS + k] = s;
         }
     }
 }
 
 // ------------------------------------------------------------------------------------------------ preprocess backward
+// DEP: the tenth slot is added in the same tile-then-view order and chained as dL/dd * d'(z) * dz/dmean, dz/dmean being the third column
+// of the view rotation (the scale does not touch it); the term joins the means' gradient after the existing ones.  Without COL no
+// harmonics are read and g_sh is not written.
+template <bool COL, bool DEP>
 __global__ __launch_bounds__(kThreads) void splat_preprocess_bwd_kernel(SplatIn in, const float* __restrict__ cams, SplatWs ws,
                                                                         const float* __restrict__ slots, float* __restrict__ g_means,
                                                                         float* __restrict__ g_cov, float* __restrict__ g_sh,
                                                                         float* __restrict__ g_opac, int V, int G, int d_sh, int use_sh, int H,
-                                                                        int W, int K) {
+                                                                        int W, int K, SplatDepth<DEP> dz) {
+    constexpr int NS = DEP ? kSlotDepth : kSlot;
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= G) return;
     float gm[3] = {0.0f, 0.0f, 0.0f}, gc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, gop = 0.0f;
-    float* gsh = g_sh + (size_t)g * 3 * d_sh;
-    for (int e = 0; e < 3 * d_sh; ++e) gsh[e] = 0.0f;
+    float* gsh = COL ? g_sh + (size_t)g * 3 * d_sh : nullptr;
+    if constexpr (COL)
+        for (int e = 0; e < 3 * d_sh; ++e) gsh[e] = 0.0f;
     for (int v = 0; v < V; ++v) {
         const size_t i = (size_t)v * G + g;
         const float* cam = cams + (int64_t)v * kCam;
@@ -578,7 +684,8 @@ __global__ __launch_bounds__(kThreads) void splat_preprocess_bwd_kernel(SplatIn 
             for (int k = 0; k < 3; ++k) gm[k] += nan;
             for (int k = 0; k < 6; ++k) gc[k] += nan;
             gop += nan;
-            for (int e = 0; e < 3 * d_sh; ++e) gsh[e] += nan;
+            if constexpr (COL)
+                for (int e = 0; e < 3 * d_sh; ++e) gsh[e] += nan;
             continue;
         }
         const unsigned n = ws.touched[i];
@@ -586,15 +693,18 @@ __global__ __launch_bounds__(kThreads) void splat_preprocess_bwd_kernel(SplatIn 
         Geo q;
         if (!splat_project(cam, in, g, H, W, q)) continue;
         // the entries' slots in tile order
-        float sl[kSlot] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        const float* sp = slots + ((size_t)v * K + ws.offs[i]) * kSlot;
+        float sl[NS] = {};
+        const float* sp = slots + ((size_t)v * K + ws.offs[i]) * NS;
         for (unsigned e = 0; e < n; ++e)
-            for (int k = 0; k < kSlot; ++k) sl[k] += sp[(size_t)e * kSlot + k];
+            for (int k = 0; k < NS; ++k)
+                if (splat_slot_used<COL>(k)) sl[k] += sp[(size_t)e * NS + k];
         const float s = cam[37], s2 = s * s;
         float dm[3] = {0.0f, 0.0f, 0.0f};   // d / d (mean * scale)
         gop += sl[5];
         // colour
-        if (use_sh) {
+        if constexpr (!COL) {
+            // depth alone: nothing to chain
+        } else if (use_sh) {
             float nrm[3], len;
             splat_direction(cam, q.m, nrm, len);
             Dual3 basis[kShMax];
@@ -674,6 +784,10 @@ __global__ __launch_bounds__(kThreads) void splat_preprocess_bwd_kernel(SplatIn 
         const float* P = cam + 16;
         for (int k = 0; k < 3; ++k) dm[k] += ghx * P[k * 4 + 0] + ghy * P[k * 4 + 1] + ghw * P[k * 4 + 3];
         for (int k = 0; k < 3; ++k) gm[k] += dm[k] * s;
+        if constexpr (DEP) {
+            const float slope = sl[NS - 1] * splat_depth_slope(dz.mode, q.t[2] / s, dz.near[v], dz.far[v]);
+            for (int k = 0; k < 3; ++k) gm[k] += slope * cam[k * 4 + 2];
+        }
     }
     for (int k = 0; k < 3; ++k) g_means[(size_t)g * 3 + k] = gm[k];
     float* oc = g_cov + (size_t)g * 9;
@@ -705,6 +819,75 @@ SplatIn splat_inputs(const float* means, const int64_t* ms, const float* cov, co
     return SplatIn{means, ms[0], ms[1], cov, cs[0], cs[1], cs[2], sh, ss[0], ss[1], ss[2], opac, os};
 }
 
+
+// what the depth entry points check beyond check_splat
+int check_splat_depth(const char* name, int V, int mode, int max_keys) {
+    MVS_REQUIRE(mode >= kModeDepth && mode <= kModeLog, "%s: mode=%d must be 0 (depth), 1 (disparity), 2 (relative_disparity) or 3 (log)", name,
+                mode);
+    MVS_REQUIRE((long long)V * max_keys * kSlotDepth < (1ll << 31), "%s: V=%d max_keys=%d exceeds the limit 10 V max_keys < 2^31", name, V,
+                max_keys);
+    return MVSDET_OK;
+}
+
+// The forward launch sequence of every form.  The caller has checked the arguments.
+template <bool COL, bool DEP>
+int splat_forward(const char* name, const SplatIn& in, const float* cams, const float* background, float* image, void* workspace,
+                  size_t workspace_bytes, int V, int G, int d_sh, int use_sh, int H, int W, int max_keys, SplatDepth<DEP> dz, hipStream_t st) {
+    MVS_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: the workspace must be 256-byte aligned", name);
+    const SplatWs ws = splat_layout(workspace, V, G, H, W, max_keys);
+    MVS_REQUIRE_WORKSPACE(name, workspace_bytes, ws.total);
+    const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile, tiles = tiles_x * tiles_y;
+    const int64_t vg = (int64_t)V * G, vk = (int64_t)V * max_keys;
+    hipLaunchKernelGGL((splat_preprocess_kernel<COL, DEP>), dim3((unsigned)((vg + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, in, cams,
+                       ws, V, G, d_sh, use_sh, H, W, tiles_x, tiles_y, dz);
+    hipLaunchKernelGGL(splat_scan_kernel, dim3(V), dim3(kThreads), 0, st, ws, G, max_keys);
+    const int64_t most = vg > vk ? vg : vk;
+    const unsigned emit_blocks = (unsigned)((most + kThreads - 1) / kThreads < 4096 ? (most + kThreads - 1) / kThreads : 4096);
+    hipLaunchKernelGGL(splat_emit_kernel, dim3(emit_blocks), dim3(kThreads), 0, st, ws, V, G, max_keys, tiles_x, tiles);
+    MVS_LAUNCH_CHECK(name);
+    const unsigned bits = tile_bits(V, (size_t)tiles);
+    size_t sort_bytes = 0;
+    hipError_t e = rocprim::radix_sort_pairs(nullptr, sort_bytes, ws.keys_in, ws.keys_out, ws.vals_in, ws.vals_out, (size_t)vk, 0, 32 + bits, st);
+    if (e != hipSuccess || sort_bytes > ws.sort_bytes) {
+        set_error("%s: the sort asks for %zu bytes, %zu set aside (%s)", name, sort_bytes, ws.sort_bytes, hipGetErrorString(e));
+        return MVSDET_ERR_WORKSPACE;
+    }
+    sort_bytes = ws.sort_bytes;
+    e = rocprim::radix_sort_pairs(ws.sort_tmp, sort_bytes, ws.keys_in, ws.keys_out, ws.vals_in, ws.vals_out, (size_t)vk, 0,
+                                                   32 + bits, st);
+    if (e != hipSuccess) {
+        set_error("%s: sort failed: %s", name, hipGetErrorString(e));
+        return MVSDET_ERR_HIP;
+    }
+    if (hipMemsetAsync(ws.ranges, 0, (size_t)V * tiles * sizeof(int2), st) != hipSuccess) {
+        set_error("%s: clearing the tile ranges failed", name);
+        return MVSDET_ERR_HIP;
+    }
+    hipLaunchKernelGGL(splat_ranges_kernel, dim3((unsigned)((vk + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, ws, vk,
+                       (unsigned)(V * tiles));
+    hipLaunchKernelGGL((splat_render_kernel<COL, DEP>), dim3(tiles_x, tiles_y, V), dim3(kThreads), 0, st, ws, background, image, G, H, W,
+                       tiles_x, tiles, dz);
+    MVS_LAUNCH_CHECK(name);
+    return MVSDET_OK;
+}
+
+// The two launches of every form's backward.
+template <bool COL, bool DEP>
+int splat_backward(const char* name, const SplatIn& in, const float* cams, const float* background, const float* g_image, void* workspace,
+                   size_t workspace_bytes, float* slots, float* g_means, float* g_covariances, float* g_harmonics, float* g_opacities, int V,
+                   int G, int d_sh, int use_sh, int H, int W, int max_keys, SplatDepth<DEP> dz, hipStream_t st) {
+    MVS_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: the workspace must be 256-byte aligned", name);
+    const SplatWs ws = splat_layout(workspace, V, G, H, W, max_keys);
+    MVS_REQUIRE_WORKSPACE(name, workspace_bytes, ws.total);
+    const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile, tiles = tiles_x * tiles_y;
+    hipLaunchKernelGGL((splat_render_bwd_kernel<COL, DEP>), dim3(tiles_x, tiles_y, V), dim3(kThreads), 0, st, ws, background, g_image, slots,
+                       G, H, W, tiles_x, tiles, dz);
+    hipLaunchKernelGGL((splat_preprocess_bwd_kernel<COL, DEP>), dim3((G + kWave - 1) / kWave), dim3(kWave), 0, st, in, cams, ws, slots,
+                       g_means, g_covariances, g_harmonics, g_opacities, V, G, d_sh, use_sh, H, W, max_keys, dz);
+    MVS_LAUNCH_CHECK(name);
+    return MVSDET_OK;
+}
+
 }  // namespace
 }  // namespace mvsdet
 
@@ -734,43 +917,9 @@ extern "C" int mvsdet_splat_forward_f32(const float* means, const int64_t* means
     MVS_REQUIRE(means && means_strides && covariances && cov_strides && harmonics && sh_strides && opacities && cams && background && image &&
                     workspace,
                 "splat_forward: NULL pointer");
-    MVS_REQUIRE(((uintptr_t)workspace & 255) == 0, "splat_forward: the workspace must be 256-byte aligned");
-    const SplatWs ws = splat_layout(workspace, V, G, H, W, max_keys);
-    MVS_REQUIRE_WORKSPACE("splat_forward", workspace_bytes, ws.total);
     const SplatIn in = splat_inputs(means, means_strides, covariances, cov_strides, harmonics, sh_strides, opacities, opacity_stride);
-    const hipStream_t st = (hipStream_t)stream;
-    const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile, tiles = tiles_x * tiles_y;
-    const int64_t vg = (int64_t)V * G, vk = (int64_t)V * max_keys;
-    hipLaunchKernelGGL(splat_preprocess_kernel, dim3((unsigned)((vg + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, in, cams, ws, V, G, d_sh,
-                       use_sh, H, W, tiles_x, tiles_y);
-    hipLaunchKernelGGL(splat_scan_kernel, dim3(V), dim3(kThreads), 0, st, ws, G, max_keys);
-    const int64_t most = vg > vk ? vg : vk;
-    const unsigned emit_blocks = (unsigned)((most + kThreads - 1) / kThreads < 4096 ? (most + kThreads - 1) / kThreads : 4096);
-    hipLaunchKernelGGL(splat_emit_kernel, dim3(emit_blocks), dim3(kThreads), 0, st, ws, V, G, max_keys, tiles_x, tiles);
-    MVS_LAUNCH_CHECK("splat_forward (preprocess)");
-    const unsigned bits = tile_bits(V, (size_t)tiles);
-    size_t sort_bytes = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, sort_bytes, ws.keys_in, ws.keys_out, ws.vals_in, ws.vals_out, (size_t)vk, 0, 32 + bits, st);
-    if (e != hipSuccess || sort_bytes > ws.sort_bytes) {
-        set_error("splat_forward: the sort asks for %zu bytes, %zu set aside (%s)", sort_bytes, ws.sort_bytes, hipGetErrorString(e));
-        return MVSDET_ERR_WORKSPACE;
-    }
-    sort_bytes = ws.sort_bytes;
-    e = rocprim::radix_sort_pairs(ws.sort_tmp, sort_bytes, ws.keys_in, ws.keys_out, ws.vals_in, ws.vals_out, (size_t)vk, 0,
-                                                   32 + bits, st);
-    if (e != hipSuccess) {
-        set_error("splat_forward: sort failed: %s", hipGetErrorString(e));
-        return MVSDET_ERR_HIP;
-    }
-    if (hipMemsetAsync(ws.ranges, 0, (size_t)V * tiles * sizeof(int2), st) != hipSuccess) {
-        set_error("splat_forward: clearing the tile ranges failed");
-        return MVSDET_ERR_HIP;
-    }
-    hipLaunchKernelGGL(splat_ranges_kernel, dim3((unsigned)((vk + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, ws, vk,
-                       (unsigned)(V * tiles));
-    hipLaunchKernelGGL(splat_render_kernel, dim3(tiles_x, tiles_y, V), dim3(kThreads), 0, st, ws, background, image, G, H, W, tiles_x, tiles);
-    MVS_LAUNCH_CHECK("splat_forward (render)");
-    return MVSDET_OK;
+    return splat_forward<true, false>("splat_forward", in, cams, background, image, workspace, workspace_bytes, V, G, d_sh, use_sh, H, W,
+                                      max_keys, SplatDepth<false>{}, (hipStream_t)stream);
 }
 
 extern "C" int mvsdet_splat_backward_f32(const float* means, const int64_t* means_strides, const float* covariances, const int64_t* cov_strides,
@@ -783,16 +932,62 @@ extern "C" int mvsdet_splat_backward_f32(const float* means, const int64_t* mean
     MVS_REQUIRE(means && means_strides && covariances && cov_strides && harmonics && sh_strides && opacities && cams && background && g_image &&
                     workspace && slots && g_means && g_covariances && g_harmonics && g_opacities,
                 "splat_backward: NULL pointer");
-    MVS_REQUIRE(((uintptr_t)workspace & 255) == 0, "splat_backward: the workspace must be 256-byte aligned");
-    const SplatWs ws = splat_layout(workspace, V, G, H, W, max_keys);
-    MVS_REQUIRE_WORKSPACE("splat_backward", workspace_bytes, ws.total);
     const SplatIn in = splat_inputs(means, means_strides, covariances, cov_strides, harmonics, sh_strides, opacities, opacity_stride);
+    return splat_backward<true, false>("splat_backward", in, cams, background, g_image, workspace, workspace_bytes, slots, g_means,
+                                       g_covariances, g_harmonics, g_opacities, V, G, d_sh, use_sh, H, W, max_keys, SplatDepth<false>{},
+                                       (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------ rendered depth
+// with_colour 1: colour + depth in one pass.  with_colour 0: depth alone -- harmonics, sh_strides, background and image / g_image /
+// g_harmonics are not read and may be NULL; d_sh and use_sh are ignored.
+extern "C" int mvsdet_splat_forward_depth_f32(const float* means, const int64_t* means_strides, const float* covariances,
+                                              const int64_t* cov_strides, const float* harmonics, const int64_t* sh_strides,
+                                              const float* opacities, int64_t opacity_stride, const float* cams, const float* near,
+                                              const float* far, const float* background, float* image, float* depth, float* values,
+                                              void* workspace, size_t workspace_bytes, int V, int G, int d_sh, int use_sh, int with_colour,
+                                              int mode, int H, int W, int max_keys, mvsdet_stream_t stream) {
+    if (!with_colour) d_sh = 1, use_sh = 0;
+    if (int rc = check_splat("splat_forward_depth", V, G, d_sh, use_sh, H, W, max_keys)) return rc;
+    if (int rc = check_splat_depth("splat_forward_depth", V, mode, max_keys)) return rc;
+    MVS_REQUIRE(means && means_strides && covariances && cov_strides && opacities && cams && near && far && depth && values && workspace &&
+                    (!with_colour || (harmonics && sh_strides && background && image)),
+                "splat_forward_depth: NULL pointer");
+    const int64_t none[3] = {0, 0, 0};
+    const SplatIn in = splat_inputs(means, means_strides, covariances, cov_strides, with_colour ? harmonics : nullptr,
+                                    with_colour ? sh_strides : none, opacities, opacity_stride);
+    const SplatDepth<true> dz{near, far, values, depth, mode};
     const hipStream_t st = (hipStream_t)stream;
-    const int tiles_x = (W + kTile - 1) / kTile, tiles_y = (H + kTile - 1) / kTile, tiles = tiles_x * tiles_y;
-    hipLaunchKernelGGL(splat_render_bwd_kernel, dim3(tiles_x, tiles_y, V), dim3(kThreads), 0, st, ws, background, g_image, slots, G, H, W,
-                       tiles_x, tiles);
-    hipLaunchKernelGGL(splat_preprocess_bwd_kernel, dim3((G + kWave - 1) / kWave), dim3(kWave), 0, st, in, cams, ws, slots, g_means,
-                       g_covariances, g_harmonics, g_opacities, V, G, d_sh, use_sh, H, W, max_keys);
-    MVS_LAUNCH_CHECK("splat_backward");
-    return MVSDET_OK;
+    if (with_colour)
+        return splat_forward<true, true>("splat_forward_depth", in, cams, background, image, workspace, workspace_bytes, V, G, d_sh, use_sh, H,
+                                         W, max_keys, dz, st);
+    return splat_forward<false, true>("splat_forward_depth", in, cams, nullptr, nullptr, workspace, workspace_bytes, V, G, d_sh, use_sh, H, W,
+                                      max_keys, dz, st);
+}
+
+extern "C" int mvsdet_splat_backward_depth_f32(const float* means, const int64_t* means_strides, const float* covariances,
+                                               const int64_t* cov_strides, const float* harmonics, const int64_t* sh_strides,
+                                               const float* opacities, int64_t opacity_stride, const float* cams, const float* near,
+                                               const float* far, const float* background, const float* g_image, const float* g_depth,
+                                               const float* values, void* workspace, size_t workspace_bytes, float* slots, float* g_means,
+                                               float* g_covariances, float* g_harmonics, float* g_opacities, int V, int G, int d_sh,
+                                               int use_sh, int with_colour, int mode, int H, int W, int max_keys, mvsdet_stream_t stream) {
+    if (!with_colour) d_sh = 1, use_sh = 0;
+    if (int rc = check_splat("splat_backward_depth", V, G, d_sh, use_sh, H, W, max_keys)) return rc;
+    if (int rc = check_splat_depth("splat_backward_depth", V, mode, max_keys)) return rc;
+    MVS_REQUIRE(means && means_strides && covariances && cov_strides && opacities && cams && near && far && g_depth && values && workspace &&
+                    slots && g_means && g_covariances && g_opacities &&
+                    (!with_colour || (harmonics && sh_strides && background && g_image && g_harmonics)),
+                "splat_backward_depth: NULL pointer");
+    const int64_t none[3] = {0, 0, 0};
+    const SplatIn in = splat_inputs(means, means_strides, covariances, cov_strides, with_colour ? harmonics : nullptr,
+                                    with_colour ? sh_strides : none, opacities, opacity_stride);
+    // the kernels only read values and g_depth; the struct is shared with the forward, which writes them
+    const SplatDepth<true> dz{near, far, const_cast<float*>(values), const_cast<float*>(g_depth), mode};
+    const hipStream_t st = (hipStream_t)stream;
+    if (with_colour)
+        return splat_backward<true, true>("splat_backward_depth", in, cams, background, g_image, workspace, workspace_bytes, slots, g_means,
+                                          g_covariances, g_harmonics, g_opacities, V, G, d_sh, use_sh, H, W, max_keys, dz, st);
+    return splat_backward<false, true>("splat_backward_depth", in, cams, nullptr, nullptr, workspace, workspace_bytes, slots, g_means,
+                                       g_covariances, nullptr, g_opacities, V, G, d_sh, use_sh, H, W, max_keys, dz, st);
 }

@@ -4,8 +4,13 @@ gs_src/model/decoder/cuda_splatting.py imports `GaussianRasterizationSettings` a
 extension that has no ROCm build.  These two classes take what render_cuda hands them and run one view of `ops.splat.rasterize`.
 `integration.patch_reference_splatting()` registers this module under the extension's name; nothing does so by itself.
 
-What is not here: `scales` / `rotations` (the covariance built inside the extension), `scale_modifier` other than 1, depth output and
-the orthographic form.  There is no CPU path.
+The reference's own, unmodified render_depth_cuda runs through these classes too: it hands every Gaussian's mapped depth over as
+`colors_precomp` in three equal channels and averages them, at the price of a second full rasterisation.  The fused form -- depth as a
+fourth blended channel of the colour's pass, or alone -- is reached through `functional.render_depth_cuda` and
+`functional.decode_splatting(depth_mode=...)`, not through this shim: the extension's call form has no depth output.
+
+What is not here: `scales` / `rotations` (the covariance built inside the extension), `scale_modifier` other than 1 and the
+orthographic form.  There is no CPU path.
 """
 from __future__ import annotations
 

@@ -510,27 +510,74 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
         raise ValueError(f"render_cuda: {extrinsics.shape[0]} cameras and {background_color.shape[0]} backgrounds for {b} batch rows")
     keys = ops.splat.default_max_keys(G) if max_keys is None else int(max_keys)
     cams = ops.splat.splat_cameras(extrinsics, intrinsics, near, far, bool(scale_invariant))
-    if b == 1 or all(t.stride(0) == 0 for t in (means, covs, shs, opacs)):
+    if _one_call(b, means, covs, shs, opacs):
         return ops.splat.rasterize(means[0], covs[0], shs[0], opacs[0], cams, background_color, h, w, keys, bool(use_sh))[0]
     return torch.cat([ops.splat.rasterize(means[i], covs[i], shs[i], opacs[i], cams[i:i + 1], background_color[i:i + 1], h, w, keys,
                                           bool(use_sh))[0] for i in range(b)])
 
 
+def _one_call(b: int, *tensors) -> bool:
+    """render_cuda's rule: B == 1, or every Gaussian tensor an expanded view of one set -> one call over the B views."""
+    return b == 1 or all(t.stride(0) == 0 for t in tensors)
+
+
+def render_depth_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, image_shape: Tuple[int, int],
+                      gaussian_means: Tensor, gaussian_covariances: Tensor, gaussian_opacities: Tensor, scale_invariant: bool = True,
+                      mode: str = "depth", *, max_keys=None) -> Tensor:
+    """gs_src/model/decoder/cuda_splatting.py:237-280: extrinsics (B,4,4), intrinsics (B,3,3), near / far (B), gaussian_means (B,G,3),
+    gaussian_covariances (B,G,3,3), gaussian_opacities (B,G) -> depth (B,h,w).  Every Gaussian's camera-space z, mapped by `mode`
+    ("depth", "disparity", "relative_disparity", "log" -- the last with the reference's inverted clamp, log(far) whenever near <= far),
+    blended over a background of 0.  The reference renders that value as three equal colour channels in a second full rasterisation and
+    returns their mean, (x + x + x) / 3; here it is blended once by `ops.splat.depth_only` and returned as x: the two can differ in
+    the last bit.  Batch rows go out as in `render_cuda`: expanded rows or B == 1 as one call, distinct rows one call each."""
+    if mode not in ops.splat.DEPTH_MODES:
+        raise ValueError(f"render_depth_cuda: mode {mode!r} must be one of {ops.splat.DEPTH_MODES}")
+    extrinsics, intrinsics, near, far, means, covs, opacs = amp_fp32(extrinsics, intrinsics, near, far, gaussian_means, gaussian_covariances,
+                                                                     gaussian_opacities)
+    if means.dim() != 3 or covs.dim() != 4 or opacs.dim() != 2:
+        raise ValueError(f"render_depth_cuda: means {tuple(means.shape)}, covariances {tuple(covs.shape)} and opacities "
+                         f"{tuple(opacs.shape)} must be (B,G,3), (B,G,3,3) and (B,G)")
+    b, G = means.shape[:2]
+    h, w = (int(v) for v in image_shape)
+    if extrinsics.shape[0] != b:
+        raise ValueError(f"render_depth_cuda: {extrinsics.shape[0]} cameras for {b} batch rows")
+    keys = ops.splat.default_max_keys(G) if max_keys is None else int(max_keys)
+    cams = ops.splat.splat_cameras(extrinsics, intrinsics, near, far, bool(scale_invariant))
+    if _one_call(b, means, covs, opacs):
+        return ops.splat.depth_only(means[0], covs[0], opacs[0], cams, near, far, h, w, keys, mode)[0]
+    return torch.cat([ops.splat.depth_only(means[i], covs[i], opacs[i], cams[i:i + 1], near[i:i + 1], far[i:i + 1], h, w, keys, mode)[0]
+                      for i in range(b)])
+
+
 def decode_splatting(gaussians, extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, image_shape: Tuple[int, int],
-                     background_color=None, *, max_keys=None) -> Tensor:
+                     background_color=None, *, max_keys=None, depth_mode=None):
     """The colour output of DecoderSplattingCUDA.forward (gs_src/model/decoder/decoder_splatting_cuda.py:37-62): gaussians with
     `.means` (b,G,3), `.covariances` (b,G,3,3), `.harmonics` (b,G,3,d_sh) and `.opacities` (b,G); extrinsics (b,v,4,4), intrinsics
     (b,v,3,3), near / far (b,v) -> colour (b,v,3,h,w).  One rasteriser call per batch element over its v views: the Gaussians are not
-    repeated per view.  background_color (3), default black (the decoder's registered buffer comes from the dataset config)."""
+    repeated per view.  background_color (3), default black (the decoder's registered buffer comes from the dataset config).
+    depth_mode: one of render_depth_cuda's modes -> (colour, depth (b,v,h,w)), both from ONE fused call per batch element
+    (`ops.splat.rasterize_depth`) where the reference rasterises a second time; the colour keeps the bits it has without it."""
     b, v = extrinsics.shape[:2]
     dev = extrinsics.device
     bg = torch.zeros(3, dtype=torch.float32, device=dev) if background_color is None else background_color.to(dev)
-    rows = []
+    if depth_mode is not None and depth_mode not in ops.splat.DEPTH_MODES:
+        raise ValueError(f"decode_splatting: depth_mode {depth_mode!r} must be None or one of {ops.splat.DEPTH_MODES}")
+    rows, depths = [], []
     for i in range(b):
-        rows.append(render_cuda(extrinsics[i], intrinsics[i], near[i], far[i], image_shape, bg.expand(v, 3),
-                                gaussians.means[i].expand(v, -1, -1), gaussians.covariances[i].expand(v, -1, -1, -1),
-                                gaussians.harmonics[i].expand(v, -1, -1, -1), gaussians.opacities[i].expand(v, -1), max_keys=max_keys))
-    return torch.stack(rows)
+        if depth_mode is None:
+            rows.append(render_cuda(extrinsics[i], intrinsics[i], near[i], far[i], image_shape, bg.expand(v, 3),
+                                    gaussians.means[i].expand(v, -1, -1), gaussians.covariances[i].expand(v, -1, -1, -1),
+                                    gaussians.harmonics[i].expand(v, -1, -1, -1), gaussians.opacities[i].expand(v, -1), max_keys=max_keys))
+            continue
+        E, K, n, f, bgs, means, covs, shs, opacs = amp_fp32(extrinsics[i], intrinsics[i], near[i], far[i], bg.expand(v, 3), gaussians.means[i],
+                                                            gaussians.covariances[i], gaussians.harmonics[i], gaussians.opacities[i])
+        h, w = (int(x) for x in image_shape)
+        keys = ops.splat.default_max_keys(means.shape[0]) if max_keys is None else int(max_keys)
+        cams = ops.splat.splat_cameras(E, K, n, f, True)
+        colour, depth, _, _ = ops.splat.rasterize_depth(means, covs, shs, opacs, cams, n, f, bgs, h, w, keys, True, depth_mode)
+        rows.append(colour)
+        depths.append(depth)
+    return torch.stack(rows) if depth_mode is None else (torch.stack(rows), torch.stack(depths))
 
 
 class PixelGaussians:

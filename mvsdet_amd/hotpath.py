@@ -582,7 +582,7 @@ class MVSDetHotPath:
 
     def novel_views(self, outputs, feature: Tensor, img_meta: dict, to_gaussians, tgt_c2w, tgt_intrinsic, tgt_shape, rgb_raw=None, *,
                     num_surfaces: int = 1, gaussian_scale_min: float = 0.5, gaussian_scale_max: float = 15.0, sh_degree: int = 4,
-                    num_select: int = 3, sh_rotation=None, background_color=None, max_keys=None) -> Tensor:
+                    num_select: int = 3, sh_rotation=None, background_color=None, max_keys=None, depth_mode=None):
         """The novel-view branch of extract_feat for one scene (mvsdet.py:519-677) -> colour (1,n_tgt,3,H,W), what
         `self.decoder.forward(...)` returns as `.color`.  outputs: the scene's `SceneOutputs`; feature (N,C,Hf,Wf); to_gaussians:
         the caller's nn.Sequential(ReLU, Linear) with num_surfaces * (2 + 7 + 3 d_sh) outputs, run by torch; tgt_c2w (n_tgt,4,4),
@@ -591,7 +591,9 @@ class MVSDetHotPath:
         feature rows, depth_coding and rgb_raw are concatenated as :561-569; opacity is the largest probability (:581-582); the depth
         along the ray is depth_coding / (depth_scale + 1e-8) (:583); then `functional.pixel_gaussians` and
         `functional.decode_splatting` with near / far = near_far_range.  Gradients reach feature, to_gaussians' parameters, depth_coding
-        and the opacity.  The scale / degree defaults are those of the shipped configs."""
+        and the opacity.  The scale / degree defaults are those of the shipped configs.  depth_mode: one of
+        `functional.render_depth_cuda`'s modes -> (colour, depth (1,n_tgt,H,W)), the decoder's `.depth`, from the same fused
+        rasteriser call; the depth carries gradients to the same places."""
         geo = outputs["geometry"]
         h, w = geo.height, geo.width
         dev = feature.device
@@ -641,7 +643,7 @@ class MVSDetHotPath:
         near = torch.full((1, n_tgt), self.near_far_range[0])
         far = torch.full((1, n_tgt), self.near_far_range[1])
         tgt, Kt, near, far = (ops._common.to_device(t, dev) for t in (tgt[None].contiguous(), Kt[None, :, :3, :3].contiguous(), near, far))
-        return F_.decode_splatting(gaussians, tgt, Kt, near, far, (H, W), background_color, max_keys=max_keys)
+        return F_.decode_splatting(gaussians, tgt, Kt, near, far, (H, W), background_color, max_keys=max_keys, depth_mode=depth_mode)
 
     def nvs_loss(self, rgb_preds, gt_rgb) -> dict:
         """`loss_nvs` of MVSDet.loss (nvs_loss_func, mvsdet.py:878-890, without use_nerf_mask): rgb_preds, one colour (1,n_tgt,3,H,W)
@@ -650,22 +652,30 @@ class MVSDetHotPath:
             rgb_preds, gt_rgb = [rgb_preds], [gt_rgb]
         return F_.nvs_loss_func(list(rgb_preds), list(gt_rgb))
 
-    def nvs_scores(self, rgb_preds, gt_rgb, evaluator=None) -> dict:
-        """What the reference's test loop stores for a scene (mvsdet.py:1017-1040: save_rendered_img_Image; no rendered depth in the
-        shipped configs, so rmse is 0): rgb_preds, the scene's colour (1,n_tgt,3,H,W) as `novel_views` returns it (or (n_tgt,3,H,W)),
+    def nvs_scores(self, rgb_preds, gt_rgb, evaluator=None, depth_preds=None, gt_depth=None) -> dict:
+        """What the reference's test loop stores for a scene (mvsdet.py:1017-1040: save_rendered_img_Image, and save_rendered_depth
+        where a rendered depth exists): rgb_preds, the scene's colour (1,n_tgt,3,H,W) as `novel_views` returns it (or (n_tgt,3,H,W)),
         gt_rgb the matching (n_tgt,3,H,W) in [0,1] -> dict(psnr=, ssim=, rmse=) as 0-dim float64 device tensors, the means over the
-        target views.  evaluator: an `evaluation.NVSEvaluator` that is fed the scene (it then scores it; no second launch).  No host
-        synchronisation."""
+        target views.  depth_preds (1,n_tgt,H,W) as `novel_views(depth_mode=...)` returns it (or (n_tgt,H,W)) with gt_depth
+        (n_tgt,H,W): rmse is then what `functional.save_rendered_depth` gives for the pair; without the pair it is 0 (the shipped
+        configs render no depth).  evaluator: an `evaluation.NVSEvaluator` that is fed the scene (it then scores it; no second
+        launch).  No host synchronisation."""
         if not isinstance(rgb_preds, Tensor):
             if len(rgb_preds) != 1:
                 raise ValueError(f"nvs_scores: one scene at a time (got {len(rgb_preds)}); NVSEvaluator.update takes lists")
             rgb_preds, gt_rgb = rgb_preds[0], gt_rgb if isinstance(gt_rgb, Tensor) else gt_rgb[0]
         rgb = rgb_preds[0] if rgb_preds.dim() == 5 else rgb_preds
+        if (depth_preds is None) != (gt_depth is None):
+            raise ValueError("nvs_scores: depth_preds and gt_depth come as a pair")
+        if depth_preds is not None:
+            if not isinstance(depth_preds, Tensor):
+                depth_preds, gt_depth = depth_preds[0], gt_depth if isinstance(gt_depth, Tensor) else gt_depth[0]
+            depth_preds = depth_preds[0] if depth_preds.dim() == 4 else depth_preds
         if evaluator is not None:
-            evaluator.update(rgb, gt_rgb)
+            evaluator.update(rgb, gt_rgb, depth_preds, gt_depth)
             scene = evaluator.last_scene
         else:
-            scene = ops.nvsmetric.nvs_score(None, rgb, gt_rgb)[1]
+            scene = ops.nvsmetric.nvs_score(None, rgb, gt_rgb, depth_preds, gt_depth)[1]
         return dict(psnr=scene[0], ssim=scene[1], rmse=scene[2])
 
     # name -> (detector tail on the side stream, view streams of the cost network beside it; None = the module's own setting)

@@ -1,4 +1,5 @@
-"""Gaussian rasteriser (csrc/splat.hip): what gs_src/model/decoder/cuda_splatting.py::render_cuda asks of `diff_gaussian_rasterization`.
+"""Gaussian rasteriser (csrc/splat.hip): what gs_src/model/decoder/cuda_splatting.py::render_cuda asks of `diff_gaussian_rasterization`,
+and render_depth_cuda's depth as a fourth blended channel of the same pass (`rasterize_depth`) or alone (`depth_only`).
 
 The names live in this module only (`ops.splat.<name>`); they are not re-exported by the package.
 """
@@ -14,6 +15,8 @@ from ._common import _NS, _lib, req, stream
 
 SPLAT_CAM = 40            # floats per view: view matrix 16, full projection 16, tan fov x / y, camera position 3, scale, 2 unused
 SPLAT_SLOT = 9            # floats per (tile, Gaussian) gradient slot of the backward
+SPLAT_SLOT_DEPTH = 10     # the same in the depth forms: one more float, dL/dd
+DEPTH_MODES = ("depth", "disparity", "relative_disparity", "log")   # render_depth_cuda's modes, in the C ABI's numbering
 SPLAT_TILE = 16
 SPLAT_KEYS_PER_GAUSSIAN = 8   # default key capacity of a view: 8 (Gaussian, tile) pairs per Gaussian (DESIGN 4.15 has the measured need)
 SPLAT_SH = (1, 4, 9, 16, 25)
@@ -183,7 +186,197 @@ def _rz_bwd(ctx, g_image, g_workspace):
 
 rasterize.register_autograd(_rz_bwd, setup_context=_rz_setup)
 
-for _op in (splat_cameras, rasterize):
+# ------------------------------------------------------------------------------------------- rendered depth
+def _depth_mode(name: str, mode: str) -> int:
+    if mode not in DEPTH_MODES:
+        raise ValueError(f"{name}: mode {mode!r} must be one of {DEPTH_MODES}")
+    return DEPTH_MODES.index(mode)
+
+
+def _check_depth(name: str, means: Tensor, covariances: Tensor, harmonics, opacities: Tensor, cams: Tensor, near: Tensor, far: Tensor,
+                 background, H: int, W: int, max_keys: int, use_sh: bool, mode: str):
+    """The checks of `_check` (with a stand-in colour where there is none) and the depth forms' own."""
+    code = _depth_mode(name, mode)
+    req(near, "near", dim=1)
+    req(far, "far", dim=1)
+    colour = harmonics is not None
+    if not colour:
+        req(means, "means", dim=2)
+        harmonics, background, use_sh = means.new_empty((means.shape[0], 3, 1)), cams.new_empty((cams.shape[0], 3)), False
+    V, G, d_sh, cams, background = _check(name, means, covariances, harmonics, opacities, cams, background, H, W, max_keys, use_sh)
+    if near.shape[0] != V or far.shape[0] != V:
+        raise ValueError(f"{name}: near {tuple(near.shape)} and far {tuple(far.shape)} must be ({V})")
+    if SPLAT_SLOT_DEPTH * V * max_keys >= 2 ** 31:
+        raise ValueError(f"{name}: V={V} max_keys={max_keys} exceeds the limit 10 V max_keys < 2^31")
+    return V, G, d_sh, cams, near.contiguous(), far.contiguous(), (background if colour else None), code
+
+
+def _depth_forward(name, means, covariances, harmonics, opacities, cams, near, far, background, H, W, max_keys, use_sh, mode):
+    V, G, d_sh, cams, near, far, background, code = _check_depth(name, means, covariances, harmonics, opacities, cams, near, far, background,
+                                                                 H, W, max_keys, use_sh, mode)
+    dev, colour = means.device, harmonics is not None
+    image = torch.empty((V, 3, H, W), dtype=torch.float32, device=dev) if colour else None
+    depth = torch.empty((V, H, W), dtype=torch.float32, device=dev)
+    values = torch.empty((V, G), dtype=torch.float32, device=dev)
+    workspace = torch.empty((workspace_bytes(V, G, H, W, max_keys),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mvsdet_splat_forward_depth_f32(
+            _lib.ptr(means), _strides(means), _lib.ptr(covariances), _strides(covariances), _lib.ptr(harmonics) if colour else None,
+            _strides(harmonics) if colour else None, _lib.ptr(opacities), opacities.stride(0), _lib.ptr(cams), _lib.ptr(near), _lib.ptr(far),
+            _lib.ptr(background) if colour else None, _lib.ptr(image) if colour else None, _lib.ptr(depth), _lib.ptr(values),
+            _lib.ptr(workspace), workspace.numel(), V, G, d_sh, int(use_sh), int(colour), code, H, W, max_keys, stream(means)), name)
+    return image, depth, values, workspace
+
+
+def _depth_backward(name, means, covariances, harmonics, opacities, cams, near, far, background, values, workspace, g_image, g_depth, H, W,
+                    max_keys, use_sh, mode):
+    V, G, d_sh, cams, near, far, background, code = _check_depth(name, means, covariances, harmonics, opacities, cams, near, far, background,
+                                                                 H, W, max_keys, use_sh, mode)
+    dev, colour = means.device, harmonics is not None
+    req(g_depth, "g_depth", dim=3)
+    req(values, "values", dim=2)
+    req(workspace, "workspace", dtype=torch.uint8, dim=1)
+    if tuple(g_depth.shape) != (V, H, W) or tuple(values.shape) != (V, G):
+        raise ValueError(f"{name}: g_depth {tuple(g_depth.shape)} and values {tuple(values.shape)} must be {(V, H, W)} and {(V, G)}")
+    if colour:
+        req(g_image, "g_image", dim=4)
+        if tuple(g_image.shape) != (V, 3, H, W):
+            raise ValueError(f"{name}: g_image {tuple(g_image.shape)} must be {(V, 3, H, W)}")
+        g_image = g_image.contiguous()
+    g_depth, values = g_depth.contiguous(), values.contiguous()
+    slots = torch.empty((V * max_keys * SPLAT_SLOT_DEPTH,), dtype=torch.float32, device=dev)
+    g_means = torch.empty((G, 3), dtype=torch.float32, device=dev)
+    g_cov = torch.empty((G, 3, 3), dtype=torch.float32, device=dev)
+    g_sh = torch.empty((G, 3, d_sh), dtype=torch.float32, device=dev) if colour else None
+    g_op = torch.empty((G,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().mvsdet_splat_backward_depth_f32(
+            _lib.ptr(means), _strides(means), _lib.ptr(covariances), _strides(covariances), _lib.ptr(harmonics) if colour else None,
+            _strides(harmonics) if colour else None, _lib.ptr(opacities), opacities.stride(0), _lib.ptr(cams), _lib.ptr(near), _lib.ptr(far),
+            _lib.ptr(background) if colour else None, _lib.ptr(g_image) if colour else None, _lib.ptr(g_depth), _lib.ptr(values),
+            _lib.ptr(workspace), workspace.numel(), _lib.ptr(slots), _lib.ptr(g_means), _lib.ptr(g_cov), _lib.ptr(g_sh) if colour else None,
+            _lib.ptr(g_op), V, G, d_sh, int(use_sh), int(colour), code, H, W, max_keys, stream(means)), name)
+    return g_means, g_cov, g_sh, g_op
+
+
+@torch.library.custom_op(f"{_NS}::splat_rasterize_depth", mutates_args=(), device_types="cuda")
+def rasterize_depth(means: Tensor, covariances: Tensor, harmonics: Tensor, opacities: Tensor, cams: Tensor, near: Tensor, far: Tensor,
+                    background: Tensor, H: int, W: int, max_keys: int, use_sh: bool, mode: str) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """`rasterize` with the rendered depth of render_depth_cuda as a fourth blended channel of the same pass -> (image (V,3,H,W),
+    depth (V,H,W), values (V,G), workspace).  near / far (V): the unscaled bounds `splat_cameras` was given; mode: one of
+    DEPTH_MODES.  values is what the reference calls fake_color -- every Gaussian's camera-space z (before the scale_invariant
+    scaling) mapped by the mode, 0 where culled; it is returned to be looked at and carries no gradient.  depth = sum values alpha T
+    over a background of 0, with the colour's alpha, T, skips and early stop; NaN for a view over its key capacity.  image has the
+    bits of `rasterize`, and the workspace is the same (`status`, `radii`).  Differentiable in means, covariances, harmonics and
+    opacities, through both outputs."""
+    return _depth_forward("rasterize_depth", means, covariances, harmonics, opacities, cams, near, far, background, H, W, max_keys, use_sh,
+                          mode)
+
+
+@rasterize_depth.register_fake
+def _(means, covariances, harmonics, opacities, cams, near, far, background, H, W, max_keys, use_sh, mode):
+    V, G = cams.shape[0], means.shape[0]
+    return (means.new_empty((V, 3, H, W)), means.new_empty((V, H, W)), means.new_empty((V, G)),
+            means.new_empty((workspace_bytes(V, G, H, W, max_keys),), dtype=torch.uint8))
+
+
+@torch.library.custom_op(f"{_NS}::splat_rasterize_depth_backward", mutates_args=(), device_types="cuda")
+def rasterize_depth_backward(means: Tensor, covariances: Tensor, harmonics: Tensor, opacities: Tensor, cams: Tensor, near: Tensor,
+                             far: Tensor, background: Tensor, values: Tensor, workspace: Tensor, g_image: Tensor, g_depth: Tensor, H: int,
+                             W: int, max_keys: int, use_sh: bool, mode: str) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Gradients of `rasterize_depth` for g_image (V,3,H,W) and g_depth (V,H,W) -> (means, covariances, harmonics, opacities).  The
+    depth enters the recurrence as one more channel and leaves one more per-(tile, Gaussian) partial sum, dL/dd, chained to the means
+    through the mode's derivative (0 for log); the fixed summation order of `rasterize_backward`, the same bits on every run."""
+    return _depth_backward("rasterize_depth_backward", means, covariances, harmonics, opacities, cams, near, far, background, values,
+                           workspace, g_image, g_depth, H, W, max_keys, use_sh, mode)
+
+
+@rasterize_depth_backward.register_fake
+def _(means, covariances, harmonics, opacities, cams, near, far, background, values, workspace, g_image, g_depth, H, W, max_keys, use_sh, mode):
+    G = means.shape[0]
+    return means.new_empty((G, 3)), means.new_empty((G, 3, 3)), means.new_empty(tuple(harmonics.shape)), means.new_empty((G,))
+
+
+@torch.library.custom_op(f"{_NS}::splat_depth_only", mutates_args=(), device_types="cuda")
+def depth_only(means: Tensor, covariances: Tensor, opacities: Tensor, cams: Tensor, near: Tensor, far: Tensor, H: int, W: int,
+               max_keys: int, mode: str) -> Tuple[Tensor, Tensor, Tensor]:
+    """The depth of `rasterize_depth` alone -> (depth (V,H,W), values (V,G), workspace): no harmonics are read, no colour is staged
+    or blended.  The same bits as the fused call's depth.  Differentiable in means, covariances and opacities."""
+    return _depth_forward("depth_only", means, covariances, None, opacities, cams, near, far, None, H, W, max_keys, False, mode)[1:]
+
+
+@depth_only.register_fake
+def _(means, covariances, opacities, cams, near, far, H, W, max_keys, mode):
+    V, G = cams.shape[0], means.shape[0]
+    return means.new_empty((V, H, W)), means.new_empty((V, G)), means.new_empty((workspace_bytes(V, G, H, W, max_keys),), dtype=torch.uint8)
+
+
+@torch.library.custom_op(f"{_NS}::splat_depth_only_backward", mutates_args=(), device_types="cuda")
+def depth_only_backward(means: Tensor, covariances: Tensor, opacities: Tensor, cams: Tensor, near: Tensor, far: Tensor, values: Tensor,
+                        workspace: Tensor, g_depth: Tensor, H: int, W: int, max_keys: int, mode: str) -> Tuple[Tensor, Tensor, Tensor]:
+    """Gradients of `depth_only` -> (means (G,3), covariances (G,3,3), opacities (G)).  Also the backward of a `rasterize_depth` whose
+    image received no gradient: the workspace is the same."""
+    gm, gc, _, go = _depth_backward("depth_only_backward", means, covariances, None, opacities, cams, near, far, None, values, workspace,
+                                    None, g_depth, H, W, max_keys, False, mode)
+    return gm, gc, go
+
+
+@depth_only_backward.register_fake
+def _(means, covariances, opacities, cams, near, far, values, workspace, g_depth, H, W, max_keys, mode):
+    G = means.shape[0]
+    return means.new_empty((G, 3)), means.new_empty((G, 3, 3)), means.new_empty((G,))
+
+
+def _no_grad_inputs(name, **tensors):
+    bad = [k for k, t in tensors.items() if t.requires_grad]
+    if bad:
+        raise RuntimeError(f"{name}: {', '.join(bad)} carry no gradient here; detach them")
+
+
+def _rd_setup(ctx, inputs, output):
+    means, covariances, harmonics, opacities, cams, near, far, background, H, W, max_keys, use_sh, mode = inputs
+    _no_grad_inputs("rasterize_depth", cams=cams, near=near, far=far, background=background)
+    ctx.mark_non_differentiable(output[2], output[3])   # the values and the workspace
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(means, covariances, harmonics, opacities, cams, near, far, background, output[2], output[3])
+    ctx.args = (H, W, max_keys, use_sh, mode)
+
+
+def _rd_bwd(ctx, g_image, g_depth, g_values, g_workspace):
+    none = (None,) * 9
+    if g_image is None and g_depth is None:
+        return (None,) * 13
+    means, covariances, harmonics, opacities, cams, near, far, background, values, workspace = ctx.saved_tensors
+    H, W, max_keys, use_sh, mode = ctx.args
+    if g_depth is None:      # the image alone was used: the colour-only backward reads the same workspace
+        return rasterize_backward(means, covariances, harmonics, opacities, cams, background, workspace, g_image, H, W, max_keys, use_sh) + none
+    if g_image is None:      # the depth alone was used
+        gm, gc, go = depth_only_backward(means, covariances, opacities, cams, near, far, values, workspace, g_depth, H, W, max_keys, mode)
+        return (gm, gc, torch.zeros_like(harmonics), go) + none
+    return rasterize_depth_backward(means, covariances, harmonics, opacities, cams, near, far, background, values, workspace, g_image,
+                                    g_depth, H, W, max_keys, use_sh, mode) + none
+
+
+def _do_setup(ctx, inputs, output):
+    means, covariances, opacities, cams, near, far, H, W, max_keys, mode = inputs
+    _no_grad_inputs("depth_only", cams=cams, near=near, far=far)
+    ctx.mark_non_differentiable(output[1], output[2])
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(means, covariances, opacities, cams, near, far, output[1], output[2])
+    ctx.args = (H, W, max_keys, mode)
+
+
+def _do_bwd(ctx, g_depth, g_values, g_workspace):
+    if g_depth is None:
+        return (None,) * 10
+    means, covariances, opacities, cams, near, far, values, workspace = ctx.saved_tensors
+    return depth_only_backward(means, covariances, opacities, cams, near, far, values, workspace, g_depth, *ctx.args) + (None,) * 7
+
+
+rasterize_depth.register_autograd(_rd_bwd, setup_context=_rd_setup)
+depth_only.register_autograd(_do_bwd, setup_context=_do_setup)
+
+for _op in (splat_cameras, rasterize, rasterize_depth, depth_only):
     _op.register_autocast("cuda", torch.float32)
 del _op
 

@@ -7,6 +7,12 @@ synchronisations (torch's sync debug mode).  The two are checked against each ot
 profiles/splat_timing.txt) and to stdout.
 
     python tools/splat_timing.py [--out FILE] [--rounds N]
+
+--depth: instead, the rendered depth at the same shape: forward + backward of the fused colour + depth call
+(ops.splat.rasterize_depth) against the two-pass route the colour rasteriser alone offers -- `rasterize` for the colour, then, as
+render_depth_cuda does, every Gaussian's depth built by torch operations from the means and rendered as three equal precomputed colour
+channels (`rasterize(use_sh=False)`, one view at a time: the value differs per view), averaged.  Both in one process, alternating
+round by round, device events; kernels and host synchronisations of one step of each.  Default --out profiles/splat_depth_timing.txt.
 """
 import argparse
 import math
@@ -25,9 +31,12 @@ from mvsdet_amd import functional as F_  # noqa: E402
 from mvsdet_amd.ops import splat  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "splat_timing.txt"))
+ap.add_argument("--out", default=None)
 ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--depth", action="store_true", help="time the fused colour + depth call against the two-pass route")
 args = ap.parse_args()
+if args.out is None:
+    args.out = os.path.join(ROOT, "profiles", "splat_depth_timing.txt" if args.depth else "splat_timing.txt")
 
 dev = torch.device("cuda:0")
 V, SRC, h, w, H, W, D = 2, 6, 59, 80, 239, 320, 25
@@ -141,6 +150,77 @@ def say(text):
     lines.append(text)
 
 
+def write_out():
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+def depth_timing(mode="depth", steps=20):
+    keys = splat.default_max_keys(G)
+    cams = splat.splat_cameras(ext, intr, near, far, True)
+    w2c_z = torch.linalg.inv(ext)[:, 2]                       # (V,4): the row that gives camera-space z; fixed cameras, built once
+    wdepth = torch.randn(V, H, W, generator=gen).to(dev)
+    black = torch.zeros(1, 3, device=dev)
+
+    def fused():
+        leaves = [t.detach().requires_grad_(True) for t in LEAVES]
+        image, depth, _, _ = splat.rasterize_depth(*leaves, cams, near, far, bg, H, W, keys, True, mode)
+        ((image * weight).sum() + (depth * wdepth).sum()).backward()
+        return image.detach(), depth.detach(), [t.grad for t in leaves]
+
+    def two_pass():
+        leaves = [t.detach().requires_grad_(True) for t in LEAVES]
+        image = splat.rasterize(*leaves, cams, bg, H, W, keys, True)[0]
+        value = leaves[0] @ w2c_z[:, :3].T + w2c_z[:, 3]       # (G,V)
+        depth = torch.stack([splat.rasterize(leaves[0], leaves[1], value[:, v, None, None].expand(G, 3, 1), leaves[3], cams[v:v + 1], black,
+                                             H, W, keys, False)[0][0].mean(0) for v in range(V)])
+        ((image * weight).sum() + (depth * wdepth).sum()).backward()
+        return image.detach(), depth.detach(), [t.grad for t in leaves]
+
+    def alone():
+        leaves = [t.detach().requires_grad_(True) for t in (means, covs, opac)]
+        depth = splat.depth_only(*leaves, cams, near, far, H, W, keys, mode)[0]
+        (depth * wdepth).sum().backward()
+        return depth.detach()
+
+    (ia, da, ga), (ib, db, gb) = fused(), two_pass()
+    say(f"rendered depth, mode {mode}: {V} views of {G} Gaussians, {H}x{W}, {D} harmonics, forward + backward of sum(image w) + sum(depth w')")
+    say(f"fused against two passes: image bits equal {bool(torch.equal(ia, ib))}; depth largest difference {float((da - db).abs().max()):.3g} "
+        f"of {float(db.abs().max()):.3g} (the value is z_s / s in the kernel and a matrix product in torch; one blend against the mean of three)")
+    for n, a, b in zip(("means", "covariances", "harmonics", "opacities"), ga, gb):
+        say(f"    d {n}: largest difference {float((a - b).abs().max()):.3g} of {float(b.abs().max()):.3g}")
+    assert float((da - db).abs().max()) <= 1e-4 * float(db.abs().max()), "the two disagree"
+    routes = (("fused colour + depth (rasterize_depth)", fused), ("two passes (rasterize + rasterize(use_sh=False) per view)", two_pass),
+              ("depth alone (depth_only)", alone))
+    for _, fn in routes:
+        for _ in range(2):
+            fn()
+    torch.cuda.synchronize()
+    ms = {name: [] for name, _ in routes}
+    for _ in range(args.rounds):                               # alternating: one round of each after the other
+        for name, fn in routes:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(steps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[name].append(e0.elapsed_time(e1) / steps)
+    for name, fn in routes:
+        syncs = count_syncs(fn)
+        n_kernels, _ = count_kernels(fn)
+        say(f"{name}: median {statistics.median(ms[name]):.3f} ms, min {min(ms[name]):.3f} ms per step over {args.rounds} rounds of {steps}; "
+            f"{syncs} host synchronisation(s); {n_kernels if n_kernels is not None else '?'} device kernels (autograd's own included)")
+    a, b = statistics.median(ms[routes[0][0]]), statistics.median(ms[routes[1][0]])
+    say(f"fused / two passes = {a / b:.3f} (medians)")
+    write_out()
+
+
+if args.depth:
+    depth_timing()
+    sys.exit(0)
+
 (ia, ga), (ib, gb) = hip(), aten()
 cams = splat.splat_cameras(ext, intr, near, far, True)
 _, ws = splat.rasterize(*LEAVES, cams, bg, H, W, splat.default_max_keys(G), True)
@@ -173,6 +253,4 @@ for name, fn, steps in (("functional.render_cuda forward + backward (HIP)", hip,
     if n_kernels is not None and n_kernels <= 60:
         for n in names:
             say(f"    {n[:150]}")
-os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as fh:
-    fh.write("\n".join(lines) + "\n")
+write_out()
