@@ -644,6 +644,47 @@ int mvsdet_adapter_backward_f32(const float* raw, int64_t raw_view_stride, int64
                                 float scale_min, float scale_max, mvsdet_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Gaussian head (csrc/gshead.hip): `to_gaussians` = nn.Sequential(ReLU, Linear) of the novel-view branch (mvsdet.py:210-216) on the
+ * rows extract_feat concatenates per source pixel (:561-569, process_rgb_raw :319-333), read in place -- no row matrix:
+ *   raw[v][r][m] = bias[m] + sum_k weight[m][k] relu(x[k]),  r = y w + x over the h x w crop of the Hf x Wf map, and for source view
+ *   ids[v]:  x[k] = feature[ids[v]][k][y][x] (k < C), x[C] = depth_coding[ids[v]][y][x], and with rgb (K = C + 4, else K = C + 1)
+ *   x[C + 1 + c] = rgb_rows[v][r][c], or from images (N,3,Hi,Wi), Hi >= 4h - 1, Wi >= 4w - 1, the mean
+ *   0.25 ((I[4y+1][4x+1] + I[4y+1][4x+2]) + (I[4y+2][4x+1] + I[4y+2][4x+2])) of image ids[v], channel c: what
+ *   F.interpolate(scale_factor=0.25, mode='bilinear') gives.  Only ratio 4.  relu is torch's: NaN stays NaN.
+ * Exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32), one output's products added in k order, the bias last.  No atomics, no
+ * host synchronisation; the same bits on every run.  DESIGN.md 4.19.
+ * Strides are HOST arrays of element strides, the w stride being 1: feature_strides[3] = n, c, h; depth_strides[2] = n, h of the
+ * (N,h,w) map; image_strides[3] = n, c, h; all in [0, 2^40).  ids (V) int64 on the device, unique; an id outside [0, N) is never
+ * used as an address: that view's raw is NaN and it gets no gradient.  weight (M,K), bias (M), raw and g (V,R,M), rgb_rows (V,R,3):
+ * contiguous.  rgb_rows and images may both be NULL (no rgb) but not both be given.  Limits: V <= 65535, h w < 2^29.
+ * mvsdet_gshead_forward_f32 (one launch) -> raw.   mvsdet_gshead_rgb_rows_f32 (one launch) -> rows (V,R,3): the image form alone.
+ * mvsdet_gshead_backward_input_f32 (one launch): g_feature[ids[v]][k][y][x] = (x[k] > 0) sum_m weight[m][k] g[v][r][m] for the
+ *   selected views' cropped pixels, g_depth_coding likewise; NOTHING else of the two buffers is written (the caller zeroes them).
+ *   The rgb columns get no gradient.
+ * mvsdet_gshead_backward_weight_f32 (two launches): g_weight (M,K) = sum_{v,r} g[v][r][m] relu(x[k]), g_bias (M) = sum_{v,r} g[v][r][m].
+ *   The pixels (v, r) are cut into chunks of chunk_pixels (rounded up to a multiple of 32; 0 = the default, 256); chunk sums go to
+ *   `partial` (mvsdet_gshead_partial_bytes; 0 for arguments the entry refuses) and are added in chunk order. */
+int mvsdet_gshead_forward_f32(const float* feature, const int64_t* feature_strides /*HOST[3]*/, const float* depth_coding,
+                              const int64_t* depth_strides /*HOST[2]*/, const float* rgb_rows /*may be NULL*/,
+                              const float* images /*may be NULL*/, const int64_t* image_strides /*HOST[3], NULL without images*/,
+                              const int64_t* ids, const float* weight, const float* bias, float* raw, int N, int V, int C, int K, int M,
+                              int h, int w, int Hf, int Wf, int Hi, int Wi, mvsdet_stream_t stream);
+int mvsdet_gshead_rgb_rows_f32(const float* images, const int64_t* image_strides /*HOST[3]*/, const int64_t* ids, float* rows, int N, int V,
+                               int h, int w, int Hi, int Wi, mvsdet_stream_t stream);
+int mvsdet_gshead_backward_input_f32(const float* feature, const int64_t* feature_strides /*HOST[3]*/, const float* depth_coding,
+                                     const int64_t* depth_strides /*HOST[2]*/, const int64_t* ids, const float* weight, const float* g,
+                                     float* g_feature, const int64_t* g_feature_strides /*HOST[3]*/, float* g_depth_coding,
+                                     const int64_t* g_depth_strides /*HOST[2]*/, int N, int V, int C, int K, int M, int h, int w, int Hf,
+                                     int Wf, mvsdet_stream_t stream);
+size_t mvsdet_gshead_partial_bytes(int V, int R, int M, int K, int chunk_pixels);
+int mvsdet_gshead_backward_weight_f32(const float* feature, const int64_t* feature_strides /*HOST[3]*/, const float* depth_coding,
+                                      const int64_t* depth_strides /*HOST[2]*/, const float* rgb_rows /*may be NULL*/,
+                                      const float* images /*may be NULL*/, const int64_t* image_strides /*HOST[3], NULL without images*/,
+                                      const int64_t* ids, const float* g, float* g_weight, float* g_bias, float* partial,
+                                      size_t partial_bytes, int chunk_pixels, int N, int V, int C, int K, int M, int h, int w, int Hf, int Wf,
+                                      int Hi, int Wi, mvsdet_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The cost network's 3x3x3 convolutions on the bf16 matrix cores, fp32 operands cut into bf16 pieces ("bf16x3":
  * x*w ~ x_hi*w_hi + x_hi*w_mid + x_mid*w_hi, fp32 accumulation; csrc/costreg_bf16.hip).  Replaces the same layers of
  * mvs_models/mvsnet.py:76-82,104-108 as mvsdet_conv3d_k3_mfma_ws_f32 does, at 3/16 of the fp32 matrix-core time; results

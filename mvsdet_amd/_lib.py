@@ -114,6 +114,12 @@ SIGNATURES = {
     "mvsdet_adapter_cameras_f32": [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _i, _i, _i, _i, _vp],
     "mvsdet_adapter_forward_f32": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp],
     "mvsdet_adapter_backward_f32": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i, _i, _i, _i, _i, _f, _f, _vp],
+    "mvsdet_gshead_forward_f32": [_vp, _i64p, _vp, _i64p, _vp, _vp, _i64p, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_gshead_rgb_rows_f32": [_vp, _i64p, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_gshead_backward_input_f32": [_vp, _i64p, _vp, _i64p, _vp, _vp, _vp, _vp, _i64p, _vp, _i64p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_gshead_partial_bytes": [_i, _i, _i, _i, _i],
+    "mvsdet_gshead_backward_weight_f32": [_vp, _i64p, _vp, _i64p, _vp, _vp, _i64p, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i,
+                                          _i, _i, _i, _i, _vp],
     "mvsdet_copy_f32": [_vp, _vp, _sz, _vp],
     "mvsdet_store_pattern_probe_f32": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_store_pattern_probe_f16": [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
@@ -191,7 +197,7 @@ _RESTYPE = {"mvsdet_last_error": ctypes.c_char_p, "mvsdet_conv3d_k3_bf16x3_stats
             "mvsdet_depth_diagnostics_workspace_bytes": ctypes.c_size_t,
             "mvsdet_depth_loss_workspace_bytes": ctypes.c_size_t,
             "mvsdet_photo_loss_workspace_bytes": ctypes.c_size_t, "mvsdet_photo_select_workspace_bytes": ctypes.c_size_t,
-            "mvsdet_splat_workspace_bytes": ctypes.c_size_t,
+            "mvsdet_splat_workspace_bytes": ctypes.c_size_t, "mvsdet_gshead_partial_bytes": ctypes.c_size_t,
             "mvsdet_eval_state_bytes": ctypes.c_size_t, "mvsdet_eval_workspace_bytes": ctypes.c_size_t,
             "mvsdet_nvs_workspace_bytes": ctypes.c_size_t,
             "mvsdet_conv3d_k3_mfma_workspace_bytes": ctypes.c_size_t, "mvsdet_bn3d_workspace_bytes": ctypes.c_size_t}

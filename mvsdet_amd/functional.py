@@ -613,6 +613,31 @@ def pixel_gaussians(extrinsics: Tensor, intrinsics: Tensor, raw: Tensor, depths:
     return PixelGaussians(*[t[None] for t in out[:3]], opac, *[t[None] for t in out[3:]])
 
 
+def process_rgb_raw(orig_rgb: Tensor, ratio, height: int, width: int, src_id) -> Tensor:
+    """MVSDet.process_rgb_raw (mvsdet.py:319-333): orig_rgb (n_img,3,Hi,Wi) denormalised images, src_id the chosen views ->
+    (1, n_src, height width, 3): F.interpolate(scale_factor=1/ratio, mode='bilinear') of the chosen images, cropped to height x width,
+    as rows.  One launch (`ops.gshead.process_rgb_raw_rows`: the mean of the four pixels around 4 d + 1.5); only ratio 4, which is
+    what the reference asserts.  No gradient to the images."""
+    if ratio != 4:
+        raise ValueError(f"process_rgb_raw: ratio = {ratio}; only 4 is supported (the reference asserts it)")
+    orig_rgb = amp_fp32(orig_rgb)
+    return ops.gshead.process_rgb_raw_rows(orig_rgb, src_id, int(height), int(width))[None]
+
+
+def gaussian_head(feature: Tensor, depth_coding: Tensor, weight: Tensor, bias: Tensor, src_id, height: int, width: int,
+                  num_surfaces: int, rgb_raw=None, denorm_images=None) -> Tensor:
+    """mvsdet.py:561-575 in one call: the rows of the chosen views (feature cropped to height x width, depth_coding, and with
+    use_rgb_gaussian the rgb) through `to_gaussians` = nn.Sequential(ReLU, Linear(weight, bias)) -> raw (n_src, height width,
+    num_surfaces, 2 + 7 + 3 d_sh), what `pixel_gaussians` takes.  The rgb comes as rgb_raw (n_src,R,3) / (1,n_src,R,3) from
+    `process_rgb_raw`, or as denorm_images (n_img,3,Hi,Wi), which the kernel reduces itself -- never both.  src_id: a sequence or
+    host tensor (checked) or an int64 device tensor.  Gradients reach feature, depth_coding, weight and bias."""
+    if rgb_raw is not None and denorm_images is not None:
+        raise ValueError("gaussian_head: rgb comes as rows (rgb_raw) or as images (denorm_images), not both")
+    feature, depth_coding, weight, bias, rgb_raw, denorm_images = amp_fp32(feature, depth_coding, weight, bias, rgb_raw, denorm_images)
+    return ops.gshead.gaussian_head(feature, depth_coding, src_id, weight, bias, int(height), int(width), int(num_surfaces), rgb_raw,
+                                    denorm_images)
+
+
 def nvs_loss_func(rgb_pred: Sequence[Tensor], gt_rgb: Sequence[Tensor]) -> dict:
     """MVSDet.nvs_loss_func (mvsdet.py:878-890) without use_nerf_mask: sum over the scenes of mean((rgb - gt)^2), rgb = the scene's
     colour (1,n_tgt,3,H,W) with its leading 1 taken off (or already (n_tgt,3,H,W)), gt (n_tgt,3,H,W) -> dict(loss_nvs=...).  The

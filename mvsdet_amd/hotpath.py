@@ -582,7 +582,8 @@ class MVSDetHotPath:
 
     def novel_views(self, outputs, feature: Tensor, img_meta: dict, to_gaussians, tgt_c2w, tgt_intrinsic, tgt_shape, rgb_raw=None, *,
                     num_surfaces: int = 1, gaussian_scale_min: float = 0.5, gaussian_scale_max: float = 15.0, sh_degree: int = 4,
-                    num_select: int = 3, sh_rotation=None, background_color=None, max_keys=None, depth_mode=None):
+                    num_select: int = 3, sh_rotation=None, background_color=None, max_keys=None, depth_mode=None,
+                    gaussian_head: str = "torch", denorm_images=None):
         """The novel-view branch of extract_feat for one scene (mvsdet.py:519-677) -> colour (1,n_tgt,3,H,W), what
         `self.decoder.forward(...)` returns as `.color`.  outputs: the scene's `SceneOutputs`; feature (N,C,Hf,Wf); to_gaussians:
         the caller's nn.Sequential(ReLU, Linear) with num_surfaces * (2 + 7 + 3 d_sh) outputs, run by torch; tgt_c2w (n_tgt,4,4),
@@ -593,7 +594,15 @@ class MVSDetHotPath:
         `functional.decode_splatting` with near / far = near_far_range.  Gradients reach feature, to_gaussians' parameters, depth_coding
         and the opacity.  The scale / degree defaults are those of the shipped configs.  depth_mode: one of
         `functional.render_depth_cuda`'s modes -> (colour, depth (1,n_tgt,H,W)), the decoder's `.depth`, from the same fused
-        rasteriser call; the depth carries gradients to the same places."""
+        rasteriser call; the depth carries gradients to the same places.
+        gaussian_head "torch" (default): the rows are concatenated and to_gaussians is run by torch, as above.  "hip": to_gaussians must
+        be nn.Sequential(ReLU, Linear); its weight and bias go to `functional.gaussian_head`, which reads feature, depth_coding and the
+        rgb in place (one kernel, no row matrix).  denorm_images (N,3,Hi,Wi): the denormalised images instead of rgb_raw
+        (never both) -- "hip" reduces them inside the kernel, "torch" through `functional.process_rgb_raw` (ratio 4 only)."""
+        if gaussian_head not in ("torch", "hip"):
+            raise ValueError(f"novel_views: gaussian_head = {gaussian_head!r} (\"torch\" or \"hip\")")
+        if rgb_raw is not None and denorm_images is not None:
+            raise ValueError("novel_views: rgb comes as rgb_raw or as denorm_images, not both")
         geo = outputs["geometry"]
         h, w = geo.height, geo.width
         dev = feature.device
@@ -612,11 +621,16 @@ class MVSDetHotPath:
         c2w = w2c.inverse().float()[src_id]
         ids, K, c2w = (ops._common.to_device(t, dev) for t in (src_id, K.contiguous(), c2w.contiguous()))
         depth_coding = outputs["depth_coding"]
-        rows = [feature[ids][:, :, :h, :w].reshape(n_src, feature.shape[1], R).transpose(1, 2), depth_coding[ids].reshape(n_src, R, 1)]
-        if rgb_raw is not None:
-            rows.append(rgb_raw.reshape(n_src, R, 3).to(rows[0].dtype))
-        raw = to_gaussians(torch.cat(rows, dim=-1))
-        raw = raw.reshape(n_src, R, int(num_surfaces), raw.shape[-1] // int(num_surfaces))
+        if gaussian_head == "hip":
+            raw = self._gaussian_head_hip(to_gaussians, feature, depth_coding, ids, h, w, int(num_surfaces), rgb_raw, denorm_images)
+        else:
+            if denorm_images is not None:
+                rgb_raw = F_.process_rgb_raw(denorm_images, 4, h, w, ids)
+            rows = [feature[ids][:, :, :h, :w].reshape(n_src, feature.shape[1], R).transpose(1, 2), depth_coding[ids].reshape(n_src, R, 1)]
+            if rgb_raw is not None:
+                rows.append(rgb_raw.reshape(n_src, R, 3).to(rows[0].dtype))
+            raw = to_gaussians(torch.cat(rows, dim=-1))
+            raw = raw.reshape(n_src, R, int(num_surfaces), raw.shape[-1] // int(num_surfaces))
         opacity = outputs["opacity"][ids][:, :h, :w].reshape(n_src, R)
         # compute_depth_scale[_MultiIntrin] (:1158-1216) through the kernel of `ray_depth`, without candidates
         Kp = torch.tensor(np.array(img_meta["lidar2img"]["intrinsic"])).clone()
@@ -644,6 +658,19 @@ class MVSDetHotPath:
         far = torch.full((1, n_tgt), self.near_far_range[1])
         tgt, Kt, near, far = (ops._common.to_device(t, dev) for t in (tgt[None].contiguous(), Kt[None, :, :3, :3].contiguous(), near, far))
         return F_.decode_splatting(gaussians, tgt, Kt, near, far, (H, W), background_color, max_keys=max_keys, depth_mode=depth_mode)
+
+    @staticmethod
+    def _gaussian_head_hip(to_gaussians, feature, depth_coding, ids, h, w, num_surfaces, rgb_raw, denorm_images):
+        """`to_gaussians` on the kernel of `functional.gaussian_head`; TypeError unless it is ReLU followed by a Linear of the rows' width."""
+        layers = list(to_gaussians) if isinstance(to_gaussians, torch.nn.Sequential) else []
+        want = feature.shape[1] + (1 if rgb_raw is None and denorm_images is None else 4)
+        if len(layers) != 2 or not isinstance(layers[0], torch.nn.ReLU) or not isinstance(layers[1], torch.nn.Linear):
+            raise TypeError(f"novel_views(gaussian_head=\"hip\"): to_gaussians must be nn.Sequential(nn.ReLU(), nn.Linear(...)), got {to_gaussians!r}")
+        linear = layers[1]
+        if linear.in_features != want or linear.bias is None:
+            raise TypeError(f"novel_views(gaussian_head=\"hip\"): the rows have {want} entries ({feature.shape[1]} feature channels, depth_coding"
+                            f"{'' if want == feature.shape[1] + 1 else ', rgb'}); to_gaussians[1] is {linear!r} and must have a bias")
+        return F_.gaussian_head(feature, depth_coding, linear.weight, linear.bias, ids, h, w, num_surfaces, rgb_raw, denorm_images)
 
     def nvs_loss(self, rgb_preds, gt_rgb) -> dict:
         """`loss_nvs` of MVSDet.loss (nvs_loss_func, mvsdet.py:878-890, without use_nerf_mask): rgb_preds, one colour (1,n_tgt,3,H,W)
