@@ -215,7 +215,12 @@ __device__ __forceinline__ float geo_backward(const Geo& g, float depth, const f
     const float inv = 1.0f / (g.nq + 1e-8f);
     const float dot = (gq[0] * g.q[0] + gq[1] * g.q[1] + gq[2] * g.q[2] + gq[3] * g.q[3]);   // gq . q_raw * inv
     // d q_a / d raw_b = inv delta_ab - raw_a raw_b inv^2 / nq = inv (delta_ab - q_a raw_b inv / nq) ; raw_b inv = q_b
-    for (int i = 0; i < 4; ++i) gt[5 + i] = inv * (gq[i] - dot * g.q[i] * ((g.nq + 1e-8f) / g.nq));
+    // nq == 0 (a zero quaternion, or squares that underflowed): the projection term vanishes against inv gq there and must not divide
+    // by nq; what is left is torch's subgradient of the norm at 0.  + 0.0f: a zero quaternion's gradient is +0 in every component
+    for (int i = 0; i < 4; ++i) {
+        const float full = inv * (gq[i] - dot * g.q[i] * ((g.nq + 1e-8f) / g.nq));
+        gt[5 + i] = g.nq > 0.0f ? full : inv * gq[i] + 0.0f;
+    }
     // scales
     const float dm = depth * cam[21];
     for (int k = 0; k < 3; ++k) {

@@ -1,11 +1,13 @@
 """The Gaussian adapter's restatement (tests/adapter_restated.py) on the CPU: the properties of its float64 rotation builder for the
 harmonics, to 1e-10, and the restatement against fixture G27 (the reference's own GaussianAdapter.forward,
-tests/golden/make_goldens_g27.py).  The GPU tests (test_gpu_adapter.py) compare the kernels with this restatement.
+tests/golden/make_goldens_g27.py).  The GPU tests (test_gpu_adapter.py) compare the kernels with this restatement.  Also the planted
+cases of tests/adapter_edges.py on the restatements alone: finite, and inside the bar that test_gpu_adapter_edges.py sets for the kernels.
 """
 import numpy as np
 import pytest
 import torch
 
+import adapter_edges as E
 import adapter_restated as A
 import splat_restated as R
 import splat_scenes as S
@@ -88,6 +90,48 @@ def test_case_inputs_meet_their_promises():
     for v in range(3):
         Cv = c["extrinsics"][v, :3, :3].astype(np.float64)
         assert abs(np.linalg.det(Cv) - 1.0) < 1e-5 and np.abs(Cv - np.eye(3)).max() > 0.05
+
+
+@pytest.mark.parametrize("name", E.NAMES)
+def test_planted_edges_are_finite_and_inside_their_own_bar(name):
+    """tests/adapter_edges.py: on every planted case both restatements are finite in every field and both gradients, and within each
+    group (and among the Gaussians no group names) the float32 restatement lies under the group's bar against float64 -- the reference
+    alone stays inside the condition test_gpu_adapter_edges.py sets for the kernel.  The zero quaternion's gradient is 0 (torch's norm
+    has the subgradient 0 at 0); the underflowing ones get a finite gradient of ordinary size."""
+    c, groups, _, _, o64, g64, o32, g32 = E.reference(name)
+    assert list(groups) == [name] and len(set(groups[name])) == len(groups[name])
+    for o, g in ((o64, g64), (o32, g32)):
+        for k, x, _ in E.quantities(c, o, g):
+            assert np.isfinite(x).all(), (name, k, x.dtype)
+    sets = dict(groups, rest=E.rest(c, groups))
+    assert sum(len(v) for v in sets.values()) == c["V"] * c["h"] * c["w"] * c["S"]           # no Gaussian is left out
+    for group, gaussians in sets.items():
+        idx = E.flat(c, gaussians)
+        for (k, x64, pp), (_, x32, _) in zip(E.quantities(c, o64, g64), E.quantities(c, o32, g32)):
+            a, b = E.rows_of(c, x64, idx, pp).astype(np.float64), E.rows_of(c, x32, idx, pp).astype(np.float64)
+            bar, own = E.group_bar(a, b)
+            print(f"{name} / {group} {k}: max|x| {np.abs(a).max():.4g}  restated f32-f64 {own:.3g}")
+            assert (np.abs(b - a) <= bar).all(), (name, group, k)
+    if name == "quat_zero":
+        for g in (g64, g32):
+            assert not E.rows_of(c, g[0], E.flat(c, groups[name]))[:, 5:9].any()
+    if name == "quat_underflow":
+        q = np.abs(E.rows_of(c, g64[0], E.flat(c, groups[name]))[:, 5:9])
+        assert np.isfinite(q).all() and q[0].max() > 0.1 and q[0].max() < 1e3
+
+
+def test_planted_edges_leave_the_case_and_the_other_gaussians_alone():
+    """adapter_restated.case keeps its promises (the planted values live in adapter_edges); a planted case differs from the clean one
+    only in the rows it names."""
+    base = E.clean()
+    assert float(np.linalg.norm(base["raw"][..., 5:9], axis=-1).min()) >= 0.1 - 1e-6 and base["depth"].min() >= 0.3
+    for name in E.NAMES:
+        c, groups = E.planted(name)
+        keep = np.ones(c["V"] * c["h"] * c["w"] * c["S"], bool)
+        keep[E.flat(c, groups[name])] = False
+        assert np.array_equal(c["raw"].reshape(keep.size, -1)[keep], base["raw"].reshape(keep.size, -1)[keep]), name
+        same_depth = np.repeat(c["depth"].reshape(-1).view(np.int32) == base["depth"].reshape(-1).view(np.int32), c["S"])
+        assert same_depth[keep].all() and not (name.startswith("depth") and same_depth[~keep].any()), name
 
 
 def test_composition_seed_stays_under_the_left_out_cap():
