@@ -557,7 +557,7 @@ int mvsdet_photo_select_bwd_f32(const int32_t* wins, const float* g_loss, float*
  * Gaussian rasteriser (csrc/splat.hip): what gs_src/model/decoder/cuda_splatting.py::render_cuda asks of its external extension
  * (Kerbl et al. 2023 with spherical harmonics up to degree 4), for V views that share one set of G Gaussians.  fp32, 16x16 tiles, no
  * float atomics, no host synchronisation; forward and backward are bit-identical from call to call.  DESIGN.md 4.15 has every
- * constant.  Limits: d_sh in {1, 4, 9, 16, 25}; V <= 65535; V G, V tiles, 9 V max_keys and 3 V H W below 2^31.
+ * constant.  Limits: d_sh in {1, 4, 9, 16, 25}; V <= 65535; V G, V tiles, 9 V max_keys (10 with depth) and 3 V H W below 2^31.
  *
  * mvsdet_splat_cameras_f32 (one launch, one thread per view): cams (V,40) = view matrix (16) and full projection (16), both in the
  *   row-vector (transposed) form render_cuda hands over, tan(fov_x / 2), tan(fov_y / 2), camera position (3), scale, 2 unused -- from
@@ -565,52 +565,45 @@ int mvsdet_photo_select_bwd_f32(const int32_t* wins, const float* g_loss, float*
  *   intrinsics (3 rows k_row_stride apart, k_view_stride between views) and near / far (V).  scale_invariant: scale = 1 / near
  *   multiplies the translation, near and far in fp32 as the reference does, and the rasteriser multiplies means by scale and
  *   covariances by scale^2 itself; otherwise scale = 1.  Inverses, field of view and the matrix product in float64, rounded once.
- * mvsdet_splat_forward_f32: means (G,3) through means_strides {g, c}, covariances (G,3,3) through cov_strides {g, row, col} (the upper
- *   triangle is read), harmonics (G,3,d_sh) through sh_strides {g, channel, k}, opacities (G) opacity_stride apart, background (V,3),
- *   -> image (V,3,H,W) contiguous.  use_sh 0: harmonics (G,3,1) are the colours themselves (no basis, no + 0.5, no clamp).
- *   max_keys: (Gaussian, tile) pairs a view may have; the count a view needs goes to its status word, the first int4 block of the
- *   workspace {needed, capacity, overflow, 0} per view.  A view that needs more writes nothing past its share: its image is NaN and
- *   the backward gives NaN for every gradient.  workspace (256-byte aligned) >= the query; the backward reads it.
- * mvsdet_splat_backward_f32 (two launches): g_image (V,3,H,W) contiguous -> g_means (G,3), g_covariances (G,3,3: upper triangle, the
- *   off-diagonals with both symmetric terms; lower triangle 0), g_harmonics (G,3,d_sh), g_opacities (G), summed over the views in
- *   ascending order.  slots: 9 V max_keys floats of scratch.  Same inputs and workspace as the forward that filled it. */
+ * mvsdet_splat_forward_f32 and mvsdet_splat_backward_f32 are the one call form of every render; with_colour and with_depth choose
+ *   what is blended: colour alone (1, 0), colour and depth in one pass (1, 1), depth alone (0, 1).  Both 0 is refused first.
+ *   Always: means (G,3) through means_strides {g, c}, covariances (G,3,3) through cov_strides {g, row, col} (the upper triangle is
+ *   read), opacities (G) opacity_stride apart, cams from above.  max_keys: (Gaussian, tile) pairs a view may have; the count a view
+ *   needs goes to its status word, the first int4 block of the workspace {needed, capacity, overflow, 0} per view.  A view that needs
+ *   more writes nothing past its share: its outputs are NaN and the backward gives NaN for every gradient.  workspace (256-byte
+ *   aligned) >= the query, the same for every form; the backward reads it.
+ *   With colour: harmonics (G,3,d_sh) through sh_strides {g, channel, k}, background (V,3) -> image (V,3,H,W) contiguous.  use_sh 0:
+ *   harmonics (G,3,1) are the colours themselves (no basis, no + 0.5, no clamp).  The image has the same bits with and without depth.
+ *   Without colour harmonics, sh_strides, background, image, g_image and g_harmonics are not touched and may be NULL; d_sh and use_sh
+ *   are ignored.
+ *   With depth (render_depth_cuda, cuda_splatting.py:237-280, as a fourth blended channel of the same pass): every
+ *   (view, Gaussian) gets one value d = f(z), z its camera-space depth before the scale_invariant scaling, near / far (V) the caller's
+ *   unscaled bounds: mode 0 depth z, 1 disparity 1 / z, 2 relative_disparity (conversions.py:17-27, eps 1e-10), 3 log as the reference
+ *   writes it, log(max(min(z, near), far)) = log(far) whenever near <= far.  values (V,G) receives d (0 where culled), depth (V,H,W)
+ *   the blend sum d alpha T over a background of 0, with the alpha, T, skips and early stop of the colour.  Without depth near, far,
+ *   depth, values and g_depth are not touched and may be NULL, and mode is ignored.
+ * mvsdet_splat_backward_f32 (two launches): g_image (V,3,H,W) and g_depth (V,H,W), contiguous, as the flags say -> g_means (G,3),
+ *   g_covariances (G,3,3: upper triangle, the off-diagonals with both symmetric terms; lower triangle 0), g_harmonics (G,3,d_sh, with
+ *   colour), g_opacities (G), summed over the views in ascending order.  Same inputs, values and workspace as the forward that filled
+ *   them; a workspace may be read by another form's backward (colour + depth forward, colour-only backward).  slots: scratch of
+ *   9 V max_keys floats without depth, 10 V max_keys with it, and that product must stay below 2^31. */
 size_t mvsdet_splat_workspace_bytes(int V, int G, int H, int W, int max_keys);
 int mvsdet_splat_cameras_f32(const float* extrinsics, int64_t ext_view_stride, const float* intrinsics, int64_t k_view_stride,
                              int64_t k_row_stride, const float* near, const float* far, int scale_invariant, float* cams, int V,
                              mvsdet_stream_t stream);
 int mvsdet_splat_forward_f32(const float* means, const int64_t* means_strides /*HOST[2]*/, const float* covariances,
                              const int64_t* cov_strides /*HOST[3]*/, const float* harmonics, const int64_t* sh_strides /*HOST[3]*/,
-                             const float* opacities, int64_t opacity_stride, const float* cams, const float* background, float* image,
-                             void* workspace, size_t workspace_bytes, int V, int G, int d_sh, int use_sh, int H, int W, int max_keys,
-                             mvsdet_stream_t stream);
+                             const float* opacities, int64_t opacity_stride, const float* cams, const float* near, const float* far,
+                             const float* background, float* image, float* depth, float* values, void* workspace,
+                             size_t workspace_bytes, int V, int G, int d_sh, int use_sh, int with_colour, int with_depth, int mode, int H,
+                             int W, int max_keys, mvsdet_stream_t stream);
 int mvsdet_splat_backward_f32(const float* means, const int64_t* means_strides /*HOST[2]*/, const float* covariances,
                               const int64_t* cov_strides /*HOST[3]*/, const float* harmonics, const int64_t* sh_strides /*HOST[3]*/,
-                              const float* opacities, int64_t opacity_stride, const float* cams, const float* background,
-                              const float* g_image, void* workspace, size_t workspace_bytes, float* slots, float* g_means,
-                              float* g_covariances, float* g_harmonics, float* g_opacities, int V, int G, int d_sh, int use_sh, int H,
-                              int W, int max_keys, mvsdet_stream_t stream);
-
-/* Rendered depth (render_depth_cuda, cuda_splatting.py:237-280) as a fourth blended channel of the same pass.  DESIGN.md 4.18.
- * Every (view, Gaussian) gets one value d = f(z), z its camera-space depth before the scale_invariant scaling, near / far (V) the
- * caller's unscaled bounds: mode 0 depth z, 1 disparity 1 / z, 2 relative_disparity (conversions.py:17-27, eps 1e-10), 3 log as the
- * reference writes it, log(max(min(z, near), far)) = log(far) whenever near <= far.  values (V,G) receives d (0 where culled), depth
- * (V,H,W) the blend sum d alpha T over a background of 0, with the alpha, T, skips and early stop of the colour; a view over its key
- * capacity is NaN.  with_colour 1: image (V,3,H,W) too, the bits of mvsdet_splat_forward_f32.  with_colour 0: harmonics, sh_strides,
- * background, image, g_image and g_harmonics are not touched and may be NULL; d_sh and use_sh are ignored.  Workspace and cams as
- * above.  The backward takes g_depth (V,H,W) beside g_image; slots: 10 V max_keys floats, and 10 V max_keys < 2^31. */
-int mvsdet_splat_forward_depth_f32(const float* means, const int64_t* means_strides /*HOST[2]*/, const float* covariances,
-                                   const int64_t* cov_strides /*HOST[3]*/, const float* harmonics, const int64_t* sh_strides /*HOST[3]*/,
-                                   const float* opacities, int64_t opacity_stride, const float* cams, const float* near, const float* far,
-                                   const float* background, float* image, float* depth, float* values, void* workspace,
-                                   size_t workspace_bytes, int V, int G, int d_sh, int use_sh, int with_colour, int mode, int H, int W,
-                                   int max_keys, mvsdet_stream_t stream);
-int mvsdet_splat_backward_depth_f32(const float* means, const int64_t* means_strides /*HOST[2]*/, const float* covariances,
-                                    const int64_t* cov_strides /*HOST[3]*/, const float* harmonics, const int64_t* sh_strides /*HOST[3]*/,
-                                    const float* opacities, int64_t opacity_stride, const float* cams, const float* near, const float* far,
-                                    const float* background, const float* g_image, const float* g_depth, const float* values,
-                                    void* workspace, size_t workspace_bytes, float* slots, float* g_means, float* g_covariances,
-                                    float* g_harmonics, float* g_opacities, int V, int G, int d_sh, int use_sh, int with_colour, int mode,
-                                    int H, int W, int max_keys, mvsdet_stream_t stream);
+                              const float* opacities, int64_t opacity_stride, const float* cams, const float* near, const float* far,
+                              const float* background, const float* g_image, const float* g_depth, const float* values,
+                              void* workspace, size_t workspace_bytes, float* slots, float* g_means, float* g_covariances,
+                              float* g_harmonics, float* g_opacities, int V, int G, int d_sh, int use_sh, int with_colour, int with_depth,
+                              int mode, int H, int W, int max_keys, mvsdet_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Gaussian adapter (csrc/adapter.hip): the pixel Gaussians the rasteriser above renders -- GaussianAdapter.forward

@@ -104,13 +104,10 @@ SIGNATURES = {
     "mvsdet_photo_select_bwd_f32": [_vp, _vp, _vp, _i, _i, _vp],
     "mvsdet_splat_workspace_bytes": [_i, _i, _i, _i, _i],
     "mvsdet_splat_cameras_f32": [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _i, _vp, _i, _vp],
-    "mvsdet_splat_forward_f32": [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "mvsdet_splat_backward_f32": [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i, _i,
-                                  _i, _i, _i, _i, _i, _vp],
-    "mvsdet_splat_forward_depth_f32": [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i,
-                                       _i, _i, _i, _i, _i, _i, _i, _vp],
-    "mvsdet_splat_backward_depth_f32": [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp,
-                                        _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_splat_forward_f32": [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i,
+                                 _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_splat_backward_f32": [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp,
+                                  _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_adapter_cameras_f32": [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _i, _i, _i, _i, _vp],
     "mvsdet_adapter_forward_f32": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp],
     "mvsdet_adapter_backward_f32": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i, _i, _i, _i, _i, _f, _f, _vp],
@@ -246,15 +243,21 @@ def check(rc: int, what: str):
         raise kinds.get(rc, RuntimeError)(f"{what} failed (code {rc}): {msg}")
 
 
+def strides(t, n=None) -> ctypes.Array:
+    """HOST int64[n] with the first n element strides of a tensor (n None: all of them)."""
+    values = t.stride() if n is None else t.stride()[:n]
+    return (ctypes.c_int64 * len(values))(*[int(v) for v in values])
+
+
 def strides4(t) -> ctypes.Array:
     """HOST int64[4] with the element strides of a 4-D tensor."""
     assert t.dim() == 4
-    return (ctypes.c_int64 * 4)(*[int(s) for s in t.stride()])
+    return strides(t)
 
 
 def strides3(t) -> ctypes.Array:
     """HOST int64[3] with the element strides of a 3-D tensor."""
-    return (ctypes.c_int64 * 3)(*[int(v) for v in t.stride()])
+    return strides(t)
 
 
 def strides4_of5(t) -> ctypes.Array:

@@ -10,6 +10,7 @@
 //             results go back through LDS and leave with coalesced stores
 //   backward  the same shape: the transposed block-diagonal product on waves 0..2, the geometry's chain rule on wave 3; every
 //             Gaussian's gradient lands in its own row, so there are no atomics and two runs give the same bits
+#include "camera_math.h"
 #include "common.h"
 #include "sh_basis.h"
 
@@ -52,18 +53,10 @@ __global__ void adapter_cameras_kernel(const float* __restrict__ ext, int64_t e_
         c[9 + i] = E[i * 4 + 3];
     }
     // K^-1 by the adjugate
-    const double c00 = K[1][1] * K[2][2] - K[1][2] * K[2][1], c01 = K[1][2] * K[2][0] - K[1][0] * K[2][2];
-    const double c02 = K[1][0] * K[2][1] - K[1][1] * K[2][0];
-    const double det = K[0][0] * c00 + K[0][1] * c01 + K[0][2] * c02;
-    c[12] = (float)(c00 / det);
-    c[15] = (float)(c01 / det);
-    c[18] = (float)(c02 / det);
-    c[13] = (float)((K[0][2] * K[2][1] - K[0][1] * K[2][2]) / det);
-    c[16] = (float)((K[0][0] * K[2][2] - K[0][2] * K[2][0]) / det);
-    c[19] = (float)((K[0][1] * K[2][0] - K[0][0] * K[2][1]) / det);
-    c[14] = (float)((K[0][1] * K[1][2] - K[0][2] * K[1][1]) / det);
-    c[17] = (float)((K[0][2] * K[1][0] - K[0][0] * K[1][2]) / det);
-    c[20] = (float)((K[0][0] * K[1][1] - K[0][1] * K[1][0]) / det);
+    double Ki[3][3];
+    inverse3(K, Ki);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) c[12 + i * 3 + j] = (float)Ki[i][j];
     // get_scale_multiplier: 0.1 * sum_i (K[:2,:2]^-1 (1/w, 1/h))_i
     const double det2 = K[0][0] * K[1][1] - K[0][1] * K[1][0];
     const double px = 1.0 / (double)w, py = 1.0 / (double)h;

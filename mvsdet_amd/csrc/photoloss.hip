@@ -15,6 +15,7 @@
 //
 // Roofline: neither.  B*h*w = 47 200 pixels per scene: the launches bound it.
 #include "block_reduce.h"
+#include "camera_math.h"
 
 namespace mvsdet {
 
@@ -59,19 +60,8 @@ __global__ void photo_geometry_kernel(const float* __restrict__ ext_l, int64_t e
         tr[i] = (double)R[i * 4 + 3];
     }
     // adjugate / determinant
-    const double c00 = K[1][1] * K[2][2] - K[1][2] * K[2][1], c01 = K[1][2] * K[2][0] - K[1][0] * K[2][2];
-    const double c02 = K[1][0] * K[2][1] - K[1][1] * K[2][0];
-    const double det = K[0][0] * c00 + K[0][1] * c01 + K[0][2] * c02;
     double inv[3][3];
-    inv[0][0] = c00 / det;
-    inv[1][0] = c01 / det;
-    inv[2][0] = c02 / det;
-    inv[0][1] = (K[0][2] * K[2][1] - K[0][1] * K[2][2]) / det;
-    inv[1][1] = (K[0][0] * K[2][2] - K[0][2] * K[2][0]) / det;
-    inv[2][1] = (K[0][1] * K[2][0] - K[0][0] * K[2][1]) / det;
-    inv[0][2] = (K[0][1] * K[1][2] - K[0][2] * K[1][1]) / det;
-    inv[1][2] = (K[0][2] * K[1][0] - K[0][0] * K[1][2]) / det;
-    inv[2][2] = (K[0][0] * K[1][1] - K[0][1] * K[1][0]) / det;
+    inverse3(K, inv);
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) g[i * 3 + j] = (float)inv[i][j];
     // T = [R_r R_l^T | t_r - R_rel t_l], P = K T

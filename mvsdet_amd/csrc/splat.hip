@@ -15,7 +15,7 @@
 //
 // Rendered depth (render_depth_cuda) is a fourth blended channel of the same pass: preprocess writes one value d(v, g)
 // per (view, Gaussian) -- the camera-space z mapped by the mode -- and render / render bwd / preprocess bwd are templates over
-// "blends colour" and "blends depth".  Colour alone is the form above, unchanged; the depth forms run behind entry points of their own.
+// "blends colour" and "blends depth".  Colour alone is the form above, unchanged; the two entry points choose the form by two flags.
 #include <cstring>   // rocPRIM calls the host memset without including it
 
 #include <rocprim/rocprim.hpp>
@@ -23,6 +23,7 @@
 #include <climits>
 
 #include "block_reduce.h"
+#include "camera_math.h"
 #include "sh_basis.h"
 
 namespace mvsdet {
@@ -180,20 +181,6 @@ __global__ void splat_cameras_kernel(const float* __restrict__ ext, int64_t e_vi
             A[i][j] = (double)E[i * 4 + j];
             K[i][j] = (double)Kp[i * k_row + j];
         }
-    auto inverse3 = [](const double (*M)[3], double (*inv)[3]) {
-        const double c00 = M[1][1] * M[2][2] - M[1][2] * M[2][1], c01 = M[1][2] * M[2][0] - M[1][0] * M[2][2];
-        const double c02 = M[1][0] * M[2][1] - M[1][1] * M[2][0];
-        const double det = M[0][0] * c00 + M[0][1] * c01 + M[0][2] * c02;
-        inv[0][0] = c00 / det;
-        inv[1][0] = c01 / det;
-        inv[2][0] = c02 / det;
-        inv[0][1] = (M[0][2] * M[2][1] - M[0][1] * M[2][2]) / det;
-        inv[1][1] = (M[0][0] * M[2][2] - M[0][2] * M[2][0]) / det;
-        inv[2][1] = (M[0][1] * M[2][0] - M[0][0] * M[2][1]) / det;
-        inv[0][2] = (M[0][1] * M[1][2] - M[0][2] * M[1][1]) / det;
-        inv[1][2] = (M[0][2] * M[1][0] - M[0][0] * M[1][2]) / det;
-        inv[2][2] = (M[0][0] * M[1][1] - M[0][1] * M[1][0]) / det;
-    };
     double R[3][3], Ki[3][3], T[3];
     inverse3(A, R);
     inverse3(K, Ki);
@@ -803,30 +790,27 @@ __global__ __launch_bounds__(kThreads) void splat_preprocess_bwd_kernel(SplatIn 
     g_opac[g] = gop;
 }
 
-int check_splat(const char* name, int V, int G, int d_sh, int use_sh, int H, int W, int max_keys) {
+// The one argument check of both entry points.  with_depth chooses the slot record the limit counts, 9 or 10 floats per key.
+int check_splat(const char* name, int V, int G, int d_sh, int use_sh, int with_depth, int mode, int H, int W, int max_keys) {
     MVS_REQUIRE(V > 0 && G > 0 && H > 0 && W > 0 && max_keys > 0, "%s: bad sizes V=%d G=%d H=%d W=%d max_keys=%d", name, V, G, H, W, max_keys);
     MVS_REQUIRE(d_sh == 1 || d_sh == 4 || d_sh == 9 || d_sh == 16 || d_sh == 25, "%s: d_sh=%d must be 1, 4, 9, 16 or 25", name, d_sh);
     MVS_REQUIRE(use_sh || d_sh == 1, "%s: precomputed colours come as d_sh = 1", name);
     const long long tiles = (long long)((W + kTile - 1) / kTile) * ((H + kTile - 1) / kTile);
+    const int slot = with_depth ? kSlotDepth : kSlot;
     MVS_REQUIRE(V <= 65535 && (long long)V * G < (1ll << 31) && (long long)V * tiles < (1ll << 31) &&
-                    (long long)V * max_keys * kSlot < (1ll << 31) && (long long)V * 3 * H * W < (1ll << 31) && (long long)G * 3 * d_sh < (1ll << 31),
-                "%s: V=%d G=%d %dx%d max_keys=%d exceeds the limits (V G, V tiles, 9 V max_keys, 3 V H W < 2^31)", name, V, G, H, W, max_keys);
+                    (long long)V * max_keys * slot < (1ll << 31) && (long long)V * 3 * H * W < (1ll << 31) && (long long)G * 3 * d_sh < (1ll << 31),
+                "%s: V=%d G=%d %dx%d max_keys=%d exceeds the limits (V G, V tiles, %d V max_keys, 3 V H W < 2^31)", name, V, G, H, W, max_keys,
+                slot);
+    MVS_REQUIRE(!with_depth || (mode >= kModeDepth && mode <= kModeLog),
+                "%s: mode=%d must be 0 (depth), 1 (disparity), 2 (relative_disparity) or 3 (log)", name, mode);
     return MVSDET_OK;
 }
 
+// The Gaussians as the kernels read them; without colour no harmonics are read and their strides are 0.
 SplatIn splat_inputs(const float* means, const int64_t* ms, const float* cov, const int64_t* cs, const float* sh, const int64_t* ss,
-                     const float* opac, int64_t os) {
+                     const float* opac, int64_t os, int with_colour) {
+    if (!with_colour) return SplatIn{means, ms[0], ms[1], cov, cs[0], cs[1], cs[2], nullptr, 0, 0, 0, opac, os};
     return SplatIn{means, ms[0], ms[1], cov, cs[0], cs[1], cs[2], sh, ss[0], ss[1], ss[2], opac, os};
-}
-
-
-// what the depth entry points check beyond check_splat
-int check_splat_depth(const char* name, int V, int mode, int max_keys) {
-    MVS_REQUIRE(mode >= kModeDepth && mode <= kModeLog, "%s: mode=%d must be 0 (depth), 1 (disparity), 2 (relative_disparity) or 3 (log)", name,
-                mode);
-    MVS_REQUIRE((long long)V * max_keys * kSlotDepth < (1ll << 31), "%s: V=%d max_keys=%d exceeds the limit 10 V max_keys < 2^31", name, V,
-                max_keys);
-    return MVSDET_OK;
 }
 
 // The forward launch sequence of every form.  The caller has checked the arguments.
@@ -894,7 +878,7 @@ int splat_backward(const char* name, const SplatIn& in, const float* cams, const
 using namespace mvsdet;
 
 extern "C" size_t mvsdet_splat_workspace_bytes(int V, int G, int H, int W, int max_keys) {
-    if (check_splat("splat_workspace_bytes", V, G, 1, 1, H, W, max_keys)) return 0;
+    if (check_splat("splat_workspace_bytes", V, G, 1, 1, 0, 0, H, W, max_keys)) return 0;
     return splat_layout(nullptr, V, G, H, W, max_keys).total;
 }
 
@@ -909,85 +893,59 @@ extern "C" int mvsdet_splat_cameras_f32(const float* extrinsics, int64_t ext_vie
     return MVSDET_OK;
 }
 
+// with_colour and with_depth choose the form: colour alone <true, false>, colour + depth <true, true>, depth alone <false, true>.
+// Without colour harmonics, sh_strides, background and image / g_image / g_harmonics are not read and may be NULL, d_sh and use_sh are
+// ignored; without depth the same holds for near, far, depth / g_depth and values, and mode is ignored.
 extern "C" int mvsdet_splat_forward_f32(const float* means, const int64_t* means_strides, const float* covariances, const int64_t* cov_strides,
                                         const float* harmonics, const int64_t* sh_strides, const float* opacities, int64_t opacity_stride,
-                                        const float* cams, const float* background, float* image, void* workspace, size_t workspace_bytes,
-                                        int V, int G, int d_sh, int use_sh, int H, int W, int max_keys, mvsdet_stream_t stream) {
-    if (int rc = check_splat("splat_forward", V, G, d_sh, use_sh, H, W, max_keys)) return rc;
-    MVS_REQUIRE(means && means_strides && covariances && cov_strides && harmonics && sh_strides && opacities && cams && background && image &&
-                    workspace,
-                "splat_forward: NULL pointer");
-    const SplatIn in = splat_inputs(means, means_strides, covariances, cov_strides, harmonics, sh_strides, opacities, opacity_stride);
-    return splat_forward<true, false>("splat_forward", in, cams, background, image, workspace, workspace_bytes, V, G, d_sh, use_sh, H, W,
-                                      max_keys, SplatDepth<false>{}, (hipStream_t)stream);
+                                        const float* cams, const float* near, const float* far, const float* background, float* image,
+                                        float* depth, float* values, void* workspace, size_t workspace_bytes, int V, int G, int d_sh,
+                                        int use_sh, int with_colour, int with_depth, int mode, int H, int W, int max_keys,
+                                        mvsdet_stream_t stream) {
+    const char* name = "splat_forward";
+    MVS_REQUIRE(with_colour || with_depth, "%s: neither colour nor depth is asked for (with_colour = with_depth = 0)", name);
+    if (!with_colour) d_sh = 1, use_sh = 0;
+    if (int rc = check_splat(name, V, G, d_sh, use_sh, with_depth, mode, H, W, max_keys)) return rc;
+    MVS_REQUIRE(means && means_strides && covariances && cov_strides && opacities && cams && workspace &&
+                    (!with_colour || (harmonics && sh_strides && background && image)) && (!with_depth || (near && far && depth && values)),
+                "%s: NULL pointer", name);
+    const SplatIn in = splat_inputs(means, means_strides, covariances, cov_strides, harmonics, sh_strides, opacities, opacity_stride, with_colour);
+    const SplatDepth<true> dz{near, far, values, depth, mode};
+    const hipStream_t st = (hipStream_t)stream;
+    if (!with_depth)
+        return splat_forward<true, false>(name, in, cams, background, image, workspace, workspace_bytes, V, G, d_sh, use_sh, H, W, max_keys,
+                                          SplatDepth<false>{}, st);
+    if (with_colour)
+        return splat_forward<true, true>(name, in, cams, background, image, workspace, workspace_bytes, V, G, d_sh, use_sh, H, W, max_keys, dz,
+                                         st);
+    return splat_forward<false, true>(name, in, cams, nullptr, nullptr, workspace, workspace_bytes, V, G, d_sh, use_sh, H, W, max_keys, dz, st);
 }
 
 extern "C" int mvsdet_splat_backward_f32(const float* means, const int64_t* means_strides, const float* covariances, const int64_t* cov_strides,
                                          const float* harmonics, const int64_t* sh_strides, const float* opacities, int64_t opacity_stride,
-                                         const float* cams, const float* background, const float* g_image, void* workspace,
+                                         const float* cams, const float* near, const float* far, const float* background,
+                                         const float* g_image, const float* g_depth, const float* values, void* workspace,
                                          size_t workspace_bytes, float* slots, float* g_means, float* g_covariances, float* g_harmonics,
-                                         float* g_opacities, int V, int G, int d_sh, int use_sh, int H, int W, int max_keys,
-                                         mvsdet_stream_t stream) {
-    if (int rc = check_splat("splat_backward", V, G, d_sh, use_sh, H, W, max_keys)) return rc;
-    MVS_REQUIRE(means && means_strides && covariances && cov_strides && harmonics && sh_strides && opacities && cams && background && g_image &&
-                    workspace && slots && g_means && g_covariances && g_harmonics && g_opacities,
-                "splat_backward: NULL pointer");
-    const SplatIn in = splat_inputs(means, means_strides, covariances, cov_strides, harmonics, sh_strides, opacities, opacity_stride);
-    return splat_backward<true, false>("splat_backward", in, cams, background, g_image, workspace, workspace_bytes, slots, g_means,
-                                       g_covariances, g_harmonics, g_opacities, V, G, d_sh, use_sh, H, W, max_keys, SplatDepth<false>{},
-                                       (hipStream_t)stream);
-}
-
-// ------------------------------------------------------------------------------------------------ rendered depth
-// with_colour 1: colour + depth in one pass.  with_colour 0: depth alone -- harmonics, sh_strides, background and image / g_image /
-// g_harmonics are not read and may be NULL; d_sh and use_sh are ignored.
-extern "C" int mvsdet_splat_forward_depth_f32(const float* means, const int64_t* means_strides, const float* covariances,
-                                              const int64_t* cov_strides, const float* harmonics, const int64_t* sh_strides,
-                                              const float* opacities, int64_t opacity_stride, const float* cams, const float* near,
-                                              const float* far, const float* background, float* image, float* depth, float* values,
-                                              void* workspace, size_t workspace_bytes, int V, int G, int d_sh, int use_sh, int with_colour,
-                                              int mode, int H, int W, int max_keys, mvsdet_stream_t stream) {
+                                         float* g_opacities, int V, int G, int d_sh, int use_sh, int with_colour, int with_depth, int mode,
+                                         int H, int W, int max_keys, mvsdet_stream_t stream) {
+    const char* name = "splat_backward";
+    MVS_REQUIRE(with_colour || with_depth, "%s: neither colour nor depth is asked for (with_colour = with_depth = 0)", name);
     if (!with_colour) d_sh = 1, use_sh = 0;
-    if (int rc = check_splat("splat_forward_depth", V, G, d_sh, use_sh, H, W, max_keys)) return rc;
-    if (int rc = check_splat_depth("splat_forward_depth", V, mode, max_keys)) return rc;
-    MVS_REQUIRE(means && means_strides && covariances && cov_strides && opacities && cams && near && far && depth && values && workspace &&
-                    (!with_colour || (harmonics && sh_strides && background && image)),
-                "splat_forward_depth: NULL pointer");
-    const int64_t none[3] = {0, 0, 0};
-    const SplatIn in = splat_inputs(means, means_strides, covariances, cov_strides, with_colour ? harmonics : nullptr,
-                                    with_colour ? sh_strides : none, opacities, opacity_stride);
-    const SplatDepth<true> dz{near, far, values, depth, mode};
-    const hipStream_t st = (hipStream_t)stream;
-    if (with_colour)
-        return splat_forward<true, true>("splat_forward_depth", in, cams, background, image, workspace, workspace_bytes, V, G, d_sh, use_sh, H,
-                                         W, max_keys, dz, st);
-    return splat_forward<false, true>("splat_forward_depth", in, cams, nullptr, nullptr, workspace, workspace_bytes, V, G, d_sh, use_sh, H, W,
-                                      max_keys, dz, st);
-}
-
-extern "C" int mvsdet_splat_backward_depth_f32(const float* means, const int64_t* means_strides, const float* covariances,
-                                               const int64_t* cov_strides, const float* harmonics, const int64_t* sh_strides,
-                                               const float* opacities, int64_t opacity_stride, const float* cams, const float* near,
-                                               const float* far, const float* background, const float* g_image, const float* g_depth,
-                                               const float* values, void* workspace, size_t workspace_bytes, float* slots, float* g_means,
-                                               float* g_covariances, float* g_harmonics, float* g_opacities, int V, int G, int d_sh,
-                                               int use_sh, int with_colour, int mode, int H, int W, int max_keys, mvsdet_stream_t stream) {
-    if (!with_colour) d_sh = 1, use_sh = 0;
-    if (int rc = check_splat("splat_backward_depth", V, G, d_sh, use_sh, H, W, max_keys)) return rc;
-    if (int rc = check_splat_depth("splat_backward_depth", V, mode, max_keys)) return rc;
-    MVS_REQUIRE(means && means_strides && covariances && cov_strides && opacities && cams && near && far && g_depth && values && workspace &&
-                    slots && g_means && g_covariances && g_opacities &&
-                    (!with_colour || (harmonics && sh_strides && background && g_image && g_harmonics)),
-                "splat_backward_depth: NULL pointer");
-    const int64_t none[3] = {0, 0, 0};
-    const SplatIn in = splat_inputs(means, means_strides, covariances, cov_strides, with_colour ? harmonics : nullptr,
-                                    with_colour ? sh_strides : none, opacities, opacity_stride);
+    if (int rc = check_splat(name, V, G, d_sh, use_sh, with_depth, mode, H, W, max_keys)) return rc;
+    MVS_REQUIRE(means && means_strides && covariances && cov_strides && opacities && cams && workspace && slots && g_means && g_covariances &&
+                    g_opacities && (!with_colour || (harmonics && sh_strides && background && g_image && g_harmonics)) &&
+                    (!with_depth || (near && far && g_depth && values)),
+                "%s: NULL pointer", name);
+    const SplatIn in = splat_inputs(means, means_strides, covariances, cov_strides, harmonics, sh_strides, opacities, opacity_stride, with_colour);
     // the kernels only read values and g_depth; the struct is shared with the forward, which writes them
     const SplatDepth<true> dz{near, far, const_cast<float*>(values), const_cast<float*>(g_depth), mode};
     const hipStream_t st = (hipStream_t)stream;
+    if (!with_depth)
+        return splat_backward<true, false>(name, in, cams, background, g_image, workspace, workspace_bytes, slots, g_means, g_covariances,
+                                           g_harmonics, g_opacities, V, G, d_sh, use_sh, H, W, max_keys, SplatDepth<false>{}, st);
     if (with_colour)
-        return splat_backward<true, true>("splat_backward_depth", in, cams, background, g_image, workspace, workspace_bytes, slots, g_means,
-                                          g_covariances, g_harmonics, g_opacities, V, G, d_sh, use_sh, H, W, max_keys, dz, st);
-    return splat_backward<false, true>("splat_backward_depth", in, cams, nullptr, nullptr, workspace, workspace_bytes, slots, g_means,
-                                       g_covariances, nullptr, g_opacities, V, G, d_sh, use_sh, H, W, max_keys, dz, st);
+        return splat_backward<true, true>(name, in, cams, background, g_image, workspace, workspace_bytes, slots, g_means, g_covariances,
+                                          g_harmonics, g_opacities, V, G, d_sh, use_sh, H, W, max_keys, dz, st);
+    return splat_backward<false, true>(name, in, cams, nullptr, nullptr, workspace, workspace_bytes, slots, g_means, g_covariances, nullptr,
+                                       g_opacities, V, G, d_sh, use_sh, H, W, max_keys, dz, st);
 }

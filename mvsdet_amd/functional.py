@@ -498,27 +498,46 @@ def render_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tenso
     (default 8 G); a view that needs more comes out NaN.  There is no CPU path.  `scene` is accepted and unused, as in the reference."""
     if not (use_sh or gaussian_sh_coefficients.shape[-1] == 1):
         raise ValueError("render_cuda: without use_sh the coefficients are the colours, (B,G,3,1)")
-    tensors = amp_fp32(extrinsics, intrinsics, near, far, background_color, gaussian_means, gaussian_covariances,
-                       gaussian_sh_coefficients, gaussian_opacities)
-    extrinsics, intrinsics, near, far, background_color, means, covs, shs, opacs = tensors
-    if means.dim() != 3 or covs.dim() != 4 or shs.dim() != 4 or opacs.dim() != 2:
-        raise ValueError(f"render_cuda: means {tuple(means.shape)}, covariances {tuple(covs.shape)}, coefficients {tuple(shs.shape)} and "
-                         f"opacities {tuple(opacs.shape)} must be (B,G,3), (B,G,3,3), (B,G,3,d_sh) and (B,G)")
+    return _render_views("render_cuda", extrinsics, intrinsics, near, far, image_shape, gaussian_means, gaussian_covariances,
+                         gaussian_opacities, gaussian_sh_coefficients, background_color, scale_invariant, use_sh, max_keys)
+
+
+def _render_views(name: str, extrinsics, intrinsics, near, far, image_shape, means, covs, opacs, shs=None, background=None,
+                  scale_invariant=True, use_sh=True, max_keys=None, depth_mode=None):
+    """What render_cuda, render_depth_cuda and decode_splatting share: amp_fp32, the shape refusal, the key capacity, one
+    `splat_cameras` launch for the B views and the one-call rule.  shs and background given, depth_mode None: `rasterize` -> colour;
+    shs None: `depth_only` -> depth; both given: `rasterize_depth` -> (colour, depth)."""
+    extrinsics, intrinsics, near, far, background, means, covs, shs, opacs = amp_fp32(extrinsics, intrinsics, near, far, background, means,
+                                                                                      covs, shs, opacs)
+    colour = shs is not None
+    if means.dim() != 3 or covs.dim() != 4 or (colour and shs.dim() != 4) or opacs.dim() != 2:
+        got, form = (f", coefficients {tuple(shs.shape)}", ", (B,G,3,d_sh)") if colour else ("", "")
+        raise ValueError(f"{name}: means {tuple(means.shape)}, covariances {tuple(covs.shape)}{got} and opacities {tuple(opacs.shape)} "
+                         f"must be (B,G,3), (B,G,3,3){form} and (B,G)")
     b, G = means.shape[:2]
     h, w = (int(v) for v in image_shape)
-    if extrinsics.shape[0] != b or background_color.shape[0] != b:
-        raise ValueError(f"render_cuda: {extrinsics.shape[0]} cameras and {background_color.shape[0]} backgrounds for {b} batch rows")
+    if extrinsics.shape[0] != b or (colour and background.shape[0] != b):
+        got = f" and {background.shape[0]} backgrounds" if colour else ""
+        raise ValueError(f"{name}: {extrinsics.shape[0]} cameras{got} for {b} batch rows")
     keys = ops.splat.default_max_keys(G) if max_keys is None else int(max_keys)
     cams = ops.splat.splat_cameras(extrinsics, intrinsics, near, far, bool(scale_invariant))
-    if _one_call(b, means, covs, shs, opacs):
-        return ops.splat.rasterize(means[0], covs[0], shs[0], opacs[0], cams, background_color, h, w, keys, bool(use_sh))[0]
-    return torch.cat([ops.splat.rasterize(means[i], covs[i], shs[i], opacs[i], cams[i:i + 1], background_color[i:i + 1], h, w, keys,
-                                          bool(use_sh))[0] for i in range(b)])
 
+    def views(i, cams, near, far, background):   # Gaussian set i under these cameras -> the outputs asked for, as a tuple
+        if not colour:
+            return ops.splat.depth_only(means[i], covs[i], opacs[i], cams, near, far, h, w, keys, depth_mode)[:1]
+        if depth_mode is None:
+            return ops.splat.rasterize(means[i], covs[i], shs[i], opacs[i], cams, background, h, w, keys, bool(use_sh))[:1]
+        return ops.splat.rasterize_depth(means[i], covs[i], shs[i], opacs[i], cams, near, far, background, h, w, keys, bool(use_sh),
+                                         depth_mode)[:2]
 
-def _one_call(b: int, *tensors) -> bool:
-    """render_cuda's rule: B == 1, or every Gaussian tensor an expanded view of one set -> one call over the B views."""
-    return b == 1 or all(t.stride(0) == 0 for t in tensors)
+    per_view = (cams, near, far, background)
+    # render_cuda's rule: B == 1, or every Gaussian tensor an expanded view of one set (stride 0) -> one call over the B views
+    if b == 1 or all(t.stride(0) == 0 for t in (means, covs, opacs, shs) if t is not None):
+        out = views(0, *per_view)
+    else:
+        rows = [views(i, *[t if t is None else t[i:i + 1] for t in per_view]) for i in range(b)]
+        out = tuple(torch.cat(parts) for parts in zip(*rows))
+    return out[0] if len(out) == 1 else out
 
 
 def render_depth_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, image_shape: Tuple[int, int],
@@ -532,21 +551,8 @@ def render_depth_cuda(extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far:
     the last bit.  Batch rows go out as in `render_cuda`: expanded rows or B == 1 as one call, distinct rows one call each."""
     if mode not in ops.splat.DEPTH_MODES:
         raise ValueError(f"render_depth_cuda: mode {mode!r} must be one of {ops.splat.DEPTH_MODES}")
-    extrinsics, intrinsics, near, far, means, covs, opacs = amp_fp32(extrinsics, intrinsics, near, far, gaussian_means, gaussian_covariances,
-                                                                     gaussian_opacities)
-    if means.dim() != 3 or covs.dim() != 4 or opacs.dim() != 2:
-        raise ValueError(f"render_depth_cuda: means {tuple(means.shape)}, covariances {tuple(covs.shape)} and opacities "
-                         f"{tuple(opacs.shape)} must be (B,G,3), (B,G,3,3) and (B,G)")
-    b, G = means.shape[:2]
-    h, w = (int(v) for v in image_shape)
-    if extrinsics.shape[0] != b:
-        raise ValueError(f"render_depth_cuda: {extrinsics.shape[0]} cameras for {b} batch rows")
-    keys = ops.splat.default_max_keys(G) if max_keys is None else int(max_keys)
-    cams = ops.splat.splat_cameras(extrinsics, intrinsics, near, far, bool(scale_invariant))
-    if _one_call(b, means, covs, opacs):
-        return ops.splat.depth_only(means[0], covs[0], opacs[0], cams, near, far, h, w, keys, mode)[0]
-    return torch.cat([ops.splat.depth_only(means[i], covs[i], opacs[i], cams[i:i + 1], near[i:i + 1], far[i:i + 1], h, w, keys, mode)[0]
-                      for i in range(b)])
+    return _render_views("render_depth_cuda", extrinsics, intrinsics, near, far, image_shape, gaussian_means, gaussian_covariances,
+                         gaussian_opacities, scale_invariant=scale_invariant, max_keys=max_keys, depth_mode=mode)
 
 
 def decode_splatting(gaussians, extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor, image_shape: Tuple[int, int],
@@ -562,22 +568,14 @@ def decode_splatting(gaussians, extrinsics: Tensor, intrinsics: Tensor, near: Te
     bg = torch.zeros(3, dtype=torch.float32, device=dev) if background_color is None else background_color.to(dev)
     if depth_mode is not None and depth_mode not in ops.splat.DEPTH_MODES:
         raise ValueError(f"decode_splatting: depth_mode {depth_mode!r} must be None or one of {ops.splat.DEPTH_MODES}")
-    rows, depths = [], []
+    rows = []
     for i in range(b):
-        if depth_mode is None:
-            rows.append(render_cuda(extrinsics[i], intrinsics[i], near[i], far[i], image_shape, bg.expand(v, 3),
-                                    gaussians.means[i].expand(v, -1, -1), gaussians.covariances[i].expand(v, -1, -1, -1),
-                                    gaussians.harmonics[i].expand(v, -1, -1, -1), gaussians.opacities[i].expand(v, -1), max_keys=max_keys))
-            continue
-        E, K, n, f, bgs, means, covs, shs, opacs = amp_fp32(extrinsics[i], intrinsics[i], near[i], far[i], bg.expand(v, 3), gaussians.means[i],
-                                                            gaussians.covariances[i], gaussians.harmonics[i], gaussians.opacities[i])
-        h, w = (int(x) for x in image_shape)
-        keys = ops.splat.default_max_keys(means.shape[0]) if max_keys is None else int(max_keys)
-        cams = ops.splat.splat_cameras(E, K, n, f, True)
-        colour, depth, _, _ = ops.splat.rasterize_depth(means, covs, shs, opacs, cams, n, f, bgs, h, w, keys, True, depth_mode)
-        rows.append(colour)
-        depths.append(depth)
-    return torch.stack(rows) if depth_mode is None else (torch.stack(rows), torch.stack(depths))
+        sets = (gaussians.means[i], gaussians.covariances[i], gaussians.opacities[i], gaussians.harmonics[i])
+        if depth_mode is not None:   # cast before the rows are expanded, so that they stay views of one set and go out as one call
+            sets = amp_fp32(*sets)
+        rows.append(_render_views("decode_splatting", extrinsics[i], intrinsics[i], near[i], far[i], image_shape,
+                                  *[t.expand(v, *t.shape) for t in sets], bg.expand(v, 3), max_keys=max_keys, depth_mode=depth_mode))
+    return torch.stack(rows) if depth_mode is None else tuple(torch.stack(t) for t in zip(*rows))
 
 
 class PixelGaussians:

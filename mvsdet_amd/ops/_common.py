@@ -19,6 +19,24 @@ def req(t: Tensor, name: str, dtype=torch.float32, dim=None):
         raise ValueError(f"mvsdet_amd: `{name}` must be {dim}-D (got shape {tuple(t.shape)})")
 
 
+def camera_inputs(name: str, extrinsics: Tensor, intrinsics: Tensor):
+    """What the one-thread-per-view camera kernels take: extrinsics (V,4,4) as rows of 4 adjacent floats, intrinsics (V,3,3) with unit
+    stride inside a row (a copy where the caller's view is laid out otherwise) -> (extrinsics, intrinsics, V, the three element
+    strides of the C entries: extrinsics view, intrinsics view, intrinsics row).  `ops.photo.photo_geometry` does not come through
+    here: its cameras have 3 or 4 rows and its intrinsics may be one matrix for all views."""
+    req(extrinsics, "extrinsics", dim=3)
+    req(intrinsics, "intrinsics", dim=3)
+    V = extrinsics.shape[0]
+    if tuple(extrinsics.shape[1:]) != (4, 4) or tuple(intrinsics.shape) != (V, 3, 3) or V < 1:
+        raise ValueError(f"{name}: extrinsics {tuple(extrinsics.shape)} and intrinsics {tuple(intrinsics.shape)} must be (V,4,4) and "
+                         "(V,3,3)")
+    if extrinsics.stride(2) != 1 or extrinsics.stride(1) != 4:
+        extrinsics = extrinsics.contiguous()
+    if intrinsics.stride(2) != 1:
+        intrinsics = intrinsics.contiguous()
+    return extrinsics, intrinsics, V, (extrinsics.stride(0), intrinsics.stride(0), intrinsics.stride(1))
+
+
 def stream(t: Tensor):
     return _lib.current_stream(t.device)
 

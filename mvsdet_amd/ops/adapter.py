@@ -10,7 +10,7 @@ from typing import Optional, Tuple
 import torch
 from torch import Tensor
 
-from ._common import _NS, _lib, req, stream
+from ._common import _NS, _lib, camera_inputs, req, stream
 
 ADAPTER_CAM = 192         # floats per view: C 9, origin 3, K^-1 9, multiplier, 2 unused, rotation blocks of the harmonics 165, 3 unused
 ADAPTER_ROT = 24          # first float of the rotation blocks
@@ -40,27 +40,20 @@ def adapter_cameras(extrinsics: Tensor, intrinsics: Tensor, h: int, w: int, sh_d
     of an h x w map and the rotation blocks D_l of the harmonics.  sh_rot None: the blocks that are right for the basis this project
     renders with (csrc/sh_basis.h); sh_rot (V, rotation_floats(d_sh)): the caller's blocks, row-major, degree after degree (degree 0
     included), applied as given.  One launch of one thread per view, float64 inside, rounded once; nothing returns to the host."""
-    req(extrinsics, "extrinsics", dim=3)
-    req(intrinsics, "intrinsics", dim=3)
-    V = extrinsics.shape[0]
+    extrinsics, intrinsics, V, (e_view, k_view, k_row) = camera_inputs("adapter_cameras", extrinsics, intrinsics)
     d_sh = _d_sh("adapter_cameras", sh_degree)
-    if tuple(extrinsics.shape[1:]) != (4, 4) or tuple(intrinsics.shape) != (V, 3, 3) or V < 1 or h < 1 or w < 1:
-        raise ValueError(f"adapter_cameras: extrinsics {tuple(extrinsics.shape)} and intrinsics {tuple(intrinsics.shape)} must be (V,4,4) "
-                         f"and (V,3,3), h and w positive (got {h}, {w})")
+    if h < 1 or w < 1:
+        raise ValueError(f"adapter_cameras: h and w must be positive (got {h}, {w})")
     if sh_rot is not None:
         req(sh_rot, "sh_rot", dim=2)
         if tuple(sh_rot.shape) != (V, rotation_floats(d_sh)):
             raise ValueError(f"adapter_cameras: sh_rot {tuple(sh_rot.shape)} must be {(V, rotation_floats(d_sh))}")
         sh_rot = sh_rot.contiguous()
-    if extrinsics.stride(2) != 1 or extrinsics.stride(1) != 4:
-        extrinsics = extrinsics.contiguous()
-    if intrinsics.stride(2) != 1:
-        intrinsics = intrinsics.contiguous()
     cams = torch.empty((V, ADAPTER_CAM), dtype=torch.float32, device=extrinsics.device)
     with torch.cuda.device(extrinsics.device):
         _lib.check(_lib.load().mvsdet_adapter_cameras_f32(
-            _lib.ptr(extrinsics), extrinsics.stride(0), _lib.ptr(intrinsics), intrinsics.stride(0), intrinsics.stride(1), _lib.ptr(sh_rot),
-            _lib.ptr(cams), V, int(h), int(w), d_sh, stream(extrinsics)), "adapter_cameras")
+            _lib.ptr(extrinsics), e_view, _lib.ptr(intrinsics), k_view, k_row, _lib.ptr(sh_rot), _lib.ptr(cams), V, int(h), int(w), d_sh,
+            stream(extrinsics)), "adapter_cameras")
     return cams
 
 

@@ -5,17 +5,12 @@ The names live in this module only (`ops.gshead.<name>`); they are not re-export
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Optional, Sequence, Tuple, Union
 
 import torch
 from torch import Tensor
 
 from ._common import _NS, _lib, req, stream, to_device
-
-
-def _i64(values) -> ctypes.Array:
-    return (ctypes.c_int64 * len(values))(*[int(v) for v in values])
 
 
 def _unit_w(t: Tensor) -> Tensor:
@@ -105,7 +100,7 @@ def _prepare(name: str, feature: Tensor, depth_coding: Tensor, ids: Tensor, weig
 def _image_args(images: Optional[Tensor]):
     if images is None:
         return None, None, 0, 0
-    return _lib.ptr(images), _i64(images.stride()[:3]), int(images.shape[2]), int(images.shape[3])
+    return _lib.ptr(images), _lib.strides(images, 3), int(images.shape[2]), int(images.shape[3])
 
 
 def forward_into(feature: Tensor, depth_coding: Tensor, ids: Tensor, weight: Tensor, bias: Tensor, h: int, w: int, raw: Tensor,
@@ -119,7 +114,7 @@ def forward_into(feature: Tensor, depth_coding: Tensor, ids: Tensor, weight: Ten
     img, img_strides, Hi, Wi = _image_args(images)
     with torch.cuda.device(feature.device):
         _lib.check(_lib.load().mvsdet_gshead_forward_f32(
-            _lib.ptr(feature), _i64(feature.stride()[:3]), _lib.ptr(depth), _i64(depth.stride()[:2]), _lib.ptr(rgb_raw), img, img_strides,
+            _lib.ptr(feature), _lib.strides(feature, 3), _lib.ptr(depth), _lib.strides(depth, 2), _lib.ptr(rgb_raw), img, img_strides,
             ids.data_ptr(), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(raw), N, V, C, K, M, int(h), int(w), int(feature.shape[2]),
             int(feature.shape[3]), Hi, Wi, stream(feature)), "gaussian_head")
 
@@ -159,8 +154,8 @@ def backward_into(feature: Tensor, depth_coding: Tensor, ids: Tensor, weight: Te
                 raise ValueError(f"gaussian_head_backward: g_feature {tuple(g_feature.shape)} / g_depth_coding {tuple(g_depth_coding.shape)} "
                                  "must have the inputs' shapes and unit stride along w")
             _lib.check(lib.mvsdet_gshead_backward_input_f32(
-                _lib.ptr(feature), _i64(feature.stride()[:3]), _lib.ptr(depth), _i64(depth.stride()[:2]), ids.data_ptr(), _lib.ptr(weight),
-                _lib.ptr(g), _lib.ptr(g_feature), _i64(g_feature.stride()[:3]), _lib.ptr(gd), _i64(gd.stride()[:2]), N, V, C, K, M, int(h),
+                _lib.ptr(feature), _lib.strides(feature, 3), _lib.ptr(depth), _lib.strides(depth, 2), ids.data_ptr(), _lib.ptr(weight),
+                _lib.ptr(g), _lib.ptr(g_feature), _lib.strides(g_feature, 3), _lib.ptr(gd), _lib.strides(gd, 2), N, V, C, K, M, int(h),
                 int(w), int(feature.shape[2]), int(feature.shape[3]), stream(feature)), "gaussian_head_backward")
         if g_weight is not None:
             req(g_weight, "g_weight", dim=2)
@@ -176,7 +171,7 @@ def backward_into(feature: Tensor, depth_coding: Tensor, ids: Tensor, weight: Te
                 raise ValueError("gaussian_head_backward: partial must be contiguous")
             img, img_strides, Hi, Wi = _image_args(images)
             _lib.check(lib.mvsdet_gshead_backward_weight_f32(
-                _lib.ptr(feature), _i64(feature.stride()[:3]), _lib.ptr(depth), _i64(depth.stride()[:2]), _lib.ptr(rgb_raw), img, img_strides,
+                _lib.ptr(feature), _lib.strides(feature, 3), _lib.ptr(depth), _lib.strides(depth, 2), _lib.ptr(rgb_raw), img, img_strides,
                 ids.data_ptr(), _lib.ptr(g), _lib.ptr(g_weight), _lib.ptr(g_bias), _lib.ptr(partial), partial.numel() * 4, int(chunk_pixels),
                 N, V, C, K, M, int(h), int(w), int(feature.shape[2]), int(feature.shape[3]), Hi, Wi, stream(feature)),
                 "gaussian_head_backward")
@@ -277,7 +272,7 @@ def process_rgb_raw_rows(images: Tensor, ids: Union[Tensor, Sequence[int]], h: i
     images = _unit_w(images.detach())
     rows = torch.empty((ids.numel(), h * w, 3), dtype=torch.float32, device=images.device)
     with torch.cuda.device(images.device):
-        _lib.check(_lib.load().mvsdet_gshead_rgb_rows_f32(_lib.ptr(images), _i64(images.stride()[:3]), ids.data_ptr(), _lib.ptr(rows),
+        _lib.check(_lib.load().mvsdet_gshead_rgb_rows_f32(_lib.ptr(images), _lib.strides(images, 3), ids.data_ptr(), _lib.ptr(rows),
                                                           int(images.shape[0]), int(ids.numel()), h, w, int(images.shape[2]),
                                                           int(images.shape[3]), stream(images)), "process_rgb_raw")
     return rows

@@ -1,7 +1,7 @@
 """The rendered depth's restatement (tests/splat_depth_restated.py) and fixture G28 on the CPU: what test_gpu_splat_depth.py stands on.
 No GPU, no kernel: the restatement against closed forms and against what the reference's own render_depth_cuda handed its rasteriser
 (tests/golden/make_goldens_g28.py), the scenes' conditions in the four modes, and the refusals that need no device -- the operators',
-functional.render_depth_cuda's, and the new C entry points' argument errors.
+functional.render_depth_cuda's, and the C entry points' argument errors in their depth forms.
 """
 import ctypes
 
@@ -120,8 +120,9 @@ def test_argument_errors_of_the_depth_entry_points_return_without_launching():
     s2, s3 = (ctypes.c_int64 * 2)(3, 1), (ctypes.c_int64 * 3)(9, 3, 1)
     # means, strides, covariances, strides, harmonics, strides, opacities, stride, cams, near, far, background, image, depth, values, workspace, bytes
     fwd = (one, s2, one, s3, one, s3, one, 1, one, one, one, one, one, one, one, one, 1 << 30)
-    sizes = lambda V=1, G=8, d_sh=4, use_sh=1, colour=1, mode=0, H=16, W=16, keys=64: (V, G, d_sh, use_sh, colour, mode, H, W, keys, None)  # noqa: E731
-    f = lib.mvsdet_splat_forward_depth_f32
+    sizes = lambda V=1, G=8, d_sh=4, use_sh=1, colour=1, depth=1, mode=0, H=16, W=16, keys=64: (  # noqa: E731
+        V, G, d_sh, use_sh, colour, depth, mode, H, W, keys, None)
+    f = lib.mvsdet_splat_forward_f32
     for mode in (-1, 4):
         assert f(*fwd, *sizes(mode=mode)) == 1 and b"mode" in lib.mvsdet_last_error()
     assert f(*fwd, *sizes(d_sh=5)) == 1 and b"d_sh" in lib.mvsdet_last_error()
@@ -138,13 +139,21 @@ def test_argument_errors_of_the_depth_entry_points_return_without_launching():
     assert f(*fwd[:4], None, None, *fwd[6:11], None, None, *fwd[13:16], 64, *sizes(colour=0)) == 2      # depth alone: past the NULL check
     # backward: ..., background, g_image, g_depth, values, workspace, bytes, slots, g_means, g_covariances, g_harmonics, g_opacities
     bwd = (one, s2, one, s3, one, s3, one, 1, one, one, one, one, one, one, one, one, 1 << 30, one, one, one, one, one)
-    b = lib.mvsdet_splat_backward_depth_f32
+    b = lib.mvsdet_splat_backward_f32
     assert b(*bwd, *sizes(mode=7)) == 1 and b"mode" in lib.mvsdet_last_error()
     assert b(*bwd, *sizes(keys=keys)) == 1 and b"10 V max_keys" in lib.mvsdet_last_error()
     for i in (0, 9, 13, 14, 17, 18, 21):                            # means, near, g_depth, values, slots, g_means, g_opacities
         assert b(*bwd[:i], None, *bwd[i + 1:], *sizes()) == 1 and b"NULL" in lib.mvsdet_last_error(), i
     assert b(*bwd[:12], None, *bwd[13:], *sizes()) == 1 and b"NULL" in lib.mvsdet_last_error()          # g_image, with colour
     assert b(*bwd[:16], 64, *bwd[17:], *sizes()) == 2 and b"workspace" in lib.mvsdet_last_error()
-    # the existing entry points keep their limit: 9 V max_keys
-    old = (one, s2, one, s3, one, s3, one, 1, one, one, one, one, 64)
-    assert lib.mvsdet_splat_forward_f32(*old, 1, 8, 4, 1, 16, 16, keys, None) == 2 and b"workspace" in lib.mvsdet_last_error()
+    # without depth the limit is 9 V max_keys, mode is not looked at, and near, far, depth, values (g_depth) may be NULL
+    plain = (*fwd[:9], None, None, *fwd[11:13], None, None, fwd[15], 64)
+    assert f(*plain, *sizes(depth=0, keys=keys)) == 2 and b"workspace" in lib.mvsdet_last_error()
+    assert f(*plain, *sizes(depth=0, mode=-1)) == 2 and b"workspace" in lib.mvsdet_last_error()
+    assert f(*plain, *sizes(depth=0)) == 2 and b"workspace" in lib.mvsdet_last_error()
+    assert b(*bwd[:9], None, None, *bwd[11:13], None, None, bwd[15], 64, *bwd[17:], *sizes(depth=0, keys=keys)) == 2
+    for i in (4, 11, 12):                                           # ... but the colour's pointers may not
+        assert f(*plain[:i], None, *plain[i + 1:], *sizes(depth=0)) == 1 and b"NULL" in lib.mvsdet_last_error(), i
+    # neither colour nor depth: refused before anything else is looked at (the sizes are bad too)
+    for fn, head in ((f, fwd), (b, bwd)):
+        assert fn(*head, *sizes(colour=0, depth=0, keys=0, mode=9)) == 1 and b"neither colour nor depth" in lib.mvsdet_last_error()

@@ -159,14 +159,20 @@ def test_argument_errors_return_without_launching():
     lib = _lib.load()
     one = ctypes.c_void_p(4096)
     s2, s3 = (ctypes.c_int64 * 2)(3, 1), (ctypes.c_int64 * 3)(9, 3, 1)
-    args = (one, s2, one, s3, one, s3, one, 1, one, one, one, one, 1 << 30)
-    assert lib.mvsdet_splat_forward_f32(*args, 1, 8, 5, 1, 16, 16, 64, None) == 1 and b"d_sh" in lib.mvsdet_last_error()
-    assert lib.mvsdet_splat_forward_f32(*args, 1, 8, 4, 0, 16, 16, 64, None) == 1 and b"precomputed" in lib.mvsdet_last_error()
-    assert lib.mvsdet_splat_forward_f32(*args, 1, 8, 4, 1, 16, 16, 0, None) == 1 and b"bad sizes" in lib.mvsdet_last_error()
-    assert lib.mvsdet_splat_forward_f32(*args, 2, 1 << 30, 4, 1, 16, 16, 64, None) == 1 and b"limits" in lib.mvsdet_last_error()
-    assert lib.mvsdet_splat_forward_f32(*args[:12], 64, 1, 8, 4, 1, 16, 16, 64, None) == 2 and b"workspace" in lib.mvsdet_last_error()
-    assert lib.mvsdet_splat_forward_f32(None, *args[1:], 1, 8, 4, 1, 16, 16, 64, None) == 1 and b"NULL" in lib.mvsdet_last_error()
-    assert lib.mvsdet_splat_backward_f32(*args[:10], None, one, 1 << 30, one, one, one, one, one, 1, 8, 4, 1, 16, 16, 64, None) == 1
+    # means, strides, covariances, strides, harmonics, strides, opacities, stride, cams, near, far, background, image, depth, values, workspace,
+    # bytes; then V, G, d_sh, use_sh, with_colour, with_depth, mode, H, W, max_keys, stream.  Colour alone: near, far, depth, values NULL
+    args = (one, s2, one, s3, one, s3, one, 1, one, None, None, one, one, None, None, one, 1 << 30)
+    f = lib.mvsdet_splat_forward_f32
+    assert f(*args, 1, 8, 5, 1, 1, 0, 0, 16, 16, 64, None) == 1 and b"d_sh" in lib.mvsdet_last_error()
+    assert f(*args, 1, 8, 4, 0, 1, 0, 0, 16, 16, 64, None) == 1 and b"precomputed" in lib.mvsdet_last_error()
+    assert f(*args, 1, 8, 4, 1, 1, 0, 0, 16, 16, 0, None) == 1 and b"bad sizes" in lib.mvsdet_last_error()
+    assert f(*args, 2, 1 << 30, 4, 1, 1, 0, 0, 16, 16, 64, None) == 1 and b"limits" in lib.mvsdet_last_error()
+    assert f(*args[:16], 64, 1, 8, 4, 1, 1, 0, 0, 16, 16, 64, None) == 2 and b"workspace" in lib.mvsdet_last_error()
+    assert f(None, *args[1:], 1, 8, 4, 1, 1, 0, 0, 16, 16, 64, None) == 1 and b"NULL" in lib.mvsdet_last_error()
+    # backward: ..., background, g_image (NULL here), g_depth, values, workspace, bytes, slots, g_means, g_covariances, g_harmonics, g_opacities
+    assert lib.mvsdet_splat_backward_f32(*args[:12], None, None, None, one, 1 << 30, one, one, one, one, one, 1, 8, 4, 1, 1, 0, 0, 16, 16, 64,
+                                         None) == 1
+    assert b"NULL" in lib.mvsdet_last_error()
     assert lib.mvsdet_splat_cameras_f32(one, 16, one, 9, 2, one, one, 1, one, 1, None) == 1 and b"intrinsics rows" in lib.mvsdet_last_error()
     assert lib.mvsdet_splat_workspace_bytes(1, 8, 16, 16, 0) == 0
 
