@@ -53,7 +53,13 @@ const char* mvsdet_last_error(void);
  *                   decode (no range tests, no clamps of the tap offsets); 0 = every plane takes the general decode
  *   "sweep_pool"    1 (default) | 0   mvsdet_plane_sweep_table_pooled_f32 builds the pooled geometry; 0 = it builds what
  *                   mvsdet_plane_sweep_table[_pitched]_f32 build
- *   "depthprob_ahead"  1 (default) | 0   mvsdet_depth_prob_topk[_strided]_f32 requests every input of a pixel before its first
+ *   "sweep_store"   0 (default) = non-temporal | 1 plain | 2 sc1 | 3 sc0 sc1 | 4 nt sc1   cache policy of the sweep's output stores
+ *                   (FAST form, two neighbours) and of mvsdet_store_pattern_probe_*; MVSDET_SWEEP_STORE.  A value selects a compiled
+ *                   instantiation: the default build carries 0 alone, the A/B build (make SWEEP_STORE_MATRIX=1) all of them, and
+ *                   mvsdet_set_option refuses a value that is not compiled in
+ *   "sweep_box_load"  0 (default) | 1 = non-temporal   cache policy of the footprint boxes' LDS-DMA and of a block's reference-feature
+ *                   loads; MVSDET_SWEEP_BOX_LOAD; compiled and refused like "sweep_store"
+ *   "depthprob_ahead"  1 (default) | 0  mvsdet_depth_prob_topk[_strided]_f32 requests every input of a pixel before its first
  *                   store (D <= 64), or runs its last pass eight planes ahead (D > 64); 0 = plane by plane, behind the stores
  *   "sweep_dsplit", "sweep_groups", "bwd_groups", "conv_*"   schedules of the sweep's plane split, of the bf16x3
  *                   convolutions and of the fp16 + MX convolution ("conv_mx_th") (csrc/common.h: struct Options)
@@ -795,7 +801,7 @@ int mvsdet_copy_f32(const float* src, float* dst, size_t n_floats, mvsdet_stream
 
 /* The plane sweep's store stream alone: the block -> address map of the fused variance kernel (mvsdet.py:467's volume,
  * (N,C,D,H,out_w_pitch) fp32; C % 32 == 0, W % 4 == 0), tile width 16 or 32, `planes_per_block` planes per block (0 = all),
- * non-temporal 16-byte stores and nothing else.  bench.py times it to report what the output LAYOUT allows on the box at hand
+ * 16-byte stores of the flavour option "sweep_store" selects (default: non-temporal) and nothing else.  bench.py times it to report what the output LAYOUT allows on the box at hand
  * (`frac_of_store_pattern_ceiling`); `var` is overwritten with arbitrary values. */
 int mvsdet_store_pattern_probe_f32(float* var, int N, int C, int D, int H, int W, int out_w_pitch, int tile_w,
                                    int planes_per_block, mvsdet_stream_t stream);

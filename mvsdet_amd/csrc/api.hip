@@ -21,12 +21,21 @@ static int env_int(const char* name, int dflt) {
     return e ? atoi(e) : dflt;
 }
 
+// an option whose values select compiled instantiations: a value this build does not carry is named on stderr and not taken
+static int env_compiled(const char* name, int dflt, bool (*compiled)(int)) {
+    const int v = env_int(name, dflt);
+    if (compiled(v)) return v;
+    fprintf(stderr, "mvsdet: %s=%d is not compiled into this build; using %d\n", name, v, dflt);
+    return dflt;
+}
+
 Options& options() {
     static Options o = {env_int("MVSDET_SWEEP_TW", 0), env_int("MVSDET_SWEEP_BOXCAP", 512), env_int("MVSDET_SWEEP_XCD", 1),
                         env_int("MVSDET_SWEEP_DSPLIT", 0), env_int("MVSDET_SWEEP_GROUPS", -1),
                         env_int("MVSDET_CONV_NSPLIT", 0), env_int("MVSDET_CONV_XCD", 1), env_int("MVSDET_CONV_SPLIT_BLOCKS", 768),
                         env_int("MVSDET_CONV_SPLIT_MIN_GROUPS", 2), env_int("MVSDET_BWD_GROUPS", 0), env_int("MVSDET_SWEEP_INSIDE", 1), env_int("MVSDET_CONV_MX_TH", 0),
-                        env_int("MVSDET_SWEEP_POOL", 1), env_int("MVSDET_DEPTHPROB_AHEAD", 1)};
+                        env_int("MVSDET_SWEEP_POOL", 1), env_int("MVSDET_DEPTHPROB_AHEAD", 1),
+                        env_compiled("MVSDET_SWEEP_STORE", kSweepStoreAuto, sweep_store_compiled), env_compiled("MVSDET_SWEEP_BOX_LOAD", 0, sweep_box_load_compiled)};
     return o;
 }
 
@@ -40,6 +49,8 @@ static int* option_slot(const char* name) {
     if (!strcmp(name, "sweep_groups")) return &o.sweep_groups;
     if (!strcmp(name, "sweep_inside")) return &o.sweep_inside;
     if (!strcmp(name, "sweep_pool")) return &o.sweep_pool;
+    if (!strcmp(name, "sweep_store")) return &o.sweep_store;
+    if (!strcmp(name, "sweep_box_load")) return &o.sweep_box_load;
     if (!strcmp(name, "depthprob_ahead")) return &o.depthprob_ahead;
     if (!strcmp(name, "conv_nsplit")) return &o.conv_nsplit;
     if (!strcmp(name, "conv_xcd")) return &o.conv_xcd;
@@ -74,7 +85,9 @@ __global__ void copy_tail_kernel(const float* __restrict__ src, float* __restric
 // slab) loops over the planes; per plane each wave issues four non-temporal stores of 8 channel rows x 16 B per lane -- the
 // block -> address map of plane_sweep_variance_kernel's FAST form on an (N,C,D,H,Wo) volume.  What this pattern reaches is the
 // ceiling of the sweep's store stream on the box at hand (a device-to-device copy is not: DESIGN.md 4.1).
-template <int TW, typename OutT>
+// ST: the store flavour of option "sweep_store", as in the slab kernel: kSweepStoreNt the non-temporal global store, any other a buffer
+// store through a resource based at the block's slab.
+template <int TW, typename OutT, int ST = kSweepStoreNt>
 __global__ __launch_bounds__(kThreads) void store_pattern_kernel(OutT* __restrict__ var, int C, int D, int H, int W, int Wo,
                                                                   int tiles_x, int tiles, int d_per_block) {
     constexpr int TH = 128 / TW;
@@ -95,6 +108,24 @@ __global__ __launch_bounds__(kThreads) void store_pattern_kernel(OutT* __restric
     const v4f vv = {1.0f * id, 2.0f, 3.0f, (float)lane};
     const v2u hv = {(unsigned)id, (unsigned)lane};   // fp16 storage: the lane's 4 pixels are 8 bytes
     const int d0 = blockIdx.y * d_per_block, d1 = min(D, d0 + d_per_block);
+    if constexpr (ST != kSweepStoreNt) {
+        // the slab kernel's addressing: resource = the slab's 32 channel rows (below 4 GiB: checked by the entry point), scalar offset of
+        // (plane, channel row 8*i), lane offset of (channel g, the pixels)
+        typedef unsigned v4u __attribute__((ext_vector_type(4)));
+        OutT* var_slab = var + ((size_t)n * C + slab * 32) * D * HWo;
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(var_slab, 0, (int)(unsigned)((size_t)32 * D * HWo * sizeof(OutT)), 0x00020000);
+        const unsigned l_off = (unsigned)(((size_t)g * D * HWo + st_off) * sizeof(OutT));
+        const v4u uv = {(unsigned)id, 2u, 3u, (unsigned)lane};
+        for (int d = d0; d < d1; ++d) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const unsigned s_off = (unsigned)(((size_t)d * HWo + (size_t)8 * i * D * HWo) * sizeof(OutT));
+                if constexpr (sizeof(OutT) == 4) __builtin_amdgcn_raw_buffer_store_b128(uv, rsrc, (int)l_off, (int)s_off, sweep_store_aux(ST));
+                else __builtin_amdgcn_raw_buffer_store_b64(hv, rsrc, (int)l_off, (int)s_off, sweep_store_aux(ST));
+            }
+        }
+        return;
+    }
     for (int d = d0; d < d1; ++d) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -126,9 +157,17 @@ static int store_pattern_probe(OutT* var, int N, int C, int D, int H, int W, int
     MVS_REQUIRE(blocks <= INT32_MAX, "store_pattern_probe: grid too large");
     const int dpb = planes_per_block > 0 ? std::min(planes_per_block, D) : D;
     dim3 grid((unsigned)blocks, (unsigned)((D + dpb - 1) / dpb));
-    if (tile_w == 16) hipLaunchKernelGGL((store_pattern_kernel<16, OutT>), grid, dim3(kThreads), 0, (hipStream_t)stream, var, C, D, H, W, Wo, tiles_x, tiles, dpb);
-    else if (tile_w == 64) hipLaunchKernelGGL((store_pattern_kernel<64, OutT>), grid, dim3(kThreads), 0, (hipStream_t)stream, var, C, D, H, W, Wo, tiles_x, tiles, dpb);
-    else hipLaunchKernelGGL((store_pattern_kernel<32, OutT>), grid, dim3(kThreads), 0, (hipStream_t)stream, var, C, D, H, W, Wo, tiles_x, tiles, dpb);
+    // the flavour the sweep takes for this tile shape, storage and volume ("sweep_store": common.h, sweep_store_for); 64-wide tiles have no
+    // sweep: they follow the 32-wide ones
+    const int st = sweep_store_for(tile_w == 16 ? 16 : 32, sizeof(OutT) == 2, (size_t)32 * D * H * Wo * sizeof(OutT));
+#define MVS_PROBE(S)                                                                                                            \
+    if (st == S) {                                                                                                              \
+        if (tile_w == 16) hipLaunchKernelGGL((store_pattern_kernel<16, OutT, S>), grid, dim3(kThreads), 0, (hipStream_t)stream, var, C, D, H, W, Wo, tiles_x, tiles, dpb); \
+        else if (tile_w == 64) hipLaunchKernelGGL((store_pattern_kernel<64, OutT, S>), grid, dim3(kThreads), 0, (hipStream_t)stream, var, C, D, H, W, Wo, tiles_x, tiles, dpb); \
+        else hipLaunchKernelGGL((store_pattern_kernel<32, OutT, S>), grid, dim3(kThreads), 0, (hipStream_t)stream, var, C, D, H, W, Wo, tiles_x, tiles, dpb); \
+    }
+    MVS_SWEEP_STORE_LIST(MVS_PROBE)
+#undef MVS_PROBE
     MVS_LAUNCH_CHECK("store_pattern_probe");
     return MVSDET_OK;
 }
@@ -146,6 +185,9 @@ extern "C" int mvsdet_store_pattern_probe_f16(void* var, int N, int C, int D, in
 extern "C" int mvsdet_set_option(const char* name, int value) {
     int* slot = option_slot(name);
     MVS_REQUIRE(slot, "set_option: unknown option '%s'", name ? name : "(null)");
+    // these two select instantiations of the slab kernel: a flavour that this build does not carry is refused, never mapped to another
+    MVS_REQUIRE(slot != &options().sweep_store || sweep_store_compiled(value), "set_option: sweep_store %d is not compiled into this build", value);
+    MVS_REQUIRE(slot != &options().sweep_box_load || sweep_box_load_compiled(value), "set_option: sweep_box_load %d is not compiled into this build", value);
     *slot = value;
     return MVSDET_OK;
 }

@@ -37,8 +37,62 @@ struct Options {
                        // take the other neighbour's idle LDS slot); 0 = it builds the geometry of mvsdet_plane_sweep_table_f32 (A/B runs, tests)
     int depthprob_ahead; // 1 (default) = depth_prob_topk requests a pixel's inputs before its first store (depth_prob_topk_ahead_kernel);
                        // 0 = the form that requests them plane by plane, behind the stores (A/B runs, tests).  Same bits.
+    int sweep_store;   // cache policy of the sweep's output stores (FAST form, K == 2): kSweepStoreAuto (-1, default: what ships for the class) |
+                       // kSweepStoreNt (0) | kSweepStorePlain | kSweepStoreSc1 | kSweepStoreSc0Sc1 | kSweepStoreNtSc1 | kSweepStoreNtBuffer.
+                       // Only the flavours of MVS_SWEEP_STORE_LIST are compiled; set_option refuses the others.
+                       // The store-pattern probe writes under the same policy.  Same bits under every value.
+    int sweep_box_load; // cache policy of the footprint boxes' LDS-DMA and of a block's reference-feature loads: 0 (default) = default policy,
+                       // 1 = non-temporal (MVS_SWEEP_LOAD_LIST).  Same bits.
 };
 Options& options();
+
+// Store flavours of option "sweep_store".  kSweepStoreNt is the non-temporal global store; the others are buffer stores whose aux
+// operand carries the policy (gfx950: 0 plain, 1 sc0, 2 nt, 16 sc1, 17 sc0 sc1, 18 nt sc1).  kSweepStoreNtBuffer is the
+// control of the A/B matrix: the policy of kSweepStoreNt through the other store instruction.
+constexpr int kSweepStoreNt = 0, kSweepStorePlain = 1, kSweepStoreSc1 = 2, kSweepStoreSc0Sc1 = 3, kSweepStoreNtSc1 = 4, kSweepStoreNtBuffer = 5;
+__host__ __device__ constexpr int sweep_store_aux(int st) {
+    return st == kSweepStorePlain ? 0 : st == kSweepStoreSc1 ? 16 : st == kSweepStoreSc0Sc1 ? 17 : st == kSweepStoreNtSc1 ? 18 : 2;
+}
+constexpr int kSweepStoreAuto = -1;   // the option's default: per class of instantiation, what the A/B kept (sweep_store_shipped)
+// What ships, per class (tile width, fp16 storage) -- the rule and the runs: profiles/r10_sweep_store_policy_ab.txt.  The 32x4 tiles with
+// fp32 storage (the headline's class) passed with MVS_SWEEP_STORE_SHIPPED; the 16x8 tiles did not, and fp16 storage was not measured.
+#define MVS_SWEEP_STORE_SHIPPED 4
+constexpr int sweep_store_shipped(int tw, bool half) { return (tw == 32 && !half) ? MVS_SWEEP_STORE_SHIPPED : kSweepStoreNt; }
+// What is compiled.  The A/B build (make SWEEP_STORE_MATRIX=1) carries every flavour on every class, for tools/sweep_store_policy_ab.py; the
+// default build carries kSweepStoreNt everywhere and the shipped flavour on the class that ships it, and no load flavour but the default
+// (non-temporal box loads lost 11 %).  X(value) per list; the slab kernel is instantiated on its FAST K == 2 forms.
+#ifdef MVS_SWEEP_STORE_MATRIX
+#define MVS_SWEEP_STORE_LIST(X) X(0) X(1) X(2) X(3) X(4) X(5)
+#define MVS_SWEEP_LOAD_NT 1
+constexpr bool sweep_class_has_flavours(int, bool) { return true; }
+#else
+#define MVS_SWEEP_STORE_LIST(X) X(0) X(MVS_SWEEP_STORE_SHIPPED)
+#define MVS_SWEEP_LOAD_NT 0
+constexpr bool sweep_class_has_flavours(int tw, bool half) { return sweep_store_shipped(tw, half) != kSweepStoreNt; }
+#endif
+#if MVS_SWEEP_LOAD_NT
+#define MVS_SWEEP_LOAD_LIST(X) X(0) X(1)
+#else
+#define MVS_SWEEP_LOAD_LIST(X) X(0)
+#endif
+inline bool sweep_store_compiled(int v) {
+#define MVS_X(S) if (v == S) return true;
+    MVS_SWEEP_STORE_LIST(MVS_X)
+#undef MVS_X
+    return v == kSweepStoreAuto;
+}
+// The flavour a launch takes: the option, or under kSweepStoreAuto what ships for the class; kSweepStoreNt where the class has no other
+// instantiation, or where the slab's 32 channel rows reach 4 GiB (a buffer store's offsets are 32 bits from the slab's base).
+inline int sweep_store_for(int tw, bool half, size_t slab_bytes) {
+    const int st = options().sweep_store == kSweepStoreAuto ? sweep_store_shipped(tw, half) : options().sweep_store;
+    return (sweep_class_has_flavours(tw, half) && slab_bytes < ((size_t)1 << 32)) ? st : kSweepStoreNt;
+}
+inline bool sweep_box_load_compiled(int v) {
+#define MVS_X(L) if (v == L) return true;
+    MVS_SWEEP_LOAD_LIST(MVS_X)
+#undef MVS_X
+    return false;
+}
 
 // where plane_sweep_coords_kernel leaves the sweep geometry inside the scratch buffer (planesweep.hip)
 struct SweepGeometry {

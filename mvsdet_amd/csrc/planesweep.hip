@@ -182,17 +182,44 @@ SweepGeometry sweep_geometry(void* scratch, int N, int K, int D, int tiles) {
 }  // namespace mvsdet
 
 namespace {
-template <int KV, int TW, bool FAST, typename OutT>
-int launch_slab(dim3 grid, hipStream_t stream, size_t lds, const float* packed, const float* ref_packed, const int64_t* nbr,
-                const SweepGeometry& geo, const unsigned short* groups, OutT* var, int n_src, int C, int S, int D, int H, int W,
-                int Wo, int tiles_x, int tiles, int d_per_block, int box_cap, int n_bt, int xcd_parts) {
+template <int KV, int TW, bool FAST, typename OutT, int ST, int LD>
+int launch_slab_as(dim3 grid, hipStream_t stream, size_t lds, const float* packed, const float* ref_packed, const int64_t* nbr,
+                   const SweepGeometry& geo, const unsigned short* groups, OutT* var, int n_src, int C, int S, int D, int H, int W,
+                   int Wo, int tiles_x, int tiles, int d_per_block, int box_cap, int n_bt, int xcd_parts) {
     // option "sweep_inside": 0 hides kFlagInside from the slab kernel, whose every plane then takes the general form
     const unsigned fl_keep = options().sweep_inside != 0 ? ~0u : ~kFlagAllInside;
-    auto* k = plane_sweep_variance_kernel<KV, TW, FAST, OutT>;
+    auto* k = plane_sweep_variance_kernel<KV, TW, FAST, OutT, ST, LD>;
     MVS_GRANT_LDS("plane_sweep_variance", k, lds, 80 * 1024);   // the largest LDS of max_box_cap()
     hipLaunchKernelGGL(k, grid, dim3(kThreads), lds, stream, packed, ref_packed, nbr, geo.header, geo.proj, geo.depth, geo.boxes, geo.flags,
                        groups, var, n_src, C, S, D, H, W, Wo, tiles_x, tiles, d_per_block, box_cap, n_bt, xcd_parts, fl_keep);
     return MVSDET_OK;
+}
+
+// Options "sweep_store" / "sweep_box_load" pick the instantiation, here on the host.  The flavours exist for the FAST form with two
+// neighbours (the shipped configs' K: the form that was measured), in the default build on the class that ships one (common.h:
+// sweep_class_has_flavours); every other form has the non-temporal stores and the default loads whatever the options say.  A buffer
+// store's offsets are 32 bits from the slab's base: a volume whose 32 channel rows reach 4 GiB (the entry point only bounds 8 rows)
+// keeps the global store too (sweep_store_for).
+template <int KV, int TW, bool FAST, typename OutT>
+int launch_slab(dim3 grid, hipStream_t stream, size_t lds, const float* packed, const float* ref_packed, const int64_t* nbr,
+                const SweepGeometry& geo, const unsigned short* groups, OutT* var, int n_src, int C, int S, int D, int H, int W,
+                int Wo, int tiles_x, int tiles, int d_per_block, int box_cap, int n_bt, int xcd_parts) {
+#define MVS_SLAB_ARGS grid, stream, lds, packed, ref_packed, nbr, geo, groups, var, n_src, C, S, D, H, W, Wo, tiles_x, tiles, d_per_block, box_cap, n_bt, xcd_parts
+    if constexpr (FAST && KV == 2 && sweep_class_has_flavours(TW, sizeof(OutT) == 2)) {
+        const int st = sweep_store_for(TW, sizeof(OutT) == 2, (size_t)kSlab * D * H * Wo * sizeof(OutT)), ld = options().sweep_box_load;
+#define MVS_POL_SL(S_, L_) if (st == S_ && ld == L_ && (S_ != kSweepStoreNt || L_ != 0)) return launch_slab_as<KV, TW, FAST, OutT, S_, L_>(MVS_SLAB_ARGS);
+#define MVS_POL_L0(S_) MVS_POL_SL(S_, 0)
+#define MVS_POL_L1(S_) MVS_POL_SL(S_, 1)
+        MVS_SWEEP_STORE_LIST(MVS_POL_L0)
+#if MVS_SWEEP_LOAD_NT
+        MVS_SWEEP_STORE_LIST(MVS_POL_L1)
+#endif
+#undef MVS_POL_L1
+#undef MVS_POL_L0
+#undef MVS_POL_SL
+    }
+    return launch_slab_as<KV, TW, FAST, OutT, kSweepStoreNt, 0>(MVS_SLAB_ARGS);
+#undef MVS_SLAB_ARGS
 }
 
 template <int TW>

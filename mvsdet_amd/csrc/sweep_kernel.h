@@ -492,13 +492,21 @@ __host__ __device__ constexpr size_t sweep_lds_bytes(int K, int box_cap) { retur
 // store (BASELINE configs[4], fp16 storage), which halves the dominant write stream.
 // FAST: every channel row of the slab exists (C % 32 == 0) and every lane's 4 pixels are all inside or all outside the
 // image with 16-byte aligned rows (W % 4 == 0): the stores are four unconditional vector stores under one lane predicate.
-template <int K, int TW, bool FAST, typename OutT = float>
+// ST: cache policy of the FAST form's output stores (option "sweep_store", sweep_store_aux() in common.h).  kSweepStoreNt is the
+//     non-temporal global store the kernel has always had, instruction for instruction; every other value is a buffer store of the
+//     same 16 (8) bytes per lane through a resource based at the block's slab, whose aux bits carry the policy.  The slab's 32
+//     channel rows must then stay below 4 GiB (the host checks it and keeps kSweepStoreNt otherwise).
+// LD: cache policy of the loads that a block issues once per texel: the LDS-DMA of the footprint boxes and the block's reference
+//     features (option "sweep_box_load": 0 = default policy, 1 = non-temporal).
+// Both are cache hints: no value depends on them.  The non-FAST form takes neither.
+template <int K, int TW, bool FAST, typename OutT = float, int ST = kSweepStoreNt, int LD = 0>
 __global__ __launch_bounds__(kThreads, (TW == 16 && K <= 2) ? 3 : 2) void plane_sweep_variance_kernel(   // 16x8 tiles: three 52-KiB blocks per CU (planesweep.hip: max_box_cap)
-    
+
     const float* __restrict__ packed, const float* __restrict__ ref_packed, const int64_t* __restrict__ nbr,
     const int4* __restrict__ header, const float* __restrict__ proj, const float* __restrict__ depth, const int4* __restrict__ boxes,
     const unsigned* __restrict__ flags, const unsigned short* __restrict__ groups, OutT* __restrict__ var, int N, int C, int S,
     int D, int H, int W, int Wo, int tiles_x, int tiles, int d_per_block, int box_cap, int n_bt, int xcd_parts, unsigned fl_keep) {
+    static_assert(FAST || (ST == kSweepStoreNt && LD == 0), "the cache policies belong to the FAST form");
     constexpr int KK = K > 0 ? K : 1;
     constexpr bool kTapsAhead = TW == 32 && K <= 2;   // all four steps' taps of a neighbour requested ahead of their arithmetic (two blocks per CU: registers to spare)
     constexpr int NP = (K + 1) / 2;             // decode passes: a lane decodes ONE (pixel-step, neighbour) pair per pass
@@ -579,7 +587,14 @@ __global__ __launch_bounds__(kThreads, (TW == 16 && K <= 2) ? 3 : 2) void plane_
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         const int pix = min(py, H - 1) * W + min(px0 + s, W - 1);
-        const float4 v = *reinterpret_cast<const float4*>(ref_img + (size_t)pix * kSlab + 4 * g);
+        float4 v;
+        if constexpr (LD == 0) {
+            v = *reinterpret_cast<const float4*>(ref_img + (size_t)pix * kSlab + 4 * g);
+        } else {
+            typedef float v4f __attribute__((ext_vector_type(4)));
+            const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(ref_img + (size_t)pix * kSlab + 4 * g));
+            v = make_float4(t.x, t.y, t.z, t.w);
+        }
         f[s][0] = (f2){v.x, v.y};
         f[s][1] = (f2){v.z, v.w};
     }
@@ -639,7 +654,7 @@ __global__ __launch_bounds__(kThreads, (TW == 16 && K <= 2) ? 3 : 2) void plane_
             float4* dst = s_box + base_f4 + q * 64;  // wave-uniform
             if (t < ntex)
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+                                                 (__attribute__((address_space(3))) void*)dst, 16, 0, LD == 0 ? 0 : 2 /* nt */);
         }
     };
 
@@ -655,9 +670,34 @@ __global__ __launch_bounds__(kThreads, (TW == 16 && K <= 2) ? 3 : 2) void plane_
     int d_pending = -1;
     OutT* const var_slab = var + ((size_t)n * C + slab * kSlab) * D * HWo;  // block-uniform: channel row 0 of the slab, plane 0
     const size_t row8 = (size_t)8 * D * HWo;                                // 8 channel rows further
+    // ST != kSweepStoreNt: the slab's 32 channel rows as one buffer resource (built from block-uniform values only).  A store's
+    // address is its base + a scalar offset (plane d, channel row 8*i) + the lane's st_off, all inside the slab's bytes, which the
+    // host keeps below 4 GiB; a store past them would be dropped by the range check.
+    __amdgpu_buffer_rsrc_t var_rsrc;
+    if constexpr (ST != kSweepStoreNt)
+        var_rsrc = __builtin_amdgcn_make_buffer_rsrc(var_slab, 0, (int)(unsigned)((size_t)kSlab * D * HWo * sizeof(OutT)), 0x00020000);
     auto flush = [&](int d) {
         OutT* plane_base = var_slab + (size_t)d * HWo;
-        if constexpr (FAST) {
+        if constexpr (FAST && ST != kSweepStoreNt) {
+            if (st_n == 4) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float* v = vout[i];
+                    const unsigned s_off = (unsigned)(((size_t)d * HWo + i * row8) * sizeof(OutT));   // scalar
+                    if constexpr (sizeof(OutT) == 4) {
+                        typedef unsigned v4u __attribute__((ext_vector_type(4)));
+                        const v4u vv = {__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
+                        __builtin_amdgcn_raw_buffer_store_b128(vv, var_rsrc, (int)st_off, (int)s_off, sweep_store_aux(ST));
+                    } else {
+                        const __half h[4] = {__float2half_rn(v[0]), __float2half_rn(v[1]), __float2half_rn(v[2]), __float2half_rn(v[3])};
+                        typedef unsigned v2u __attribute__((ext_vector_type(2)));
+                        const v2u vv = {(unsigned)__half_as_ushort(h[0]) | ((unsigned)__half_as_ushort(h[1]) << 16),
+                                        (unsigned)__half_as_ushort(h[2]) | ((unsigned)__half_as_ushort(h[3]) << 16)};
+                        __builtin_amdgcn_raw_buffer_store_b64(vv, var_rsrc, (int)st_off, (int)s_off, sweep_store_aux(ST));
+                    }
+                }
+            }
+        } else if constexpr (FAST) {
             if (st_n == 4) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {

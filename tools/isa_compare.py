@@ -25,6 +25,10 @@ FLAGS = "-O3 --offload-arch=gfx950 -std=c++17 -fPIC -ffp-contract=off -fno-math-
 # Filled in for the comparison at hand -- {"mvsdet::store_pattern_kernel": (2, "false")} when its PAIR parameter went, for
 # profiles/retired_forms_isa.txt -- and empty when the kernels of both trees have the same template parameters.
 DROPPED_PARAMS = {}
+# Template parameters that a kernel has gained at its END in --after: the values that stand for the --before kernel.  An --after
+# instantiation with exactly these trailing values is compared under its --before name; any other is listed as ADDED.
+# {"mvsdet::plane_sweep_variance_kernel": ["0", "0"]} for the store / load policies (profiles/r10_sweep_store_policy_isa.txt).
+ADDED_PARAMS = {"mvsdet::plane_sweep_variance_kernel": ["0", "0"], "mvsdet::store_pattern_kernel": ["0"]}
 
 
 def assemble(src: str, out: str) -> None:
@@ -68,6 +72,17 @@ def drop_param(name: str) -> str:
     return name + "   [retired form]"
 
 
+def strip_added(name: str) -> str:
+    m = re.match(r"^([\w:]+)<(.*)>$", name)
+    if not m or m.group(1) not in ADDED_PARAMS:
+        return name
+    tail = ADDED_PARAMS[m.group(1)]
+    args = split_args(m.group(2))
+    if args[-len(tail):] == tail:
+        return f"{m.group(1)}<{', '.join(args[:-len(tail)])}>"
+    return name
+
+
 def kernels_of(asm_path: str, before: bool):
     """{demangled kernel name: (figures, hash, instruction count)}"""
     text = open(asm_path).read()
@@ -98,7 +113,7 @@ def kernels_of(asm_path: str, before: bool):
         vg, acc = int(val[".amdhsa_next_free_vgpr"]), int(val[".amdhsa_accum_offset"])
         fig = (f"vgpr {min(vg, acc)}+{max(vg - acc, 0)}", f"sgpr {val['.amdhsa_next_free_sgpr']}", f"lds {val['.amdhsa_group_segment_fixed_size']}",
                f"scratch {val['.amdhsa_private_segment_fixed_size']}")
-        res[drop_param(name) if before else name] = (fig, h, ninstr)
+        res[drop_param(name) if before else strip_added(name)] = (fig, h, ninstr)
     return res
 
 
