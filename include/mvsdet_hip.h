@@ -844,6 +844,29 @@ int mvsdet_neck_gemm_dw_bf16x3(const float* x, const float* grad_out, float* dw,
                                int transposed, int N, int Cin, int Cout, int D, int H, int W, mvsdet_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Level 0 of the 2-D feature pyramid in front of the sweep (mvsdet.py:374-376 `x = self.neck(x)[0]`) on the bf16 matrix cores with
+ * three-term split operands (csrc/fpn.hip).  Forward only; fp32 in and out; no atomics (the same bits on every run).
+ * The module is mmdet.models.necks.FPN as shipped: in_channels=[256,512,1024,2048], out_channels=256, num_outs=4, start_level=0, no
+ * add_extra_convs, no norm, no activation, upsample_cfg=dict(mode='nearest').  mmdet is not part of this tree; this is the builder's
+ * reading of it:
+ *     L3 = lat3(c5);  L2 = lat2(c4) + up(L3);  L1 = lat1(c3) + up(L2);  L0 = lat0(c2) + up(L1);  out0 = conv3x3(L0) == FPN(inputs)[0]
+ * lat_i = 1x1 convolution with bias, conv3x3 with padding 1 and bias, up = F.interpolate(size = the finer level's, mode='nearest'):
+ * source index min((int)floorf(dst * ((float)in / (float)out)), in - 1) in float32, as ATen computes it (the integer form dst*in/out
+ * differs, e.g. at 46 <- 14).  The 3x3 output convolutions of levels 1-3, which MVSDet drops, are not computed.
+ *   mvsdet_fpn_lateral_bf16x3: out (N,Cout,H,W) = W (Cout,Cin) x (N,Cin,H,W) + bias [+ top (N,Cout,Ht,Wt) at the nearest source index];
+ *       top NULL = no addition (Ht, Wt ignored), else 1 <= Ht <= H, 1 <= Wt <= W.  wsplit = mvsdet_gemm_split_weight of the (Cout, Cin)
+ *       matrix; Cin % 32 == 0, Cout % 128 == 0, any H, W >= 1, N H W < 2^31.  Contiguous tensors.
+ *   mvsdet_fpn_conv3x3_bf16x3: conv3x3(x (N,Cin,H,W)) + bias, zero padding 1, written as fp32 (N,Cout,H,W) to `out` and / or as packed
+ *       maps (mvsdet_packed_bytes(N,Cout,H,W), what mvsdet_pack_features_f32 makes of `out`) to `packed`: each where its pointer is not
+ *       NULL, at least one.  wsplit = mvsdet_gemm_split_weight of the (Cout, 9 Cin) tap-major matrix w.permute(0,2,3,1).reshape(Cout, 9 Cin)
+ *       (k = Cin (3 dy + dx) + c); Cin % 32 == 0, Cout % 128 == 0, N <= 65535.  packed 16-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+int mvsdet_fpn_lateral_bf16x3(const float* x, const void* wsplit, const float* bias, const float* top, float* out, int N, int Cin,
+                              int Cout, int H, int W, int Ht, int Wt, mvsdet_stream_t stream);
+int mvsdet_fpn_conv3x3_bf16x3(const float* x, const void* wsplit, const float* bias, float* out, float* packed, int N, int Cin, int Cout,
+                              int H, int W, mvsdet_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Detection post-processing of the ScanNet head (NerfDetHead.predict_by_feat / _nms / aligned_3d_nms, nerfdet_head.py:301-420,
  * 564-628) on the caller's stream, no host synchronisation (csrc/detect.hip).  fp32; labels int64.
  *

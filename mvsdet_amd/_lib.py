@@ -75,6 +75,8 @@ SIGNATURES = {
     "mvsdet_convT3d_k2_s2_dx_bf16x3": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_neck_gemm_dw_partial_bytes": [_i, _i, _i, _i],
     "mvsdet_neck_gemm_dw_bf16x3": [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_fpn_lateral_bf16x3": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_fpn_conv3x3_bf16x3": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "mvsdet_conv3d_k3_cout2_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "mvsdet_conv3d_k3_cout2_sum_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "mvsdet_backproject_weigh_f32": [_vp, _i64p, _vp, _vp, _vp, _vp, _i64p, _vp, _vp, _vp, _vp,

@@ -242,6 +242,9 @@ class MVSDetHotPath:
         self.cost_regularization = cost_regularization
         self.neck_3d = neck_3d   # mvsdet.py:681-698: x = self.neck_3d(torch.stack(volumes)); SURVEY 8 f-3 (mvsdet_amd.neck)
         self.bbox_head = bbox_head   # nerfdet_head.py:116-118: the head's convolutions on the neck's levels (mvsdet_amd.head)
+        # opt-in: an `mvsdet_amd.fpn.FPNLevel0` (mvsdet.py:374-376, `self.neck(x)[0]`) for `forward_scene_from_stages`; every other
+        # entry starts from the feature map and never looks at it
+        self.fpn = None
         # opt-in: with a test_cfg (nms_pre, score_thr, iou_thr), out["detections"] = the padded boxes of predict_by_feat
         # (ops.HeadPrediction; 7-wide and class-major for a head with `arkit_head`) made from out["head"] and out["valid"] on the
         # stream the head ran on
@@ -477,15 +480,18 @@ class MVSDetHotPath:
         return mean.view(C, nx, ny, nz), count.view(1, nx, ny, nz).long()
 
     def _front(self, feature: Tensor, img_meta: dict, cost_logits: Optional[Tensor], geo: Optional[SceneGeometry],
-               net_streams: Optional[int] = None):
+               net_streams: Optional[int] = None, packed: Optional[Tensor] = None):
         """a1..a4 and the cost network of one scene on the caller's stream -> (geo, packed, variance, cost_logits).
-        net_streams: CostRegNet3DGS.view_streams for this call (None: the module's own setting)."""
+        net_streams: CostRegNet3DGS.view_streams for this call (None: the module's own setting).
+        packed: the packed maps of `feature` where the caller has them already (`forward_scene_from_stages`: the pyramid's 3x3
+        kernel wrote them); used by the inference branch only, in place of its packing launch."""
         if geo is None:
             geo = self.prepare_scene(img_meta, feature.device)
         if feature.is_cuda and not (feature.requires_grad and torch.is_grad_enabled()) and geo.neighbor_ids.shape[1] > 0:
             n, c, h_, w_ = feature.shape
             tab = self.sweep_geometry_async(geo, h_, w_)     # side stream: beside the packing
-            packed = ops.pack_features(feature.detach())
+            if packed is None:
+                packed = ops.pack_features(feature.detach())
             variance = self.cost_volume_tabled(packed, geo, tab, c, h_, w_)
         elif feature.is_cuda and feature.requires_grad and torch.is_grad_enabled() and geo.neighbor_ids.shape[1] > 0:
             # training: ONE packing pass and ONE geometry for the forward sweep, the lifting and the backward sweep
@@ -817,9 +823,26 @@ class MVSDetHotPath:
         `gt_depth` (N,Hg,Wg), any size: the result gains `weight_gap` and `src_rmse` (0-dim device tensors: what the reference's
         backproject_Weigh returns with gt_depth), `depth_diagnostics` (N,4) {gap_i, orig_gap, new_gap, n_reduce} per view and
         `gt_depth_resized` (N,h,w); they are made in the tail, on the stream the lifting runs on.  None: no such key."""
+        return self._scene(feature, img_meta, cost_logits, geo, gt_depth)
+
+    def forward_scene_from_stages(self, stages: Sequence[Tensor], img_meta: dict, **kw) -> dict:
+        """`forward_scene` from the four backbone maps instead of the pyramid's output: `self.fpn` (an `mvsdet_amd.fpn.FPNLevel0`)
+        makes the feature map AND its packed form -- on its HIP route the 3x3 kernel's epilogue writes both -- and the scene path
+        sweeps that packed tensor instead of launching `ops.pack_features`.  Keyword arguments as `forward_scene`'s.  The result
+        gains `feature`, the (N,256,H0,W0) map."""
+        if self.fpn is None:
+            raise ValueError("forward_scene_from_stages needs `fpn` (MVSDetHotPath.fpn = FPNLevel0.from_module(model.neck))")
+        feature, packed = self.fpn(stages, packed=True)
+        out = self._scene(feature, img_meta, kw.pop("cost_logits", None), kw.pop("geo", None), kw.pop("gt_depth", None), packed, **kw)
+        out._put("feature", feature)
+        return out
+
+    def _scene(self, feature: Tensor, img_meta: dict, cost_logits: Optional[Tensor], geo: Optional[SceneGeometry],
+               gt_depth: Optional[Tensor], packed: Optional[Tensor] = None) -> dict:
+        """`forward_scene`; packed: `_front`'s."""
         route, on_side, net_streams, tuning = self._route(feature, cost_logits)
         watching = tuning is not None and tuning["choice"] is not None   # a kept side route: `_watch`
-        geo, packed, variance, cost_logits = self._front(feature, img_meta, cost_logits, geo, net_streams)
+        geo, packed, variance, cost_logits = self._front(feature, img_meta, cost_logits, geo, net_streams, packed)
         if watching:
             self._watch(tuning, variance.device)
         elif tuning is not None:
