@@ -3,6 +3,7 @@
 //
 //     x = x_hi + x_mid (+ 2^-16 |x|),  w = w_hi + w_mid (+ ...),   x*w ~ x_hi*w_hi + x_hi*w_mid + x_mid*w_hi
 //
+// (the three products: bf16x3_mfma32 / bf16x3_mfma16 and the fragment types are in mfma.h; the cut is this file's bf_cut8, see there.)
 // Every product of two bf16 pieces is exact in fp32 and the bf16 MFMAs accumulate in fp32, so the three
 // MFMAs leave out only the terms of relative size 2^-16 (x_mid*w_mid, x_lo*w_hi, x_hi*w_lo): measured on the network
 // (tools/study/split_bf16_emulation.py, G8 fixture) 2e-6 .. 4e-6 on the logits, 5e-7 on the depth probabilities -- the
@@ -29,13 +30,11 @@
 // One barrier per weight sub-stage: wait for the own DMAs of the stage, barrier, issue the DMAs of the next stage into
 // the buffers the barrier has just freed, compute.
 #include "common.h"
+#include "mfma.h"
 
 #include <algorithm>
 
 namespace mvsdet {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16b __attribute__((ext_vector_type(16)));
 
 constexpr int kBfW = 16;             // tile width (voxels along w): one MFMA column group = 2 h-rows of 16
 constexpr int kBfPairs = 14;         // tap pairs (27 taps + 1 empty)
@@ -48,7 +47,7 @@ __host__ __device__ constexpr size_t bf_lds_bytes(int TD, int TH, int TW, int su
     return (size_t)(2 * 2 * bf_in_slots(TD, TH, TW) + 2 * bf_w_slots(subp)) * 16;
 }
 
-// Which output channel an accumulator register holds.  The 32x32 MFMA leaves row (r & 3) + 8 * (r >> 2) + 4 * hh of a row group in
+// Which output channel an accumulator register holds.  The 32x32 MFMA leaves row mfma32_row(r, hh) (mfma.h) of a row group in
 // register r of lane half hh = lane >> 5; the weights are laid out (split_conv_weight_kernel) so that row carries channel
 //     8 * (2 * (r >> 3) + hh) + (r & 7)
 // of the group: registers 8q .. 8q+7 of a lane are then EIGHT CONSECUTIVE channels = one 16-byte unit of the SCL form, and a
@@ -86,7 +85,9 @@ __device__ __forceinline__ void xcd_block_id(int xcd_map, unsigned& bx, unsigned
         bz = moved / (gridDim.x * gridDim.y);
     }
 }
-// fp32 x 8 -> the two bf16 pieces (round to nearest even; the remainder is exact in fp32 and rounded once)
+// fp32 x 8 -> the two bf16 pieces (round to nearest even; the remainder is exact in fp32 and rounded once).  This file's own form of
+// the cut: with mfma.h's bf16x3_cut8 the neck's 256 -> 128 and 512 -> 128 output layers were 0.9 % and 1.8 % slower, past the parent's
+// spread (0.1810 -> 0.1826 and 0.0736 -> 0.0749 ms, profiles/mfma_header_ab.txt), so it keeps the form it was measured with.
 __device__ __forceinline__ void bf_cut8(const float (&v)[8], uint4& hi, uint4& mid) {
     unsigned h[4], m[4];
 #pragma unroll
@@ -455,15 +456,14 @@ __global__ __launch_bounds__(TD * TH * TW * 4 / CGN) void conv3d_k3_bf16x3_kerne
     // Never read.  Four zeroed 32x32 accumulators ahead of the real ones are what the 32x32x16 form of this kernel left behind when it
     // was removed: without them hipcc allocates the registers of six of the nine instantiations differently (same instruction count,
     // tools/isa_compare.py), and the kernels that were measured are the ones to ship.  Drop them with the next change that re-measures.
-    f32x16b acc32[2][2];
+    f32x16 acc32[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc32[a][b][r] = 0.0f;
-    typedef float f32x4b __attribute__((ext_vector_type(4)));
-    f32x4b acc[4][CGN];  // [row group (16 output channels)][column group (16 voxels)]
+    f32x4 acc[4][CGN];  // [row group (16 output channels)][column group (16 voxels)]
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -495,9 +495,7 @@ __global__ __launch_bounds__(TD * TH * TW * 4 / CGN) void conv3d_k3_bf16x3_kerne
             for (int a = 0; a < 4; ++a)
 #pragma unroll
                 for (int b = 0; b < CGN; ++b) {
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[a][1], B[b][0], acc[a][b], 0, 0, 0);   // w_mid * x_hi
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[a][0], B[b][1], acc[a][b], 0, 0, 0);   // w_hi * x_mid
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[a][0], B[b][0], acc[a][b], 0, 0, 0);   // w_hi * x_hi
+                    bf16x3_mfma16(acc[a][b], A[a][0], A[a][1], B[b][0], B[b][1]);
                 }
         }
     };
@@ -826,7 +824,7 @@ __global__ __launch_bounds__(TD * TH * TW * 2 / CG) void conv3d_k3_s2_bf16x3_ker
         const int dz = g / (TH / RG), hy = RG * (g % (TH / RG)) + col / TW;
         vb[b] = (dz * HH + hy) * HW + col % TW;
     }
-    f32x16b acc[2 * OB][CG];
+    f32x16 acc[2 * OB][CG];
 #pragma unroll
     for (int a = 0; a < 2 * OB; ++a)
 #pragma unroll
@@ -857,9 +855,7 @@ __global__ __launch_bounds__(TD * TH * TW * 2 / CG) void conv3d_k3_s2_bf16x3_ker
             for (int a = 0; a < 2 * OB; ++a)
 #pragma unroll
                 for (int b = 0; b < CG; ++b) {
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[a][1], B[b][0], acc[a][b], 0, 0, 0);
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[a][0], B[b][1], acc[a][b], 0, 0, 0);
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[a][0], B[b][0], acc[a][b], 0, 0, 0);
+                    bf16x3_mfma32(acc[a][b], A[a][0], A[a][1], B[b][0], B[b][1]);
                 }
         }
     };
@@ -1045,7 +1041,7 @@ __device__ __forceinline__ void convT3d_k3_s2_bf16x3_body(
         const int dz = g / (TH / RG), hy = RG * (g % (TH / RG)) + col / TW;
         vb[b] = (dz * HH + hy) * HW + col % TW;
     }
-    f32x16b acc[2][2][CG];   // [w parity][row group][column group]
+    f32x16 acc[2][2][CG];   // [w parity][row group][column group]
 #pragma unroll
     for (int pw = 0; pw < 2; ++pw)
 #pragma unroll
@@ -1078,9 +1074,7 @@ __device__ __forceinline__ void convT3d_k3_s2_bf16x3_body(
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int b = 0; b < CG; ++b) {
-                    acc[pw][a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[a][1], B[b][0], acc[pw][a][b], 0, 0, 0);
-                    acc[pw][a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[a][0], B[b][1], acc[pw][a][b], 0, 0, 0);
-                    acc[pw][a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[a][0], B[b][0], acc[pw][a][b], 0, 0, 0);
+                    bf16x3_mfma32(acc[pw][a][b], A[a][0], A[a][1], B[b][0], B[b][1]);
                 }
         }
     };
@@ -1266,7 +1260,7 @@ __global__ __launch_bounds__(TD * TH * TW * 2) void convT3d_k3_s2_bf16x3_fused_k
 
     const int g = wave;
     const int vb = ((g / (TH / RG)) * HH + RG * (g % (TH / RG)) + col / TW) * HW + col % TW;
-    f32x16b acc[8];   // output parity class pi = 4 * pd + 2 * ph + pw
+    f32x16 acc[8];   // output parity class pi = 4 * pd + 2 * ph + pw
 #pragma unroll
     for (int pi = 0; pi < 8; ++pi)
 #pragma unroll
@@ -1285,9 +1279,7 @@ __global__ __launch_bounds__(TD * TH * TW * 2) void convT3d_k3_s2_bf16x3_fused_k
                 const int toff = hh ? ct_tap_off<HH, HW>(pi, 2 * pj + 1) : ct_tap_off<HH, HW>(pi, 2 * pj);
                 const bf16x8 a0 = ain[(pl * 2 + 0) * 64], a1 = ain[(pl * 2 + 1) * 64];
                 const bf16x8 b0 = bin[toff], b1 = bin[(size_t)INS + toff];
-                acc[pi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[pi], 0, 0, 0);
-                acc[pi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[pi], 0, 0, 0);
-                acc[pi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[pi], 0, 0, 0);
+                bf16x3_mfma32(acc[pi], a0, a1, b0, b1);
             }
         }
     };

@@ -15,12 +15,11 @@
 // Bound: fp32 MFMA, 64 FLOP/clk/SIMD = 157 TFLOP/s; 2.04 TFLOP at (40,256,12,60,80) = 13 ms at peak.
 // Measured 15.1 ms = 135 TFLOP/s (MIOpen: 33.6 ms).
 #include "conv_host.h"
+#include "mfma.h"
 
 #include <algorithm>
 
 namespace mvsdet {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // The 32 B-columns of an MFMA are 32 voxels along w (TWC = 32: tile 2 x 4 x 32) or two h-rows of 16 (TWC = 16: tile
 // 2 x 8 x 16): the launcher picks the one that pads W less (W = 80: 96 vs 80).
@@ -169,7 +168,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv3d_k3_mfma_kernel(
             float sc[16], sh[16], rv[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int o = ob64 * kC0Out + ob * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
+                const int o = mfma32_row(r, kk, ob64 * kC0Out + ob * 32);
                 const size_t idx = ((size_t)n * Cout + o) * vol + (size_t)d * plane + (size_t)h * W + w;
                 const bool fin = nsplit == 1;
                 sc[r] = (fin && scale) ? scale[o] : 1.0f;
@@ -178,7 +177,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv3d_k3_mfma_kernel(
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int o = ob64 * kC0Out + ob * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
+                const int o = mfma32_row(r, kk, ob64 * kC0Out + ob * 32);
                 float v = acc[ob][rb][r];
                 const size_t idx = ((size_t)n * Cout + o) * vol + (size_t)d * plane + (size_t)h * W + w;
                 if (nsplit > 1) {
@@ -485,14 +484,14 @@ __global__ __launch_bounds__(kThreads, 2) void convT3d_k3_s2_mfma_kernel(
             float2 rv[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int o = ob64 * kC0Out + ob * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
+                const int o = mfma32_row(r, kk, ob64 * kC0Out + ob * 32);
                 sc[r] = scale ? scale[o] : 1.0f;
                 sh[r] = scale ? shift[o] : 0.0f;
                 rv[r] = residual ? *reinterpret_cast<const float2*>(residual + ((size_t)n * Cout + o) * ovol + pos) : make_float2(0.f, 0.f);
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int o = ob64 * kC0Out + ob * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
+                const int o = mfma32_row(r, kk, ob64 * kC0Out + ob * 32);
                 float2 v = make_float2(acc[0][ob][rb][r], acc[1][ob][rb][r]);
                 if (scale) {
                     v.x = fmaf(v.x, sc[r], sh[r]);

@@ -20,10 +20,9 @@
 // fine tensor, their X the coarse one).  Same kernel on a 1 x 4 x 8 tile of dY with a 3 x 9 x 17 halo of X; walking along
 // d, two of the three ring planes are new per tile.
 #include "common.h"
+#include "mfma.h"
 
 namespace mvsdet {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kDwTapsPerWave = 7;
 
@@ -205,7 +204,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv3d_k3_dw_mfma_kernel(const fl
         if (t >= 27) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int o = o0 + (r & 3) + 8 * (r >> 2) + 4 * kk, c = c0 + col;
+            const int o = o0 + mfma32_row(r, kk), c = c0 + col;
             if (o < Cout && c < Cin) partial[(((size_t)split * Cout + o) * Cin + c) * 27 + t] = acc[i][r];
         }
     }

@@ -17,13 +17,9 @@
 //   per row of the tile and wave: 2 A + 6 B ds_read_b128 feed 9 MFMAs
 // partial[split][o][c][27] as the fp32 kernel: the caller adds the splits up.
 #include "common.h"
+#include "mfma.h"
 
 namespace mvsdet {
-
-typedef short dwb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float dwb_f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned dwb_u32x4 __attribute__((ext_vector_type(4)));
-typedef float dwb_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kDbTH = 4, kDbTW = 16;
 constexpr int kDbComputeWaves = 8, kDbLoaderWaves = 4;
@@ -45,6 +41,8 @@ static_assert(kDbXRoles <= kDbLoaders && kDbYRoles <= kDbLoaders, "one loader th
 
 __device__ float4 g_dwb_zero;   // zero-initialised: the source of every padding element
 
+// A cut of this file's own, not mfma.h's bf16x3_cut8: with the shared one the kernel is 441 instructions shorter and 9 - 12 % slower
+// (conv0 5.76 -> 6.29 ms, profiles/mfma_header_ab.txt), so it keeps the form it was measured with.
 __device__ __forceinline__ unsigned dwb_pack(__bf16 a, __bf16 b) {
     return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
 }
@@ -54,7 +52,7 @@ __device__ __forceinline__ void dwb_split2(float f0, float f1, unsigned& hi, uns
     hi = dwb_pack(a0, a1);
     mid = dwb_pack((__bf16)(f0 - (float)a0), (__bf16)(f1 - (float)a1));  // exact difference, rounded once
 }
-__device__ __forceinline__ void dwb_split8(const dwb_f32x4& a, const dwb_f32x4& b, uint4& hi, uint4& mid) {
+__device__ __forceinline__ void dwb_split8(const f32x4& a, const f32x4& b, uint4& hi, uint4& mid) {
     dwb_split2(a.x, a.y, hi.x, mid.x);
     dwb_split2(a.z, a.w, hi.y, mid.y);
     dwb_split2(b.x, b.y, hi.z, mid.z);
@@ -131,7 +129,7 @@ __global__ __launch_bounds__(kDbThreads) void conv3d_k3_dw_bf16x3_kernel(const f
         const float* const ychan = gy + (size_t)min(o0 + yo, Cout - 1) * vol;
         const bool xc_ok = xthread && c0 + xc < Cin, yo_ok = ythread && o0 + yo < Cout;
 
-        struct Regs { dwb_f32x4 xv[6], yv[4]; };
+        struct Regs { f32x4 xv[6], yv[4]; };
         struct Pos { int i, d; };   // column of the split, plane (d == D: the zero plane)
         Regs sets[kDbDepth];
         // X plane at stream position px and dY tile at position py (a position beyond the stream or a plane D: zeros)
@@ -145,7 +143,7 @@ __global__ __launch_bounds__(kDbThreads) void conv3d_k3_dw_bf16x3_kernel(const f
 #pragma unroll
                 for (int k = 0; k < 6; ++k) {
                     const int w = w0 - 4 + 4 * k;
-                    g.xv[k] = *reinterpret_cast<const dwb_f32x4*>((ok & (w >= 0) & (w < W)) ? row + w : zero);
+                    g.xv[k] = *reinterpret_cast<const f32x4*>((ok & (w >= 0) & (w < W)) ? row + w : zero);
                 }
             }
             {
@@ -157,7 +155,7 @@ __global__ __launch_bounds__(kDbThreads) void conv3d_k3_dw_bf16x3_kernel(const f
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int w = w0 + 4 * k;
-                    g.yv[k] = *reinterpret_cast<const dwb_f32x4*>((ok & (w < W)) ? row + w : zero);
+                    g.yv[k] = *reinterpret_cast<const f32x4*>((ok & (w < W)) ? row + w : zero);
                 }
             }
         };
@@ -177,7 +175,7 @@ __global__ __launch_bounds__(kDbThreads) void conv3d_k3_dw_bf16x3_kernel(const f
                 *reinterpret_cast<uint4*>(dx + 16) = hi;
                 *reinterpret_cast<uint4*>(dx + kDbXPieceB + 16) = mid;
                 // (w0-2, w0-1) = xv[0].zw, (w0+16, w0+17) = xv[5].xy; the 16-byte store also covers the row's padding
-                dwb_split8(dwb_f32x4{g.xv[0].z, g.xv[0].w, g.xv[5].x, g.xv[5].y}, dwb_f32x4{0.f, 0.f, 0.f, 0.f}, hi, mid);
+                dwb_split8(f32x4{g.xv[0].z, g.xv[0].w, g.xv[5].x, g.xv[5].y}, f32x4{0.f, 0.f, 0.f, 0.f}, hi, mid);
                 *reinterpret_cast<uint4*>(dx + 32) = hi;
                 *reinterpret_cast<uint4*>(dx + kDbXPieceB + 32) = mid;
             }
@@ -198,9 +196,9 @@ __global__ __launch_bounds__(kDbThreads) void conv3d_k3_dw_bf16x3_kernel(const f
         if (Q > 0) {
             // plane -1 of the first column (slot 3) is zero; planes 0, 1 and the first dY tile are committed before the loop
 #pragma unroll
-            for (int k = 0; k < 6; ++k) sets[0].xv[k] = dwb_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int k = 0; k < 6; ++k) sets[0].xv[k] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int k = 0; k < 4; ++k) sets[0].yv[k] = dwb_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int k = 0; k < 4; ++k) sets[0].yv[k] = f32x4{0.f, 0.f, 0.f, 0.f};
             commit(sets[0], 3, 1);
             fetch(sets[0], at(0), at(0));
             commit(sets[0], 0, 0);
@@ -224,7 +222,7 @@ __global__ __launch_bounds__(kDbThreads) void conv3d_k3_dw_bf16x3_kernel(const f
     }
 
     // -------------------------------------------------------------------------------------------------- multiplying waves
-    dwb_f32x16 acc[4];   // the three kw of the wave's (kd,kh) pair; waves 0..2: tap kw = wave of the pair (2,2)
+    f32x16 acc[4];   // the three kw of the wave's (kd,kh) pair; waves 0..2: tap kw = wave of the pair (2,2)
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -239,15 +237,15 @@ __global__ __launch_bounds__(kDbThreads) void conv3d_k3_dw_bf16x3_kernel(const f
 
     // one row of the tile: 8 ds_read_b128, 10 v_alignbit, 9 MFMAs
     auto row_mfma = [&](const char* xs, const char* xs22, const char* ys, int r) {
-        const dwb_bf16x8 a_hi = *reinterpret_cast<const dwb_bf16x8*>(ys + r * 32);
-        const dwb_bf16x8 a_mid = *reinterpret_cast<const dwb_bf16x8*>(ys + kDbYPieceB + r * 32);
-        dwb_bf16x8 bq[3][2];
+        const bf16x8 a_hi = *reinterpret_cast<const bf16x8*>(ys + r * 32);
+        const bf16x8 a_mid = *reinterpret_cast<const bf16x8*>(ys + kDbYPieceB + r * 32);
+        bf16x8 bq[3][2];
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
             const char* rowp = xs + p * kDbXPieceB + r * kDbXRowB;
-            const dwb_u32x4 own = *reinterpret_cast<const dwb_u32x4*>(rowp + own_off);   // this half's 8 voxels
-            dwb_u32x4 oth = *reinterpret_cast<const dwb_u32x4*>(rowp + oth_off);         // the other half's
-            dwb_u32x4 edg = *reinterpret_cast<const dwb_u32x4*>(rowp + 32);              // (w0-2,w0-1), (w0+16,w0+17)
+            const u32x4 own = *reinterpret_cast<const u32x4*>(rowp + own_off);   // this half's 8 voxels
+            u32x4 oth = *reinterpret_cast<const u32x4*>(rowp + oth_off);         // the other half's
+            u32x4 edg = *reinterpret_cast<const u32x4*>(rowp + 32);              // (w0-2,w0-1), (w0+16,w0+17)
             // one word of each is used: keep the whole ds_read_b128 (conflict-free at this channel pitch) -- narrowed
             // to a ds_read_b32 it banks modulo 32 and the 32 channels of a half wave fall on 8 banks
             asm volatile("" : "+v"(oth));
@@ -256,9 +254,9 @@ __global__ __launch_bounds__(kDbThreads) void conv3d_k3_dw_bf16x3_kernel(const f
             const unsigned R = hh ? edg.y : oth.x;     // low half = the voxel after own
             const unsigned t1 = __builtin_amdgcn_alignbit(own.y, own.x, 16), t2 = __builtin_amdgcn_alignbit(own.z, own.y, 16),
                            t3 = __builtin_amdgcn_alignbit(own.w, own.z, 16);
-            bq[0][p] = __builtin_bit_cast(dwb_bf16x8, (dwb_u32x4{__builtin_amdgcn_alignbit(own.x, L, 16), t1, t2, t3}));   // w-1
-            bq[1][p] = __builtin_bit_cast(dwb_bf16x8, own);                                                               // w
-            bq[2][p] = __builtin_bit_cast(dwb_bf16x8, (dwb_u32x4{t1, t2, t3, __builtin_amdgcn_alignbit(R, own.w, 16)}));   // w+1
+            bq[0][p] = __builtin_bit_cast(bf16x8, (u32x4{__builtin_amdgcn_alignbit(own.x, L, 16), t1, t2, t3}));   // w-1
+            bq[1][p] = __builtin_bit_cast(bf16x8, own);                                                               // w
+            bq[2][p] = __builtin_bit_cast(bf16x8, (u32x4{t1, t2, t3, __builtin_amdgcn_alignbit(R, own.w, 16)}));   // w+1
         }
         // consecutive MFMAs go to different accumulators
 #pragma unroll
@@ -268,19 +266,19 @@ __global__ __launch_bounds__(kDbThreads) void conv3d_k3_dw_bf16x3_kernel(const f
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw) acc[kw] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_mid, bq[kw][0], acc[kw], 0, 0, 0);
         if (extra) {   // wave-uniform
-            dwb_bf16x8 be[2];
+            bf16x8 be[2];
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
                 const char* rowp = xs22 + p * kDbXPieceB + r * kDbXRowB;
-                const dwb_u32x4 own = *reinterpret_cast<const dwb_u32x4*>(rowp + own_off);
-                dwb_u32x4 side = *reinterpret_cast<const dwb_u32x4*>(rowp + side_off);
+                const u32x4 own = *reinterpret_cast<const u32x4*>(rowp + own_off);
+                u32x4 side = *reinterpret_cast<const u32x4*>(rowp + side_off);
                 asm volatile("" : "+v"(side));
                 const unsigned t1 = __builtin_amdgcn_alignbit(own.y, own.x, 16), t2 = __builtin_amdgcn_alignbit(own.z, own.y, 16),
                                t3 = __builtin_amdgcn_alignbit(own.w, own.z, 16);
-                dwb_u32x4 v = own;                                                                      // kw = 1
-                if (wave == 0) v = dwb_u32x4{__builtin_amdgcn_alignbit(own.x, hh ? side.w : side.x, 16), t1, t2, t3};   // w-1
-                if (wave == 2) v = dwb_u32x4{t1, t2, t3, __builtin_amdgcn_alignbit(hh ? side.y : side.x, own.w, 16)};   // w+1
-                be[p] = __builtin_bit_cast(dwb_bf16x8, v);
+                u32x4 v = own;                                                                      // kw = 1
+                if (wave == 0) v = u32x4{__builtin_amdgcn_alignbit(own.x, hh ? side.w : side.x, 16), t1, t2, t3};   // w-1
+                if (wave == 2) v = u32x4{t1, t2, t3, __builtin_amdgcn_alignbit(hh ? side.y : side.x, own.w, 16)};   // w+1
+                be[p] = __builtin_bit_cast(bf16x8, v);
             }
             acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, be[0], acc[3], 0, 0, 0);
             acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_hi, be[1], acc[3], 0, 0, 0);
@@ -295,20 +293,20 @@ __global__ __launch_bounds__(kDbThreads) void conv3d_k3_dw_bf16x3_kernel(const f
 #pragma unroll
         for (int r = 0; r < kDbTH; ++r) row_mfma(xs, xs22, ys, r);
     }
-    // partial[split][o][c][tap]; C/D map: column = lane & 31 (c), row = (reg & 3) + 8*(reg >> 2) + 4*(lane >> 5) (o)
+    // partial[split][o][c][tap]; column = lane & 31 (c), row = mfma32_row (o)
 #pragma unroll
     for (int kw = 0; kw < 3; ++kw) {
         const int t = (kd * 3 + kh) * 3 + kw;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int o = o0 + (r & 3) + 8 * (r >> 2) + 4 * hh, c = c0 + r32;
+            const int o = o0 + mfma32_row(r, hh), c = c0 + r32;
             if (o < Cout && c < Cin) partial[(((size_t)split * Cout + o) * Cin + c) * 27 + t] = acc[kw][r];
         }
     }
     if (extra) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int o = o0 + (r & 3) + 8 * (r >> 2) + 4 * hh, c = c0 + r32;
+            const int o = o0 + mfma32_row(r, hh), c = c0 + r32;
             if (o < Cout && c < Cin) partial[(((size_t)split * Cout + o) * Cin + c) * 27 + 24 + wave] = acc[3][r];
         }
     }

@@ -27,11 +27,9 @@
 //           load a 64-byte request of its own, and the address path bounded the kernel: conv1 0.74 -> 0.63 ms, conv3 0.39 -> 0.335.
 // partial[split][o][c][27] as the other weight-gradient kernels: the caller adds the splits up.
 #include "common.h"
+#include "mfma.h"
 
 namespace mvsdet {
-
-typedef short ds2_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float ds2_f32x4 __attribute__((ext_vector_type(4)));
 
 #ifndef MVS_S2DW_FINE
 #define MVS_S2DW_FINE 6
@@ -66,6 +64,8 @@ static_assert(kS2dFRoles <= kS2dFineWaves * 64 && kS2dYRoles == 2 * kS2dYWaves *
 
 __device__ float4 g_ds2_zero;   // zero-initialised: the source of every padding element
 
+// A cut of this file's own, not mfma.h's bf16x3_split2: with the shared one the kernel is 396 instructions shorter and 9 - 14 % slower
+// (conv1 0.50 -> 0.57 ms, profiles/mfma_header_ab.txt), so it keeps the form it was measured with.
 __device__ __forceinline__ unsigned ds2_pack(__bf16 a, __bf16 b) {
     return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
 }
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(kS2dThreads) void conv3d_k3_s2_dw_bf16x3_kernel(con
                 it_chan[ps] = (unsigned)((size_t)min(c0 + ch, Cin - 1) * fvol);
                 it_ok[ps] = it_live[ps] && c0 + ch < Cin;
             }
-            struct FSet { ds2_f32x4 v[kS2dFPasses]; float left[kS2dFPasses]; };
+            struct FSet { f32x4 v[kS2dFPasses]; float left[kS2dFPasses]; };
             FSet sets[kS2dDepth];
             auto fetch_fine = [&](FSet& g, Pos p) {
                 const int2 e = tab[min(p.i, mine - 1)];
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(kS2dThreads) void conv3d_k3_s2_dw_bf16x3_kernel(con
                     const bool ok = (p.i < mine) & it_ok[ps] & (h >= 0) & (h < H);   // '&': no short-circuit branches
                     const float* row = view + it_chan[ps] + (size_t)d * HW + min(max(h, 0), H - 1) * W;
                     const int w = 2 * w0 + 4 * it_k[ps];
-                    g.v[ps] = *reinterpret_cast<const ds2_f32x4*>((ok & (w < W)) ? row + w : zero);
+                    g.v[ps] = *reinterpret_cast<const f32x4*>((ok & (w < W)) ? row + w : zero);
                     g.left[ps] = *((ok & (w0 > 0) & (2 * w0 <= W)) ? row + 2 * w0 - 1 : zero);   // x[2w0-1]: used by quarter 0
                 }
             };
@@ -226,8 +226,8 @@ __global__ __launch_bounds__(kS2dThreads) void conv3d_k3_s2_dw_bf16x3_kernel(con
             y_chan[ps] = (unsigned)((size_t)min(o0 + yo, Cout - 1) * cvol);
             y_ok[ps] = o0 + yo < Cout;
         }
-        ds2_f32x4 ysets[kS2dDepth][kS2dYPasses];
-        auto fetch_y = [&](ds2_f32x4* yv, Pos p) {
+        f32x4 ysets[kS2dDepth][kS2dYPasses];
+        auto fetch_y = [&](f32x4* yv, Pos p) {
             const int2 e = tab[min(p.i, mine - 1)];
             const int h0 = e.y >> 16, w0 = e.y & 0xffff;
             const float* const view = gy + (size_t)e.x * Cout * cvol;
@@ -236,10 +236,10 @@ __global__ __launch_bounds__(kS2dThreads) void conv3d_k3_s2_dw_bf16x3_kernel(con
                 const int h = h0 + y_row[ps], w = w0 + 4 * y_half[ps];
                 const bool ok = (p.i < mine) & y_ok[ps] & (h < Hc) & (w < Wc);
                 const float* row = view + y_chan[ps] + (size_t)p.s * HWc + min(h, Hc - 1) * Wc;
-                yv[ps] = *reinterpret_cast<const ds2_f32x4*>(ok ? row + w : zero);
+                yv[ps] = *reinterpret_cast<const f32x4*>(ok ? row + w : zero);
             }
         };
-        auto commit_y = [&](ds2_f32x4* yv, int buf) {
+        auto commit_y = [&](f32x4* yv, int buf) {
 #pragma unroll
             for (int ps = 0; ps < kS2dYPasses; ++ps) asm volatile("" : "+v"(yv[ps]));
 #pragma unroll
@@ -277,7 +277,6 @@ __global__ __launch_bounds__(kS2dThreads) void conv3d_k3_s2_dw_bf16x3_kernel(con
     }
 
     // -------------------------------------------------------------------------------------------------- multiplying waves
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x4 acc[4][4];   // [the three kw of the wave's (kd,kh) pair; waves 0..2: tap kw = wave of the pair (2,2)][coarse channel group]
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -300,16 +299,16 @@ __global__ __launch_bounds__(kS2dThreads) void conv3d_k3_s2_dw_bf16x3_kernel(con
         const char* const ycur = ybase + yb * kS2dYBufB;
         if (kd != 0 || s + 1 < Dc) {                            // wave-uniform
             const char* const ys = kd == 0 ? ybase + yb1 * kS2dYBufB : ycur;
-            ds2_bf16x8 ah[4], am[4], bh[3], bm[3];
+            bf16x8 ah[4], am[4], bh[3], bm[3];
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
-                ah[a] = *reinterpret_cast<const ds2_bf16x8*>(ys + a * 256);
-                am[a] = *reinterpret_cast<const ds2_bf16x8*>(ys + kS2dYPieceB + a * 256);
+                ah[a] = *reinterpret_cast<const bf16x8*>(ys + a * 256);
+                am[a] = *reinterpret_cast<const bf16x8*>(ys + kS2dYPieceB + a * 256);
             }
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
-                bh[kw] = *reinterpret_cast<const ds2_bf16x8*>(fs + kUnit[kw] * kS2dFUnitB);
-                bm[kw] = *reinterpret_cast<const ds2_bf16x8*>(fs + kS2dFPieceB + kUnit[kw] * kS2dFUnitB);
+                bh[kw] = *reinterpret_cast<const bf16x8*>(fs + kUnit[kw] * kS2dFUnitB);
+                bm[kw] = *reinterpret_cast<const bf16x8*>(fs + kS2dFPieceB + kUnit[kw] * kS2dFUnitB);
             }
             // consecutive MFMAs go to different accumulators
 #pragma unroll
@@ -327,14 +326,14 @@ __global__ __launch_bounds__(kS2dThreads) void conv3d_k3_s2_dw_bf16x3_kernel(con
         }
         if (extra) {                                            // tap (2,2,kw = wave): odd plane, Y[s]
             const char* const fe = fbase22 + (q & 1) * kS2dFPairB;
-            ds2_bf16x8 ah[4], am[4];
+            bf16x8 ah[4], am[4];
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
-                ah[a] = *reinterpret_cast<const ds2_bf16x8*>(ycur + a * 256);
-                am[a] = *reinterpret_cast<const ds2_bf16x8*>(ycur + kS2dYPieceB + a * 256);
+                ah[a] = *reinterpret_cast<const bf16x8*>(ycur + a * 256);
+                am[a] = *reinterpret_cast<const bf16x8*>(ycur + kS2dYPieceB + a * 256);
             }
-            const ds2_bf16x8 bh = *reinterpret_cast<const ds2_bf16x8*>(fe);
-            const ds2_bf16x8 bm = *reinterpret_cast<const ds2_bf16x8*>(fe + kS2dFPieceB);
+            const bf16x8 bh = *reinterpret_cast<const bf16x8*>(fe);
+            const bf16x8 bm = *reinterpret_cast<const bf16x8*>(fe + kS2dFPieceB);
 #pragma unroll
             for (int a = 0; a < 4; ++a) acc[3][a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[a], bh, acc[3][a], 0, 0, 0);
 #pragma unroll

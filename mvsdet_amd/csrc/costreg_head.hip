@@ -15,6 +15,7 @@
 // Accumulation order: channels ascending, then kh, kw, kd -- fp32 FMA chain; differs from MIOpen's / ATen's order by
 // rounding only (tests compare against ATen-CPU conv3d within 1e-5 of the output scale).
 #include "common.h"
+#include "mfma.h"
 
 namespace mvsdet {
 
@@ -424,10 +425,6 @@ __global__ __launch_bounds__(kThreads) void conv3d_k3_cout2_dw_kernel(const floa
 //   block : 4 independent waves (their own gy rows in LDS, no barrier in the loop); the four accumulator sets are added
 //           through the LDS at the end: partial[block][o][c][27], the caller adds the blocks up
 // The fp32 kernel above: 1.0 ms at (40,64,12,60,80); this one is bound by the x stream.
-typedef short hd_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float hd_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned hd_u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kHdwRows = 19;   // 2 output channels x 3 x 3 neighbouring rows of grad_out, and a row that stays zero
 constexpr int kHdwLead = 4;    // floats in front of a row's voxel 0 (the last of them is the left halo): the data is 16-byte aligned
 
@@ -437,22 +434,6 @@ __host__ __device__ constexpr int hdw_pitch(int W) {
     return p % 32 == 0 ? p + 4 : p;
 }
 __host__ __device__ constexpr size_t hdw_lds_bytes(int Cin, int W) { return ((size_t)4 * kHdwRows * hdw_pitch(W) + (size_t)Cin * 64) * sizeof(float); }
-
-__device__ __forceinline__ unsigned hd_pack(__bf16 a, __bf16 b) {
-    return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
-}
-// 8 floats -> their bf16 roundings (hi) and the roundings of the exact remainders (mid)
-__device__ __forceinline__ void hd_cut8(const float (&f)[8], hd_bf16x8& hi, hd_bf16x8& mid) {
-    hd_u32x4 h, m;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const __bf16 a0 = (__bf16)f[2 * p], a1 = (__bf16)f[2 * p + 1];
-        h[p] = hd_pack(a0, a1);
-        m[p] = hd_pack((__bf16)(f[2 * p] - (float)a0), (__bf16)(f[2 * p + 1] - (float)a1));
-    }
-    hi = __builtin_bit_cast(hd_bf16x8, h);
-    mid = __builtin_bit_cast(hd_bf16x8, m);
-}
 
 template <int MT>
 __global__ __launch_bounds__(kThreads) void conv3d_k3_cout2_dw_bf16x3_kernel(const float* __restrict__ x, const float* __restrict__ gy,
@@ -477,11 +458,11 @@ __global__ __launch_bounds__(kThreads) void conv3d_k3_cout2_dw_bf16x3_kernel(con
     const int HW = H * W, W4 = W >> 2;
     const size_t vol = (size_t)D * HW;
     const int nrows = N * D * H, ksteps = (W + 31) >> 5;
-    hd_f32x4 acc[MT][4];
+    f32x4 acc[MT][4];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = hd_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     for (int row = blockIdx.x * 4 + wave; row < nrows; row += gridDim.x * 4) {
         const int n = row / (D * H), dh = row - n * (D * H), d = dh / H, h = dh - d * H;
@@ -499,7 +480,7 @@ __global__ __launch_bounds__(kThreads) void conv3d_k3_cout2_dw_bf16x3_kernel(con
         const float* xr = x + ((size_t)n * Cin + r16) * vol + (size_t)d * HW + (size_t)h * W + 4 * g;
         for (int ks = 0; ks < ksteps; ++ks) {
             const int w0 = 32 * ks + 4 * g;
-            hd_bf16x8 ahi[MT], amid[MT];
+            bf16x8 ahi[MT], amid[MT];
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
                 const float* p = xr + (size_t)(16 * mt) * vol + 32 * ks;
@@ -507,20 +488,16 @@ __global__ __launch_bounds__(kThreads) void conv3d_k3_cout2_dw_bf16x3_kernel(con
                 if (w0 < W) v0 = *reinterpret_cast<const float4*>(p);
                 if (w0 + 16 < W) v1 = *reinterpret_cast<const float4*>(p + 16);
                 const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                hd_cut8(f, ahi[mt], amid[mt]);
+                bf16x3_cut8(f, ahi[mt], amid[mt]);
             }
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
                 const float* b = rows + boff[nt] + 32 * ks;
                 const float f[8] = {b[0], b[1], b[2], b[3], b[16], b[17], b[18], b[19]};
-                hd_bf16x8 bhi, bmid;
-                hd_cut8(f, bhi, bmid);
+                bf16x8 bhi, bmid;
+                bf16x3_cut8(f, bhi, bmid);
 #pragma unroll
-                for (int mt = 0; mt < MT; ++mt) {
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(amid[mt], bhi, acc[mt][nt], 0, 0, 0);
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi[mt], bmid, acc[mt][nt], 0, 0, 0);
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi[mt], bhi, acc[mt][nt], 0, 0, 0);
-                }
+                for (int mt = 0; mt < MT; ++mt) bf16x3_mfma16(acc[mt][nt], ahi[mt], amid[mt], bhi, bmid);
             }
         }
         __builtin_amdgcn_wave_barrier();   // the row's reads are issued before the next row's stores (one wave: LDS in order)

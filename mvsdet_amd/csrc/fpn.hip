@@ -1,5 +1,5 @@
 // Level 0 of the 2-D feature pyramid that feeds the sweep (mvsdet.py:374-376: `x = self.neck(x)[0]`) on the bf16 matrix cores with
-// three-term split operands -- the same hi / mid cut and the same three products as neck_gemm.hip.
+// three-term split operands: the hi / mid cut, the three products and the laterals' GEMM block are mfma.h's, shared with neck_gemm.hip.
 //
 // The module is mmdet.models.necks.FPN in the shipped configuration (in_channels=[256,512,1024,2048], out_channels=256, num_outs=4,
 // start_level=0, no add_extra_convs, no norm, no activation, upsample_cfg=dict(mode='nearest')).  mmdet is not part of this tree; the
@@ -16,10 +16,9 @@
 // 88 pairs in <= out < 130, e.g. 46 <- 14); the two scales are divided on the host and handed to the kernel.
 //
 // fpn_lateral_kernel: C[256][v] = W[256][Cin] x[Cin][v] + bias [+ top at the nearest source index], the plain sibling of
-//   neck_gemm_bf16x3_kernel MODE 0.  Block = 128 rows x 64 columns, 4 waves of 32 rows x two 32-column accumulators.  The columns run
-//   over ALL views' pixels, v = n H W + pixel: the 8x10 level of 40 views is 3200 columns = 50 full blocks, not 40 x two blocks of
-//   which the second is three quarters empty.  A from L2 in fragment order (mvsdet_gemm_split_weight), B cut on the way into a
-//   double-buffered LDS stage (16 KiB).
+//   neck_gemm_bf16x3_kernel MODE 0 on the same gemm_bf16x3_block (128 rows x 64 columns, A from L2 in mvsdet_gemm_split_weight's
+//   fragment order).  The columns run over ALL views' pixels, v = n H W + pixel: the 8x10 level of 40 views is 3200 columns = 50 full
+//   blocks, not 40 x two blocks of which the second is three quarters empty.
 //
 // fpn_conv3x3_kernel: implicit GEMM, M = Cout, K = 9 Cin tap-major (k = Cin tap + c, tap = 3 dy + dx; the matrix is
 //   w.permute(0,2,3,1).reshape(Cout, 9 Cin)).  Block = 128 rows x a tile of kFcTW x kFcTH = 16 x 8 pixels of one view, 4 waves of 32
@@ -28,39 +27,20 @@
 //   taps read their B fragments from it at shifted addresses (16 consecutive lanes = 256 consecutive bytes: conflict-free), so an
 //   input value is fetched and cut once per block, not nine times.  Two stages (2 x 22.5 KiB): the next 32 channels are fetched into
 //   registers under this chunk's 216 MFMAs per wave.  The epilogue writes fp32 NCHW and / or the packed maps: a lane's sixteen rows
-//   (i & 3) + 8 (i >> 2) + 4 (lane >> 5) of a 32-row tile are, for each i & 3, the four channels 8 i' + g (g = (i & 3) + 4 (lane >> 5))
+//   mfma32_row(i, lane >> 5) = (i & 3) + 8 (i >> 2) + 4 (lane >> 5) of a 32-row tile are, for each i & 3, the four channels 8 i' + g (g = (i & 3) + 4 (lane >> 5))
 //   = packed q = 4 g .. 4 g + 3: one 16-byte store per (i & 3), no shuffle.
 //
 // No atomics: the same bits on every run.
 #include "common.h"
+#include "mfma.h"
 
 namespace mvsdet {
 
-typedef short fp_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float fp_f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned fp_u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kFpBM = 128, kFpBN = 64, kFpBK = 32;
 constexpr int kFcTW = 16, kFcTH = 8;                        // the 3x3 kernel's pixel tile
 constexpr int kFcHW = kFcTW + 2, kFcHH = kFcTH + 2;          // its halo tile
 constexpr int kFcHalo = kFcHW * kFcHH;                       // 180 halo pixels
 constexpr int kFcUnits = 4 * kFcHalo;                        // (k-group of 8, halo pixel) staging units per 32 channels
 constexpr int kFcRounds = (kFcUnits + kThreads - 1) / kThreads;
-
-// copies of neck_gemm.hip's helpers (that file's are its own translation unit's)
-__device__ __forceinline__ unsigned fp_pack(float a, float b) {
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    const bf2 v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
-// 8 floats -> their bf16 roundings (hi) and the roundings of the exact remainders (mid)
-__device__ __forceinline__ void fp_cut8(const float (&f)[8], fp_u32x4& hi, fp_u32x4& mid) {
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        hi[p] = fp_pack(f[2 * p], f[2 * p + 1]);
-        mid[p] = fp_pack(f[2 * p] - __uint_as_float(hi[p] << 16), f[2 * p + 1] - __uint_as_float(hi[p] & 0xffff0000u));
-    }
-}
 
 // ATen's nearest source index (UpSample.h: nearest_neighbor_compute_source_index), scale = (float)in / (float)out
 __device__ __forceinline__ int fp_nearest(int dst, float scale, int in) { return min((int)floorf((float)dst * scale), in - 1); }
@@ -70,9 +50,8 @@ __global__ __launch_bounds__(kThreads) void fpn_lateral_kernel(const float* __re
                                                                const float* __restrict__ bias, const float* __restrict__ top,
                                                                float* __restrict__ out, int M, int K, int HW, int W, int V, int Ht, int Wt,
                                                                float scale_h, float scale_w) {
-    __shared__ uint4 s_b[2][2][4][kFpBN];   // [stage][piece][k-group of 8][column]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int m0 = blockIdx.y * kFpBM, v0 = blockIdx.x * kFpBN;
+    const int m0 = blockIdx.y * kGemmBM, v0 = blockIdx.x * kGemmBN;
 
     // staging duty: column v0 + (tid & 63), channels 8 * (tid >> 6) .. + 7 of the step
     const int sv = v0 + (tid & 63), skq = tid >> 6;
@@ -82,52 +61,15 @@ __global__ __launch_bounds__(kThreads) void fpn_lateral_kernel(const float* __re
     float f[8];
     auto fetch = [&](int ks) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = sv_ok ? xs[(size_t)(ks * kFpBK + j) * HW] : 0.0f;
-    };
-    auto put = [&](int buf) {
-        fp_u32x4 hi, mid;
-        fp_cut8(f, hi, mid);
-        s_b[buf][0][skq][tid & 63] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-        s_b[buf][1][skq][tid & 63] = make_uint4(mid[0], mid[1], mid[2], mid[3]);
+        for (int j = 0; j < 8; ++j) f[j] = sv_ok ? xs[(size_t)(ks * kGemmBK + j) * HW] : 0.0f;
     };
 
-    fp_f32x16 acc[2];
+    f32x16 acc[2];
 #pragma unroll
     for (int c = 0; c < 2; ++c)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[c][i] = 0.0f;
-
-    const int rt = (m0 >> 5) + wave;                     // the wave's row tile
-    const uint4* wa = ws + (size_t)rt * (K / 16) * 2 * 64 + lane;
-    const int nks = K / kFpBK;
-    fetch(0);
-    put(0);
-    __syncthreads();
-    for (int ks = 0; ks < nks; ++ks) {
-        const int buf = ks & 1;
-        if (ks + 1 < nks) fetch(ks + 1);                 // in flight under the MFMAs below
-        uint4 a_hi[2], a_mid[2];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            a_hi[s] = wa[((size_t)(2 * ks + s) * 2 + 0) * 64];
-            a_mid[s] = wa[((size_t)(2 * ks + s) * 2 + 1) * 64];
-        }
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const fp_bf16x8 Ah = __builtin_bit_cast(fp_bf16x8, a_hi[s]), Am = __builtin_bit_cast(fp_bf16x8, a_mid[s]);
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const int kq = 2 * s + (lane >> 5), col = 32 * c + (lane & 31);
-                const fp_bf16x8 Bh = __builtin_bit_cast(fp_bf16x8, s_b[buf][0][kq][col]);
-                const fp_bf16x8 Bm = __builtin_bit_cast(fp_bf16x8, s_b[buf][1][kq][col]);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh, acc[c], 0, 0, 0);   // small terms first
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, acc[c], 0, 0, 0);
-            }
-        }
-        if (ks + 1 < nks) put(buf ^ 1);                  // the other stage: its readers finished before the last barrier
-        __syncthreads();
-    }
+    gemm_bf16x3_block(acc, f, fetch, ws, m0, K, tid, wave);
 
     // ---- epilogue: + bias [+ top at the nearest source pixel]
     const int half = lane >> 5;
@@ -146,7 +88,7 @@ __global__ __launch_bounds__(kThreads) void fpn_lateral_kernel(const float* __re
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * half;
+            const int row = mfma32_row(i, half);
             float val = acc[c][i] + bias[m0 + 32 * wave + row];
             if (t) val += t[(size_t)row * tplane];
             o[(size_t)row * HW] = val;
@@ -160,7 +102,7 @@ __global__ __launch_bounds__(kThreads) void fpn_conv3x3_kernel(const float* __re
                                                                float* __restrict__ packed, int M, int Cin, int H, int W, int tiles_x) {
     __shared__ uint4 s_h[2][2][4][kFcHalo];   // [stage][piece][k-group of 8][halo pixel]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = blockIdx.z, m0 = blockIdx.y * kFpBM;
+    const int n = blockIdx.z, m0 = blockIdx.y * kGemmBM;
     const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
     const int y0 = ty * kFcTH, x0 = tx * kFcTW;
     const size_t HW = (size_t)H * W;
@@ -183,7 +125,7 @@ __global__ __launch_bounds__(kThreads) void fpn_conv3x3_kernel(const float* __re
     }
     float f[kFcRounds][8];
     auto fetch = [&](int chunk) {
-        const float* xc = xn + (size_t)(chunk * kFpBK) * HW;
+        const float* xc = xn + (size_t)(chunk * kGemmBK) * HW;
 #pragma unroll
         for (int r = 0; r < kFcRounds; ++r)
 #pragma unroll
@@ -193,15 +135,15 @@ __global__ __launch_bounds__(kThreads) void fpn_conv3x3_kernel(const float* __re
 #pragma unroll
         for (int r = 0; r < kFcRounds; ++r) {
             if (tid + kThreads * r < kFcUnits) {
-                fp_u32x4 hi, mid;
-                fp_cut8(f[r], hi, mid);
+                u32x4 hi, mid;
+                bf16x3_cut8(f[r], hi, mid);
                 s_h[buf][0][skq[r]][shp[r]] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
                 s_h[buf][1][skq[r]][shp[r]] = make_uint4(mid[0], mid[1], mid[2], mid[3]);
             }
         }
     };
 
-    fp_f32x16 acc[4];
+    f32x16 acc[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -213,7 +155,7 @@ __global__ __launch_bounds__(kThreads) void fpn_conv3x3_kernel(const float* __re
     // the lane's pixel inside accumulator t: tile row 2 t + ly, column lx; its halo pixel under tap (dy, dx) is hbase + t 2 kFcHW + dy kFcHW + dx
     const int lx = lane & 15, ly = (lane >> 4) & 1, half = lane >> 5;
     const int hbase = ly * kFcHW + lx;
-    const int nch = Cin / kFpBK;
+    const int nch = Cin / kGemmBK;
     fetch(0);
     put(0);
     __syncthreads();
@@ -223,20 +165,18 @@ __global__ __launch_bounds__(kThreads) void fpn_conv3x3_kernel(const float* __re
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int dy = tap / 3, dx = tap - 3 * dy;
-            const int k16 = (tap * Cin + ch * kFpBK) / 16;
+            const int k16 = (tap * Cin + ch * kGemmBK) / 16;
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                const fp_bf16x8 Ah = __builtin_bit_cast(fp_bf16x8, wa[((size_t)(k16 + s) * 2 + 0) * 64]);
-                const fp_bf16x8 Am = __builtin_bit_cast(fp_bf16x8, wa[((size_t)(k16 + s) * 2 + 1) * 64]);
+                const bf16x8 Ah = __builtin_bit_cast(bf16x8, wa[((size_t)(k16 + s) * 2 + 0) * 64]);
+                const bf16x8 Am = __builtin_bit_cast(bf16x8, wa[((size_t)(k16 + s) * 2 + 1) * 64]);
                 const int kq = 2 * s + half;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const int hp = hbase + (2 * t + dy) * kFcHW + dx;
-                    const fp_bf16x8 Bh = __builtin_bit_cast(fp_bf16x8, s_h[buf][0][kq][hp]);
-                    const fp_bf16x8 Bm = __builtin_bit_cast(fp_bf16x8, s_h[buf][1][kq][hp]);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh, acc[t], 0, 0, 0);   // small terms first
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, acc[t], 0, 0, 0);
+                    const bf16x8 Bh = __builtin_bit_cast(bf16x8, s_h[buf][0][kq][hp]);
+                    const bf16x8 Bm = __builtin_bit_cast(bf16x8, s_h[buf][1][kq][hp]);
+                    bf16x3_mfma32(acc[t], Ah, Am, Bh, Bm);
                 }
             }
         }
@@ -248,7 +188,7 @@ __global__ __launch_bounds__(kThreads) void fpn_conv3x3_kernel(const float* __re
     const int mw = m0 + 32 * wave;
     float b[16];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) b[i] = bias[mw + (i & 3) + 8 * (i >> 2) + 4 * half];
+    for (int i = 0; i < 16; ++i) b[i] = bias[mw + mfma32_row(i, half)];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int y = y0 + 2 * t + ly, xx = x0 + lx;
@@ -257,7 +197,7 @@ __global__ __launch_bounds__(kThreads) void fpn_conv3x3_kernel(const float* __re
         if (out) {
             float* o = out + ((size_t)n * M + mw) * HW + pix;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) o[(size_t)((i & 3) + 8 * (i >> 2) + 4 * half) * HW] = acc[t][i] + b[i];
+            for (int i = 0; i < 16; ++i) o[(size_t)mfma32_row(i, half) * HW] = acc[t][i] + b[i];
         }
         if (packed) {   // slab mw / 32; registers a, a + 4, a + 8, a + 12 are channels 8 i' + g of the slab, g = a + 4 half: q = 4 g + i'
             float* p = packed + (((size_t)n * (M / 32) + (mw >> 5)) * HW + pix) * 32 + 16 * half;
@@ -277,10 +217,10 @@ extern "C" int mvsdet_fpn_lateral_bf16x3(const float* x, const void* wsplit, con
                                          int Cin, int Cout, int H, int W, int Ht, int Wt, mvsdet_stream_t stream) {
     MVS_REQUIRE(x && wsplit && bias && out, "fpn_lateral_bf16x3: NULL pointer");
     MVS_REQUIRE(N > 0 && H > 0 && W > 0, "fpn_lateral_bf16x3: bad shape N=%d H=%d W=%d", N, H, W);
-    MVS_REQUIRE(Cin > 0 && Cin % kFpBK == 0 && Cout > 0 && Cout % kFpBM == 0, "fpn_lateral_bf16x3: Cin=%d must be a multiple of %d and Cout=%d of %d",
-                Cin, kFpBK, Cout, kFpBM);
-    MVS_REQUIRE(Cout / kFpBM <= 65535, "fpn_lateral_bf16x3: too many rows");
-    MVS_REQUIRE((long long)N * H * W <= INT32_MAX - kFpBN, "fpn_lateral_bf16x3: N H W = %lld columns exceed 2^31", (long long)N * H * W);
+    MVS_REQUIRE(Cin > 0 && Cin % kGemmBK == 0 && Cout > 0 && Cout % kGemmBM == 0, "fpn_lateral_bf16x3: Cin=%d must be a multiple of %d and Cout=%d of %d",
+                Cin, kGemmBK, Cout, kGemmBM);
+    MVS_REQUIRE(Cout / kGemmBM <= 65535, "fpn_lateral_bf16x3: too many rows");
+    MVS_REQUIRE((long long)N * H * W <= INT32_MAX - kGemmBN, "fpn_lateral_bf16x3: N H W = %lld columns exceed 2^31", (long long)N * H * W);
     MVS_REQUIRE(((uintptr_t)wsplit & 15u) == 0 && ((uintptr_t)x & 3u) == 0 && ((uintptr_t)out & 3u) == 0 && ((uintptr_t)bias & 3u) == 0,
                 "fpn_lateral_bf16x3: wsplit must be 16-byte, the tensors 4-byte aligned");
     if (top) {
@@ -291,7 +231,7 @@ extern "C" int mvsdet_fpn_lateral_bf16x3(const float* x, const void* wsplit, con
         Ht = Wt = 1;
     }
     const int V = N * H * W;
-    dim3 grid((unsigned)((V + kFpBN - 1) / kFpBN), (unsigned)(Cout / kFpBM));
+    dim3 grid((unsigned)((V + kGemmBN - 1) / kGemmBN), (unsigned)(Cout / kGemmBM));
     hipLaunchKernelGGL(fpn_lateral_kernel, grid, dim3(kThreads), 0, (hipStream_t)stream, x, static_cast<const uint4*>(wsplit), bias, top, out, Cout,
                        Cin, H * W, W, V, Ht, Wt, (float)Ht / (float)H, (float)Wt / (float)W);
     MVS_LAUNCH_CHECK("fpn_lateral_bf16x3");
@@ -303,15 +243,15 @@ extern "C" int mvsdet_fpn_conv3x3_bf16x3(const float* x, const void* wsplit, con
     MVS_REQUIRE(x && wsplit && bias, "fpn_conv3x3_bf16x3: NULL pointer");
     MVS_REQUIRE(out || packed, "fpn_conv3x3_bf16x3: NULL pointer: at least one of out and packed must be given");
     MVS_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0, "fpn_conv3x3_bf16x3: bad shape N=%d H=%d W=%d", N, H, W);
-    MVS_REQUIRE(Cin > 0 && Cin % kFpBK == 0 && Cout > 0 && Cout % kFpBM == 0, "fpn_conv3x3_bf16x3: Cin=%d must be a multiple of %d and Cout=%d of %d",
-                Cin, kFpBK, Cout, kFpBM);
-    MVS_REQUIRE(Cout / kFpBM <= 65535 && Cin <= INT32_MAX / 9, "fpn_conv3x3_bf16x3: too many channels");
+    MVS_REQUIRE(Cin > 0 && Cin % kGemmBK == 0 && Cout > 0 && Cout % kGemmBM == 0, "fpn_conv3x3_bf16x3: Cin=%d must be a multiple of %d and Cout=%d of %d",
+                Cin, kGemmBK, Cout, kGemmBM);
+    MVS_REQUIRE(Cout / kGemmBM <= 65535 && Cin <= INT32_MAX / 9, "fpn_conv3x3_bf16x3: too many channels");
     const long long tiles_x = (W + kFcTW - 1) / kFcTW, tiles_y = (H + kFcTH - 1) / kFcTH;
     MVS_REQUIRE((long long)H * W < INT32_MAX && tiles_x * tiles_y < INT32_MAX, "fpn_conv3x3_bf16x3: map %d x %d too large", H, W);
     MVS_REQUIRE(((uintptr_t)wsplit & 15u) == 0 && ((uintptr_t)x & 3u) == 0 && ((uintptr_t)out & 3u) == 0 && ((uintptr_t)bias & 3u) == 0 &&
                     ((uintptr_t)packed & 15u) == 0,
                 "fpn_conv3x3_bf16x3: wsplit and packed must be 16-byte, the tensors 4-byte aligned");
-    dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)(Cout / kFpBM), (unsigned)N);
+    dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)(Cout / kGemmBM), (unsigned)N);
     hipLaunchKernelGGL(fpn_conv3x3_kernel, grid, dim3(kThreads), 0, (hipStream_t)stream, x, static_cast<const uint4*>(wsplit), bias, out, packed,
                        Cout, Cin, H, W, (int)tiles_x);
     MVS_LAUNCH_CHECK("fpn_conv3x3_bf16x3");

@@ -28,12 +28,11 @@
 // K + 1, M, R and the pixel tiles all have tails: they are zeros in registers / LDS, never a read past a row.  An id outside [0, N)
 // reads nothing: that view's x is NaN (so is its raw), and it gets no gradient.
 #include "common.h"
+#include "mfma.h"
 
 #include <algorithm>
 
 namespace mvsdet {
-
-typedef float gh_f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kGhKB = 32;        // k per LDS stage (16 MFMA steps)
 constexpr int kGhRowTiles = 3;   // forward: row tiles of 32 m per block
@@ -69,7 +68,7 @@ __device__ __forceinline__ float gh_x(const GhSrc& s, int64_t id, bool ok, int v
     return 0.25f * ((p[0] + p[1]) + (p[s.iH] + p[s.iH + 1]));
 }
 
-__device__ __forceinline__ void gh_zero(gh_f32x16& a) {
+__device__ __forceinline__ void gh_zero(f32x16& a) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) a[i] = 0.0f;
 }
@@ -88,7 +87,7 @@ __global__ __launch_bounds__(kThreads) void gshead_forward_kernel(GhSrc s, const
     const int y = in ? r / s.w : 0, x = in ? r - y * s.w : 0;
     const int K = s.K, Kt = K + 1;
 
-    gh_f32x16 acc[kGhRowTiles];
+    f32x16 acc[kGhRowTiles];
 #pragma unroll
     for (int t = 0; t < kGhRowTiles; ++t) gh_zero(acc[t]);
 
@@ -182,7 +181,7 @@ __global__ __launch_bounds__(kThreads) void gshead_backward_input_kernel(GhSrc s
     if (id < 0 || id >= s.N) return;                     // uniform: a view that does not exist gets no gradient
     const int K = s.K, Kout = s.C + 1;
 
-    gh_f32x16 acc[kGhDxTiles];
+    f32x16 acc[kGhDxTiles];
 #pragma unroll
     for (int t = 0; t < kGhDxTiles; ++t) gh_zero(acc[t]);
 
@@ -215,7 +214,7 @@ __global__ __launch_bounds__(kThreads) void gshead_backward_input_kernel(GhSrc s
     for (int t = 0; t < kGhDxTiles; ++t) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int k = k0 + 32 * t + (i & 3) + 8 * (i >> 2) + 4 * half;
+            const int k = mfma32_row(i, half, k0 + 32 * t);
             if (k < s.C) {
                 const float xv = s.feature[id * s.fN + (int64_t)k * s.fC + (int64_t)y * s.fH + x];
                 g_feature[id * gfN + (int64_t)k * gfC + (int64_t)y * gfH + x] = xv > 0.0f ? acc[t][i] : 0.0f;
@@ -240,7 +239,7 @@ __global__ __launch_bounds__(kThreads) void gshead_backward_weight_kernel(GhSrc 
     const long long P = (long long)V * s.R;
     const long long qbeg = (long long)blockIdx.y * chunk, qend = qbeg + chunk < P ? qbeg + chunk : P;
 
-    gh_f32x16 acc[kGhRowTiles];
+    f32x16 acc[kGhRowTiles];
 #pragma unroll
     for (int t = 0; t < kGhRowTiles; ++t) gh_zero(acc[t]);
 
@@ -297,7 +296,7 @@ __global__ __launch_bounds__(kThreads) void gshead_backward_weight_kernel(GhSrc 
     for (int t = 0; t < kGhRowTiles; ++t) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int m = m0 + 32 * t + (i & 3) + 8 * (i >> 2) + 4 * half;
+            const int m = mfma32_row(i, half, m0 + 32 * t);
             if (m < M) o[(size_t)m * Kt + k] = acc[t][i];
         }
     }

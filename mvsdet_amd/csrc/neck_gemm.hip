@@ -10,45 +10,23 @@
 // permuting clamp for the 2x2x2 interleave: four Cijk kernels, ~20 small launches and ~0.35 ms of a 2.2 ms neck).  Here:
 // one kernel per layer, bias, ReLU and the interleave in its epilogue, the sub-sampling in its gather.
 //
-// Block = 128 rows (M) x 64 voxels, 4 waves; wave w = rows 32w .. 32w+31 x both 32-voxel column tiles (2 accumulators of
-// v_mfma_f32_32x32x16_bf16); K in steps of 32 channels.  A: the weight matrix cut into bf16 hi / mid ONCE per weight version
-// (mvsdet_gemm_split_weight, kept on the module) in fragment order [M/32][K/16][piece][64 lanes][8]: a wave's fragment is 1 KiB
-// of one coalesced load from L2, no LDS.  B: a thread fetches the 8 channels of its voxel (coalesced along the voxels), cuts
-// them and writes two 16-byte units; fragments are conflict-free ds_read_b128.  Double-buffered LDS (16 KiB), the next step's
-// channel values fetched into registers before this step's MFMAs.
+// Block = 128 rows (M) x 64 voxels, K in steps of 32 channels: gemm_bf16x3_block of mfma.h (the weight matrix cut into bf16 hi / mid ONCE
+// per weight version by mvsdet_gemm_split_weight and kept on the module, read in fragment order from L2; the activations cut on the way
+// into a double-buffered LDS stage).  A thread fetches the 8 channels of its voxel, coalesced along the voxels.
 //
 // Training (autograd) adds the two layers' input gradients as MODEs 2 and 3 of the same kernel (A = the transposed / reshaped
 // weight matrix, split per call) and their weight gradients as one NT GEMM that reduces over the voxels (neck_gemm_dw_bf16x3_kernel:
 // both operands activations, cut into bf16 pieces on the way into the LDS; split-K partial sums added in a fixed order).
 //
-// Row order for the transposed layer: m = 8 o + 4 p + 2 q + r, so that the 32x32 accumulator's rows (reg & 3) + 4 (lane >> 5)
-// + 8 (reg >> 2) give a lane four output channels (reg >> 2) at depth parity p = lane >> 5 with (q, r) = reg & 3: a float2
+// Row order for the transposed layer: m = 8 o + 4 p + 2 q + r, so that the 32x32 accumulator's rows (mfma32_row of mfma.h: (reg & 3)
+// + 4 (lane >> 5) + 8 (reg >> 2)) give a lane four output channels (reg >> 2) at depth parity p = lane >> 5 with (q, r) = reg & 3: a float2
 // store {r = 0, 1} per (channel, q), contiguous along w across the lanes of a row.
 #include "common.h"
+#include "mfma.h"
 
 #include <algorithm>
 
 namespace mvsdet {
-
-typedef short ng_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float ng_f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned ng_u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kNgBM = 128, kNgBN = 64, kNgBK = 32;
-
-__device__ __forceinline__ unsigned ng_pack(float a, float b) {
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    const bf2 v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
-// 8 floats -> their bf16 roundings (hi) and the roundings of the exact remainders (mid)
-__device__ __forceinline__ void ng_cut8(const float (&f)[8], ng_u32x4& hi, ng_u32x4& mid) {
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        hi[p] = ng_pack(f[2 * p], f[2 * p + 1]);
-        mid[p] = ng_pack(f[2 * p] - __uint_as_float(hi[p] << 16), f[2 * p + 1] - __uint_as_float(hi[p] & 0xffff0000u));
-    }
-}
 
 // wmat (M, K) fp32 row-major -> [M/32][K/16][2 pieces][64 lanes][8 bf16]: lane = 32 * (k-group of 8) + row of the tile
 __global__ __launch_bounds__(kThreads) void gemm_split_weight_kernel(const float* __restrict__ wmat, uint4* __restrict__ ws, int M, int K) {
@@ -62,8 +40,8 @@ __global__ __launch_bounds__(kThreads) void gemm_split_weight_kernel(const float
     float f[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) f[j] = src[j];
-    ng_u32x4 hi, mid;
-    ng_cut8(f, hi, mid);
+    u32x4 hi, mid;
+    bf16x3_cut8(f, hi, mid);
     ws[(t * 2 + 0) * 64 + lane] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
     ws[(t * 2 + 1) * 64 + lane] = make_uint4(mid[0], mid[1], mid[2], mid[3]);
 }
@@ -78,9 +56,8 @@ template <int MODE>
 __global__ __launch_bounds__(kThreads) void neck_gemm_bf16x3_kernel(const float* __restrict__ x, const uint4* __restrict__ ws,
                                                                     const float* __restrict__ bias, float* __restrict__ out, int M,
                                                                     int K, int D, int H, int W, int relu) {
-    __shared__ uint4 s_b[2][2][4][kNgBN];   // [stage][piece][k-group of 8][voxel]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = blockIdx.z, m0 = blockIdx.y * kNgBM, v0 = blockIdx.x * kNgBN;
+    const int n = blockIdx.z, m0 = blockIdx.y * kGemmBM, v0 = blockIdx.x * kGemmBN;
     // the voxel grid the columns run over: MODEs 0 and 2 the coarse grid of D x H x W, MODEs 1 and 3 the grid D x H x W itself
     const bool coarse = MODE == 0 || MODE == 2;
     const int Dv = coarse ? D / 2 : D, Hv = coarse ? H / 2 : H, Wv = coarse ? W / 2 : W;
@@ -114,53 +91,16 @@ __global__ __launch_bounds__(kThreads) void neck_gemm_bf16x3_kernel(const float*
                 f[j] = sv_ok ? xs[(size_t)(4 * ks) * plane + (j >> 2) * HW2 + ((j >> 1) & 1) * W2 + (j & 1)] : 0.0f;
         } else {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) f[j] = sv_ok ? xs[(size_t)(ks * kNgBK + j) * plane] : 0.0f;
+            for (int j = 0; j < 8; ++j) f[j] = sv_ok ? xs[(size_t)(ks * kGemmBK + j) * plane] : 0.0f;
         }
     };
-    auto put = [&](int buf) {
-        ng_u32x4 hi, mid;
-        ng_cut8(f, hi, mid);
-        s_b[buf][0][skq][tid & 63] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-        s_b[buf][1][skq][tid & 63] = make_uint4(mid[0], mid[1], mid[2], mid[3]);
-    };
 
-    ng_f32x16 acc[2];
+    f32x16 acc[2];
 #pragma unroll
     for (int c = 0; c < 2; ++c)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[c][i] = 0.0f;
-
-    const int rt = (m0 >> 5) + wave;                     // the wave's row tile
-    const uint4* wa = ws + (size_t)rt * (K / 16) * 2 * 64 + lane;
-    const int nks = K / kNgBK;
-    fetch(0);
-    put(0);
-    __syncthreads();
-    for (int ks = 0; ks < nks; ++ks) {
-        const int buf = ks & 1;
-        if (ks + 1 < nks) fetch(ks + 1);                 // in flight under the MFMAs below
-        uint4 a_hi[2], a_mid[2];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            a_hi[s] = wa[((size_t)(2 * ks + s) * 2 + 0) * 64];
-            a_mid[s] = wa[((size_t)(2 * ks + s) * 2 + 1) * 64];
-        }
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const ng_bf16x8 Ah = __builtin_bit_cast(ng_bf16x8, a_hi[s]), Am = __builtin_bit_cast(ng_bf16x8, a_mid[s]);
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const int kq = 2 * s + (lane >> 5), col = 32 * c + (lane & 31);
-                const ng_bf16x8 Bh = __builtin_bit_cast(ng_bf16x8, s_b[buf][0][kq][col]);
-                const ng_bf16x8 Bm = __builtin_bit_cast(ng_bf16x8, s_b[buf][1][kq][col]);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh, acc[c], 0, 0, 0);   // small terms first
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm, acc[c], 0, 0, 0);
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, acc[c], 0, 0, 0);
-            }
-        }
-        if (ks + 1 < nks) put(buf ^ 1);                  // the other stage: its readers finished before the last barrier
-        __syncthreads();
-    }
+    gemm_bf16x3_block(acc, f, fetch, ws, m0, K, tid, wave);
 
     // ---- epilogue
     const int half = lane >> 5;
@@ -173,16 +113,16 @@ __global__ __launch_bounds__(kThreads) void neck_gemm_bf16x3_kernel(const float*
             const size_t vol = (size_t)D * H * W;
             float* o = out + ((size_t)n * M + m0 + 32 * wave) * vol + ((size_t)2 * d * H + 2 * h) * W + 2 * w;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) o[(size_t)((i & 3) + 8 * (i >> 2) + 4 * half) * vol] += acc[c][i];
+            for (int i = 0; i < 16; ++i) o[(size_t)mfma32_row(i, half) * vol] += acc[c][i];
         } else if (MODE == 3) {
             float* o = out + ((size_t)n * M + m0 + 32 * wave) * V + v;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) o[(size_t)((i & 3) + 8 * (i >> 2) + 4 * half) * V] = acc[c][i];
+            for (int i = 0; i < 16; ++i) o[(size_t)mfma32_row(i, half) * V] = acc[c][i];
         } else if (MODE == 0) {
             float* o = out + ((size_t)n * M + m0 + 32 * wave) * V + v;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int row = (i & 3) + 8 * (i >> 2) + 4 * half;
+                const int row = mfma32_row(i, half);
                 float val = acc[c][i] + bias[m0 + 32 * wave + row];
                 if (relu) val = fmaxf(val, 0.0f);
                 o[(size_t)row * V] = val;
@@ -264,16 +204,16 @@ __global__ __launch_bounds__(kThreads) void neck_gemm_dw_bf16x3_kernel(const flo
         }
     };
     auto put = [&](int buf) {
-        ng_u32x4 hi, mid;
-        ng_cut8(fa, hi, mid);
+        u32x4 hi, mid;
+        bf16x3_cut8(fa, hi, mid);
         s_t[buf][0][0][r][kgs] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
         s_t[buf][0][1][r][kgs] = make_uint4(mid[0], mid[1], mid[2], mid[3]);
-        ng_cut8(fb, hi, mid);
+        bf16x3_cut8(fb, hi, mid);
         s_t[buf][1][0][r][kgs] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
         s_t[buf][1][1][r][kgs] = make_uint4(mid[0], mid[1], mid[2], mid[3]);
     };
 
-    ng_f32x16 acc;
+    f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
     const int ar = 32 * (wave >> 1) + (lane & 31), br = 32 * (wave & 1) + (lane & 31);
@@ -288,24 +228,22 @@ __global__ __launch_bounds__(kThreads) void neck_gemm_dw_bf16x3_kernel(const flo
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             const int q = 2 * s + (lane >> 5);
-            const ng_bf16x8 Ah = __builtin_bit_cast(ng_bf16x8, s_t[buf][0][0][ar][q ^ ((ar >> 2) & 3)]);
-            const ng_bf16x8 Am = __builtin_bit_cast(ng_bf16x8, s_t[buf][0][1][ar][q ^ ((ar >> 2) & 3)]);
-            const ng_bf16x8 Bh = __builtin_bit_cast(ng_bf16x8, s_t[buf][1][0][br][q ^ ((br >> 2) & 3)]);
-            const ng_bf16x8 Bm = __builtin_bit_cast(ng_bf16x8, s_t[buf][1][1][br][q ^ ((br >> 2) & 3)]);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh, acc, 0, 0, 0);   // small terms first
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, acc, 0, 0, 0);
+            const bf16x8 Ah = __builtin_bit_cast(bf16x8, s_t[buf][0][0][ar][q ^ ((ar >> 2) & 3)]);
+            const bf16x8 Am = __builtin_bit_cast(bf16x8, s_t[buf][0][1][ar][q ^ ((ar >> 2) & 3)]);
+            const bf16x8 Bh = __builtin_bit_cast(bf16x8, s_t[buf][1][0][br][q ^ ((br >> 2) & 3)]);
+            const bf16x8 Bm = __builtin_bit_cast(bf16x8, s_t[buf][1][1][br][q ^ ((br >> 2) & 3)]);
+            bf16x3_mfma32(acc, Ah, Am, Bh, Bm);
         }
         if (st + 1 < nsteps) put(buf ^ 1);
         __syncthreads();
     }
-    // C/D map: column = lane & 31 (j), row = (i & 3) + 8 (i >> 2) + 4 (lane >> 5) (m)
+    // column = lane & 31 (j), row = mfma32_row (m)
     const int j = j0 + 32 * (wave & 1) + (lane & 31);
     if (j >= J) return;
     float* o = out + (size_t)split * M * J;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-        const int m = m0 + 32 * (wave >> 1) + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
+        const int m = m0 + 32 * (wave >> 1) + mfma32_row(i, lane >> 5);
         if (m < M) o[(size_t)m * J + j] = acc[i];
     }
 }
@@ -325,13 +263,13 @@ __global__ __launch_bounds__(kThreads) void neck_gemm_dw_reduce_kernel(const flo
 using namespace mvsdet;
 
 extern "C" size_t mvsdet_gemm_split_weight_bytes(int M, int K) {
-    if (M <= 0 || K <= 0 || M % kNgBM || K % kNgBK) return 0;
+    if (M <= 0 || K <= 0 || M % kGemmBM || K % kGemmBK) return 0;
     return (size_t)(M / 32) * (K / 16) * 2 * 64 * 16;
 }
 
 extern "C" int mvsdet_gemm_split_weight(const float* wmat, void* wsplit, int M, int K, mvsdet_stream_t stream) {
     MVS_REQUIRE(wmat && wsplit, "gemm_split_weight: NULL pointer");
-    MVS_REQUIRE(M > 0 && K > 0 && M % kNgBM == 0 && K % kNgBK == 0, "gemm_split_weight: M=%d must be a multiple of %d, K=%d of %d", M, kNgBM, K, kNgBK);
+    MVS_REQUIRE(M > 0 && K > 0 && M % kGemmBM == 0 && K % kGemmBK == 0, "gemm_split_weight: M=%d must be a multiple of %d, K=%d of %d", M, kGemmBM, K, kGemmBK);
     MVS_REQUIRE(((uintptr_t)wsplit & 15u) == 0, "gemm_split_weight: wsplit must be 16-byte aligned");
     const size_t units = (size_t)(M / 32) * (K / 16) * 64;
     hipLaunchKernelGGL(gemm_split_weight_kernel, dim3((unsigned)((units + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
@@ -344,9 +282,9 @@ static int neck_gemm_check(const char* name, const void* x, const void* ws, cons
                            int D, int H, int W) {
     MVS_REQUIRE(x && ws && bias && out, "%s: NULL pointer", name);
     MVS_REQUIRE(N > 0 && N <= 65535 && D > 0 && H > 0 && W > 0, "%s: bad shape N=%d D=%d H=%d W=%d", name, N, D, H, W);
-    MVS_REQUIRE(K > 0 && K % kNgBK == 0 && M > 0 && M % kNgBM == 0, "%s: Cin=%d must be a multiple of %d and the row count %d of %d", name, K,
-                kNgBK, M, kNgBM);
-    MVS_REQUIRE(M / kNgBM <= 65535, "%s: too many rows", name);
+    MVS_REQUIRE(K > 0 && K % kGemmBK == 0 && M > 0 && M % kGemmBM == 0, "%s: Cin=%d must be a multiple of %d and the row count %d of %d", name, K,
+                kGemmBK, M, kGemmBM);
+    MVS_REQUIRE(M / kGemmBM <= 65535, "%s: too many rows", name);
     MVS_REQUIRE(((uintptr_t)ws & 15u) == 0 && ((uintptr_t)out & 7u) == 0, "%s: wsplit must be 16-byte, out 8-byte aligned", name);
     MVS_REQUIRE((long long)D * H * W < INT32_MAX / 8, "%s: volume too large", name);
     return MVSDET_OK;
@@ -357,7 +295,7 @@ extern "C" int mvsdet_conv3d_k1_s2_bf16x3(const float* x, const void* wsplit, co
     if (int rc = neck_gemm_check("conv3d_k1_s2_bf16x3", x, wsplit, bias, out, N, Cin, Cout, D, H, W)) return rc;
     MVS_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, "conv3d_k1_s2_bf16x3: D, H, W must be even");
     const int V = (D / 2) * (H / 2) * (W / 2);
-    dim3 grid((unsigned)((V + kNgBN - 1) / kNgBN), (unsigned)(Cout / kNgBM), (unsigned)N);
+    dim3 grid((unsigned)((V + kGemmBN - 1) / kGemmBN), (unsigned)(Cout / kGemmBM), (unsigned)N);
     hipLaunchKernelGGL(neck_gemm_bf16x3_kernel<0>, grid, dim3(kThreads), 0, (hipStream_t)stream, x, static_cast<const uint4*>(wsplit), bias,
                        out, Cout, Cin, D, H, W, relu);
     MVS_LAUNCH_CHECK("conv3d_k1_s2_bf16x3");
@@ -369,7 +307,7 @@ extern "C" int mvsdet_convT3d_k2_s2_bf16x3(const float* x, const void* wsplit, c
     MVS_REQUIRE(Cout > 0 && Cout <= INT32_MAX / 8, "convT3d_k2_s2_bf16x3: bad Cout");
     if (int rc = neck_gemm_check("convT3d_k2_s2_bf16x3", x, wsplit, bias, out, N, Cin, 8 * Cout, D, H, W)) return rc;
     const int V = D * H * W;
-    dim3 grid((unsigned)((V + kNgBN - 1) / kNgBN), (unsigned)(8 * Cout / kNgBM), (unsigned)N);
+    dim3 grid((unsigned)((V + kGemmBN - 1) / kGemmBN), (unsigned)(8 * Cout / kGemmBM), (unsigned)N);
     hipLaunchKernelGGL(neck_gemm_bf16x3_kernel<1>, grid, dim3(kThreads), 0, (hipStream_t)stream, x, static_cast<const uint4*>(wsplit), bias,
                        out, 8 * Cout, Cin, D, H, W, relu);
     MVS_LAUNCH_CHECK("convT3d_k2_s2_bf16x3");
@@ -386,7 +324,7 @@ extern "C" int mvsdet_conv3d_k1_s2_dx_bf16x3(const float* grad_out, const void* 
     MVS_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, "conv3d_k1_s2_dx_bf16x3: D, H, W must be even");
     MVS_REQUIRE(((uintptr_t)grad_out & 3u) == 0 && ((uintptr_t)grad_x & 3u) == 0, "conv3d_k1_s2_dx_bf16x3: tensors must be 4-byte aligned");
     const int V = (D / 2) * (H / 2) * (W / 2);
-    dim3 grid((unsigned)((V + kNgBN - 1) / kNgBN), (unsigned)(Cin / kNgBM), (unsigned)N);
+    dim3 grid((unsigned)((V + kGemmBN - 1) / kGemmBN), (unsigned)(Cin / kGemmBM), (unsigned)N);
     hipLaunchKernelGGL(neck_gemm_bf16x3_kernel<2>, grid, dim3(kThreads), 0, (hipStream_t)stream, grad_out, static_cast<const uint4*>(wsplit),
                        nullptr, grad_x, Cin, Cout, D, H, W, 0);
     MVS_LAUNCH_CHECK("conv3d_k1_s2_dx_bf16x3");
@@ -400,7 +338,7 @@ extern "C" int mvsdet_convT3d_k2_s2_dx_bf16x3(const float* grad_out, const void*
     if (int rc = neck_gemm_check("convT3d_k2_s2_dx_bf16x3", grad_out, wsplit, one, grad_x, N, 8 * Cout, Cin, D, H, W)) return rc;
     MVS_REQUIRE((long long)8 * D * H * W < INT32_MAX / 8, "convT3d_k2_s2_dx_bf16x3: volume too large");
     const int V = D * H * W;
-    dim3 grid((unsigned)((V + kNgBN - 1) / kNgBN), (unsigned)(Cin / kNgBM), (unsigned)N);
+    dim3 grid((unsigned)((V + kGemmBN - 1) / kGemmBN), (unsigned)(Cin / kGemmBM), (unsigned)N);
     hipLaunchKernelGGL(neck_gemm_bf16x3_kernel<3>, grid, dim3(kThreads), 0, (hipStream_t)stream, grad_out, static_cast<const uint4*>(wsplit),
                        nullptr, grad_x, Cin, 8 * Cout, D, H, W, 0);
     MVS_LAUNCH_CHECK("convT3d_k2_s2_dx_bf16x3");

@@ -434,3 +434,55 @@ def test_conv3d_k3_dw_bf16x3_needs_rows_of_whole_float4(gpu):
     x = torch.randn(1, 8, 2, 4, 18, device=gpu)
     with pytest.raises(ValueError, match="multiple of 4"):
         ops.conv3d_k3_dw(x, x.clone(), 0, 1, True)
+
+
+def bf16x3_edge_vector():
+    """64 floats at the edges of the fp32 -> (hi, mid) cut: signed zeros and ones, the ties of the first and of the second rounding,
+    the carry into the exponent, the last float whose bf16 rounding is finite and the next one, FLT_MAX, tiny normals, two
+    subnormals, infinities and a NaN; the remaining slots from the LCG."""
+    import os
+    import sys
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    if golden not in sys.path:
+        sys.path.insert(0, golden)
+    from lcg import lcg_uniform
+    bits = lambda b: np.array([b], dtype=np.uint32).view(np.float32)[0]
+    fmax, fmin = np.finfo(np.float32).max, np.finfo(np.float32).tiny
+    head = [0.0, -0.0, 1.0, -1.0, 1 + 2.0 ** -8, 1 + 3 * 2.0 ** -8, 1 + 2.0 ** -8 + 2.0 ** -16, 1 + 2.0 ** -8 + 3 * 2.0 ** -16,
+            float.fromhex("0x1.fep+0"), float.fromhex("0x1.ffp+0"), bits(0x7f7f7fff), bits(0x7f7f8000), fmax, -fmax, 1e-30, -1e-30,
+            fmin, -fmin, bits(0x00000001), bits(0x007fffff), np.inf, -np.inf, np.nan]
+    v = np.concatenate([np.array(head, dtype=np.float32), lcg_uniform(64 - len(head), 950)]).astype(np.float32)
+    assert v.shape == (64,) and v[4] != 1.0 and v[6] != v[4] and v[10] < v[11] < fmax
+    return v
+
+
+def test_the_cut_at_its_edges_in_scl_pack_and_gemm_split_weight(gpu):
+    """csrc/mfma.h's cut, through the two kernels that store its pieces as they are: every finite, normal or zero entry of the edge
+    vector is cut exactly as ops.split_bf16 cuts it (both pieces, bit for bit), an infinity keeps its sign in hi, a NaN stays one."""
+    from mvsdet_amd import ops
+    v = torch.from_numpy(bf16x3_edge_vector())
+    exact = (torch.isfinite(v) & ((v == 0) | (v.abs() >= float(np.finfo(np.float32).tiny))))
+    assert int(exact.sum()) == 64 - 5
+    bits = lambda t: t.contiguous().view(torch.int16)
+
+    def check(hi, mid, src):
+        eh, em = ops.split_bf16(src)
+        ok = exact.view(-1)[torch.arange(src.numel()) % 64].view(src.shape)     # both layouts repeat the vector every 64 elements
+        assert torch.equal(bits(hi)[ok], bits(eh)[ok]) and torch.equal(bits(mid)[ok], bits(em)[ok])
+        inf = torch.isinf(src)
+        assert int(inf.sum()) > 0 and torch.equal(hi.float()[inf], src[inf])
+        nan = torch.isnan(src)
+        assert int(nan.sum()) > 0 and bool(torch.isnan(hi.float()[nan]).all()) and bool(torch.isnan(mid.float()[nan]).all())
+
+    x = v.view(1, 1, 2, 4, 8).permute(0, 4, 1, 2, 3).contiguous()            # (1, 8, 1, 2, 4): element (c, h, w) = v[8 (4 h + w) + c]
+    hi, mid = ops.scl_pack(x.to(gpu)).pieces()
+    check(hi.cpu().permute(0, 2, 3, 4, 1), mid.cpu().permute(0, 2, 3, 4, 1), x.permute(0, 2, 3, 4, 1))
+    wm = v.repeat(64).view(128, 32)
+    got = ops.gemm_split_weight(wm.to(gpu)).cpu().view(4, 2, 2, 2, 32, 8)      # [row tile][k16][piece][k-group][row][8]: lane = 32 (k-group) + row
+    src = wm.view(4, 32, 2, 2, 8).permute(0, 2, 3, 1, 4)                       # the same order from the matrix
+    eh, em = ops.split_bf16(src)
+    okm = exact.repeat(64).view(128, 32).view(4, 32, 2, 2, 8).permute(0, 2, 3, 1, 4)
+    assert torch.equal(bits(got[:, :, 0])[okm], bits(eh)[okm]) and torch.equal(bits(got[:, :, 1])[okm], bits(em)[okm])
+    inf, nan = torch.isinf(src), torch.isnan(src)
+    assert torch.equal(got[:, :, 0].float()[inf], src[inf])
+    assert bool(torch.isnan(got[:, :, 0].float()[nan]).all()) and bool(torch.isnan(got[:, :, 1].float()[nan]).all())

@@ -3,7 +3,7 @@ Makefile's flags + --cuda-device-only -S) and compares, kernel by kernel, the in
 (registers, LDS, scratch), with branch labels renumbered and the kernel's own symbol masked -- so that a refactor that only removes
 kernels or drops a template parameter shows as "same" for every kernel it keeps.  No GPU needed.
 
-    python tools/isa_compare.py --before <parent checkout>/mvsdet_amd/csrc [--after mvsdet_amd/csrc] [--out profiles/NAME.txt]
+    python tools/isa_compare.py --before <parent checkout>/mvsdet_amd/csrc [--after mvsdet_amd/csrc] [--out profiles/NAME.txt] [--brief]
 
 One line per kernel: name, VGPRs (arch + acc), SGPRs, LDS and scratch bytes, instructions, hash before, hash after, verdict.
 Exit status 1 if a kernel present on both sides differs."""
@@ -28,7 +28,7 @@ DROPPED_PARAMS = {}
 # Template parameters that a kernel has gained at its END in --after: the values that stand for the --before kernel.  An --after
 # instantiation with exactly these trailing values is compared under its --before name; any other is listed as ADDED.
 # {"mvsdet::plane_sweep_variance_kernel": ["0", "0"]} for the store / load policies (profiles/r10_sweep_store_policy_isa.txt).
-ADDED_PARAMS = {"mvsdet::plane_sweep_variance_kernel": ["0", "0"], "mvsdet::store_pattern_kernel": ["0"]}
+ADDED_PARAMS = {}
 
 
 def assemble(src: str, out: str) -> None:
@@ -133,6 +133,7 @@ def main() -> int:
     ap.add_argument("--out", default=None, help="also write the table to this file")
     ap.add_argument("--jobs", type=int, default=4)
     ap.add_argument("--asm-dir", default=None, help="keep the assembly here (before_*.s, after_*.s) and reuse what is already there")
+    ap.add_argument("--brief", action="store_true", help="list only the kernels that are not the same; each file's line counts the rest")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmpdir:
         tmp = os.path.abspath(a.asm_dir) if a.asm_dir else tmpdir   # assemble() runs the compiler inside the source directory
@@ -142,7 +143,8 @@ def main() -> int:
     rows, same, differ, removed, added = [], 0, 0, 0, 0
     for f in sorted(set(before) | set(after)):
         kb, ka = before.get(f, {}), after.get(f, {})
-        rows.append(f"## {f}: {len(kb)} kernels before, {len(ka)} after")
+        unlisted = sum(1 for name in set(kb) & set(ka) if kb[name] == ka[name]) if a.brief else 0
+        rows.append(f"## {f}: {len(kb)} kernels before, {len(ka)} after" + (f", {unlisted} of them same and not listed" if a.brief else ""))
         for name in sorted(set(kb) | set(ka)):
             b, k = kb.get(name), ka.get(name)
             fig, n = (k or b)[0], (k or b)[2]
@@ -153,6 +155,8 @@ def main() -> int:
             else:
                 removed, added = removed + (k is None), added + (b is None)
                 verdict = "removed" if k is None else "ADDED"
+            if a.brief and verdict == "same":
+                continue
             rows.append(f"{name} | {' | '.join(fig)} | {n} instructions | {b[1] if b else '-':16} | {k[1] if k else '-':16} | {verdict}")
     rows.append(f"## total: {same} same, {differ} different, {removed} removed, {added} added")
     text = "\n".join(["# kernel | registers | LDS | scratch | instructions | hash before | hash after | verdict (tools/isa_compare.py)"] + rows) + "\n"
