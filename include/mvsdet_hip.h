@@ -61,6 +61,8 @@ const char* mvsdet_last_error(void);
  *                   loads; MVSDET_SWEEP_BOX_LOAD; compiled and refused like "sweep_store"
  *   "depthprob_ahead"  1 (default) | 0  mvsdet_depth_prob_topk[_strided]_f32 requests every input of a pixel before its first
  *                   store (D <= 64), or runs its last pass eight planes ahead (D > 64); 0 = plane by plane, behind the stores
+ *   "pixel_dsplit"  0 (default: by the grid size) | n > 0   the per-pixel form's blocks walk ceil(D / min(n, D)) consecutive depth hypotheses
+ *                   each, the forwards at most 4 (mvsdet_pixel_form_blocking shows the outcome); MVSDET_PIXEL_DSPLIT
  *   "sweep_dsplit", "sweep_groups", "bwd_groups", "conv_*"   schedules of the sweep's plane split, of the bf16x3
  *                   convolutions and of the fp16 + MX convolution ("conv_mx_th") (csrc/common.h: struct Options)
  * "sweep_tw" decides the layout of the sweep geometry: consume one (mvsdet_plane_sweep_variance_tabled_f32) under the
@@ -245,6 +247,15 @@ int mvsdet_plane_sweep_groupcorr_bwd_packed_f32(const float* packed, const int64
                                                 const int64_t* depth_strides, const float* grad, float* gfeat, void* workspace,
                                                 size_t workspace_bytes, int N, int K, int C, int G, int D, int H, int W,
                                                 mvsdet_stream_t stream);
+/* HOST query, nothing is launched: how the per-pixel form above (variance, compatibility warp's backward, group correlation and its
+ * backward) cuts a problem into blocks under the options in force -- the very function the launches call.  G = 0: variance / warp;
+ * G > 0: group correlation with G groups.  backward != 0: the backward launch.
+ *   units        what blocks are dealt over: 32-channel slabs, or for group widths that are multiples of 32 the G groups
+ *   xcd_parts    1, or 8 / units where an XCD owns a unit (forward, units in {1, 2, 4}, "sweep_xcd" != 0)
+ *   d_per_block  consecutive depth hypotheses a block walks (the forward: at most 4); the last block of a (view, tile, unit) may walk fewer
+ * Shapes and group widths are checked as by the entry points (MVSDET_ERR_INVALID_ARG).  For tests and tools. */
+int mvsdet_pixel_form_blocking(int N, int C, int G, int D, int H, int W, int backward, int* units /*HOST*/, int* xcd_parts /*HOST*/,
+                               int* d_per_block /*HOST*/);
 
 /* ---------------------------------------------------------------------------------------------
  * a5-a7  depth probability, top-k plane selection, depth expectation --

@@ -181,6 +181,7 @@ SIGNATURES = {
     "mvsdet_plane_sweep_variance_pixel_bwd_packed_f32": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_plane_sweep_groupcorr_packed_f32": [_vp, _vp, _vp, _vp, _i64p, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_plane_sweep_groupcorr_bwd_packed_f32": [_vp, _vp, _vp, _vp, _i64p, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_pixel_form_blocking": [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
 }
 _RESTYPE = {"mvsdet_last_error": ctypes.c_char_p, "mvsdet_conv3d_k3_bf16x3_stats_parts": ctypes.c_size_t, "mvsdet_convT3d_k3_s2_bf16x3_stats_parts": ctypes.c_size_t, "mvsdet_gemm_split_weight_bytes": ctypes.c_size_t, "mvsdet_neck_gemm_dw_partial_bytes": ctypes.c_size_t, "mvsdet_scl_bytes": ctypes.c_size_t, "mvsdet_pscl_bytes": ctypes.c_size_t,
             "mvsdet_split_conv_weight_bytes": ctypes.c_size_t, "mvsdet_packed_bytes": ctypes.c_size_t,
@@ -283,3 +284,12 @@ def sweep_tile_shape(K: int, D: int, H: int, W: int):
     tw, th, cap = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
     check(load().mvsdet_plane_sweep_tile_shape(K, D, H, W, ctypes.byref(tw), ctypes.byref(th), ctypes.byref(cap)), "sweep_tile_shape")
     return tw.value, th.value, cap.value
+
+
+def pixel_form_blocking(N: int, C: int, G: int, D: int, H: int, W: int, backward: bool = False):
+    """(units, xcd_parts, d_per_block) of a launch of the per-pixel form under the options in force (mvsdet_pixel_form_blocking);
+    G = 0: variance / compatibility warp, G > 0: group correlation with G groups."""
+    u, parts, dpb = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    check(load().mvsdet_pixel_form_blocking(N, C, G, D, H, W, int(bool(backward)), ctypes.byref(u), ctypes.byref(parts), ctypes.byref(dpb)),
+          "pixel_form_blocking")
+    return u.value, parts.value, dpb.value

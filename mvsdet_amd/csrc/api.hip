@@ -35,7 +35,8 @@ Options& options() {
                         env_int("MVSDET_CONV_NSPLIT", 0), env_int("MVSDET_CONV_XCD", 1), env_int("MVSDET_CONV_SPLIT_BLOCKS", 768),
                         env_int("MVSDET_CONV_SPLIT_MIN_GROUPS", 2), env_int("MVSDET_BWD_GROUPS", 0), env_int("MVSDET_SWEEP_INSIDE", 1), env_int("MVSDET_CONV_MX_TH", 0),
                         env_int("MVSDET_SWEEP_POOL", 1), env_int("MVSDET_DEPTHPROB_AHEAD", 1),
-                        env_compiled("MVSDET_SWEEP_STORE", kSweepStoreAuto, sweep_store_compiled), env_compiled("MVSDET_SWEEP_BOX_LOAD", 0, sweep_box_load_compiled)};
+                        env_compiled("MVSDET_SWEEP_STORE", kSweepStoreAuto, sweep_store_compiled), env_compiled("MVSDET_SWEEP_BOX_LOAD", 0, sweep_box_load_compiled),
+                        env_int("MVSDET_PIXEL_DSPLIT", 0)};
     return o;
 }
 
@@ -46,6 +47,7 @@ static int* option_slot(const char* name) {
     if (!strcmp(name, "sweep_boxcap")) return &o.sweep_boxcap;
     if (!strcmp(name, "sweep_xcd")) return &o.sweep_xcd;
     if (!strcmp(name, "sweep_dsplit")) return &o.sweep_dsplit;
+    if (!strcmp(name, "pixel_dsplit")) return &o.pixel_dsplit;
     if (!strcmp(name, "sweep_groups")) return &o.sweep_groups;
     if (!strcmp(name, "sweep_inside")) return &o.sweep_inside;
     if (!strcmp(name, "sweep_pool")) return &o.sweep_pool;

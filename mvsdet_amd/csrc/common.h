@@ -43,6 +43,8 @@ struct Options {
                        // The store-pattern probe writes under the same policy.  Same bits under every value.
     int sweep_box_load; // cache policy of the footprint boxes' LDS-DMA and of a block's reference-feature loads: 0 (default) = default policy,
                        // 1 = non-temporal (MVS_SWEEP_LOAD_LIST).  Same bits.
+    int pixel_dsplit;  // the per-pixel form (pixel_form.h: pixel_blocking): 0 = by the grid size; n > 0: every block walks ceil(D / min(n, D))
+                       // consecutive hypotheses, the forward at most 4.  The forwards' bits do not depend on it (tests, A/B runs).
 };
 Options& options();
 

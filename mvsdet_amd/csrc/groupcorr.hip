@@ -221,12 +221,6 @@ __global__ __launch_bounds__(kThreads) void groupcorr_bwd_kernel(const float* __
     pixel_bwd_ref_flush(b, s_ref, gpacked, HW);
 }
 
-bool gc_width_ok(int C, int G) {
-    if (G < 1 || C < 1 || C % G != 0) return false;
-    const int cg = C / G;
-    return cg == 4 || cg == 8 || cg == 16 || cg % 32 == 0;
-}
-
 int gc_check(const char* name, const void* nbr, const void* proj, const float* depth, const int64_t* ds, int N, int K, int C, int G, int D,
              int H, int W) {
     MVS_REQUIRE(nbr && proj && depth && ds, "%s: NULL neighbour ids / proj / depth / depth_strides", name);
@@ -253,20 +247,18 @@ extern "C" int mvsdet_plane_sweep_groupcorr_packed_f32(const float* packed, cons
     const int S = num_slabs(C), HW = H * W, cg = C / G;
     const int mode = cg == 4 ? kCg4 : (cg == 8 ? kCg8 : (cg == 16 ? kCg16 : kCgSlabs));
     const int SG = mode == kCgSlabs ? cg / kSlab : 1;
-    const int U = mode == kCgSlabs ? G : S;   // units: a group's slabs, or one slab of whole groups
-    const int tiles = (HW + kTilePix - 1) / kTilePix;
-    const int n_bt = N * tiles;
-    const PixelGrid pg = pixel_grid(n_bt, U);   // an XCD owns a unit
-    const int dpb = pixel_d_per_block(pg.grid_x, D, 4);
+    const PixelBlocking pb = pixel_blocking(N, C, G, D, H, W, false);   // an XCD owns a unit
+    const int U = pb.units;   // units: a group's slabs (mode kCgSlabs: G of them), or one slab of whole groups (S)
+    const int tiles = pb.tiles, n_bt = pb.n_bt, dpb = pb.d_per_block;
     MVS_REQUIRE((D + dpb - 1) / dpb <= 65535, "%s: grid too large", name);
     const int vec = (HW % 4 == 0) && ((uintptr_t)out % 16 == 0);
     const float inv_cg = 1.0f / (float)cg;
-    dim3 grid((unsigned)pg.grid_x, (unsigned)((D + dpb - 1) / dpb));
+    dim3 grid((unsigned)pb.grid_x, (unsigned)((D + dpb - 1) / dpb));
     hipStream_t st = (hipStream_t)stream;
     const long long ds_n = depth_strides[0], ds_d = depth_strides[1], ds_p = depth_strides[2];
 #define MVS_GC_FWD(KV, MV)                                                                                                            \
     hipLaunchKernelGGL((plane_sweep_groupcorr_kernel<KV, MV>), grid, dim3(kThreads), 0, st, packed, nbr, proj, depth, ds_n, ds_d, ds_p, \
-                       out, N, G, S, SG, U, D, H, W, tiles, dpb, n_bt, pg.xcd_parts, inv_cg, vec)
+                       out, N, G, S, SG, U, D, H, W, tiles, dpb, n_bt, pb.xcd_parts, inv_cg, vec)
 #define MVS_GC_FWD_K(KV)                              \
     case KV:                                          \
         if (mode == kCg4) MVS_GC_FWD(KV, kCg4);       \
@@ -296,15 +288,14 @@ extern "C" int mvsdet_plane_sweep_groupcorr_bwd_packed_f32(const float* packed, 
     hipStream_t st = (hipStream_t)stream;
     if (int rc = pixel_bwd_prologue(name, workspace, workspace_bytes, N, C, H, W, st)) return rc;
     float* gpacked = static_cast<float*>(workspace);
-    const int S = num_slabs(C), HW = H * W, cg = C / G;
+    const int S = num_slabs(C), cg = C / G;
     const int SG = cg >= kSlab ? cg / kSlab : 1, ngl = cg >= kSlab ? 1 : kSlab / cg;
     const int lg_shift = cg == 4 ? 2 : (cg == 8 ? 3 : (cg == 16 ? 4 : 5));
-    const int tiles = (HW + kTilePix - 1) / kTilePix;
-    const long long nblocks = (long long)N * tiles * S;
-    const int dpb = pixel_d_per_block(nblocks, D, 0);
+    const PixelBlocking pb = pixel_blocking(N, C, G, D, H, W, true);
+    const int tiles = pb.tiles, dpb = pb.d_per_block;
     const float inv_cg = 1.0f / (float)cg;
     const long long ds_n = depth_strides[0], ds_d = depth_strides[1], ds_p = depth_strides[2];
-    dim3 grid((unsigned)nblocks, (unsigned)((D + dpb - 1) / dpb));
+    dim3 grid((unsigned)pb.grid_x, (unsigned)((D + dpb - 1) / dpb));
 #define MVS_GC_BWD(KV)                                                                                                              \
     case KV:                                                                                                                        \
         hipLaunchKernelGGL((groupcorr_bwd_kernel<KV>), grid, dim3(kThreads), 0, st, packed, nbr, proj, depth, ds_n, ds_d, ds_p, grad, \

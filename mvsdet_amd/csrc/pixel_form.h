@@ -284,10 +284,12 @@ __device__ __forceinline__ void pixel_bwd_ref_flush(const PixelBwdBlock& b, cons
 // ------------------------------------------------------------------------------------------------------------------- host
 // (static: pack.h's kernels are each translation unit's own)
 
-// hypotheses per block: all of them unless the grid would be too small to fill the chip
+// hypotheses per block: all of them unless the grid would be too small to fill the chip; option "pixel_dsplit" n > 0 sets the split
 static int pixel_d_per_block(long long nblocks, int D, int at_most) {
     int dsplit = 1;
-    while (nblocks * dsplit < 2048 && dsplit < D) dsplit *= 2;
+    if (options().pixel_dsplit > 0) dsplit = options().pixel_dsplit;
+    else
+        while (nblocks * dsplit < 2048 && dsplit < D) dsplit *= 2;
     dsplit = std::min(dsplit, D);
     int dpb = (D + dsplit - 1) / dsplit;
     if (at_most > 0) dpb = std::min(dpb, at_most);
@@ -319,6 +321,43 @@ static PixelGrid pixel_grid(int n_bt, int U) {
         pg.grid_x = 8LL * ((n_bt + pg.xcd_parts - 1) / pg.xcd_parts);
     }
     return pg;
+}
+
+// the group widths the correlation is compiled for
+static bool gc_width_ok(int C, int G) {
+    if (G < 1 || C < 1 || C % G != 0) return false;
+    const int cg = C / G;
+    return cg == 4 || cg == 8 || cg == 16 || cg % 32 == 0;
+}
+
+// How a launch of the per-pixel form is cut into blocks: the ONE place every entry point and the query
+// mvsdet_pixel_form_blocking take it from.  G = 0: variance / compatibility warp (a unit is a slab); G > 0: group correlation
+// with G groups of a checked width (a unit is a slab of whole groups, or the slabs of one group).
+//   forward:  grid (grid_x, ceil(D / d_per_block)), units dealt by pixel_block with xcd_parts; at most 4 hypotheses per block
+//   backward: grid (N * tiles * S, ceil(D / d_per_block)), a unit is a slab (id % S), no XCD parts; no cap
+struct PixelBlocking {
+    int tiles, n_bt;    // 128-pixel tiles of a map; (view, tile) pairs
+    int units, xcd_parts;
+    long long grid_x;
+    int d_per_block;
+};
+static PixelBlocking pixel_blocking(int N, int C, int G, int D, int H, int W, bool backward) {
+    PixelBlocking pb;
+    const int S = num_slabs(C);
+    pb.tiles = (H * W + kTilePix - 1) / kTilePix;
+    pb.n_bt = N * pb.tiles;
+    if (backward) {
+        pb.units = S;
+        pb.xcd_parts = 1;
+        pb.grid_x = (long long)pb.n_bt * S;
+    } else {
+        pb.units = (G > 0 && (C / G) % kSlab == 0) ? G : S;
+        const PixelGrid pg = pixel_grid(pb.n_bt, pb.units);   // an XCD owns a unit
+        pb.xcd_parts = pg.xcd_parts;
+        pb.grid_x = pg.grid_x;
+    }
+    pb.d_per_block = pixel_d_per_block(pb.grid_x, D, backward ? 0 : 4);
+    return pb;
 }
 
 // The backward's start: the workspace holds the packed gradient map, zeroed here for the atomics.

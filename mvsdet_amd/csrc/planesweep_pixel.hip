@@ -221,10 +221,9 @@ int pixel_bwd_launch(const char* name, const float* packed, const int64_t* nbr, 
     if (int rc = pixel_bwd_prologue(name, workspace, workspace_bytes, N, C, H, W, stream)) return rc;
     float* gpacked = static_cast<float*>(workspace);
     const int S = num_slabs(C);
-    const int tiles = (H * W + kTilePix - 1) / kTilePix;
-    const long long nblocks = (long long)N * tiles * S;
-    const int dpb = pixel_d_per_block(nblocks, D, 0);
-    dim3 grid((unsigned)nblocks, (unsigned)((D + dpb - 1) / dpb));
+    const PixelBlocking pb = pixel_blocking(N, C, 0, D, H, W, true);
+    const int tiles = pb.tiles, dpb = pb.d_per_block;
+    dim3 grid((unsigned)pb.grid_x, (unsigned)((D + dpb - 1) / dpb));
 #define MVS_PIXEL_BWD(KV)                                                                                                       \
     case KV:                                                                                                                    \
         hipLaunchKernelGGL((sweep_pixel_bwd_kernel<KV, WARP>), grid, dim3(kThreads), 0, stream, packed, nbr, proj, depth, g, gpacked, \
@@ -269,22 +268,20 @@ extern "C" int mvsdet_plane_sweep_variance_pixel_packed_f32(const float* packed,
     MVS_REQUIRE(K == 0 || (nbr && proj && depth), "%s: NULL neighbour ids / proj / depth with K=%d", name, K);
     if (int rc = pixel_shape_check(name, N, K, 0, C, D, H, W)) return rc;
     const int S = num_slabs(C), HW = H * W;
-    const int tiles = (HW + kTilePix - 1) / kTilePix;
-    const int n_bt = N * tiles;
-    const PixelGrid pg = pixel_grid(n_bt, S);   // an XCD owns a slab
-    const int dpb = pixel_d_per_block(pg.grid_x, D, 4);
+    const PixelBlocking pb = pixel_blocking(N, C, 0, D, H, W, false);   // an XCD owns a slab
+    const int tiles = pb.tiles, n_bt = pb.n_bt, dpb = pb.d_per_block;
     MVS_REQUIRE((D + dpb - 1) / dpb <= 65535, "%s: grid too large", name);
     const bool fast = (C % kSlab == 0) && (HW % 4 == 0) && ((uintptr_t)var % 16 == 0);
-    dim3 grid((unsigned)pg.grid_x, (unsigned)((D + dpb - 1) / dpb));
+    dim3 grid((unsigned)pb.grid_x, (unsigned)((D + dpb - 1) / dpb));
     hipStream_t st = (hipStream_t)stream;
 #define MVS_PIXEL_FWD(KV)                                                                                                          \
     case KV:                                                                                                                       \
         if (fast)                                                                                                                  \
             hipLaunchKernelGGL((plane_sweep_variance_pixel_kernel<KV, true>), grid, dim3(kThreads), 0, st, packed, nbr, proj, depth, var, \
-                               N, C, S, D, H, W, tiles, dpb, n_bt, pg.xcd_parts);                                                     \
+                               N, C, S, D, H, W, tiles, dpb, n_bt, pb.xcd_parts);                                                    \
         else                                                                                                                       \
             hipLaunchKernelGGL((plane_sweep_variance_pixel_kernel<KV, false>), grid, dim3(kThreads), 0, st, packed, nbr, proj, depth, var, \
-                               N, C, S, D, H, W, tiles, dpb, n_bt, pg.xcd_parts);                                                     \
+                               N, C, S, D, H, W, tiles, dpb, n_bt, pb.xcd_parts);                                                    \
         break;
     switch (K) {
         MVS_PIXEL_FWD(0)
@@ -295,6 +292,23 @@ extern "C" int mvsdet_plane_sweep_variance_pixel_packed_f32(const float* packed,
     }
 #undef MVS_PIXEL_FWD
     MVS_LAUNCH_CHECK(name);
+    return MVSDET_OK;
+}
+
+// HOST query: how the per-pixel form cuts this problem into blocks under the options in force -- pixel_blocking, what the launches
+// themselves call.  Nothing is launched.
+extern "C" int mvsdet_pixel_form_blocking(int N, int C, int G, int D, int H, int W, int backward, int* units, int* xcd_parts,
+                                          int* d_per_block) {
+    const char* name = "pixel_form_blocking";
+    MVS_REQUIRE(units && xcd_parts && d_per_block, "%s: NULL pointer", name);
+    if (int rc = pixel_shape_check(name, N, 1, 0, C, D, H, W)) return rc;
+    MVS_REQUIRE(G >= 0, "%s: G=%d is negative (0: variance / warp, G > 0: group correlation)", name, G);
+    MVS_REQUIRE(G == 0 || gc_width_ok(C, G),
+                "%s: C=%d G=%d: the group width C/G must divide C and be 4, 8, 16 or a multiple of 32", name, C, G);
+    const PixelBlocking pb = pixel_blocking(N, C, G, D, H, W, backward != 0);
+    *units = pb.units;
+    *xcd_parts = pb.xcd_parts;
+    *d_per_block = pb.d_per_block;
     return MVSDET_OK;
 }
 

@@ -16,6 +16,11 @@ def sample_grid(proj, depth, H, W):
     """fp32 sampling grid (B, D*H, W, 2) and the denominators Z (B, D, H*W) of module.py:136.  proj (B,4,4) =
     src_proj @ inverse(ref_proj); depth (B,D,H,W)."""
     B, D = depth.shape[:2]
+    # Inputs on a GPU (a test whose volume is too large for the CPU): the grid is still built HERE, on the CPU, and handed to the
+    # inputs' device -- it is small (B D H W 2), and it is the arithmetic fixture G22 pins.  torch's GPU kernels do not repeat it:
+    # a division by a Python scalar (:137-138) is a multiplication by its reciprocal there, one rounding away in gx and gy.
+    dev = depth.device
+    proj, depth = proj.cpu(), depth.cpu()
     with torch.no_grad():
         rot, trans = proj[:, :3, :3], proj[:, :3, 3:4]
         ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
@@ -29,7 +34,7 @@ def sample_grid(proj, depth, H, W):
         gx = xy[:, 0] / ((W - 1) / 2) - 1                                       # :137
         gy = xy[:, 1] / ((H - 1) / 2) - 1                                       # :138
         grid = torch.stack((gx, gy), dim=3).view(B, D * H, W, 2)
-    return grid, pts[:, 2]
+    return grid.to(dev), pts[:, 2].to(dev)
 
 
 def homo_warp_pixel(src_fea, proj, depth):
