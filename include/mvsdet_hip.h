@@ -856,7 +856,7 @@ int mvsdet_neck_gemm_dw_bf16x3(const float* x, const float* grad_out, float* dw,
 
 /* ---------------------------------------------------------------------------------------------
  * Level 0 of the 2-D feature pyramid in front of the sweep (mvsdet.py:374-376 `x = self.neck(x)[0]`) on the bf16 matrix cores with
- * three-term split operands (csrc/fpn.hip).  Forward only; fp32 in and out; no atomics (the same bits on every run).
+ * three-term split operands (csrc/fpn.hip; gradients: csrc/fpn_bwd.hip, below).  fp32 in and out; no atomics (the same bits on every run).
  * The module is mmdet.models.necks.FPN as shipped: in_channels=[256,512,1024,2048], out_channels=256, num_outs=4, start_level=0, no
  * add_extra_convs, no norm, no activation, upsample_cfg=dict(mode='nearest').  mmdet is not part of this tree; this is the builder's
  * reading of it:
@@ -876,6 +876,24 @@ int mvsdet_fpn_lateral_bf16x3(const float* x, const void* wsplit, const float* b
                               int Cout, int H, int W, int Ht, int Wt, mvsdet_stream_t stream);
 int mvsdet_fpn_conv3x3_bf16x3(const float* x, const void* wsplit, const float* bias, float* out, float* packed, int N, int Cin, int Cout,
                               int H, int W, mvsdet_stream_t stream);
+/* Its gradients (csrc/fpn_bwd.hip; no atomics, every sum in a fixed order: the same bits on every run).  The two input gradients are
+ * the forward entries above: gL0 = mvsdet_fpn_conv3x3_bf16x3 on the flipped, transposed weight w3'[c,o,dy,dx] = w3[o,c,2-dy,2-dx] with a
+ * zero bias, dx_i = mvsdet_fpn_lateral_bf16x3 on the split of W_i^T (C_i, Cout) with a zero bias and no top (so C_i % 128 == 0).
+ *   mvsdet_fpn_dw_bf16x3: the weight gradient of a 1x1 (taps = 1) or 3x3 padding-1 (taps = 9) convolution, bf16x3 with the PIXELS as the
+ *       reduction: dw (Cout,C,kh,kw)[o,c,dy,dx] = sum_{n,y,x} gy (N,Cout,H,W)[n,o,y,x] x (N,C,H,W)[n,c,y+dy-1,x+dx-1] (zero outside; taps = 1:
+ *       dy = dx = 1 only).  The kernel's channel rule: C % 32 == 0 (a block's 32 input channels), Cout % 128 == 0; N <= 65535,
+ *       N H W < 2^31; any H, W >= 1; 4-byte aligned contiguous tensors.  K is split over mvsdet_fpn_dw_splits(...) blocks, each writing
+ *       its fp32 partial to `workspace` (at least mvsdet_fpn_dw_workspace_bytes(...) bytes, 4-byte aligned); the same entry then adds the
+ *       splits in ascending order into dw.  Both queries are host only and return 0 for a shape the kernel refuses.
+ *   mvsdet_fpn_top_down_grad_f32: the adjoint of the top-down nearest gather: gt (N,C,Ht,Wt)[.., yt, xt] = the sum of g (N,C,H,W) over the
+ *       pixels whose source index (the float32 one above) is (yt, xt), rows ascending, then columns ascending; 1 <= Ht <= H, 1 <= Wt <= W.
+ *   mvsdet_fpn_bias_grad_f32: db (C) = the sum of g (N,C,H,W) over views and pixels. */
+int mvsdet_fpn_dw_splits(int taps, int N, int C, int Cout, int H, int W);
+size_t mvsdet_fpn_dw_workspace_bytes(int taps, int N, int C, int Cout, int H, int W);
+int mvsdet_fpn_dw_bf16x3(const float* gy, const float* x, float* dw, void* workspace, size_t workspace_bytes, int taps, int N, int C, int Cout,
+                         int H, int W, mvsdet_stream_t stream);
+int mvsdet_fpn_top_down_grad_f32(const float* g, float* gt, int N, int C, int H, int W, int Ht, int Wt, mvsdet_stream_t stream);
+int mvsdet_fpn_bias_grad_f32(const float* g, float* db, int N, int C, int H, int W, mvsdet_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Detection post-processing of the ScanNet head (NerfDetHead.predict_by_feat / _nms / aligned_3d_nms, nerfdet_head.py:301-420,
