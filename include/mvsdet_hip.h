@@ -896,6 +896,31 @@ int mvsdet_fpn_top_down_grad_f32(const float* g, float* gt, int N, int C, int H,
 int mvsdet_fpn_bias_grad_f32(const float* g, float* db, int N, int C, int H, int W, mvsdet_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The bottleneck layers of the 2-D backbone (ResNet-50, style='pytorch', norm_eval=True, frozen BatchNorm) on the bf16 matrix cores
+ * with three-term split operands (csrc/resnet.hip).  fp32 NCHW in and out; no atomics (the same bits on every run); 64-bit element
+ * offsets.  mmdet is not part of this tree; this is the builder's reading of ResNet v1.5 (`torchvision://resnet50`):
+ *     bottleneck(x; planes p, stride s): a = relu(bn1(conv1x1(x)));  b = relu(bn2(conv3x3(a, stride s, pad 1)));  c = bn3(conv1x1(b));
+ *         id = bn_d(conv1x1(x, stride s)) where the block has a downsample branch, else x;  out = relu(c + id)
+ *     layer1..4 = (3, 4, 6, 3) blocks of planes (64, 128, 256, 512), strides (1, 2, 2, 2), the first block of each with the branch;
+ *     bn(y) = y * scale + shift, scale = weight / sqrt(running_var + eps), shift = bias - running_mean * scale;  no convolution has a bias.
+ * A strided layer's output is ((H - 1) / s + 1) x ((W - 1) / s + 1).  `scale` is folded into the weight rows on the host BEFORE the
+ * split; `shift` is the kernels' per-channel addend.  The matrix handed in has ceil(Cout / 128) * 128 rows, those from Cout on zero
+ * (mvsdet_gemm_split_weight wants M % 128 == 0); nothing is stored for them.  The epilogue order is fixed: (acc + shift) + residual, then
+ * ReLU as `v < 0 ? 0 : v`, so a NaN stays a NaN (torch.relu's rule).
+ *   mvsdet_resnet_conv1x1_bf16x3: out (N,Cout,Ho,Wo) = [relu]( (W' x[.., s y, s x] + shift) [+ residual (N,Cout,Ho,Wo)] ); residual may
+ *       be NULL.  wsplit = the split of the (ceil128(Cout), Cin) matrix.  The GEMM's columns run over all views' output pixels.
+ *   mvsdet_resnet_conv3x3_bf16x3: out (N,Cout,Ho,Wo) = [relu]( conv3x3(x, stride s, zero padding 1) + shift ).  wsplit = the split of the
+ *       (ceil128(Cout), 9 Cin) tap-major matrix w'.permute(0,2,3,1).reshape(Cout, 9 Cin), zero rows appended (k = Cin (3 dy + dx) + c).
+ *       N <= 65535.
+ * Both: stride 1 or 2; Cin % 32 == 0, Cout % 32 == 0; any H, W >= 1 with H W < 2^31; N Ho Wo < 2^31; wsplit 16-byte aligned, contiguous
+ * 4-byte aligned tensors; relu 0 or 1.  Everything else is refused on the host before any launch.
+ * ------------------------------------------------------------------------------------------- */
+int mvsdet_resnet_conv1x1_bf16x3(const float* x, const void* wsplit, const float* shift, const float* residual, float* out, int N, int Cin,
+                                 int Cout, int H, int W, int stride, int relu, mvsdet_stream_t stream);
+int mvsdet_resnet_conv3x3_bf16x3(const float* x, const void* wsplit, const float* shift, float* out, int N, int Cin, int Cout, int H, int W,
+                                 int stride, int relu, mvsdet_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Detection post-processing of the ScanNet head (NerfDetHead.predict_by_feat / _nms / aligned_3d_nms, nerfdet_head.py:301-420,
  * 564-628) on the caller's stream, no host synchronisation (csrc/detect.hip).  fp32; labels int64.
  *

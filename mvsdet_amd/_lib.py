@@ -82,6 +82,8 @@ SIGNATURES = {
     "mvsdet_fpn_dw_bf16x3": [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_fpn_top_down_grad_f32": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_fpn_bias_grad_f32": [_vp, _vp, _i, _i, _i, _i, _vp],
+    "mvsdet_resnet_conv1x1_bf16x3": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_resnet_conv3x3_bf16x3": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_conv3d_k3_cout2_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "mvsdet_conv3d_k3_cout2_sum_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "mvsdet_backproject_weigh_f32": [_vp, _i64p, _vp, _vp, _vp, _vp, _i64p, _vp, _vp, _vp, _vp,

@@ -245,6 +245,8 @@ class MVSDetHotPath:
         # opt-in: an `mvsdet_amd.fpn.FPNLevel0` (mvsdet.py:374-376, `self.neck(x)[0]`) for `forward_scene_from_stages`; every other
         # entry starts from the feature map and never looks at it
         self.fpn = None
+        # opt-in: an `mvsdet_amd.resnet.ResNetStages` (the 2-D backbone's C2..C5) for `forward_scene_from_images`
+        self.backbone = None
         # opt-in: with a test_cfg (nms_pre, score_thr, iou_thr), out["detections"] = the padded boxes of predict_by_feat
         # (ops.HeadPrediction; 7-wide and class-major for a head with `arkit_head`) made from out["head"] and out["valid"] on the
         # stream the head ran on
@@ -835,6 +837,17 @@ class MVSDetHotPath:
         feature, packed = self.fpn(stages, packed=True)
         out = self._scene(feature, img_meta, kw.pop("cost_logits", None), kw.pop("geo", None), kw.pop("gt_depth", None), packed, **kw)
         out._put("feature", feature)
+        return out
+
+    def forward_scene_from_images(self, img: Tensor, img_meta: dict, **kw) -> dict:
+        """`forward_scene_from_stages` from the images (N,3,H,W): `self.backbone` (an `mvsdet_amd.resnet.ResNetStages`) makes the four
+        maps C2..C5 that `self.fpn` takes.  Keyword arguments as `forward_scene`'s.  The result gains `stages`, the tuple of maps."""
+        if self.backbone is None or self.fpn is None:
+            raise ValueError("forward_scene_from_images needs `backbone` and `fpn` (MVSDetHotPath.backbone = "
+                             "ResNetStages.from_module(model.backbone), MVSDetHotPath.fpn = FPNLevel0.from_module(model.neck))")
+        stages = self.backbone(img)
+        out = self.forward_scene_from_stages(stages, img_meta, **kw)
+        out._put("stages", stages)
         return out
 
     def _scene(self, feature: Tensor, img_meta: dict, cost_logits: Optional[Tensor], geo: Optional[SceneGeometry],

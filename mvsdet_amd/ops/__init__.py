@@ -40,6 +40,7 @@ from . import splat  # noqa: F401  (ops.splat.<name>: not re-exported)
 from . import adapter  # noqa: F401  (ops.adapter.<name>: not re-exported)
 from . import gshead  # noqa: F401  (ops.gshead.<name>: not re-exported)
 from . import fpn  # noqa: F401  (ops.fpn.<name>: not re-exported)
+from . import resnet  # noqa: F401  (ops.resnet.<name>: not re-exported)
 
 # ------------------------------------------------------------------------------------------- --amp (tools/train.py:24-28)
 # Under torch.autocast the 2-D backbone hands out float16 / bfloat16 maps.  The hot path computes in float32 -- the rule torch's own
