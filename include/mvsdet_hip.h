@@ -919,6 +919,42 @@ int mvsdet_resnet_conv1x1_bf16x3(const float* x, const void* wsplit, const float
                                  int Cout, int H, int W, int stride, int relu, mvsdet_stream_t stream);
 int mvsdet_resnet_conv3x3_bf16x3(const float* x, const void* wsplit, const float* shift, float* out, int N, int Cin, int Cout, int H, int W,
                                  int stride, int relu, mvsdet_stream_t stream);
+/* Their gradients (csrc/resnet_bwd.hip; no atomics, every sum in a fixed order: the same bits on every run).  One bottleneck, g = dL/dout:
+ *     gz = gate(g, out);  dW3 = scale3 (.) (gz b^T);  gb = gate(W3'^T gz, b);  dW2 = scale2 (.) dw3x3_s(gb, a);
+ *     ga = gate(convT3x3_s(gb; W2'), a);  dW1 = scale1 (.) (ga x^T);  dx = (W1'^T ga) + (gz | spread_s(Wd'^T gz));
+ *     dWd = scaled (.) (gz x[.., s y, s x]^T);   spread_s puts (yo, xo) at (s yo, s xo), zero elsewhere
+ * gate(v, y) = y <= 0 ? 0 : v on the SAVED OUTPUT y of the ReLU: ATen's threshold_backward, the gradient rule of torch.relu.  The gradient
+ * becomes +0.0 where y is 0.0, -0.0 or negative (whatever v holds, a NaN included) and passes where y is positive, +inf or NaN.  The rows'
+ * `scale (.)` is the caller's; the stride-1 weight gradients are mvsdet_fpn_dw_bf16x3.  In every entry C = the layer's INPUT channels (the
+ * rows of the GEMM, any multiple of 32: the matrix handed in has ceil(C / 128) * 128 rows, those from C on zero) and Cout = its output
+ * channels (the reduction, a multiple of 32); `gate` = the gate map at the output's shape, NULL = no gate.
+ *   mvsdet_resnet_relu_gate_f32: out[e] = gate(g[e], y[e]) for `total` elements.
+ *   mvsdet_resnet_conv1x1_dx_bf16x3: out (N,C,H,W) = gate( (W'^T g (N,Cout,H,W)) [+ residual], gate ), the additions in that order.  wsplit =
+ *       the split of the (ceil128(C), Cout) matrix W'^T.  residual NULL = none; spread = 1: residual (N,C,H,W); spread = 2: residual
+ *       (N,C,(H-1)/2+1,(W-1)/2+1) added at (y / 2, x / 2) where y and x are both even, nothing added elsewhere.  N H W < 2^31.
+ *   mvsdet_resnet_conv3x3_dx_bf16x3: out (N,C,H,W) = gate( convT3x3_s(g (N,Cout,Ho,Wo); W'), gate ), the input gradient of the padding-1 3x3 of
+ *       stride s at an input of H x W (Ho = (H-1)/s+1).  s = 1: wsplit = the split of the (ceil128(C), 9 Cout) tap-major matrix of the
+ *       flipped, transposed weight w'[c,o,dy,dx] = W'[o,c,2-dy,2-dx]; one launch.  s = 2: the inserted zeros are never multiplied: the
+ *       pixels fall into four parity classes (py, px) = (y & 1, x & 1) of (1+py)(1+px) taps (dy = 1 for an even y; dy = 0, 2 for an odd
+ *       one, reading output rows (y+1)/2 and (y-1)/2), one GEMM launch each; wsplit = the four classes' splits behind one another in the
+ *       order (0,0), (0,1), (1,0), (1,1), class (py, px) the (ceil128(C), taps Cout) matrix with column (tap index) Cout + o holding
+ *       W'[o,c,dy,dx], the class's taps ordered dy ascending, then dx ascending.  N <= 65535, N H W < 2^31.
+ *   mvsdet_resnet_dw_s2_bf16x3: the weight gradient of a stride-2 1x1 (taps = 1) or padding-1 3x3 (taps = 9) convolution, bf16x3 with the
+ *       OUTPUT pixels as the reduction: dw (Cout,C,kh,kw)[o,c,dy,dx] = sum_{n,yo,xo} gy (N,Cout,Ho,Wo)[n,o,yo,xo] x (N,C,H,W)[n,c,2yo+dy-1,
+ *       2xo+dx-1] (zero outside; taps = 1: dy = dx = 1 only).  Only the real multiply-adds.  C % 32 == 0, Cout % 128 == 0, N <= 65535,
+ *       H W < 2^31, N Ho Wo < 2^31.  K is split over mvsdet_resnet_dw_s2_splits(...) blocks, each writing its fp32 partial to `workspace` (at
+ *       least mvsdet_resnet_dw_s2_workspace_bytes(...) bytes; a shorter one: MVSDET_ERR_WORKSPACE); the same entry then adds the splits in
+ *       ascending order into dw.  Both queries are host only and return 0 for a shape the kernel refuses.
+ * All: wsplit 16-byte aligned, contiguous 4-byte aligned tensors; everything else is refused on the host before any launch. */
+int mvsdet_resnet_relu_gate_f32(const float* g, const float* y, float* out, long long total, mvsdet_stream_t stream);
+int mvsdet_resnet_conv1x1_dx_bf16x3(const float* g, const void* wsplit, const float* residual, const float* gate, float* out, int N, int C,
+                                    int Cout, int H, int W, int spread, mvsdet_stream_t stream);
+int mvsdet_resnet_conv3x3_dx_bf16x3(const float* g, const void* wsplit, const float* gate, float* out, int N, int C, int Cout, int H, int W,
+                                    int stride, mvsdet_stream_t stream);
+int mvsdet_resnet_dw_s2_splits(int taps, int N, int C, int Cout, int H, int W);
+size_t mvsdet_resnet_dw_s2_workspace_bytes(int taps, int N, int C, int Cout, int H, int W);
+int mvsdet_resnet_dw_s2_bf16x3(const float* gy, const float* x, float* dw, void* workspace, size_t workspace_bytes, int taps, int N, int C,
+                               int Cout, int H, int W, mvsdet_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Detection post-processing of the ScanNet head (NerfDetHead.predict_by_feat / _nms / aligned_3d_nms, nerfdet_head.py:301-420,

@@ -84,6 +84,12 @@ SIGNATURES = {
     "mvsdet_fpn_bias_grad_f32": [_vp, _vp, _i, _i, _i, _i, _vp],
     "mvsdet_resnet_conv1x1_bf16x3": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_resnet_conv3x3_bf16x3": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_resnet_relu_gate_f32": [_vp, _vp, _vp, ctypes.c_longlong, _vp],
+    "mvsdet_resnet_conv1x1_dx_bf16x3": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_resnet_conv3x3_dx_bf16x3": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "mvsdet_resnet_dw_s2_splits": [_i, _i, _i, _i, _i, _i],
+    "mvsdet_resnet_dw_s2_workspace_bytes": [_i, _i, _i, _i, _i, _i],
+    "mvsdet_resnet_dw_s2_bf16x3": [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp],
     "mvsdet_conv3d_k3_cout2_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "mvsdet_conv3d_k3_cout2_sum_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "mvsdet_backproject_weigh_f32": [_vp, _i64p, _vp, _vp, _vp, _vp, _i64p, _vp, _vp, _vp, _vp,
@@ -207,7 +213,7 @@ _RESTYPE = {"mvsdet_last_error": ctypes.c_char_p, "mvsdet_conv3d_k3_bf16x3_stats
             "mvsdet_splat_workspace_bytes": ctypes.c_size_t, "mvsdet_gshead_partial_bytes": ctypes.c_size_t,
             "mvsdet_eval_state_bytes": ctypes.c_size_t, "mvsdet_eval_workspace_bytes": ctypes.c_size_t,
             "mvsdet_nvs_workspace_bytes": ctypes.c_size_t,
-            "mvsdet_fpn_dw_workspace_bytes": ctypes.c_size_t,
+            "mvsdet_fpn_dw_workspace_bytes": ctypes.c_size_t, "mvsdet_resnet_dw_s2_workspace_bytes": ctypes.c_size_t,
             "mvsdet_conv3d_k3_mfma_workspace_bytes": ctypes.c_size_t, "mvsdet_bn3d_workspace_bytes": ctypes.c_size_t}
 
 

@@ -30,6 +30,7 @@
 // fpn_bias_grad_kernel: one block per channel, a thread's elements ascending, the block's sum on block_reduce.h.
 #include "block_reduce.h"
 #include "common.h"
+#include "dw_sum.h"
 #include "mfma.h"
 
 namespace mvsdet {
@@ -258,15 +259,10 @@ __global__ __launch_bounds__(kThreads, 2) void fpn_dw_kernel(const float* __rest
         for (int i = 0; i < 16; ++i) pw[((size_t)t * Cout + mfma32_row(i, hh)) * C] = acc[t][i];
 }
 
-// dw (Cout,C,kh,kw)[o][c][tap] = partial[0][tap][o][c] + partial[1][tap][o][c] + ... in ascending order; one thread per element
+// dw (Cout,C,kh,kw)[o][c][tap] = the splits' partials added in ascending order (dw_sum.h); one thread per element
 __global__ __launch_bounds__(kThreads) void fpn_dw_sum_kernel(const float* __restrict__ partial, float* __restrict__ dw, int nsplit, int taps,
                                                               long long oc) {
-    const long long e = (long long)blockIdx.x * kThreads + threadIdx.x;   // index into [tap][o][c]
-    if (e >= oc * taps) return;
-    float s = 0.0f;
-    for (int k = 0; k < nsplit; ++k) s = s + partial[(size_t)k * taps * oc + e];
-    const long long tap = e / oc, r = e - tap * oc;
-    dw[r * taps + tap] = s;
+    dw_sum_splits(partial, dw, nsplit, taps, oc);
 }
 
 // g (N,C,H,W) -> gt (N,C,Ht,Wt): gt[.., yt, xt] = sum of g over the pixels (y, x) whose nearest source is (yt, xt)
