@@ -871,6 +871,14 @@ int mvsdet_neck_gemm_dw_bf16x3(const float* x, const float* grad_out, float* dw,
  *       maps (mvsdet_packed_bytes(N,Cout,H,W), what mvsdet_pack_features_f32 makes of `out`) to `packed`: each where its pointer is not
  *       NULL, at least one.  wsplit = mvsdet_gemm_split_weight of the (Cout, 9 Cin) tap-major matrix w.permute(0,2,3,1).reshape(Cout, 9 Cin)
  *       (k = Cin (3 dy + dx) + c); Cin % 32 == 0, Cout % 128 == 0, N <= 65535.  packed 16-byte aligned.
+ * Values (both entries, and the input gradients that run on them; tests/test_gpu_backbone_edges.py).  The range is fp32's: x is cut
+ * into two bf16 pieces inside the kernel, so x 2^k gives out 2^k bit for bit while nothing over- or underflows (bias and top zero), and
+ * every |x| <= 0x7f7f7f80, the largest value two pieces hold, keeps a finite hi piece.
+ *     Non-finite x: an infinity (hi = inf, mid = inf - inf) and a finite |x| >= 0x7f7f8000 (it rounds to an infinite hi, mid = -inf) yield
+ *     NaN, not inf, in the receptive field of that element.
+ *     A NaN (or the NaN such a value yields) reaches exactly the receptive field of its element: every output channel -- a zero weight
+ *     does not stop it, 0 * NaN = NaN -- at the pixels that read it, in its own view; every other output element keeps its bits, in
+ *     `out` and in `packed`.
  * ------------------------------------------------------------------------------------------- */
 int mvsdet_fpn_lateral_bf16x3(const float* x, const void* wsplit, const float* bias, const float* top, float* out, int N, int Cin,
                               int Cout, int H, int W, int Ht, int Wt, mvsdet_stream_t stream);
@@ -885,6 +893,10 @@ int mvsdet_fpn_conv3x3_bf16x3(const float* x, const void* wsplit, const float* b
  *       N H W < 2^31; any H, W >= 1; 4-byte aligned contiguous tensors.  K is split over mvsdet_fpn_dw_splits(...) blocks, each writing
  *       its fp32 partial to `workspace` (at least mvsdet_fpn_dw_workspace_bytes(...) bytes, 4-byte aligned); the same entry then adds the
  *       splits in ascending order into dw.  Both queries are host only and return 0 for a shape the kernel refuses.
+ *       Values: fp32's range (gy 2^k against x 2^-k keeps dw's bits).  A non-finite gy[n,o,..] (NaN, an infinity, a finite value of
+ *       magnitude >= 0x7f7f8000) stays in ROW o of dw, one in x[n,c,..] in COLUMN c: every other row (column) keeps its bits.  Inside
+ *       that row (column) the taps that pair the element with an element of the other map are NaN; further taps may be NaN as well (the
+ *       padding and the ragged edge of a tile are zeros that are multiplied: 0 * NaN), which nothing promises either way.
  *   mvsdet_fpn_top_down_grad_f32: the adjoint of the top-down nearest gather: gt (N,C,Ht,Wt)[.., yt, xt] = the sum of g (N,C,H,W) over the
  *       pixels whose source index (the float32 one above) is (yt, xt), rows ascending, then columns ascending; 1 <= Ht <= H, 1 <= Wt <= W.
  *   mvsdet_fpn_bias_grad_f32: db (C) = the sum of g (N,C,H,W) over views and pixels. */
@@ -914,6 +926,14 @@ int mvsdet_fpn_bias_grad_f32(const float* g, float* db, int N, int C, int H, int
  *       N <= 65535.
  * Both: stride 1 or 2; Cin % 32 == 0, Cout % 32 == 0; any H, W >= 1 with H W < 2^31; N Ho Wo < 2^31; wsplit 16-byte aligned, contiguous
  * 4-byte aligned tensors; relu 0 or 1.  Everything else is refused on the host before any launch.
+ * Values (tests/test_gpu_backbone_edges.py).  The range is fp32's: x is cut into two bf16 pieces inside the kernel, so x 2^k gives
+ * out 2^k bit for bit while nothing over- or underflows (shift zero, no residual), and every |x| <= 0x7f7f7f80, the largest value two
+ * pieces hold, keeps a finite hi piece.
+ *     Non-finite x: an infinity (hi = inf, mid = inf - inf) and a finite |x| >= 0x7f7f8000 (it rounds to an infinite hi, mid = -inf) yield
+ *     NaN, not inf, in the receptive field of that element.
+ *     A NaN (or the NaN such a value yields) reaches exactly the receptive field of its element: every output channel -- a zero weight
+ *     does not stop it -- at the output pixels that read it (the strided 1x1 reads even pixels only), in its own view, through shift,
+ *     residual and ReLU; every other output element keeps its bits.
  * ------------------------------------------------------------------------------------------- */
 int mvsdet_resnet_conv1x1_bf16x3(const float* x, const void* wsplit, const float* shift, const float* residual, float* out, int N, int Cin,
                                  int Cout, int H, int W, int stride, int relu, mvsdet_stream_t stream);
@@ -945,7 +965,15 @@ int mvsdet_resnet_conv3x3_bf16x3(const float* x, const void* wsplit, const float
  *       H W < 2^31, N Ho Wo < 2^31.  K is split over mvsdet_resnet_dw_s2_splits(...) blocks, each writing its fp32 partial to `workspace` (at
  *       least mvsdet_resnet_dw_s2_workspace_bytes(...) bytes; a shorter one: MVSDET_ERR_WORKSPACE); the same entry then adds the splits in
  *       ascending order into dw.  Both queries are host only and return 0 for a shape the kernel refuses.
- * All: wsplit 16-byte aligned, contiguous 4-byte aligned tensors; everything else is refused on the host before any launch. */
+ * All: wsplit 16-byte aligned, contiguous 4-byte aligned tensors; everything else is refused on the host before any launch.
+ * Values (tests/test_gpu_backbone_edges.py): fp32's range, as the forward entries.
+ *     The input gradients: a non-finite g[n,o,yo,xo] (NaN, an infinity, a finite magnitude >= 0x7f7f8000: all three come out as NaN)
+ *     reaches exactly the input pixels that output pixel was computed from -- 1x1: the pixel itself; 3x3: (s yo + dy - 1, s xo + dx - 1)
+ *     inside the map -- in every channel of view n; every other element keeps its bits.  Under a gate a dropped position is +0.0
+ *     whatever reached it, so the NaNs are the field's positions whose gate passes.
+ *     The stride-2 weight gradient: a non-finite gy[n,o,..] stays in ROW o of dw, one in x[n,c,..] in COLUMN c (an x the convolution never
+ *     reads, an odd pixel under taps = 1, changes nothing); the taps that pair the element with an element of the other map are NaN,
+ *     further taps of that row (column) may be (0 * NaN at the padding and the ragged edge), which nothing promises either way. */
 int mvsdet_resnet_relu_gate_f32(const float* g, const float* y, float* out, long long total, mvsdet_stream_t stream);
 int mvsdet_resnet_conv1x1_dx_bf16x3(const float* g, const void* wsplit, const float* residual, const float* gate, float* out, int N, int C,
                                     int Cout, int H, int W, int spread, mvsdet_stream_t stream);
